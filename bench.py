@@ -27,9 +27,15 @@ Workloads (--workload):
   cfg3b8 cfg3's shape packed with 8 bit planes (any byte alphabet: the engine's HammingMetric<2,8> instances)
   mink64 / mink1280  N=50 000 fp16 embeddings of D = 64 / 1280, Minkowski p=2 kNN k=16
 
-With one GPU and the default workload the line also carries `extra`: short runs of cfg2, cfg3d, cfg5, cfg3b8,
-mink64 and mink1280 in the same invocation (their own ms_per_step / kernel_ms / value), mirrored - workload,
-ms_per_step, kernel_ms, frac - in `roofline.other_workloads` (the driver keeps top-level keys only).
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit, ms_per_step, config).
+Everything else it can report runs only with --full: the PCIe-inclusive step (`pcie_inclusive`), the `roofline`
+object, the CPU baseline (`cpu_baseline`) and, with one GPU and the default workload, `extra`: short runs of cfg2,
+cfg3d, cfg5, cfg3b8, mink64 and mink1280 in the same invocation (their own ms_per_step / kernel_ms / value),
+mirrored - workload, ms_per_step, kernel_ms, frac - in `roofline.other_workloads` (the driver keeps top-level keys only).
+
+--dump-outputs DIR writes what the last timed step computed (kNN indices / distances, or the CSR arrays) as
+DIR/<name>.npy, integer outputs as float64 (indices) or float32 (distances, weights); outputs over 64 MB in all are cut
+to a fixed seeded sample.  The inputs are seeded, so two builds can be compared output for output.
 
 roofline: the all-pairs kernel is bound by vector-instruction issue, not by HBM (the operand matrix is
 cache resident): `frac` = wave-instructions per second / the SIMD-32 issue peak, with the per-launch
@@ -80,10 +86,31 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="auto", choices=["auto"] + list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the sub-records (cfg2, cfg3d, cfg5, cfg3b8, mink64, mink1280)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the PCIe-inclusive step, the roofline, the sub-records and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the sub-records (cfg2, cfg3d, cfg5, cfg3b8, mink64, mink1280)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU budget of the baseline sample")
     return ap.parse_args()
+
+
+DUMP_BYTES = 63_000_000          # --dump-outputs writes at most 64 MB, .npy headers included
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """Writes numpy arrays as out_dir/<name><suffix>.npy: int32/int64 (indices, indptr) as float64, which holds them
+    exactly, everything else (uint8 distances, fp16 weights) as float32.  When the whole exceeds DUMP_BYTES, every
+    array is cut to the same fraction of its flattened elements at positions drawn with a fixed seed."""
+    conv = {n: a.astype(np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize >= 4 else np.float32) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in conv.items():
+        if total > DUMP_BYTES:
+            keep = int(a.size * DUMP_BYTES / total)
+            pos = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, n + suffix + ".npy"), a)
 
 
 def kernel_src_sha():
@@ -148,8 +175,9 @@ class Ctx:
     pass
 
 
-def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie):
-    """Times `steps` steps of one workload; returns (record dict for rank 0, host tokens or None, wl)."""
+def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie, want_outputs=False):
+    """Times `steps` steps of one workload; returns (record dict for rank 0, host tokens or None, wl).  With
+    `want_outputs` the record carries `outputs`: the last timed step's results as host numpy arrays."""
     from prograph_amd import _native, synth, sharded
     import torch.distributed as dist
 
@@ -171,7 +199,7 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
     if wl["mode"] == "mink":
         if G != 1 or use_dist:
             raise SystemExit("the Minkowski workloads are single-GPU")
-        return run_minkowski(name, wl, dev, steps, warmup)
+        return run_minkowski(name, wl, dev, steps, warmup, want_outputs)
     if wl["mode"] == "lev":
         if G != 1 or use_dist:
             raise SystemExit("cfg5 is a single-GPU workload")
@@ -213,7 +241,7 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
             result.update(st)
             if record:
                 kern_ev.append((e0, e1))
-            return
+            return {"knn_indices": idx, "knn_distances": d}
         full = c.tok_dev if not use_dist else sharded.allgather_tokens(shard_dev, N)
         planes = _native.pack(full, bits=wl.get("bits", 5), check=False)   # validity word read once after the timed steps
         c.flags.append(planes.flags)
@@ -239,6 +267,7 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
                                                  _native._ptr(weights), 0, _native._stream()), "compact_sym")
             result["nnz"] = nnz
             result["path"] = "symmetric (every unordered pair once)"
+            res = {"indptr": indptr, "indices": indices[:nnz], "weights": weights[:nnz]}
         elif wl["mode"] == "eps":
             _native.eps_slots_only(planes, planes, _native.CMP_LE, wl["eps"], lo, rows_local, cap, slot_idx, slot_w, counts)
             e1.record()
@@ -255,11 +284,14 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
                                              _native._ptr(indptr), _native._ptr(indices), _native._ptr(weights), 0,
                                              _native._stream()), "compact")
             result["nnz"] = nnz
+            res = {"indptr": indptr, "indices": indices[:nnz], "weights": weights[:nnz]}
         else:
             _native.knn_graph(planes, planes, k, row0=lo, nrows=rows_local, out=out)
             e1.record()
+            res = {"knn_indices": out[0], "knn_distances": out[1]}
         if record:
             kern_ev.append((e0, e1))
+        return res
 
     def fence():
         if use_dist:
@@ -271,9 +303,11 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
     fence()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step(True)
+        last = step(True)
     fence()
     elapsed = time.perf_counter() - t0
+    # before the PCIe-inclusive step, which writes the kNN buffers again
+    outputs = {n: t.cpu().numpy() for n, t in last.items()} if want_outputs else None
     if use_dist:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -302,11 +336,11 @@ def run_workload(name, G, rank, dev, use_dist, backend, steps, warmup, want_pcie
     if wl["mode"] == "lev":
         engine = "valu"                       # the bag filter runs on pg_nsq_kernel<BagMetric> (SAD is not bilinear)
     rec = {"name": name, "N": N, "L": L, "k": k, "rows_local": rows_local, "kern_ms": kern_ms, "ms_per_step": ms_per_step,
-           "value": value, "pcie_ms": pcie_ms, "result": result, "engine": engine}
+           "value": value, "pcie_ms": pcie_ms, "result": result, "engine": engine, "outputs": outputs}
     return rec, tok_host, wl
 
 
-def run_minkowski(name, wl, dev, steps, warmup):
+def run_minkowski(name, wl, dev, steps, warmup, want_outputs=False):
     """kNN graph of N fp16 embeddings under Minkowski p = 2 with the reference's fp16 rounding: per block of rows the
     distance block (pg_minkowski_dense) and the canonical ranks 1..k (pg_f16_knn), as Prograph._build_graph_minkowski
     walks them.  Kernel time = the HIP-event time of all launches of a step."""
@@ -321,27 +355,30 @@ def run_minkowski(name, wl, dev, steps, warmup):
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
         xp = _native.pack_f16(X)
-        last = None
+        knn = []
         for r0 in range(0, N, rows_per_block):
             yp = _native.pack_f16(X[r0:r0 + rows_per_block])
             block = _native.minkowski_dense(xp, yp)
-            last = _native.f16_knn(block, k, first=1)
+            knn.append(_native.f16_knn(block, k, first=1))
         e1.record()
         if record:
             kern_ev.append((e0, e1))
-        return last
+        return knn
 
     for _ in range(warmup):
         step(False)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step(True)
+        last = step(True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    outputs = ({"knn_indices": torch.cat([b[0] for b in last]).cpu().numpy(),
+                "knn_distances": torch.cat([b[1] for b in last]).cpu().numpy()} if want_outputs else None)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in kern_ev]))
     rec = {"name": name, "N": N, "L": D, "k": k, "rows_local": N, "kern_ms": kern_ms, "ms_per_step": elapsed / steps * 1e3,
-           "value": float(N) * N * steps / elapsed, "pcie_ms": None, "result": {}, "engine": "valu (pg_minkowski_dense)"}
+           "value": float(N) * N * steps / elapsed, "pcie_ms": None, "result": {}, "engine": "valu (pg_minkowski_dense)",
+           "outputs": outputs}
     return rec, None, wl
 
 
@@ -451,24 +488,18 @@ def main():
 
     # one GPU: the headline configuration; several GPUs: BASELINE.json configs[3] (SURVEY.md §8-d weak scaling)
     name = a.workload if a.workload != "auto" else ("cfg3" if G == 1 else "cfg4")
-    rec, tok_host, wl = run_workload(name, G, rank, dev, use_dist, backend, a.steps, a.warmup, want_pcie=True)
+    rec, tok_host, wl = run_workload(name, G, rank, dev, use_dist, backend, a.steps, a.warmup, want_pcie=a.full,
+                                     want_outputs=bool(a.dump_outputs))
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rec["outputs"], suffix=f"_rank{rank}" if G > 1 else "")
 
     if rank == 0:
-        sha = kernel_src_sha()
-        pmc = {}
-        pmc_path = os.path.join(REPO, "profiles", "pmc_summary.json")
-        if os.path.exists(pmc_path):
-            try:
-                pmc = json.load(open(pmc_path))
-            except Exception:
-                pmc = {}
         line = {
             "metric": "sequence-pairs/s", "value": rec["value"], "unit": "sequence-pairs/s", "n_gpus": G,
             "steps": a.steps, "warmup": a.warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
             "config": {"workload": workload_text(rec, wl, G), "N": rec["N"], "L": rec["L"], "rows_per_gpu": rec["rows_local"],
                        "alphabet": "5-bit tokens 1..20", "parallelism": f"rowblock{G}", "engine": rec["engine"]},
-            "roofline": roofline(rec, wl, pmc, sha),
         }
         if wl["mode"] == "eps":
             line["config"]["nnz"] = rec["result"].get("nnz")
@@ -476,35 +507,45 @@ def main():
                 line["config"]["path"] = rec["result"]["path"]
         if wl["mode"] == "lev":
             line["config"].update({"candidates": rec["result"].get("candidates"), "filter_passes": rec["result"].get("filter_passes")})
-        if rec["pcie_ms"] is not None:
-            line["pcie_inclusive"] = {"ms_per_step": rec["pcie_ms"], "value": float(rec["rows_local"]) * rec["N"] / (rec["pcie_ms"] * 1e-3),
-                                      "note": "host tokens H2D + step + results D2H (pageable memory); reported only, not `value`"}
-        # the other single-GPU configurations, a few steps each, in the same invocation
-        if G == 1 and not use_dist and a.workload == "auto" and not a.no_extra:
-            extra = []
-            for sub in ("cfg2", "cfg3d", "cfg5", "cfg3b8", "mink64", "mink1280"):
-                torch.cuda.empty_cache()
-                nst, nwu = (2, 1) if sub == "mink1280" else (5, 2)
-                srec, _, swl = run_workload(sub, 1, 0, dev, False, backend, steps=nst, warmup=nwu, want_pcie=False)
-                e = {"workload": workload_text(srec, swl, 1), "steps": nst, "warmup": nwu, "ms_per_step": srec["ms_per_step"],
-                     "value": srec["value"], "unit": "sequence-pairs/s", "engine": srec["engine"],
-                     "roofline": roofline(srec, swl, pmc, sha)}
-                if swl["mode"] == "eps":
-                    e["nnz"] = srec["result"].get("nnz")
-                    e["path"] = srec["result"].get("path")
-                if swl["mode"] == "lev":
-                    e["candidates"] = srec["result"].get("candidates")
-                extra.append(e)
-            line["extra"] = extra
-            # (the driver's record keeps top-level keys only: the sub-records' essentials ride inside `roofline`)
-            line["roofline"]["other_workloads"] = [
-                {"workload": e["workload"], "ms_per_step": e["ms_per_step"], "kernel_ms": e["roofline"]["kernel_ms"],
-                 "value": e["value"], "engine": e["engine"], "bound": e["roofline"]["bound"], "frac": e["roofline"]["frac"],
-                 "kernel": e["roofline"]["kernel"]} for e in extra]
-        if not use_dist and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(tok_host, wl, a.cpu_seconds)
-        else:
-            line["cpu_baseline"] = None
+        if a.full:
+            sha = kernel_src_sha()
+            pmc = {}
+            pmc_path = os.path.join(REPO, "profiles", "pmc_summary.json")
+            if os.path.exists(pmc_path):
+                try:
+                    pmc = json.load(open(pmc_path))
+                except Exception:
+                    pmc = {}
+            line["roofline"] = roofline(rec, wl, pmc, sha)
+            if rec["pcie_ms"] is not None:
+                line["pcie_inclusive"] = {"ms_per_step": rec["pcie_ms"], "value": float(rec["rows_local"]) * rec["N"] / (rec["pcie_ms"] * 1e-3),
+                                          "note": "host tokens H2D + step + results D2H (pageable memory); reported only, not `value`"}
+            # the other single-GPU configurations, a few steps each, in the same invocation
+            if G == 1 and not use_dist and a.workload == "auto" and not a.no_extra:
+                extra = []
+                for sub in ("cfg2", "cfg3d", "cfg5", "cfg3b8", "mink64", "mink1280"):
+                    torch.cuda.empty_cache()
+                    nst, nwu = (2, 1) if sub == "mink1280" else (5, 2)
+                    srec, _, swl = run_workload(sub, 1, 0, dev, False, backend, steps=nst, warmup=nwu, want_pcie=False)
+                    e = {"workload": workload_text(srec, swl, 1), "steps": nst, "warmup": nwu, "ms_per_step": srec["ms_per_step"],
+                         "value": srec["value"], "unit": "sequence-pairs/s", "engine": srec["engine"],
+                         "roofline": roofline(srec, swl, pmc, sha)}
+                    if swl["mode"] == "eps":
+                        e["nnz"] = srec["result"].get("nnz")
+                        e["path"] = srec["result"].get("path")
+                    if swl["mode"] == "lev":
+                        e["candidates"] = srec["result"].get("candidates")
+                    extra.append(e)
+                line["extra"] = extra
+                # (the driver's record keeps top-level keys only: the sub-records' essentials ride inside `roofline`)
+                line["roofline"]["other_workloads"] = [
+                    {"workload": e["workload"], "ms_per_step": e["ms_per_step"], "kernel_ms": e["roofline"]["kernel_ms"],
+                     "value": e["value"], "engine": e["engine"], "bound": e["roofline"]["bound"], "frac": e["roofline"]["frac"],
+                     "kernel": e["roofline"]["kernel"]} for e in extra]
+            if not use_dist and not a.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(tok_host, wl, a.cpu_seconds)
+            else:
+                line["cpu_baseline"] = None
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)
         print(json.dumps(line), flush=True)

@@ -1145,12 +1145,12 @@ def test_probe_gated_alternatives_agree(nat, monkeypatch, force):
 @one_engine
 def test_bench_json_line_contract():
     """bench.py prints ONE JSON line with the driver's keys, a roofline object (bound / achieved / peak / unit /
-    frac / traffic) and a cpu_baseline slot; run on the smallest workload with two steps."""
+    frac / traffic) and a cpu_baseline slot with --full; run on the smallest workload with two steps."""
     import json, subprocess, sys
     here = os.path.dirname(os.path.abspath(__file__))
     env = {k: v for k, v in os.environ.items() if not k.startswith("PG_")}      # the bench's own engine choice
     out = subprocess.run([sys.executable, os.path.join(here, "..", "bench.py"), "--workload", "cfg2", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, env=env)
+                          "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -1164,3 +1164,31 @@ def test_bench_json_line_contract():
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert key in roof, key
     assert roof["bound"] in ("valu", "hbm", "mfma") and (roof["frac"] is None or 0 < roof["frac"] <= 1)
+
+
+@one_engine
+def test_bench_plain_run_dumps_the_last_step(nat, tmp_path):
+    """A plain bench.py run prints the headline line only (no roofline, PCIe step, sub-records or CPU baseline), and
+    --dump-outputs writes what its timed path computed: cfg3's kNN lists, equal to knn_graph on the same seeded input."""
+    import json, subprocess, sys
+    from prograph_amd import synth
+    here = os.path.dirname(os.path.abspath(__file__))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("PG_")}
+    out = subprocess.run([sys.executable, os.path.join(here, "..", "bench.py"), "--workload", "cfg3", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in rec, key
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    for key in ("roofline", "pcie_inclusive", "extra", "cpu_baseline"):
+        assert key not in rec, key
+    assert sorted(os.listdir(tmp_path)) == ["knn_distances.npy", "knn_indices.npy"]
+    idx, dist = np.load(tmp_path / "knn_indices.npy"), np.load(tmp_path / "knn_distances.npy")
+    assert idx.dtype == np.float64 and dist.dtype == np.float32 and idx.shape == dist.shape == (200_000, 16)
+    tok = synth.clustered_tokens(200_000, 64)
+    p = _planes(nat, tok, 5)
+    ridx, rdist = nat.knn_graph(p, p, 16)
+    assert np.array_equal(idx, ridx.cpu().numpy()) and np.array_equal(dist, rdist.cpu().numpy())

@@ -65,8 +65,9 @@ def check_kernel(name, instrs, labels, g):
 
 
 bad = 0
+tmp = tempfile.TemporaryDirectory()      # private to this run: a fixed name in the shared temp directory collides between users
 for g in gs:
-    out = os.path.join(tempfile.gettempdir(), f"ring_g{g}.s")
+    out = os.path.join(tmp.name, f"ring_g{g}.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + extra + [f"-DPG_G={g}", "-S", "--cuda-device-only", "pg_nsq_inst.hip", "-o", out],
                           cwd=SRC, stderr=subprocess.DEVNULL)
     kernel, instrs, labels, in_asm, nloads, nk = None, [], {}, False, 0, 0

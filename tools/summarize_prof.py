@@ -42,7 +42,7 @@ def steps_run(bench_json):
 
 
 out_dir, wl = sys.argv[1], sys.argv[2]
-res = {"workload": wl, "kernel": None, "counters": {}, "command": f"python bench.py --workload {wl} --no-cpu-baseline --no-extra",
+res = {"workload": wl, "kernel": None, "counters": {}, "command": f"python bench.py --workload {wl} --full --no-cpu-baseline --no-extra",
        "kernel_src_sha": kernel_src_sha(), "per": "step (sums over a kernel's launches of one step)"}
 S = steps_run(f"{out_dir}/bench_trace.json")
 for f in newest(f"{out_dir}/trace/**/*_kernel_stats.csv"):
