@@ -343,6 +343,35 @@ int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int 
                     const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream);
 
 /*
+ * Fused Minkowski graphs: the distances of pg_minkowski_dense (same per-pair arithmetic, bit for bit) selected
+ * on the fly in LDS tiles, so the (M, N) block never reaches HBM.  Replaces `distance(X, batch)` followed by
+ * `torch.sort(...)[:, 1:k+1]` (prograph/prograph.py:726, :756-763) and by `comp(d, eps) & (d > 0)` ->
+ * `torch.where` (:731-739) of `build_graph(representation="Embedded", distance=minkowski)`.  Operands as for
+ * pg_minkowski_dense (pg_pack_f16 buffers; x_npad a multiple of 256, y_npad >= m).
+ *   pg_minkowski_knn       result of pg_f16_knn(pg_minkowski_dense(...)): ranks first..first+k-1 of every Y row's
+ *                          (value, column) order over the n X vectors, descending values when similarity != 0;
+ *                          first + k <= 64; missing ranks idx -1, weight 0.  idx_out int32 [m*k], w_out fp16 [m*k]
+ *   pg_minkowski_eps_slots the epsilon test of pg_f16_eps_* (eps_f16 rounded as there) in ONE distance sweep:
+ *                          counts[r] = exact number of matches of row r, its first `cap` matching columns
+ *                          (ascending) and fp16 values in slot_idx / slot_w [r*cap ...]  (int32 / fp16 [m*cap])
+ *   pg_minkowski_eps_compact  after pg_exclusive_scan(counts) -> indptr: rows with counts <= cap copied from their
+ *                          slot into indices / weights at indptr[r]; rows beyond cap are left alone
+ *   pg_minkowski_eps_fill_rows  the sweep again for the n_list rows of row_list (int64, e.g. the rows with
+ *                          counts > cap from pg_compact_flags), every match written at indptr[row] in ascending
+ *                          column order.  Together: the CSR of pg_f16_eps_count/_fill, with one host sync (nnz)
+ */
+int pg_minkowski_knn(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
+                     int d, int similarity, int k, int first, int32_t *idx_out, void *w_out_f16, void *stream);
+int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m,
+                           int64_t y_npad, int d, int similarity, int cmp, float eps_f16, int cap, int32_t *slot_idx,
+                           void *slot_w_f16, uint32_t *counts, void *stream);
+int pg_minkowski_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const void *slot_w_f16, const uint32_t *counts,
+                             const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream);
+int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m,
+                               int64_t y_npad, int d, int similarity, int cmp, float eps_f16, const int64_t *row_list,
+                               int64_t n_list, const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream);
+
+/*
  * Multi-GPU: the path's ONE collective (e).  The N^2 pair space shards row-block
  * wise, one process per GPU; every rank needs the whole token matrix, so the ranks all-gather their
  * row shards once (RCCL over xGMI: 64 MB at N = 1M, L = 64) and never talk again.  The reference has

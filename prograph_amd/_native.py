@@ -32,6 +32,7 @@ SYMBOLS = [
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_eps_count", "pg_f16_eps_fill",
+    "pg_minkowski_knn", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact", "pg_minkowski_eps_fill_rows",
 ]
 
 
@@ -112,6 +113,12 @@ def _load():
         lib.pg_f16_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_f16_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _vp]
         lib.pg_f16_eps_fill.argtypes = [_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
+        lib.pg_minkowski_knn.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]
+        lib.pg_minkowski_eps_slots.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _i32,
+                                               _vp, _vp, _vp, _vp]
+        lib.pg_minkowski_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_minkowski_eps_fill_rows.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _vp,
+                                                   _i64, _vp, _vp, _vp, _vp]
         lib.pg_comm_unique_id.argtypes = [_vp]
         lib.pg_comm_init.argtypes = [ctypes.POINTER(_vp), _i32, _i32, _vp]
         lib.pg_comm_destroy.argtypes = [_vp]
@@ -615,6 +622,73 @@ def f16_eps(block, cmp, eps, similarity=False):
         _check(L.pg_f16_eps_fill(_ptr(block), m, n, block.stride(0), int(cmp), e16, 1 if similarity else 0, _ptr(indptr),
                                  _ptr(indices), _ptr(weights), _stream()), "pg_f16_eps_fill")
     return indptr, indices, weights
+
+
+def _f16_rows(yp, r0, r1):
+    """Pointer to vector r0 of a PackedF16 with its npad: chunk q of vector r0 + i sits at (q*npad + r0 + i)*16, so rows
+    [r0, r1) are an operand of their own without a copy."""
+    return ctypes.c_void_p(yp.buf.data_ptr() + 16 * r0), r1 - r0
+
+
+def minkowski_knn(xp, yp, k, first=1, similarity=False):
+    """f16_knn(minkowski_dense(xp, yp, similarity), k, first, descending=similarity) in one fused sweep (pg_minkowski_knn):
+    the distances are selected in LDS and never written out.  Returns (idx int32 (m, k), w fp16 (m, k))."""
+    if xp.d != yp.d:
+        raise ValueError("operands must have the same dimension")
+    dev = xp.buf.device
+    idx = torch.empty((yp.n, int(k)), dtype=torch.int32, device=dev)
+    w = torch.empty((yp.n, int(k)), dtype=torch.float16, device=dev)
+    _check(lib().pg_minkowski_knn(_ptr(xp.buf), xp.n, xp.npad, _ptr(yp.buf), yp.n, yp.npad, xp.d, 1 if similarity else 0,
+                                  int(k), int(first), _ptr(idx), _ptr(w), _stream()), "pg_minkowski_knn")
+    return idx, w
+
+
+def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256):
+    """f16_eps(minkowski_dense(xp, yp, similarity), cmp, eps, similarity) with ONE distance sweep per row block: exact
+    counts plus up to `cap` entries per row in slots (pg_minkowski_eps_slots), scan, compaction, and a second sweep over
+    just the rows with more than `cap` matches, written straight into the CSR (pg_minkowski_eps_fill_rows).  One host
+    sync per block (nnz and the number of such rows); blocks keep the slots within 256 MB.
+    Returns (indptr int64 [m+1], indices int32 [nnz], weights fp16 [nnz])."""
+    if xp.d != yp.d:
+        raise ValueError("operands must have the same dimension")
+    L = lib()
+    dev = xp.buf.device
+    cap = max(1, int(cap))
+    e16 = float(np.float16(eps))
+    sim = 1 if similarity else 0
+    rows_per_block = max(64, (256 << 20) // (cap * 6))                # int32 + fp16 per slot
+    parts = []
+    for r0 in range(0, yp.n, rows_per_block):
+        y, m = _f16_rows(yp, r0, min(yp.n, r0 + rows_per_block))
+        counts = torch.empty(m, dtype=torch.int32, device=dev)
+        slot_idx = torch.empty(m * cap, dtype=torch.int32, device=dev)
+        slot_w = torch.empty(m * cap, dtype=torch.float16, device=dev)
+        _check(L.pg_minkowski_eps_slots(_ptr(xp.buf), xp.n, xp.npad, y, m, yp.npad, xp.d, sim, int(cmp), e16, cap,
+                                        _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _stream()), "pg_minkowski_eps_slots")
+        indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
+        _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+        over = counts > cap
+        nnz, n_over = (int(v) for v in torch.stack([indptr[-1], over.sum()]).cpu())     # the one sync
+        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+        weights = torch.empty(max(nnz, 1), dtype=torch.float16, device=dev)[:nnz]
+        if nnz:
+            _check(L.pg_minkowski_eps_compact(m, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(indptr), _ptr(indices),
+                                              _ptr(weights), _stream()), "pg_minkowski_eps_compact")
+        if n_over:
+            rows = compact_flags(over.to(torch.uint8), count=n_over)
+            _check(L.pg_minkowski_eps_fill_rows(_ptr(xp.buf), xp.n, xp.npad, y, m, yp.npad, xp.d, sim, int(cmp), e16, _ptr(rows),
+                                                n_over, _ptr(indptr), _ptr(indices), _ptr(weights), _stream()),
+                   "pg_minkowski_eps_fill_rows")
+        del slot_idx, slot_w
+        parts.append((indptr, indices, weights))
+    if len(parts) == 1:
+        return parts[0]
+    base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
+    for indptr, _, _ in parts:
+        ptrs.append(indptr[1:] + base)
+        base += int(indptr[-1].item())
+    return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
 
 
 COMM_ID_BYTES = 128

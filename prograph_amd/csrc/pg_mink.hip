@@ -52,6 +52,59 @@ __global__ __launch_bounds__(256) void pg_pack_f16_kernel(const __half *__restri
   }
 }
 
+// ---- the per-pair arithmetic, shared by the dense kernel and the fused graph kernels -------------------------
+// one 16-byte chunk (8 halfs) of a pair: difference and square rounded to fp16 two elements per instruction,
+// fp32 accumulation in element order (fdot2 against (1, 1): exact products)
+__device__ __forceinline__ float mk_chunk(float acc, uint4 xv, uint4 yv) {
+  const pg_h2 ones = {(_Float16)1.0f, (_Float16)1.0f};
+  const pg_h2 d0 = __builtin_bit_cast(pg_h2, xv.x) - __builtin_bit_cast(pg_h2, yv.x);
+  const pg_h2 d1 = __builtin_bit_cast(pg_h2, xv.y) - __builtin_bit_cast(pg_h2, yv.y);
+  const pg_h2 d2 = __builtin_bit_cast(pg_h2, xv.z) - __builtin_bit_cast(pg_h2, yv.z);
+  const pg_h2 d3 = __builtin_bit_cast(pg_h2, xv.w) - __builtin_bit_cast(pg_h2, yv.w);
+  float p = __builtin_amdgcn_fdot2(d0 * d0, ones, acc, false);
+  p = __builtin_amdgcn_fdot2(d1 * d1, ones, p, false);
+  p = __builtin_amdgcn_fdot2(d2 * d2, ones, p, false);
+  return __builtin_amdgcn_fdot2(d3 * d3, ones, p, false);
+}
+
+// the accumulated sum -> fp16 distance bits (or similarity 1/(1+d))
+__device__ __forceinline__ unsigned short mk_finish(float acc, int similarity) {
+  const _Float16 s16 = (_Float16)acc;                               // the float sum as fp16
+  __half d16 = __float2half_rn(sqrtf((float)s16));                  // pow(., 1/2) on the fp16 value
+  if (similarity) {                                                 // 1 / (1 + d): two fp16 roundings (minkowski.py:40)
+    const __half t = __float2half_rn(1.0f + __half2float(d16));
+    d16 = __float2half_rn(1.0f / __half2float(t));
+  }
+  return __half_as_ushort(d16);
+}
+
+// acc[r] = sum over all chunks of Y row r (staged in ybuf) against column c of X.  Y rows go through LDS one
+// segment of MK_SEG chunks at a time: the thread stages chunk (tid % MK_SEG) of row (tid / MK_SEG), whose Y
+// index is `yrow` (< 0: a row past the end, staged as zeros).  staged != 0: nq <= MK_SEG and ybuf already
+// holds the whole rows (the fused kernels load them once).  Chunk order = element order, for every caller.
+__device__ __forceinline__ void mk_accumulate(float (&acc)[MK_ROWS], const uint4 *__restrict__ xp, long long xnpad, long long c,
+                                              const uint4 *__restrict__ yp, long long ynpad, long long yrow, int nq,
+                                              uint4 (*ybuf)[MK_SEG], bool staged) {
+#pragma unroll
+  for (int r = 0; r < MK_ROWS; ++r) acc[r] = 0.0f;
+  for (int q0 = 0; q0 < nq; q0 += MK_SEG) {
+    if (!staged) {
+      __syncthreads();
+      const int rr = threadIdx.x / MK_SEG, qq = threadIdx.x % MK_SEG;     // 16 x 16 = 256 chunks per segment
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (yrow >= 0 && q0 + qq < nq) v = yp[(long long)(q0 + qq) * ynpad + yrow];
+      ybuf[rr][qq] = v;
+      __syncthreads();
+    }
+    const int qn = nq - q0 < MK_SEG ? nq - q0 : MK_SEG;
+    for (int qq = 0; qq < qn; ++qq) {
+      const uint4 xv = xp[(long long)(q0 + qq) * xnpad + c];
+#pragma unroll
+      for (int r = 0; r < MK_ROWS; ++r) acc[r] = mk_chunk(acc[r], xv, ybuf[r][qq]);
+    }
+  }
+}
+
 // (M, N) fp16 distance (or similarity) matrix: out[m * ldo + n] = minkowski2(Y[m], X[n])
 __global__ __launch_bounds__(256) void pg_mink_dense_kernel(const uint4 *__restrict__ xp, long long n, long long xnpad,
                                                             const uint4 *__restrict__ yp, long long m, long long ynpad,
@@ -61,48 +114,13 @@ __global__ __launch_bounds__(256) void pg_mink_dense_kernel(const uint4 *__restr
   const long long r0 = (long long)blockIdx.y * MK_ROWS;
   const int nr = (int)((m - r0) < MK_ROWS ? (m - r0) : MK_ROWS);
   const long long c = col < xnpad ? col : xnpad - 1;
+  const int srow = threadIdx.x / MK_SEG;
   float acc[MK_ROWS];
-#pragma unroll
-  for (int r = 0; r < MK_ROWS; ++r) acc[r] = 0.0f;
-  const pg_h2 ones = {(_Float16)1.0f, (_Float16)1.0f};
-  for (int q0 = 0; q0 < nq; q0 += MK_SEG) {
-    __syncthreads();
-    {
-      const int rr = threadIdx.x / MK_SEG, qq = threadIdx.x % MK_SEG;     // 16 x 16 = 256 chunks per segment
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (rr < nr && q0 + qq < nq) v = yp[(long long)(q0 + qq) * ynpad + r0 + rr];
-      ybuf[rr][qq] = v;
-    }
-    __syncthreads();
-    const int qn = nq - q0 < MK_SEG ? nq - q0 : MK_SEG;
-    for (int qq = 0; qq < qn; ++qq) {
-      const uint4 xv = xp[(long long)(q0 + qq) * xnpad + c];
-      const pg_h2 x0 = __builtin_bit_cast(pg_h2, xv.x), x1 = __builtin_bit_cast(pg_h2, xv.y);
-      const pg_h2 x2 = __builtin_bit_cast(pg_h2, xv.z), x3 = __builtin_bit_cast(pg_h2, xv.w);
-#pragma unroll
-      for (int r = 0; r < MK_ROWS; ++r) {
-        const uint4 yv = ybuf[r][qq];
-        const pg_h2 d0 = x0 - __builtin_bit_cast(pg_h2, yv.x), d1 = x1 - __builtin_bit_cast(pg_h2, yv.y);
-        const pg_h2 d2 = x2 - __builtin_bit_cast(pg_h2, yv.z), d3 = x3 - __builtin_bit_cast(pg_h2, yv.w);
-        float p = __builtin_amdgcn_fdot2(d0 * d0, ones, acc[r], false);
-        p = __builtin_amdgcn_fdot2(d1 * d1, ones, p, false);
-        p = __builtin_amdgcn_fdot2(d2 * d2, ones, p, false);
-        acc[r] = __builtin_amdgcn_fdot2(d3 * d3, ones, p, false);
-      }
-    }
-  }
+  mk_accumulate(acc, xp, xnpad, c, yp, ynpad, srow < nr ? r0 + srow : -1, nq, ybuf, false);
   if (col < n) {
 #pragma unroll
     for (int r = 0; r < MK_ROWS; ++r) {
-      if (r < nr) {
-        const _Float16 s16 = (_Float16)acc[r];                          // the float sum as fp16
-        __half d16 = __float2half_rn(sqrtf((float)s16));                  // pow(., 1/2) on the fp16 value
-        if (similarity) {                                               // 1 / (1 + d): two fp16 roundings (minkowski.py:40)
-          const __half t = __float2half_rn(1.0f + __half2float(d16));
-          d16 = __float2half_rn(1.0f / __half2float(t));
-        }
-        out[(r0 + r) * ldo + col] = d16;
-      }
+      if (r < nr) out[(r0 + r) * ldo + col] = __ushort_as_half(mk_finish(acc[r], similarity));
     }
   }
 }
@@ -192,6 +210,178 @@ __global__ __launch_bounds__(256) void pg_f16_eps_kernel(const __half *__restric
   if (!indptr && lane == 0) counts[row] = cnt;
 }
 
+// ---- fused distance + selection: no (M, N) block in HBM -----------------------------------------------------
+// A workgroup owns MK_ROWS rows (Y vectors) and sweeps all N columns in tiles of MK_TILE: each thread computes its
+// column's distances to the 16 rows with the dense kernel's arithmetic (mk_accumulate / mk_finish), the tile's fp16
+// values go to LDS, then wave w selects for rows 4w .. 4w+3 from the tile, 64 columns per ballot.  Rows of the
+// D <= 128 embeddings are staged in LDS once per workgroup, longer ones one segment at a time per tile.
+#define MK_TILE 256
+#define MK_RPW (MK_ROWS / 4)      // rows per wave in the selection
+
+// Y index of the row this thread stages: rows r0 .. r0+15, or row_list[g*16 .. g*16+15] (restricted sweeps);
+// -1 past the end
+__device__ __forceinline__ long long mk_group_row(int rr, long long m, const long long *__restrict__ row_list, long long n_list) {
+  const long long g = (long long)blockIdx.x * MK_ROWS + rr;
+  if (!row_list) return g < m ? g : -1;
+  if (g >= n_list) return -1;
+  const long long r = row_list[g];
+  return r >= 0 && r < m ? r : -1;
+}
+
+// one 256-column tile of the group's fp16 values into LDS: tile[r][j] = value of row r, column t0 + j
+__device__ __forceinline__ void mk_tile(unsigned short (*tile)[MK_TILE], const uint4 *__restrict__ xp, long long xnpad, long long t0,
+                                        const uint4 *__restrict__ yp, long long ynpad, long long yrow, int nq, uint4 (*ybuf)[MK_SEG],
+                                        bool staged, int similarity) {
+  float acc[MK_ROWS];
+  mk_accumulate(acc, xp, xnpad, t0 + threadIdx.x, yp, ynpad, yrow, nq, ybuf, staged);   // t0 + 255 < xnpad: npad % 256 == 0
+  __syncthreads();                                                   // the previous tile's selection is done
+#pragma unroll
+  for (int r = 0; r < MK_ROWS; ++r) tile[r][threadIdx.x] = mk_finish(acc[r], similarity);
+  __syncthreads();
+}
+
+__device__ __forceinline__ void mk_stage_once(uint4 (*ybuf)[MK_SEG], const uint4 *__restrict__ yp, long long ynpad, long long yrow,
+                                              int nq) {
+  const int rr = threadIdx.x / MK_SEG, qq = threadIdx.x % MK_SEG;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (yrow >= 0 && qq < nq) v = yp[(long long)qq * ynpad + yrow];
+  ybuf[rr][qq] = v;
+  __syncthreads();
+}
+
+// ranks first .. first+k-1 of every row's (key, column) order over all n columns: pg_f16_knn on the fly
+__global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restrict__ xp, long long n, long long xnpad,
+                                                          const uint4 *__restrict__ yp, long long m, long long ynpad, int nq,
+                                                          int similarity, int k, int first, int *__restrict__ idx,
+                                                          unsigned short *__restrict__ w) {
+  __shared__ uint4 ybuf[MK_ROWS][MK_SEG];
+  __shared__ unsigned short tile[MK_ROWS][MK_TILE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long r0 = (long long)blockIdx.x * MK_ROWS;
+  const int nr = (int)((m - r0) < MK_ROWS ? (m - r0) : MK_ROWS);
+  const long long yrow = mk_group_row(threadIdx.x / MK_SEG, m, nullptr, 0);
+  const bool staged = nq <= MK_SEG;
+  if (staged) mk_stage_once(ybuf, yp, ynpad, yrow, nq);
+  const int last = first + k - 1;
+  u32 lk[MK_RPW], lc[MK_RPW], tk[MK_RPW], tc[MK_RPW];      // lane j = j-th smallest (key, column); entry of lane `last`
+#pragma unroll
+  for (int j = 0; j < MK_RPW; ++j) lk[j] = lc[j] = tk[j] = tc[j] = 0xFFFFFFFFu;
+  for (long long t0 = 0; t0 < n; t0 += MK_TILE) {
+    mk_tile(tile, xp, xnpad, t0, yp, ynpad, yrow, nq, ybuf, staged, similarity);
+    const int ncol = (int)(n - t0 < MK_TILE ? n - t0 : MK_TILE);
+#pragma unroll
+    for (int j = 0; j < MK_RPW; ++j) {
+      const int r = wv * MK_RPW + j;
+      if (r >= nr) continue;                                         // wave-uniform
+      for (int s0 = 0; s0 < ncol; s0 += 64) {
+        const int cc = s0 + lane;
+        const u32 key = cc < ncol ? mk_key(tile[r][cc], similarity) : 0xFFFFFFFFu;
+        const u32 col = (u32)(t0 + cc);
+        const bool cand = cc < ncol && (key < tk[j] || (key == tk[j] && col < tc[j]));
+        u64 mask = __builtin_amdgcn_ballot_w64(cand);
+        while (mask) {
+          const int b = __builtin_ctzll(mask);
+          mask &= mask - 1;
+          const u32 xk = __builtin_amdgcn_readlane(key, b), xc = (u32)(t0 + s0 + b);
+          if (xk < tk[j] || (xk == tk[j] && xc < tc[j])) {
+            const bool keep = lk[j] < xk || (lk[j] == xk && lc[j] <= xc);     // entries not after x stay
+            const u32 pk = wave_shr1(lk[j], 0u), pc = wave_shr1(lc[j], 0u);
+            const bool prev_after = pk > xk || (pk == xk && pc > xc);          // lane-1's entry also moves, else x lands here
+            lk[j] = keep ? lk[j] : (prev_after ? pk : xk);
+            lc[j] = keep ? lc[j] : (prev_after ? pc : xc);
+            tk[j] = __builtin_amdgcn_readlane(lk[j], last);
+            tc[j] = __builtin_amdgcn_readlane(lc[j], last);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < MK_RPW; ++j) {
+    const int r = wv * MK_RPW + j;
+    if (r < nr && lane >= first && lane <= last) {
+      const long long o = (r0 + r) * (long long)k + (lane - first);
+      const bool none = lc[j] == 0xFFFFFFFFu;
+      idx[o] = none ? -1 : (int)lc[j];
+      w[o] = none ? 0 : (unsigned short)(similarity ? 0xFFFFu - lk[j] : lk[j]);    // mk_key inverted
+    }
+  }
+}
+
+// epsilon selection in the same sweep.  Slot mode (row_list == NULL): every row's exact match count into counts[],
+// its first `cap` matches (ascending columns) into its slot.  Fill mode: the rows of row_list only, every match
+// written at indptr[row] (counts from a slot pass, so the segments fit).
+__global__ __launch_bounds__(256) void pg_mink_eps_kernel(const uint4 *__restrict__ xp, long long n, long long xnpad,
+                                                          const uint4 *__restrict__ yp, long long m, long long ynpad, int nq,
+                                                          int similarity, int cmp, float eps, const long long *__restrict__ row_list,
+                                                          long long n_list, int cap, int *__restrict__ slot_idx,
+                                                          unsigned short *__restrict__ slot_w, u32 *__restrict__ counts,
+                                                          const long long *__restrict__ indptr, int *__restrict__ indices,
+                                                          unsigned short *__restrict__ weights) {
+  __shared__ uint4 ybuf[MK_ROWS][MK_SEG];
+  __shared__ unsigned short tile[MK_ROWS][MK_TILE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long yrow = mk_group_row(threadIdx.x / MK_SEG, m, row_list, n_list);
+  const bool staged = nq <= MK_SEG;
+  if (staged) mk_stage_once(ybuf, yp, ynpad, yrow, nq);
+  long long row[MK_RPW], base[MK_RPW];
+  u32 cnt[MK_RPW];
+#pragma unroll
+  for (int j = 0; j < MK_RPW; ++j) {
+    row[j] = mk_group_row(wv * MK_RPW + j, m, row_list, n_list);
+    base[j] = row[j] < 0 ? 0 : (row_list ? indptr[row[j]] : row[j] * (long long)cap);
+    cnt[j] = 0;
+  }
+  for (long long t0 = 0; t0 < n; t0 += MK_TILE) {
+    mk_tile(tile, xp, xnpad, t0, yp, ynpad, yrow, nq, ybuf, staged, similarity);
+    const int ncol = (int)(n - t0 < MK_TILE ? n - t0 : MK_TILE);
+#pragma unroll
+    for (int j = 0; j < MK_RPW; ++j) {
+      if (row[j] < 0) continue;                                      // wave-uniform
+      const int r = wv * MK_RPW + j;
+      for (int s0 = 0; s0 < ncol; s0 += 64) {
+        const int cc = s0 + lane;
+        const unsigned short v = cc < ncol ? tile[r][cc] : 0;
+        const bool hit = cc < ncol && mk_match(__half2float(__ushort_as_half(v)), eps, cmp, similarity);
+        const u64 mask = __builtin_amdgcn_ballot_w64(hit);
+        if (hit) {
+          const long long o = (long long)cnt[j] + mask_rank(mask);
+          if (row_list) {
+            indices[base[j] + o] = (int)(t0 + cc);
+            weights[base[j] + o] = v;
+          } else if (o < cap) {
+            slot_idx[base[j] + o] = (int)(t0 + cc);
+            slot_w[base[j] + o] = v;
+          }
+        }
+        cnt[j] += (u32)__popcll(mask);
+      }
+    }
+  }
+  if (!row_list && lane == 0) {
+#pragma unroll
+    for (int j = 0; j < MK_RPW; ++j)
+      if (row[j] >= 0) counts[row[j]] = cnt[j];
+  }
+}
+
+// slots -> CSR for the rows that kept all their matches (count <= cap); one wave per row
+__global__ __launch_bounds__(256) void pg_mink_eps_compact_kernel(long long m, int cap, const int *__restrict__ slot_idx,
+                                                                  const unsigned short *__restrict__ slot_w,
+                                                                  const u32 *__restrict__ counts, const long long *__restrict__ indptr,
+                                                                  int *__restrict__ indices, unsigned short *__restrict__ weights) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= m) return;
+  const u32 cnt = counts[row];
+  if (cnt > (u32)cap) return;                                        // pg_minkowski_eps_fill_rows writes this row
+  const long long o = indptr[row], s = row * (long long)cap;
+  for (u32 i = lane; i < cnt; i += 64) {
+    indices[o + i] = slot_idx[s + i];
+    weights[o + i] = slot_w[s + i];
+  }
+}
+
 static int mfail(int code, const char *msg) {
   pg_set_error(msg);
   return code;
@@ -258,6 +448,62 @@ int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int 
       (const __half *)dist_f16, m, n, ld, cmp, eps_f16, similarity ? 1 : 0, nullptr, (const long long *)indptr, indices,
       (__half *)weights_f16);
   return mlaunched("pg_f16_eps_kernel(fill)");
+}
+
+static int mk_operands_bad(const void *xp, int64_t n, int64_t x_npad, const void *yp, int64_t m, int64_t y_npad, int d) {
+  return !xp || !yp || n <= 0 || m <= 0 || d <= 0 || x_npad < n || x_npad % 256 || y_npad < m;
+}
+
+int pg_minkowski_knn(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad, int d,
+                     int similarity, int k, int first, int32_t *idx_out, void *w_out_f16, void *stream) {
+  if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !idx_out || !w_out_f16)
+    return mfail(PG_E_BADARG, "pg_minkowski_knn: bad argument");
+  if (k < 1 || first < 0 || first + k > 64) return mfail(PG_E_BADARG, "pg_minkowski_knn: first + k must be at most 64");
+  if (n > 0xFFFFFFFFll - 1 || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
+    return mfail(PG_E_BADARG, "pg_minkowski_knn: too many vectors for one launch");
+  pg_mink_knn_kernel<<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, k, first,
+      idx_out, (unsigned short *)w_out_f16);
+  return mlaunched("pg_mink_knn_kernel");
+}
+
+int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
+                           int d, int similarity, int cmp, float eps_f16, int cap, int32_t *slot_idx, void *slot_w_f16,
+                           uint32_t *counts, void *stream) {
+  if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !slot_idx || !slot_w_f16 || !counts || cap < 1 ||
+      cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+    return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: bad argument");
+  if (n > 0x7FFFFFFFll || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
+    return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: too many vectors for one launch");
+  pg_mink_eps_kernel<<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, cmp, eps_f16,
+      nullptr, 0, cap, slot_idx, (unsigned short *)slot_w_f16, counts, nullptr, nullptr, nullptr);
+  return mlaunched("pg_mink_eps_kernel(slots)");
+}
+
+int pg_minkowski_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const void *slot_w_f16, const uint32_t *counts,
+                             const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
+  if (!slot_idx || !slot_w_f16 || !counts || !indptr || !indices || !weights_f16 || m <= 0 || cap < 1)
+    return mfail(PG_E_BADARG, "pg_minkowski_eps_compact: bad argument");
+  pg_mink_eps_compact_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      m, cap, slot_idx, (const unsigned short *)slot_w_f16, counts, (const long long *)indptr, indices,
+      (unsigned short *)weights_f16);
+  return mlaunched("pg_mink_eps_compact_kernel");
+}
+
+int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
+                               int d, int similarity, int cmp, float eps_f16, const int64_t *row_list, int64_t n_list,
+                               const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
+  if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !row_list || n_list <= 0 || !indptr || !indices ||
+      !weights_f16 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+    return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: bad argument");
+  if (n > 0x7FFFFFFFll || (n_list + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
+    return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: too many vectors for one launch");
+  pg_mink_eps_kernel<<<dim3((unsigned)((n_list + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, cmp, eps_f16,
+      (const long long *)row_list, n_list, 1, nullptr, nullptr, nullptr, (const long long *)indptr, indices,
+      (unsigned short *)weights_f16);
+  return mlaunched("pg_mink_eps_kernel(fill)");
 }
 
 }  // extern "C"

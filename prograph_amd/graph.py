@@ -6,6 +6,9 @@ The reference hands back a Python list of N `(indices, weights)` tuples per grap
 produces CSR / (N,k) arrays on the device; these classes keep that form (device resident,
 no per-row Python objects) and materialise the reference's tuples only on request, as
 zero-copy views into two host arrays.
+
+Weights are Hamming distances (uint8 / int16 / float32; similarities are formed on the host) or fp16 Minkowski values
+(distances or similarities as the kernels computed them: those are final and pass through unchanged).
 """
 import numpy as np
 import torch
@@ -14,7 +17,7 @@ from . import _native
 
 
 class CSRGraph:
-    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|float32 [nnz]."""
+    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|float32|float16 [nnz]."""
 
     def __init__(self, indptr, indices, weights, ncols, similarity=False, row0=0):
         self.indptr, self.indices, self.weights = indptr, indices, weights
@@ -30,10 +33,13 @@ class CSRGraph:
 
     def host(self):
         """(indptr, indices int64, weights) as numpy, weights in the reference's dtype:
-        int64 Hamming distances, or float32 similarities 1/(1+d) (hamming.py:38)."""
+        int64 Hamming distances, float32 similarities 1/(1+d) (hamming.py:38), or the fp16 Minkowski values as they are
+        (minkowski.py:36-40)."""
         indptr = self.indptr.cpu().numpy()
         idx = self.indices.to(torch.int64).cpu().numpy()
-        if self.similarity:
+        if self.weights.dtype == torch.float16:
+            w = self.weights.cpu().numpy()
+        elif self.similarity:
             w = (1 / (1 + self.weights.to(torch.int64))).cpu().numpy()
         else:
             w = self.weights.to(torch.int64).cpu().numpy()
@@ -52,6 +58,8 @@ class CSRGraph:
     def _w(self, boolean_weights):
         if boolean_weights:
             return None
+        if self.weights.dtype == torch.float16:
+            return self.weights.to(torch.float32)           # Minkowski values: exact in float32
         if self.similarity:
             return (1 / (1 + self.weights.to(torch.int64))).to(torch.float32)
         if self.weights.dtype not in (torch.uint8, torch.float32):
@@ -118,7 +126,8 @@ class CSRGraph:
 
 
 class KNNGraph:
-    """k nearest neighbours: idx int32 (n,k), dist uint8 (n,k); canonical (distance, index) order."""
+    """k nearest neighbours: idx int32 (n,k), dist uint8|int16 (n,k) or fp16 Minkowski values; canonical (distance, index)
+    order (descending values for Minkowski similarities)."""
 
     def __init__(self, idx, dist, ncols, similarity=False, row0=0):
         self.idx, self.dist = idx, dist
@@ -131,6 +140,8 @@ class KNNGraph:
     def host(self):
         kk = min(self.idx.shape[1], max(self.ncols - 1, 0))    # ranks beyond N-1 do not exist ([:,1:k+1])
         idx = self.idx[:, :kk].to(torch.int64).cpu().numpy()
+        if self.dist.dtype == torch.float16:
+            return idx, self.dist[:, :kk].cpu().numpy()
         d = self.dist[:, :kk].to(torch.int64)
         w = (1 / (1 + d)).cpu().numpy() if self.similarity else d.cpu().numpy()
         return idx, w

@@ -466,17 +466,10 @@ class Prograph:
                 idxs = np.asarray(idxs)
                 if idxs.dtype == bool:
                     idxs = np.nonzero(idxs)[0]
+        g = None
         if distance is minkowski and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
-            if output == "csr":
-                raise NotImplementedError("output='csr' (device-resident graphs) exists for the Hamming path only; "
-                                          "Minkowski graphs are returned as the reference's tuples")
-            out = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp)
-            if out is not None:
-                if store is not None and idxs is None:
-                    self.graph[store] = out       # (no device graph is kept: the consumers take the column path)
-                    self.csr_graphs.pop(store, None)
-                return out
-        native = distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
+            g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
+        native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:
             try:
@@ -485,14 +478,13 @@ class Prograph:
                 native = False                      # not byte tokens / L > 128: generic torch path
         if native and k and planes.n > _native.MAX_N_KNN:
             native = False
-        g = None
-        if not native and distance is hamming and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
+        if g is None and not native and distance is hamming and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
             g = self._build_graph_long(idxs, eps, k, similarity, representation, comp)
         if not native and g is None:
             return self._build_graph_generic(idxs, batch_size, eps, k, similarity, representation, distance, comp)
 
         if g is not None:
-            pass                                    # sequences beyond one record of the fused engines: built above
+            pass                                    # Minkowski embeddings, or sequences beyond one record: built above
         elif eps:
             # similarity: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the mirrored integer test on d
             # (:720-721, :734); both sides are the same correctly rounded float32 quotient when d == eps
@@ -583,14 +575,15 @@ class Prograph:
         return CSRGraph(torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts]), n,
                         similarity=similarity)
 
-    def _build_graph_minkowski(self, idxs, eps, k, similarity, representation, comp):
+    def _build_graph_minkowski(self, idxs, eps, k, similarity, representation, comp, cap=256):
         """
         `build_graph(representation=<embedding>, distance=minkowski)` on the HIP kernels:
-        the fp16 staging of the reference (:726), then per block of rows the fp16 distance matrix
-        (`pg_minkowski_dense`, rounding like the reference's fp16 tensor ops) and the selection on the
-        device - the canonical (value, column) ranks 1..k (`pg_f16_knn`; the reference drops sorted rank
-        0, :761-763) or the thresholded CSR (`pg_f16_eps_*`; :734-739).  Returns None when the
-        representation is not a numeric matrix (the generic path then reports as the reference would).
+        the fp16 staging of the reference (:726), then the fused sweeps that compute the fp16 distances
+        (rounding like the reference's fp16 tensor ops) and select from them on the device - the canonical
+        (value, column) ranks 1..k (`pg_minkowski_knn`; the reference drops sorted rank 0, :761-763) or the
+        thresholded CSR (`pg_minkowski_eps_*`; :734-739) - without an (N, N) block in HBM.  Returns a KNNGraph /
+        CSRGraph with fp16 weights, or None when the staged embedding is not a non-empty 2-D fp16 device tensor
+        (the generic path then reports as the reference would).
         """
         try:
             mat = np.vstack(self(representation))
@@ -605,25 +598,15 @@ class Prograph:
         if similarity and eps:
             eps = 1 / (1 + eps)                                          # :720-721
         xp = _native.pack_f16(X)
-        rows_per_block = max(64, min(n, (1 << 27) // max(n, 1)))          # <= 256 MB of fp16 distances at a time
-        out = []
-        empty = (np.array([], dtype=int), np.array([], dtype=int))
-        for r0 in range(0, n, rows_per_block):
-            yp = _native.pack_f16(X[r0:r0 + rows_per_block])
-            block = _native.minkowski_dense(xp, yp, similarity=similarity)
-            if k:
-                kk = min(k, n - 1)
-                idx, w = _native.f16_knn(block, kk, first=1, descending=similarity) if kk else (None, None)
-                if kk:
-                    idx, w = idx.to(torch.int64).cpu().numpy(), w.cpu().numpy()
-                    out.extend(zip(list(idx), list(w)))
-                else:
-                    out.extend((np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float16)) for _ in range(block.shape[0]))
-            else:
-                indptr, indices, wts = _native.f16_eps(block, _CMP_CODE[comp], eps, similarity=similarity)
-                ip, ix, ww = indptr.cpu().numpy(), indices.to(torch.int64).cpu().numpy(), wts.cpu().numpy()
-                out.extend((ix[a:b], ww[a:b]) if b > a else empty for a, b in zip(ip[:-1].tolist(), ip[1:].tolist()))
-        return out
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=X.device),
+                                torch.zeros((n, 0), dtype=torch.float16, device=X.device), n, similarity=similarity)
+            idx, w = _native.minkowski_knn(xp, xp, kk, first=1, similarity=similarity)
+            return KNNGraph(idx, w, n, similarity=similarity)
+        indptr, indices, wts = _native.minkowski_eps(xp, xp, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
         """
