@@ -372,6 +372,50 @@ int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, 
                                int64_t n_list, const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream);
 
 /*
+ * Cosine graphs of fp16 embeddings on the matrix cores: `build_graph(representation="Embedded",
+ * distance=cosine)`.  The reference exports `cosine` without implementing it; the arithmetic is this library's
+ * contract (prograph_amd/csrc/pg_cos.hip).  Operands are pg_pack_f16 buffers (x_npad a multiple
+ * of 256, y_npad >= m) plus their pg_cosine_prep norms; p, nx and ny are fp32 sums of exact fp16 products from
+ * one v_mfma_f32_32x32x16_f16 tile routine in a fixed K order, and
+ *   d = 1 if nx == 0 or ny == 0;  else 0 if p == nx == ny bitwise;  else clamp(1 - (p*ry)*rx, 0, 2)  (fp32 steps),
+ *   similarity != 0: s = 1/(1+d);  r = 1/sqrt(n), correctly rounded.
+ *   pg_cosine_prep         norms / rnorms fp32 [npad] = n and 1/sqrt(n) of every vector of a packed buffer (n = 0
+ *                          past the end); flags uint32[1] set to 1 when one of the first n vectors holds an inf or
+ *                          nan (the caller must not use the distances then)
+ *   pg_cosine_dense        out[m*ldo + n] = fp32 distance (similarity != 0: 1/(1+d)) of Y[m] and X[n]
+ *   pg_cosine_knn          ranks first..first+k-1 of every Y row's (value, column) order over the n X vectors of
+ *                          that block, descending values when similarity != 0, ties by ascending column;
+ *                          first + k <= 64; missing ranks idx -1, weight 0.  idx_out int32 [m*k], w_out fp32 [m*k]
+ *   pg_cosine_eps_slots    comp(d, eps) & (d > 0)  [similarities: comp(eps, s) & (s < 1)], eps an fp32 value, in
+ *                          ONE sweep: counts[r] = exact number of matches of row r, its first `cap` matching columns
+ *                          (ascending) and values in slot_idx / slot_w [r*cap ...]  (int32 / fp32 [m*cap])
+ *   pg_cosine_eps_compact  after pg_exclusive_scan(counts) -> indptr: rows with counts <= cap copied from their slot
+ *                          into indices / weights at indptr[r]; rows beyond cap are left alone
+ *   pg_cosine_eps_fill_rows  the sweep again for the n_list rows of row_list (int64, e.g. the rows with counts > cap
+ *                          from pg_compact_flags), every match written at indptr[row] in ascending column order.
+ *                          Together: the CSR of thresholding pg_cosine_dense, with one host sync (nnz)
+ * The dense and the fused kernels share the tile routine and the epilogue: their results are equal bit for bit.
+ */
+int pg_cosine_prep(const void *packed, int64_t n, int64_t npad, int d, float *norms, float *rnorms, uint32_t *flags,
+                   void *stream);
+int pg_cosine_dense(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                    const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                    int similarity, float *out, int64_t ldo, void *stream);
+int pg_cosine_knn(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                  const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                  int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream);
+int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                        const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                        int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w, uint32_t *counts,
+                        void *stream);
+int pg_cosine_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const float *slot_w, const uint32_t *counts,
+                          const int64_t *indptr, int32_t *indices, float *weights, void *stream);
+int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                            const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
+                            int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
+                            const int64_t *indptr, int32_t *indices, float *weights, void *stream);
+
+/*
  * Multi-GPU: the path's ONE collective (e).  The N^2 pair space shards row-block
  * wise, one process per GPU; every rank needs the whole token matrix, so the ranks all-gather their
  * row shards once (RCCL over xGMI: 64 MB at N = 1M, L = 64) and never talk again.  The reference has

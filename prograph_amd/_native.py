@@ -33,6 +33,8 @@ SYMBOLS = [
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_eps_count", "pg_f16_eps_fill",
     "pg_minkowski_knn", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact", "pg_minkowski_eps_fill_rows",
+    "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_eps_slots", "pg_cosine_eps_compact",
+    "pg_cosine_eps_fill_rows",
 ]
 
 
@@ -119,6 +121,13 @@ def _load():
         lib.pg_minkowski_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_minkowski_eps_fill_rows.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _vp,
                                                    _i64, _vp, _vp, _vp, _vp]
+        _ops = [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32]     # x, y operands of pg_cosine_*
+        lib.pg_cosine_prep.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]
+        lib.pg_cosine_dense.argtypes = _ops + [_vp, _i64, _vp]
+        lib.pg_cosine_knn.argtypes = _ops + [_i32, _i32, _vp, _vp, _vp]
+        lib.pg_cosine_eps_slots.argtypes = _ops + [_i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
+        lib.pg_cosine_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_cosine_eps_fill_rows.argtypes = _ops + [_i32, ctypes.c_float, _vp, _i64, _vp, _vp, _vp, _vp]
         lib.pg_comm_unique_id.argtypes = [_vp]
         lib.pg_comm_init.argtypes = [ctypes.POINTER(_vp), _i32, _i32, _vp]
         lib.pg_comm_destroy.argtypes = [_vp]
@@ -680,6 +689,135 @@ def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256):
             _check(L.pg_minkowski_eps_fill_rows(_ptr(xp.buf), xp.n, xp.npad, y, m, yp.npad, xp.d, sim, int(cmp), e16, _ptr(rows),
                                                 n_over, _ptr(indptr), _ptr(indices), _ptr(weights), _stream()),
                    "pg_minkowski_eps_fill_rows")
+        del slot_idx, slot_w
+        parts.append((indptr, indices, weights))
+    if len(parts) == 1:
+        return parts[0]
+    base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
+    for indptr, _, _ in parts:
+        ptrs.append(indptr[1:] + base)
+        base += int(indptr[-1].item())
+    return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
+
+
+class CosineOperand:
+    """A PackedF16 with its pg_cosine_prep results: norms / rnorms fp32 [npad] (n and 1/sqrt(n) per vector) and
+    `nonfinite` (a uint32[1] device flag, 1 when some element is inf or nan)."""
+    __slots__ = ("packed", "norms", "rnorms", "flag")
+
+    def __init__(self, packed, norms, rnorms, flag):
+        self.packed, self.norms, self.rnorms, self.flag = packed, norms, rnorms, flag
+
+    @property
+    def n(self):
+        return self.packed.n
+
+    @property
+    def d(self):
+        return self.packed.d
+
+    def nonfinite(self):
+        """Does some element hold an inf or nan?  (reads the flag: a host sync)"""
+        return bool(int(self.flag.item()))
+
+    def rows(self, r0, r1):
+        """(packed ptr, norms ptr, rnorms ptr, m) of vectors [r0, r1): the _f16_rows offset on all three arrays."""
+        y, m = _f16_rows(self.packed, r0, r1)
+        return y, ctypes.c_void_p(self.norms.data_ptr() + 4 * r0), ctypes.c_void_p(self.rnorms.data_ptr() + 4 * r0), m
+
+
+def cosine_prep(x):
+    """(N, D) fp16 device tensor (or a PackedF16) -> CosineOperand: the packed vectors, their fp32 norms and
+    reciprocal roots from the cosine tile routine (pg_cosine_prep), and the non-finite flag."""
+    xp = x if isinstance(x, PackedF16) else pack_f16(x)
+    dev = xp.buf.device
+    norms = torch.empty(xp.npad, dtype=torch.float32, device=dev)
+    rnorms = torch.empty(xp.npad, dtype=torch.float32, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(lib().pg_cosine_prep(_ptr(xp.buf), xp.n, xp.npad, xp.d, _ptr(norms), _ptr(rnorms), _ptr(flag), _stream()),
+           "pg_cosine_prep")
+    return CosineOperand(xp, norms, rnorms, flag)
+
+
+def _cos_ops(xc, y, yn, yr, m, ynpad):
+    if xc is None:
+        raise TypeError("cosine operands come from cosine_prep")
+    xp = xc.packed
+    return [_ptr(xp.buf), _ptr(xc.norms), _ptr(xc.rnorms), xp.n, xp.npad, y, yn, yr, m, ynpad, xp.d]
+
+
+def _cos_same_d(xc, yc):
+    if xc.d != yc.d:
+        raise ValueError("operands must have the same dimension")
+
+
+def cosine_dense(xc, yc, similarity=False):
+    """(M, N) fp32 block: cosine distance (or 1/(1+d)) of every Y vector against every X vector (pg_cosine_dense).
+    Operands from cosine_prep; the caller checks their non-finite flags."""
+    _cos_same_d(xc, yc)
+    dev = xc.packed.buf.device
+    out = torch.empty((yc.n, xc.n), dtype=torch.float32, device=dev)
+    for r0 in range(0, yc.n, 65535 * 32):                            # grid.y limit of one launch
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + 65535 * 32))
+        _check(lib().pg_cosine_dense(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, _ptr(out[r0:]),
+                                     out.stride(0), _stream()), "pg_cosine_dense")
+    return out
+
+
+_COS_ROWS = 1 << 20          # Y rows per launch of the fused cosine kernels
+
+
+def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
+    """Ranks first..first+k-1 of every row of cosine_dense(xc, yc, similarity) in (value, column) order - descending
+    for similarities, ties by column - in one fused sweep (pg_cosine_knn), Y rows in blocks.
+    Returns (idx int32 (m, k), w fp32 (m, k)); missing ranks idx -1, weight 0."""
+    _cos_same_d(xc, yc)
+    dev = xc.packed.buf.device
+    idx = torch.empty((yc.n, int(k)), dtype=torch.int32, device=dev)
+    w = torch.empty((yc.n, int(k)), dtype=torch.float32, device=dev)
+    for r0 in range(0, yc.n, rows_per_block):
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
+        _check(lib().pg_cosine_knn(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k), int(first),
+                                   _ptr(idx[r0:]), _ptr(w[r0:]), _stream()), "pg_cosine_knn")
+    return idx, w
+
+
+def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256):
+    """CSR of the entries of cosine_dense(xc, yc, similarity) with comp(d, eps) & (d > 0)  [comp(eps, s) & (s < 1)],
+    `eps` rounded to fp32 first (as torch does when an fp32 tensor meets a Python number).  The minkowski_eps
+    structure: one sweep into per-row slots with exact counts, scan, compaction, and a second sweep over the rows
+    with more than `cap` matches; one host sync per block of rows.
+    Returns (indptr int64 [m+1], indices int32 [nnz], weights fp32 [nnz])."""
+    _cos_same_d(xc, yc)
+    L = lib()
+    dev = xc.packed.buf.device
+    cap = max(1, int(cap))
+    e32 = float(np.float32(eps))
+    sim = 1 if similarity else 0
+    rows_per_block = max(64, (256 << 20) // (cap * 8))                # int32 + fp32 per slot
+    parts = []
+    for r0 in range(0, yc.n, rows_per_block):
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
+        ops = _cos_ops(xc, y, yn, yr, m, yc.packed.npad)
+        counts = torch.empty(m, dtype=torch.int32, device=dev)
+        slot_idx = torch.empty(m * cap, dtype=torch.int32, device=dev)
+        slot_w = torch.empty(m * cap, dtype=torch.float32, device=dev)
+        _check(L.pg_cosine_eps_slots(*ops, sim, int(cmp), e32, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _stream()),
+               "pg_cosine_eps_slots")
+        indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
+        _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+        over = counts > cap
+        nnz, n_over = (int(v) for v in torch.stack([indptr[-1], over.sum()]).cpu())     # the one sync
+        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+        weights = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)[:nnz]
+        if nnz:
+            _check(L.pg_cosine_eps_compact(m, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(indptr), _ptr(indices),
+                                           _ptr(weights), _stream()), "pg_cosine_eps_compact")
+        if n_over:
+            rows = compact_flags(over.to(torch.uint8), count=n_over)
+            _check(L.pg_cosine_eps_fill_rows(*ops, sim, int(cmp), e32, _ptr(rows), n_over, _ptr(indptr), _ptr(indices),
+                                             _ptr(weights), _stream()), "pg_cosine_eps_fill_rows")
         del slot_idx, slot_w
         parts.append((indptr, indices, weights))
     if len(parts) == 1:

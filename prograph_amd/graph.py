@@ -8,7 +8,8 @@ no per-row Python objects) and materialise the reference's tuples only on reques
 zero-copy views into two host arrays.
 
 Weights are Hamming distances (uint8 / int16 / float32; similarities are formed on the host) or fp16 Minkowski values
-(distances or similarities as the kernels computed them: those are final and pass through unchanged).
+(distances or similarities as the kernels computed them: those are final and pass through unchanged).  `final=True`
+marks weights of any dtype as final values in the same way - the fp32 cosine distances or similarities.
 """
 import numpy as np
 import torch
@@ -17,11 +18,16 @@ from . import _native
 
 
 class CSRGraph:
-    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|float32|float16 [nnz]."""
+    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|float32|float16 [nnz].
+    final=True: the weights are final values (not Hamming distances) whatever their dtype."""
 
-    def __init__(self, indptr, indices, weights, ncols, similarity=False, row0=0):
+    def __init__(self, indptr, indices, weights, ncols, similarity=False, row0=0, final=False):
         self.indptr, self.indices, self.weights = indptr, indices, weights
         self.ncols, self.similarity, self.row0 = int(ncols), bool(similarity), int(row0)
+        self.final = bool(final)
+
+    def _passes_through(self):
+        return self.final or self.weights.dtype == torch.float16
 
     @property
     def nrows(self):
@@ -37,7 +43,7 @@ class CSRGraph:
         (minkowski.py:36-40)."""
         indptr = self.indptr.cpu().numpy()
         idx = self.indices.to(torch.int64).cpu().numpy()
-        if self.weights.dtype == torch.float16:
+        if self._passes_through():
             w = self.weights.cpu().numpy()
         elif self.similarity:
             w = (1 / (1 + self.weights.to(torch.int64))).cpu().numpy()
@@ -58,8 +64,8 @@ class CSRGraph:
     def _w(self, boolean_weights):
         if boolean_weights:
             return None
-        if self.weights.dtype == torch.float16:
-            return self.weights.to(torch.float32)           # Minkowski values: exact in float32
+        if self._passes_through():
+            return self.weights.to(torch.float32)           # final values (Minkowski fp16: exact in float32)
         if self.similarity:
             return (1 / (1 + self.weights.to(torch.int64))).to(torch.float32)
         if self.weights.dtype not in (torch.uint8, torch.float32):
@@ -127,11 +133,13 @@ class CSRGraph:
 
 class KNNGraph:
     """k nearest neighbours: idx int32 (n,k), dist uint8|int16 (n,k) or fp16 Minkowski values; canonical (distance, index)
-    order (descending values for Minkowski similarities)."""
+    order (descending values for Minkowski similarities).  final=True: the values are final (cosine fp32) whatever
+    their dtype."""
 
-    def __init__(self, idx, dist, ncols, similarity=False, row0=0):
+    def __init__(self, idx, dist, ncols, similarity=False, row0=0, final=False):
         self.idx, self.dist = idx, dist
         self.ncols, self.similarity, self.row0 = int(ncols), bool(similarity), int(row0)
+        self.final = bool(final)
 
     @property
     def nrows(self):
@@ -140,7 +148,7 @@ class KNNGraph:
     def host(self):
         kk = min(self.idx.shape[1], max(self.ncols - 1, 0))    # ranks beyond N-1 do not exist ([:,1:k+1])
         idx = self.idx[:, :kk].to(torch.int64).cpu().numpy()
-        if self.dist.dtype == torch.float16:
+        if self.final or self.dist.dtype == torch.float16:
             return idx, self.dist[:, :kk].cpu().numpy()
         d = self.dist[:, :kk].to(torch.int64)
         w = (1 / (1 + d)).cpu().numpy() if self.similarity else d.cpu().numpy()
@@ -157,7 +165,7 @@ class KNNGraph:
         indptr = torch.arange(0, n * kk + 1, kk, dtype=torch.int64, device=self.idx.device) if kk else \
             torch.zeros(n + 1, dtype=torch.int64, device=self.idx.device)
         return CSRGraph(indptr, self.idx[:, :kk].reshape(-1).contiguous(), self.dist[:, :kk].reshape(-1).contiguous(),
-                        self.ncols, similarity=self.similarity, row0=self.row0)
+                        self.ncols, similarity=self.similarity, row0=self.row0, final=self.final)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -180,7 +188,7 @@ def fingerprint(tokens):
 
 def save_graphs(path, graphs, tokens_fingerprint=None):
     """{name: CSRGraph | KNNGraph} -> one .npz (arrays `<name>/indptr|indices|weights` or `<name>/idx|dist`
-    plus a small meta vector [kind, ncols, similarity, row0]); `__fingerprint__` = fingerprint of the token matrix."""
+    plus a small meta vector [kind, ncols, similarity, row0, final]); `__fingerprint__` = fingerprint of the token matrix."""
     out = {}
     if tokens_fingerprint is not None:
         out["__fingerprint__"] = np.array([tokens_fingerprint], dtype=np.uint64)
@@ -188,12 +196,12 @@ def save_graphs(path, graphs, tokens_fingerprint=None):
         if isinstance(g, KNNGraph):
             out[f"{name}/idx"] = g.idx.cpu().numpy()
             out[f"{name}/dist"] = g.dist.cpu().numpy()
-            out[f"{name}/meta"] = np.array([1, g.ncols, int(g.similarity), g.row0], dtype=np.int64)
+            out[f"{name}/meta"] = np.array([1, g.ncols, int(g.similarity), g.row0, int(g.final)], dtype=np.int64)
         else:
             out[f"{name}/indptr"] = g.indptr.cpu().numpy()
             out[f"{name}/indices"] = g.indices.cpu().numpy()
             out[f"{name}/weights"] = g.weights.cpu().numpy()
-            out[f"{name}/meta"] = np.array([0, g.ncols, int(g.similarity), g.row0], dtype=np.int64)
+            out[f"{name}/meta"] = np.array([0, g.ncols, int(g.similarity), g.row0, int(g.final)], dtype=np.int64)
     np.savez(path, **out)
 
 
@@ -212,7 +220,11 @@ def load_graphs(path, device=None, tokens_fingerprint=None):
         if not key.endswith("/meta"):
             continue
         name = key[:-5]
-        kind, ncols, sim, row0 = (int(v) for v in z[key])
+        meta = [int(v) for v in z[key]]
+        if len(meta) not in (4, 5):
+            continue
+        kind, ncols, sim, row0 = meta[:4]
+        final = bool(meta[4]) if len(meta) == 5 else False           # side-cars written before `final` have 4 entries
         if kind == 1:
             idx = z[f"{name}/idx"]
             if idx.ndim != 2 or z[f"{name}/dist"].shape != idx.shape or (idx.size and (idx.min() < -1 or idx.max() >= ncols)):
@@ -224,7 +236,8 @@ def load_graphs(path, device=None, tokens_fingerprint=None):
                 continue
         t = lambda a: torch.from_numpy(np.ascontiguousarray(z[f"{name}/{a}"])).to(device)
         if kind == 1:
-            graphs[name] = KNNGraph(t("idx"), t("dist"), ncols, similarity=bool(sim), row0=row0)
+            graphs[name] = KNNGraph(t("idx"), t("dist"), ncols, similarity=bool(sim), row0=row0, final=final)
         else:
-            graphs[name] = CSRGraph(t("indptr"), t("indices"), t("weights"), ncols, similarity=bool(sim), row0=row0)
+            graphs[name] = CSRGraph(t("indptr"), t("indices"), t("weights"), ncols, similarity=bool(sim), row0=row0,
+                                    final=final)
     return graphs

@@ -33,7 +33,7 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import hamming, minkowski
+from .distance import cosine, hamming, minkowski
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
@@ -469,6 +469,8 @@ class Prograph:
         g = None
         if distance is minkowski and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
             g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
+        if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
+            g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:
@@ -484,7 +486,7 @@ class Prograph:
             return self._build_graph_generic(idxs, batch_size, eps, k, similarity, representation, distance, comp)
 
         if g is not None:
-            pass                                    # Minkowski embeddings, or sequences beyond one record: built above
+            pass                                    # Minkowski / cosine embeddings, or sequences beyond one record: built above
         elif eps:
             # similarity: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the mirrored integer test on d
             # (:720-721, :734); both sides are the same correctly rounded float32 quotient when d == eps
@@ -607,6 +609,40 @@ class Prograph:
             return KNNGraph(idx, w, n, similarity=similarity)
         indptr, indices, wts = _native.minkowski_eps(xp, xp, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
+    def _build_graph_cosine(self, idxs, eps, k, similarity, representation, comp, cap=256):
+        """
+        `build_graph(representation=<embedding>, distance=cosine)` on the matrix-core kernels: the fp16 staging
+        (:726), norms and the non-finite check (`pg_cosine_prep`), then the fused sweeps that compute the fp32
+        cosine values and select from them on the device - the (value, column) ranks 1..k (`pg_cosine_knn`; rank
+        0 dropped as in :761-763) or the thresholded CSR (`pg_cosine_eps_*`; :734-739).  Returns a KNNGraph /
+        CSRGraph with final fp32 weights, or None (the generic path then) when the staged embedding is not a
+        non-empty 2-D fp16 device tensor or holds an inf or nan.
+        """
+        try:
+            mat = np.vstack(self(representation))
+            X = torch.as_tensor(mat, dtype=torch.float16, device=_native.device())
+        except (ValueError, TypeError):
+            return None
+        if X.dim() != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not X.is_cuda:
+            return None
+        if idxs is not None:
+            X = X[torch.as_tensor(np.asarray(idxs), device=X.device)]
+        n = X.shape[0]
+        xc = _native.cosine_prep(X)
+        if xc.nonfinite():
+            return None
+        if similarity and eps:
+            eps = 1 / (1 + eps)                                          # :720-721
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=X.device),
+                                torch.zeros((n, 0), dtype=torch.float32, device=X.device), n, similarity=similarity, final=True)
+            idx, w = _native.cosine_knn(xc, xc, kk, first=1, similarity=similarity)
+            return KNNGraph(idx, w, n, similarity=similarity, final=True)
+        indptr, indices, wts = _native.cosine_eps(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
         """
