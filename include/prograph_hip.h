@@ -326,6 +326,7 @@ int pg_compact_flags(const uint8_t *flags, int64_t n, int64_t *out_idx, int64_t 
  *   pg_minkowski_dense   out[m*ldo + n] = fp16 distance (similarity != 0: 1/(1+d)) of Y[m] and X[n]
  *   pg_f16_knn           ranks first..first+k-1 of every row of such a block in (value, column) order
  *                        (descending != 0: largest first, the similarity sort of :758); first + k <= 64
+ *                        (more ranks: pg_f16_knn_round below)
  *   pg_f16_eps_count/_fill  comp(d, eps) & (d > 0)  [similarities: comp(eps, s) & (s < 1)], eps_f16 = the
  *                        threshold rounded to fp16 as torch does when it compares an fp16 tensor with a
  *                        Python number; count -> pg_exclusive_scan -> fill (columns ascending, fp16 weights)
@@ -337,6 +338,18 @@ int pg_minkowski_dense(const void *x_packed, int64_t n, int64_t x_npad, const vo
                        int64_t y_npad, int d, int similarity, void *out_f16, int64_t ldo, void *stream);
 int pg_f16_knn(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, int first, int descending,
                int32_t *idx_out, void *w_out_f16, void *stream);
+/*
+ * pg_f16_knn_round — kNN beyond 63 neighbours on such a block, the pg_knn_hamming_round scheme: round 1 is pg_f16_knn
+ * with first = 1, k = 63; every later round writes the next k (1..64) ranks of each row's (value, column) order,
+ * i.e. the k smallest pairs strictly AFTER the row's floor: key > fk || (key == fk && column > fc).  The floor of row
+ * r is the previous round's last output entry, read at floor_idx[r*floor_ld] / floor_w_f16[r*floor_ld] (its fp16
+ * bits give the key back exactly, so no key array is needed; point both into the previous round's last column).
+ * A floor index of -1 marks an exhausted row: the round writes idx -1, weight 0 for it, as for ranks that do not
+ * exist.  Output rows are ldo elements apart (ldo >= k), so rounds write straight into column slices of one result.
+ */
+int pg_f16_knn_round(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, int descending,
+                     const int32_t *floor_idx, const void *floor_w_f16, int64_t floor_ld, int32_t *idx_out,
+                     void *w_out_f16, int64_t ldo, void *stream);
 int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                      uint32_t *counts, void *stream);
 int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
@@ -350,7 +363,8 @@ int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int 
  * pg_minkowski_dense (pg_pack_f16 buffers; x_npad a multiple of 256, y_npad >= m).
  *   pg_minkowski_knn       result of pg_f16_knn(pg_minkowski_dense(...)): ranks first..first+k-1 of every Y row's
  *                          (value, column) order over the n X vectors, descending values when similarity != 0;
- *                          first + k <= 64; missing ranks idx -1, weight 0.  idx_out int32 [m*k], w_out fp16 [m*k]
+ *                          first + k <= 64 (more ranks: pg_minkowski_knn_round); missing ranks idx -1, weight 0.
+ *                          idx_out int32 [m*k], w_out fp16 [m*k]
  *   pg_minkowski_eps_slots the epsilon test of pg_f16_eps_* (eps_f16 rounded as there) in ONE distance sweep:
  *                          counts[r] = exact number of matches of row r, its first `cap` matching columns
  *                          (ascending) and fp16 values in slot_idx / slot_w [r*cap ...]  (int32 / fp16 [m*cap])
@@ -362,6 +376,16 @@ int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int 
  */
 int pg_minkowski_knn(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
                      int d, int similarity, int k, int first, int32_t *idx_out, void *w_out_f16, void *stream);
+/*
+ * pg_minkowski_knn_round — pg_minkowski_knn beyond 63 neighbours: one more fused sweep per round writes the next k
+ * (1..64) ranks of every Y row, the pairs strictly after the row's floor in (value, column) order.  Round 1 is
+ * pg_minkowski_knn with first = 1, k = 63.  Floors, exhausted rows (-1) and the output stride ldo exactly as in
+ * pg_f16_knn_round: the floor is the previous round's last fp16 weight and index, read with row stride floor_ld.
+ */
+int pg_minkowski_knn_round(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m,
+                           int64_t y_npad, int d, int similarity, int k, const int32_t *floor_idx,
+                           const void *floor_w_f16, int64_t floor_ld, int32_t *idx_out, void *w_out_f16, int64_t ldo,
+                           void *stream);
 int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m,
                            int64_t y_npad, int d, int similarity, int cmp, float eps_f16, int cap, int32_t *slot_idx,
                            void *slot_w_f16, uint32_t *counts, void *stream);
@@ -385,7 +409,8 @@ int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, 
  *   pg_cosine_dense        out[m*ldo + n] = fp32 distance (similarity != 0: 1/(1+d)) of Y[m] and X[n]
  *   pg_cosine_knn          ranks first..first+k-1 of every Y row's (value, column) order over the n X vectors of
  *                          that block, descending values when similarity != 0, ties by ascending column;
- *                          first + k <= 64; missing ranks idx -1, weight 0.  idx_out int32 [m*k], w_out fp32 [m*k]
+ *                          first + k <= 64 (more ranks: pg_cosine_knn_round); missing ranks idx -1, weight 0.
+ *                          idx_out int32 [m*k], w_out fp32 [m*k]
  *   pg_cosine_eps_slots    comp(d, eps) & (d > 0)  [similarities: comp(eps, s) & (s < 1)], eps an fp32 value, in
  *                          ONE sweep: counts[r] = exact number of matches of row r, its first `cap` matching columns
  *                          (ascending) and values in slot_idx / slot_w [r*cap ...]  (int32 / fp32 [m*cap])
@@ -404,6 +429,17 @@ int pg_cosine_dense(const void *x_packed, const float *x_norms, const float *x_r
 int pg_cosine_knn(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
                   const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
                   int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream);
+/*
+ * pg_cosine_knn_round — pg_cosine_knn beyond 63 neighbours, as pg_minkowski_knn_round: one more fused sweep per
+ * round writes the next k (1..64) ranks of every Y row after its floor.  The floor is the previous round's last
+ * fp32 weight and index (floor_w / floor_idx, row stride floor_ld): fp32 values pass through unchanged, so the
+ * weight gives the key back exactly.  Exhausted rows (floor index -1) and the output stride ldo as in
+ * pg_f16_knn_round.
+ */
+int pg_cosine_knn_round(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                        const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                        int similarity, int k, const int32_t *floor_idx, const float *floor_w, int64_t floor_ld,
+                        int32_t *idx_out, float *w_out, int64_t ldo, void *stream);
 int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
                         const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
                         int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w, uint32_t *counts,

@@ -31,10 +31,10 @@ SYMBOLS = [
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
-    "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_eps_count", "pg_f16_eps_fill",
-    "pg_minkowski_knn", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact", "pg_minkowski_eps_fill_rows",
-    "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_eps_slots", "pg_cosine_eps_compact",
-    "pg_cosine_eps_fill_rows",
+    "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
+    "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
+    "pg_minkowski_eps_fill_rows", "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_knn_round",
+    "pg_cosine_eps_slots", "pg_cosine_eps_compact", "pg_cosine_eps_fill_rows",
 ]
 
 
@@ -113,9 +113,12 @@ def _load():
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
         lib.pg_f16_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
+        lib.pg_f16_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_f16_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _vp]
         lib.pg_f16_eps_fill.argtypes = [_vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
         lib.pg_minkowski_knn.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]
+        lib.pg_minkowski_knn_round.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp,
+                                               _i64, _vp]
         lib.pg_minkowski_eps_slots.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _i32,
                                                _vp, _vp, _vp, _vp]
         lib.pg_minkowski_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -125,6 +128,7 @@ def _load():
         lib.pg_cosine_prep.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]
         lib.pg_cosine_dense.argtypes = _ops + [_vp, _i64, _vp]
         lib.pg_cosine_knn.argtypes = _ops + [_i32, _i32, _vp, _vp, _vp]
+        lib.pg_cosine_knn_round.argtypes = _ops + [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_cosine_eps_slots.argtypes = _ops + [_i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
         lib.pg_cosine_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_cosine_eps_fill_rows.argtypes = _ops + [_i32, ctypes.c_float, _vp, _i64, _vp, _vp, _vp, _vp]
@@ -601,8 +605,40 @@ def minkowski_dense(xp, yp, similarity=False):
     return out
 
 
+def knn_rounds(m, k, first, wdtype, dev, head, step):
+    """Ranks first..first+k-1 (first + k > 64, k <= MAX_K_ROUNDS) of the pg_*_knn_round scheme -> (idx int32 (m, k),
+    w (m, k) of wdtype).  head(kk) is the floor-free call for ranks first..63 (kk = 64 - first); then
+    step(kk, floor_idx, floor_w, idx_out, w_out) writes the next kk <= 64 ranks after each row's floor - the
+    previous round's last column - straight into the column slice idx_out / w_out of the result."""
+    if not 64 - first < k <= MAX_K_ROUNDS:
+        raise ValueError(f"the rounds produce {65 - first}..{MAX_K_ROUNDS} ranks per row, not {k}")
+    idx = torch.empty((m, k), dtype=torch.int32, device=dev)
+    w = torch.empty((m, k), dtype=wdtype, device=dev)
+    done = 64 - first
+    idx[:, :done], w[:, :done] = head(done)
+    while done < k:
+        kk = min(64, k - done)
+        step(kk, idx[:, done - 1], w[:, done - 1], idx[:, done:done + kk], w[:, done:done + kk])
+        done += kk
+    return idx, w
+
+
+def f16_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):
+    """One round of pg_f16_knn_round: the next k <= 64 ranks of every row of an fp16 block after its floor
+    (floor_idx / floor_w: (m,) views of the previous round's last column) into the (m, k) views idx_out / w_out."""
+    m, n = block.shape
+    _check(lib().pg_f16_knn_round(_ptr(block), m, n, block.stride(0), int(k), 1 if descending else 0, _ptr(floor_idx),
+                                  _ptr(floor_w), floor_idx.stride(0), _ptr(idx_out), _ptr(w_out), idx_out.stride(0),
+                                  _stream()), "pg_f16_knn_round")
+
+
 def f16_knn(block, k, first=1, descending=False):
-    """Ranks first..first+k-1 of every row of an fp16 block in (value, column) order -> (idx int32, w fp16)."""
+    """Ranks first..first+k-1 of every row of an fp16 block in (value, column) order -> (idx int32, w fp16).
+    first + k > 64 (k <= MAX_K_ROUNDS): in rounds of 64 ranks over the same block (knn_rounds)."""
+    if first + k > 64:
+        return knn_rounds(block.shape[0], int(k), int(first), torch.float16, block.device,
+                          lambda kk: f16_knn(block, kk, first, descending),
+                          lambda kk, fi, fw, oi, ow: f16_knn_round(block, kk, fi, fw, oi, ow, descending))
     m, n = block.shape
     idx = torch.empty((m, k), dtype=torch.int32, device=block.device)
     w = torch.empty((m, k), dtype=torch.float16, device=block.device)
@@ -639,11 +675,24 @@ def _f16_rows(yp, r0, r1):
     return ctypes.c_void_p(yp.buf.data_ptr() + 16 * r0), r1 - r0
 
 
+def minkowski_knn_round(xp, yp, k, floor_idx, floor_w, idx_out, w_out, similarity=False):
+    """One round of pg_minkowski_knn_round: the next k <= 64 ranks of every Y row after its floor, one fused sweep
+    (views as for f16_knn_round)."""
+    _check(lib().pg_minkowski_knn_round(_ptr(xp.buf), xp.n, xp.npad, _ptr(yp.buf), yp.n, yp.npad, xp.d, 1 if similarity else 0,
+                                        int(k), _ptr(floor_idx), _ptr(floor_w), floor_idx.stride(0), _ptr(idx_out), _ptr(w_out),
+                                        idx_out.stride(0), _stream()), "pg_minkowski_knn_round")
+
+
 def minkowski_knn(xp, yp, k, first=1, similarity=False):
     """f16_knn(minkowski_dense(xp, yp, similarity), k, first, descending=similarity) in one fused sweep (pg_minkowski_knn):
-    the distances are selected in LDS and never written out.  Returns (idx int32 (m, k), w fp16 (m, k))."""
+    the distances are selected in LDS and never written out.  Returns (idx int32 (m, k), w fp16 (m, k)).
+    first + k > 64 (k <= MAX_K_ROUNDS): one more sweep per 64 ranks (knn_rounds)."""
     if xp.d != yp.d:
         raise ValueError("operands must have the same dimension")
+    if first + k > 64:
+        return knn_rounds(yp.n, int(k), int(first), torch.float16, xp.buf.device,
+                          lambda kk: minkowski_knn(xp, yp, kk, first, similarity),
+                          lambda kk, fi, fw, oi, ow: minkowski_knn_round(xp, yp, kk, fi, fw, oi, ow, similarity))
     dev = xp.buf.device
     idx = torch.empty((yp.n, int(k)), dtype=torch.int32, device=dev)
     w = torch.empty((yp.n, int(k)), dtype=torch.float16, device=dev)
@@ -767,11 +816,27 @@ def cosine_dense(xc, yc, similarity=False):
 _COS_ROWS = 1 << 20          # Y rows per launch of the fused cosine kernels
 
 
+def cosine_knn_round(xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity=False, rows_per_block=_COS_ROWS):
+    """One round of pg_cosine_knn_round: the next k <= 64 ranks of every Y row after its floor, one fused sweep per
+    block of Y rows (views as for f16_knn_round)."""
+    fld, ldo = floor_idx.stride(0), idx_out.stride(0)
+    for r0 in range(0, yc.n, rows_per_block):
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
+        _check(lib().pg_cosine_knn_round(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k),
+                                         _ptr(floor_idx[r0:]), _ptr(floor_w[r0:]), fld, _ptr(idx_out[r0:]), _ptr(w_out[r0:]),
+                                         ldo, _stream()), "pg_cosine_knn_round")
+
+
 def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
     """Ranks first..first+k-1 of every row of cosine_dense(xc, yc, similarity) in (value, column) order - descending
     for similarities, ties by column - in one fused sweep (pg_cosine_knn), Y rows in blocks.
-    Returns (idx int32 (m, k), w fp32 (m, k)); missing ranks idx -1, weight 0."""
+    Returns (idx int32 (m, k), w fp32 (m, k)); missing ranks idx -1, weight 0.
+    first + k > 64 (k <= MAX_K_ROUNDS): one more sweep per 64 ranks (knn_rounds), in the same row blocks."""
     _cos_same_d(xc, yc)
+    if first + k > 64:
+        return knn_rounds(yc.n, int(k), int(first), torch.float32, xc.packed.buf.device,
+                          lambda kk: cosine_knn(xc, yc, kk, first, similarity, rows_per_block),
+                          lambda kk, fi, fw, oi, ow: cosine_knn_round(xc, yc, kk, fi, fw, oi, ow, similarity, rows_per_block))
     dev = xc.packed.buf.device
     idx = torch.empty((yc.n, int(k)), dtype=torch.int32, device=dev)
     w = torch.empty((yc.n, int(k)), dtype=torch.float32, device=dev)

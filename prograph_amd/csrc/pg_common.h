@@ -240,6 +240,14 @@ __device__ __forceinline__ u32 wave_shr1(u32 v, u32 fill) {
   return (u32)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false);
 }
 
+// ---- the floor of a kNN round (pg_*_knn_round): the (key, column) of the previous round's last entry; only pairs
+// strictly after it are candidates.  An exhausted row (floor index -1) gets the largest pair, so nothing follows it.
+__device__ __forceinline__ void knn_floor(int fidx, u32 fkey, u32 &fk, u32 &fc) {
+  fk = fidx < 0 ? 0xFFFFFFFFu : fkey;
+  fc = fidx < 0 ? 0xFFFFFFFFu : (u32)fidx;
+}
+__device__ __forceinline__ bool knn_after(u32 key, u32 col, u32 fk, u32 fc) { return key > fk || (key == fk && col > fc); }
+
 // ---- filter signature of the MFMA engine (pg_mm.h; written by pg_pack_planes) -------------------------------
 // v_mfma_f32_32x32x64_f8f6f4 with FP4 (E2M1) operands: K = 64 four-bit elements in the 16 bytes a lane holds,
 // at the cycles of the int8 32x32x32 form.  54 of them carry the signature - the plane-0 bits of the sequence,

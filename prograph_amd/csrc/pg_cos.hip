@@ -183,12 +183,17 @@ __device__ __forceinline__ void cs_insert(u32 &lk, u32 &lc, u32 &tk, u32 &tc, u3
   }
 }
 
+// FLOOR (pg_cosine_knn_round, first = 0): only pairs after each row's floor are candidates, rows written ldo elements
+// apart.  The floors sit lane-per-row in one VGPR pair (lane i and i + 32: row slot i, the cs_wave_row order) and are
+// read with readlane, instead of 32 more per-row values next to the lists.
+template <bool FLOOR>
 __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict__ xp, const float *__restrict__ nx,
                                                          const float *__restrict__ rx, long long n, long long xnpad,
                                                          const uint4 *__restrict__ yp, const float *__restrict__ ny,
                                                          const float *__restrict__ ry, long long m, long long ynpad, int nq,
                                                          int similarity, int k, int first, int *__restrict__ idx,
-                                                         float *__restrict__ w) {
+                                                         float *__restrict__ w, const int *__restrict__ floor_idx,
+                                                         const float *__restrict__ floor_w, long long floor_ld, long long ldo) {
   const int lane = threadIdx.x & 63, h = lane >> 5;
   const long long yr = cs_wave_row(lane & 31, m, nullptr, 0);
   if (__builtin_amdgcn_readfirstlane((int)(cs_wave_row(0, m, nullptr, 0) < 0))) return;    // a wave past the end
@@ -203,6 +208,8 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
   u32 lk[CS_T], lc[CS_T], tk[CS_T], tc[CS_T];
 #pragma unroll
   for (int i = 0; i < CS_T; ++i) lk[i] = lc[i] = tk[i] = tc[i] = 0xFFFFFFFFu;
+  u32 fkv = 0, fcv = 0;                                              // lane i: the floor of row slot i & 31
+  if (FLOOR && yr >= 0) knn_floor(floor_idx[yr * floor_ld], cs_key(floor_w[yr * floor_ld], similarity), fkv, fcv);
   for (long long x0 = 0; x0 < n; x0 += CS_T) {
     const long long col = x0 + (lane & 31);
     const bool cok = col < n;
@@ -214,7 +221,12 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
       const int i0 = cs_row(r, 0), i1 = cs_row(r, 1);
       const u32 key = cs_key(cs_finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity), similarity);
       const u32 thk = h ? tk[i1] : tk[i0], thc = h ? tc[i1] : tc[i0];
-      const bool cand = cok && (key < thk || (key == thk && (u32)col < thc));
+      bool cand = cok && (key < thk || (key == thk && (u32)col < thc));
+      if (FLOOR) {
+        const u32 f0k = __builtin_amdgcn_readlane(fkv, i0), f0c = __builtin_amdgcn_readlane(fcv, i0);
+        const u32 f1k = __builtin_amdgcn_readlane(fkv, i1), f1c = __builtin_amdgcn_readlane(fcv, i1);
+        cand = cand && knn_after(key, (u32)col, h ? f1k : f0k, h ? f1c : f0c);
+      }
       const u64 mask = __builtin_amdgcn_ballot_w64(cand);
       if ((u32)mask) cs_insert(lk[i0], lc[i0], tk[i0], tc[i0], (u32)mask, key, 0, x0, last);
       if ((u32)(mask >> 32)) cs_insert(lk[i1], lc[i1], tk[i1], tc[i1], (u32)(mask >> 32), key, 32, x0, last);
@@ -224,7 +236,7 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
   for (int i = 0; i < CS_T; ++i) {
     const long long row = cs_wave_row(i, m, nullptr, 0);
     if (row >= 0 && lane >= first && lane <= last) {
-      const long long o = row * (long long)k + (lane - first);
+      const long long o = row * (FLOOR ? ldo : (long long)k) + (lane - first);
       const bool none = lc[i] == 0xFFFFFFFFu;
       idx[o] = none ? -1 : (int)lc[i];
       w[o] = none ? 0.0f : cs_unkey(lk[i], similarity);
@@ -373,10 +385,26 @@ int pg_cosine_knn(const void *x_packed, const float *x_norms, const float *x_rno
     return cfail(PG_E_BADARG, "pg_cosine_knn: bad argument");
   if (k < 1 || first < 0 || first + k > 64) return cfail(PG_E_BADARG, "pg_cosine_knn: first + k must be at most 64");
   if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return cfail(PG_E_BADARG, "pg_cosine_knn: too many vectors for one launch");
-  pg_cos_knn_kernel<<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+  pg_cos_knn_kernel<false><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, k, first, idx_out, w_out);
+      similarity ? 1 : 0, k, first, idx_out, w_out, nullptr, nullptr, 0, k);
   return claunched("pg_cos_knn_kernel");
+}
+
+int pg_cosine_knn_round(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                        const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                        int similarity, int k, const int32_t *floor_idx, const float *floor_w, int64_t floor_ld,
+                        int32_t *idx_out, float *w_out, int64_t ldo, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out ||
+      !floor_idx || !floor_w || floor_ld < 0 || ldo < k)
+    return cfail(PG_E_BADARG, "pg_cosine_knn_round: bad argument");
+  if (k < 1 || k > 64) return cfail(PG_E_BADARG, "pg_cosine_knn_round: k must be 1..64");
+  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
+    return cfail(PG_E_BADARG, "pg_cosine_knn_round: too many vectors for one launch");
+  pg_cos_knn_kernel<true><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, k, 0, idx_out, w_out, floor_idx, floor_w, floor_ld, ldo);
+  return claunched("pg_cos_knn_kernel(round)");
 }
 
 int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,

@@ -130,10 +130,15 @@ __device__ __forceinline__ u32 mk_key(unsigned short bits, int descending) {
   return descending ? (0xFFFFu - (u32)bits) : (u32)bits;
 }
 
-// ranks first .. first+k-1 of every row's (key, column) order (the stable sort of :758-760), one wave per row
+// ranks first .. first+k-1 of every row's (key, column) order (the stable sort of :758-760), one wave per row.
+// FLOOR (pg_f16_knn_round, first = 0): only pairs after the row's floor (knn_floor) are candidates, and rows are
+// written ldo elements apart; the floor is the previous round's last entry, whose fp16 bits give its key back.
+template <bool FLOOR>
 __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *__restrict__ dist, long long m, long long n,
                                                          long long ld, int k, int first, int descending, int *__restrict__ idx,
-                                                         unsigned short *__restrict__ w) {
+                                                         unsigned short *__restrict__ w, const int *__restrict__ floor_idx,
+                                                         const unsigned short *__restrict__ floor_w, long long floor_ld,
+                                                         long long ldo) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= m) return;
@@ -141,10 +146,13 @@ __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *_
   u32 lk = 0xFFFFFFFFu, lc = 0xFFFFFFFFu;                 // lane j = j-th smallest (key, column)
   const int last = first + k - 1;
   u32 tk = 0xFFFFFFFFu, tc = 0xFFFFFFFFu;                 // current entry of lane `last`
+  u32 fk = 0, fc = 0;
+  if (FLOOR) knn_floor(floor_idx[row * floor_ld], mk_key(floor_w[row * floor_ld], descending), fk, fc);
   for (long long c0 = 0; c0 < n; c0 += 64) {
     const long long c = c0 + lane;
     const u32 key = c < n ? mk_key(d[c], descending) : 0xFFFFFFFFu;
     bool cand = c < n && (key < tk || (key == tk && (u32)c < tc));
+    if (FLOOR) cand = cand && knn_after(key, (u32)c, fk, fc);
     u64 mask = __builtin_amdgcn_ballot_w64(cand);
     while (mask) {
       const int j = __builtin_ctzll(mask);
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *_
     }
   }
   if (lane >= first && lane <= last) {
-    const long long o = row * (long long)k + (lane - first);
+    const long long o = row * (FLOOR ? ldo : (long long)k) + (lane - first);
     idx[o] = lc == 0xFFFFFFFFu ? -1 : (int)lc;
     w[o] = lc == 0xFFFFFFFFu ? 0 : d[lc];
   }
@@ -249,11 +257,15 @@ __device__ __forceinline__ void mk_stage_once(uint4 (*ybuf)[MK_SEG], const uint4
   __syncthreads();
 }
 
-// ranks first .. first+k-1 of every row's (key, column) order over all n columns: pg_f16_knn on the fly
+// ranks first .. first+k-1 of every row's (key, column) order over all n columns: pg_f16_knn on the fly.
+// FLOOR (pg_minkowski_knn_round, first = 0): only pairs after each row's floor, rows written ldo elements apart.
+template <bool FLOOR>
 __global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restrict__ xp, long long n, long long xnpad,
                                                           const uint4 *__restrict__ yp, long long m, long long ynpad, int nq,
                                                           int similarity, int k, int first, int *__restrict__ idx,
-                                                          unsigned short *__restrict__ w) {
+                                                          unsigned short *__restrict__ w, const int *__restrict__ floor_idx,
+                                                          const unsigned short *__restrict__ floor_w, long long floor_ld,
+                                                          long long ldo) {
   __shared__ uint4 ybuf[MK_ROWS][MK_SEG];
   __shared__ unsigned short tile[MK_ROWS][MK_TILE];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -266,6 +278,13 @@ __global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restric
   u32 lk[MK_RPW], lc[MK_RPW], tk[MK_RPW], tc[MK_RPW];      // lane j = j-th smallest (key, column); entry of lane `last`
 #pragma unroll
   for (int j = 0; j < MK_RPW; ++j) lk[j] = lc[j] = tk[j] = tc[j] = 0xFFFFFFFFu;
+  u32 fk[MK_RPW], fc[MK_RPW];                                        // the rows' floors (wave-uniform)
+#pragma unroll
+  for (int j = 0; j < MK_RPW; ++j) {
+    fk[j] = fc[j] = 0;
+    const long long row = r0 + wv * MK_RPW + j;
+    if (FLOOR && row < m) knn_floor(floor_idx[row * floor_ld], mk_key(floor_w[row * floor_ld], similarity), fk[j], fc[j]);
+  }
   for (long long t0 = 0; t0 < n; t0 += MK_TILE) {
     mk_tile(tile, xp, xnpad, t0, yp, ynpad, yrow, nq, ybuf, staged, similarity);
     const int ncol = (int)(n - t0 < MK_TILE ? n - t0 : MK_TILE);
@@ -277,7 +296,8 @@ __global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restric
         const int cc = s0 + lane;
         const u32 key = cc < ncol ? mk_key(tile[r][cc], similarity) : 0xFFFFFFFFu;
         const u32 col = (u32)(t0 + cc);
-        const bool cand = cc < ncol && (key < tk[j] || (key == tk[j] && col < tc[j]));
+        bool cand = cc < ncol && (key < tk[j] || (key == tk[j] && col < tc[j]));
+        if (FLOOR) cand = cand && knn_after(key, col, fk[j], fc[j]);
         u64 mask = __builtin_amdgcn_ballot_w64(cand);
         while (mask) {
           const int b = __builtin_ctzll(mask);
@@ -300,7 +320,7 @@ __global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restric
   for (int j = 0; j < MK_RPW; ++j) {
     const int r = wv * MK_RPW + j;
     if (r < nr && lane >= first && lane <= last) {
-      const long long o = (r0 + r) * (long long)k + (lane - first);
+      const long long o = (r0 + r) * (FLOOR ? ldo : (long long)k) + (lane - first);
       const bool none = lc[j] == 0xFFFFFFFFu;
       idx[o] = none ? -1 : (int)lc[j];
       w[o] = none ? 0 : (unsigned short)(similarity ? 0xFFFFu - lk[j] : lk[j]);    // mk_key inverted
@@ -426,9 +446,22 @@ int pg_f16_knn(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, in
                void *w_out_f16, void *stream) {
   if (!dist_f16 || !idx_out || !w_out_f16 || m <= 0 || n <= 0 || ld < n) return mfail(PG_E_BADARG, "pg_f16_knn: bad argument");
   if (k < 1 || first < 0 || first + k > 64) return mfail(PG_E_BADARG, "pg_f16_knn: first + k must be at most 64");
-  pg_f16_knn_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
-      (const unsigned short *)dist_f16, m, n, ld, k, first, descending ? 1 : 0, idx_out, (unsigned short *)w_out_f16);
+  pg_f16_knn_kernel<false><<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const unsigned short *)dist_f16, m, n, ld, k, first, descending ? 1 : 0, idx_out, (unsigned short *)w_out_f16, nullptr,
+      nullptr, 0, k);
   return mlaunched("pg_f16_knn_kernel");
+}
+
+int pg_f16_knn_round(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, int descending, const int32_t *floor_idx,
+                     const void *floor_w_f16, int64_t floor_ld, int32_t *idx_out, void *w_out_f16, int64_t ldo, void *stream) {
+  if (!dist_f16 || !idx_out || !w_out_f16 || !floor_idx || !floor_w_f16 || m <= 0 || n <= 0 || ld < n || floor_ld < 0 ||
+      ldo < k)
+    return mfail(PG_E_BADARG, "pg_f16_knn_round: bad argument");
+  if (k < 1 || k > 64) return mfail(PG_E_BADARG, "pg_f16_knn_round: k must be 1..64");
+  pg_f16_knn_kernel<true><<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const unsigned short *)dist_f16, m, n, ld, k, 0, descending ? 1 : 0, idx_out, (unsigned short *)w_out_f16, floor_idx,
+      (const unsigned short *)floor_w_f16, floor_ld, ldo);
+  return mlaunched("pg_f16_knn_kernel(round)");
 }
 
 int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
@@ -461,10 +494,25 @@ int pg_minkowski_knn(const void *x_packed, int64_t n, int64_t x_npad, const void
   if (k < 1 || first < 0 || first + k > 64) return mfail(PG_E_BADARG, "pg_minkowski_knn: first + k must be at most 64");
   if (n > 0xFFFFFFFFll - 1 || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
     return mfail(PG_E_BADARG, "pg_minkowski_knn: too many vectors for one launch");
-  pg_mink_knn_kernel<<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
+  pg_mink_knn_kernel<false><<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, k, first,
-      idx_out, (unsigned short *)w_out_f16);
+      idx_out, (unsigned short *)w_out_f16, nullptr, nullptr, 0, k);
   return mlaunched("pg_mink_knn_kernel");
+}
+
+int pg_minkowski_knn_round(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
+                           int d, int similarity, int k, const int32_t *floor_idx, const void *floor_w_f16, int64_t floor_ld,
+                           int32_t *idx_out, void *w_out_f16, int64_t ldo, void *stream) {
+  if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !idx_out || !w_out_f16 || !floor_idx || !floor_w_f16 ||
+      floor_ld < 0 || ldo < k)
+    return mfail(PG_E_BADARG, "pg_minkowski_knn_round: bad argument");
+  if (k < 1 || k > 64) return mfail(PG_E_BADARG, "pg_minkowski_knn_round: k must be 1..64");
+  if (n > 0xFFFFFFFFll - 1 || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
+    return mfail(PG_E_BADARG, "pg_minkowski_knn_round: too many vectors for one launch");
+  pg_mink_knn_kernel<true><<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, k, 0,
+      idx_out, (unsigned short *)w_out_f16, floor_idx, (const unsigned short *)floor_w_f16, floor_ld, ldo);
+  return mlaunched("pg_mink_knn_kernel(round)");
 }
 
 int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,

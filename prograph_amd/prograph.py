@@ -467,9 +467,9 @@ class Prograph:
                 if idxs.dtype == bool:
                     idxs = np.nonzero(idxs)[0]
         g = None
-        if distance is minkowski and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
+        if distance is minkowski and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
-        if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
+        if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
@@ -480,7 +480,7 @@ class Prograph:
                 native = False                      # not byte tokens / L > 128: generic torch path
         if native and k and planes.n > _native.MAX_N_KNN:
             native = False
-        if g is None and not native and distance is hamming and comp in _CMP_CODE and (k is None or k <= _native.MAX_K):
+        if g is None and not native and distance is hamming and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_long(idxs, eps, k, similarity, representation, comp)
         if not native and g is None:
             return self._build_graph_generic(idxs, batch_size, eps, k, similarity, representation, distance, comp)
@@ -519,7 +519,8 @@ class Prograph:
         Per block of rows the distance matrix comes from the dense kernel - the sequence cut into column
         segments of whole records, their distances accumulated in place (`pg_hamming_dense`, fp16 output:
         integers up to 2048 are exact) - and the selection runs on the device as for fp16 embeddings: the
-        canonical (distance, column) ranks 1..k (`pg_f16_knn`; :756-763) or the thresholded CSR
+        canonical (distance, column) ranks 1..k (`pg_f16_knn`, k > 63 in rounds over the same block:
+        `pg_f16_knn_round`; :756-763) or the thresholded CSR
         (`pg_f16_eps_*`; :734-739).  Returns a KNNGraph / CSRGraph with int16 weights, or None when the
         representation is not byte tokens or longer than 2048 positions (the generic batch loop then).
         """
@@ -582,7 +583,8 @@ class Prograph:
         `build_graph(representation=<embedding>, distance=minkowski)` on the HIP kernels:
         the fp16 staging of the reference (:726), then the fused sweeps that compute the fp16 distances
         (rounding like the reference's fp16 tensor ops) and select from them on the device - the canonical
-        (value, column) ranks 1..k (`pg_minkowski_knn`; the reference drops sorted rank 0, :761-763) or the
+        (value, column) ranks 1..k (`pg_minkowski_knn`, k > 63 one more sweep per 64 ranks: `pg_minkowski_knn_round`;
+        the reference drops sorted rank 0, :761-763) or the
         thresholded CSR (`pg_minkowski_eps_*`; :734-739) - without an (N, N) block in HBM.  Returns a KNNGraph /
         CSRGraph with fp16 weights, or None when the staged embedding is not a non-empty 2-D fp16 device tensor
         (the generic path then reports as the reference would).
@@ -614,7 +616,8 @@ class Prograph:
         """
         `build_graph(representation=<embedding>, distance=cosine)` on the matrix-core kernels: the fp16 staging
         (:726), norms and the non-finite check (`pg_cosine_prep`), then the fused sweeps that compute the fp32
-        cosine values and select from them on the device - the (value, column) ranks 1..k (`pg_cosine_knn`; rank
+        cosine values and select from them on the device - the (value, column) ranks 1..k (`pg_cosine_knn`, k > 63 in
+        rounds: `pg_cosine_knn_round`; rank
         0 dropped as in :761-763) or the thresholded CSR (`pg_cosine_eps_*`; :734-739).  Returns a KNNGraph /
         CSRGraph with final fp32 weights, or None (the generic path then) when the staged embedding is not a
         non-empty 2-D fp16 device tensor or holds an inf or nan.
