@@ -241,6 +241,26 @@ int pg_knn_hamming_round(const void *row_planes, int64_t row_npad, int64_t row0,
                          int32_t *idx_out, uint8_t *dist_out, void *workspace, void *stream);
 
 /*
+ * pg_query_knn_hamming — k nearest DATABASE sequences of every QUERY sequence, ranks 0..k-1 of
+ * each query's (distance, column) order (a query equal to a database row has that row first;
+ * ties go to the lower column).  Query and database planes are packed with the same width l and
+ * the same bits; ndb < 2^24 (the column field of the key).  1 <= k <= 64 per call.  floor_keys:
+ * NULL for the first round, else per query the last key of the previous round (last_keys of that
+ * call): only keys greater than it are candidates, so rounds of 64 continue the same order up to
+ * any k.  last_keys (nullable): per query the key (distance << 24 | column) of rank k-1.
+ * Ranks that do not exist get idx = -1, dist = 255 (and last key 0xFFFFFFFF).
+ *   idx_out int32 [nq*k], dist_out uint8 [nq*k]
+ * The database is swept in column pieces (a handful of queries still fills the chip) whose
+ * sorted lists a second kernel merges; workspace holds them: pass workspace_bytes >=
+ * pg_query_workspace_bytes(nq, ndb, k) for the planned piece count.  A smaller workspace gives
+ * fewer pieces (the same result, slower); 0 bytes means one piece.  No host synchronisation.
+ */
+int64_t pg_query_workspace_bytes(int64_t nq, int64_t ndb, int k);
+int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb,
+                         int64_t db_npad, int l, int bits, int k, const uint32_t *floor_keys, uint32_t *last_keys,
+                         int32_t *idx_out, uint8_t *dist_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * pg_index_flags — the fused 1xN pass of `Prograph.indexing` (prograph/prograph.py:
  * 298-325): distance of every sequence to reference row `ref`, a 256-bin histogram of
  * those distances (for the `d in np.unique(d_data)` assertion, :305), and

@@ -35,6 +35,7 @@ SYMBOLS = [
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
     "pg_minkowski_eps_fill_rows", "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_knn_round",
     "pg_cosine_eps_slots", "pg_cosine_eps_compact", "pg_cosine_eps_fill_rows",
+    "pg_query_workspace_bytes", "pg_query_knn_hamming",
 ]
 
 
@@ -101,6 +102,10 @@ def _load():
         lib.pg_knn_hamming.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
         lib.pg_knn_hamming_round.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                              _vp, _vp, _vp]
+        lib.pg_query_workspace_bytes.restype = _i64
+        lib.pg_query_workspace_bytes.argtypes = [_i64, _i64, _i32]
+        lib.pg_query_knn_hamming.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                             _i64, _vp]
         lib.pg_index_flags.argtypes = [_vp, _i64, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_compact_flags.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp]
         lib.pg_csr_row_stats.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -435,6 +440,37 @@ def knn_graph(rp, cp, k, row0=0, nrows=None, out=None):
     _check(lib().pg_knn_hamming(_ptr(rp.buf), rp.npad, row0, nrows, _ptr(cp.buf), cp.npad, cp.n, cp.g * 32,
                                 _bits2(rp, cp), int(k), _ptr(idx), _ptr(dist), _ptr(workspace(nrows, dev)), _stream()),
            "pg_knn_hamming")
+    return idx, dist
+
+
+def query_knn(qp, dp, k):
+    """Ranks 0..k-1 of every query row of `qp` against the database `dp` (pg_query_knn_hamming): (nq, k) int32 indices
+    and uint8 distances in the canonical (distance, column) order, rank 0 kept.  k <= MAX_K_ROUNDS: rounds of 64
+    ranks, each continuing after the previous round's last key.  Ranks that do not exist: -1 / 255."""
+    if not 1 <= int(k) <= MAX_K_ROUNDS:
+        raise ValueError(f"k must be in 1..{MAX_K_ROUNDS}")
+    L = lib()
+    bits = _bits2(qp, dp)
+    dev = dp.buf.device
+    k = int(k)
+    idx = torch.empty((qp.n, k), dtype=torch.int32, device=dev)
+    dist = torch.empty((qp.n, k), dtype=torch.uint8, device=dev)
+    keys = [torch.empty(qp.n, dtype=torch.int32, device=dev) for _ in range(2)] if k > 64 else [None, None]
+    done = 0
+    while done < k:
+        kk = min(64, k - done)
+        ws_bytes = int(L.pg_query_workspace_bytes(qp.n, dp.n, kk))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ri, rd = (idx, dist) if kk == k else (torch.empty((qp.n, kk), dtype=torch.int32, device=dev),
+                                                torch.empty((qp.n, kk), dtype=torch.uint8, device=dev))
+        _check(L.pg_query_knn_hamming(_ptr(qp.buf), qp.n, qp.npad, _ptr(dp.buf), dp.n, dp.npad, dp.g * 32, bits, kk,
+                                      _ptr(keys[0]) if done else None, _ptr(keys[1]), _ptr(ri), _ptr(rd), _ptr(ws),
+                                      ws_bytes, _stream()), "pg_query_knn_hamming")
+        if kk != k:
+            idx[:, done:done + kk] = ri
+            dist[:, done:done + kk] = rd
+        keys = keys[::-1]
+        done += kk
     return idx, dist
 
 

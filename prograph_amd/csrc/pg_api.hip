@@ -1143,6 +1143,123 @@ int pg_knn_hamming_round(const void *row_planes, int64_t row_npad, int64_t row0,
                     first_round ? nullptr : floor_keys, last_keys, idx_out, dist_out, workspace, stream);
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// Queries against a database (pg_query_knn_hamming).  Pieces per query group: enough workgroups to give every CU about
+// eight (a single query against 200 000 sequences: 391 tiles of 128 columns -> about a hundred pieces), at least four
+// tiles per piece (one per wave), and pieces x k within what the merge kernel holds in LDS.  A function of (nq, ndb, k)
+// only, so that pg_query_workspace_bytes and the call agree; the call then bounds it by the workspace it was given.
+// ---------------------------------------------------------------------------------------
+#define PG_QUERY_TARGET_WG 2048
+static int query_pieces(int64_t nq, int64_t ndb, int k) {
+  const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
+  const long long ntiles = (ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  long long p = (PG_QUERY_TARGET_WG + ngrp - 1) / ngrp;
+  const long long byTiles = (ntiles + 3) / 4, byLds = PG_QUERY_MERGE_KEYS / (k > 0 ? k : 1);
+  if (p > byTiles) p = byTiles;
+  if (p > byLds) p = byLds;
+  return (int)(p < 1 ? 1 : p);
+}
+
+// one workgroup per query: its pieces x k keys (sorted lists of k) into LDS with independent loads, the four waves each
+// insert a quarter of them into a 64-lane list (pg_query_knn_kernel's insertion), the four lists merged as there
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_query_merge_kernel(const u32 *partial, int pieces, int k, int *idx,
+                                                                       unsigned char *dist, u32 *lastKeys) {
+  __shared__ u32 keys[PG_QUERY_MERGE_KEYS];
+  __shared__ u32 lists[PG_WG_WAVES][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long q = blockIdx.x;
+  const int n = pieces * k;
+  const u32 *src = partial + q * (long long)n;
+  for (int e = threadIdx.x; e < n; e += PG_WG_THREADS) keys[e] = src[e];
+  __syncthreads();
+  u32 l = 0xFFFFFFFFu, t = 0xFFFFFFFFu;
+  for (int e0 = wv * 64; e0 < n; e0 += PG_WG_WAVES * 64) {
+    const u32 key = e0 + lane < n ? keys[e0 + lane] : 0xFFFFFFFFu;
+    u64 m = __builtin_amdgcn_ballot_w64(key < t);
+    while (m) {
+      const int j = __builtin_ctzll(m);
+      m &= m - 1;
+      const u32 x = (u32)__builtin_amdgcn_readlane((int)key, j);
+      if (x < t) {
+        const u32 prev = wave_shr1(l, 0u);
+        l = (l <= x) ? l : (prev > x ? prev : x);
+        t = (u32)__builtin_amdgcn_readlane((int)l, k - 1);
+      }
+    }
+  }
+  lists[wv][lane] = l;
+  __syncthreads();
+  if (wv != 0) return;
+  for (int w = 1; w < PG_WG_WAVES; ++w) {
+    const u32 other = lists[w][lane];
+    u64 m = __builtin_amdgcn_ballot_w64(other < t && lane < k);
+    while (m) {
+      const int j = __builtin_ctzll(m);
+      m &= m - 1;
+      const u32 x = (u32)__builtin_amdgcn_readlane((int)other, j);
+      if (x < t) {
+        const u32 prev = wave_shr1(l, 0u);
+        l = (l <= x) ? l : (prev > x ? prev : x);
+        t = (u32)__builtin_amdgcn_readlane((int)l, k - 1);
+      }
+    }
+  }
+  if (lane < k) {
+    idx[q * k + lane] = l == 0xFFFFFFFFu ? -1 : (int)(l & 0x00FFFFFFu);
+    dist[q * k + lane] = (unsigned char)(l >> 24);
+    if (lastKeys && lane == k - 1) lastKeys[q] = l;
+  }
+}
+
+typedef int (*query_fn)(int, const QueryParams &, long long, hipStream_t);
+static const query_fn kQuery[8] = {pg_launch_query_g1, pg_launch_query_g2, pg_launch_query_g3, pg_launch_query_g4,
+                                   pg_launch_query_g5, pg_launch_query_g6, pg_launch_query_g7, pg_launch_query_g8};
+
+extern "C" {
+
+int64_t pg_query_workspace_bytes(int64_t nq, int64_t ndb, int k) {
+  if (nq <= 0 || ndb <= 0 || k < 1 || k > 64) return 0;
+  const int pieces = query_pieces(nq, ndb, k);
+  return pieces > 1 ? (int64_t)nq * pieces * k * 4 : 0;
+}
+
+int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb,
+                         int64_t db_npad, int l, int bits, int k, const uint32_t *floor_keys, uint32_t *last_keys,
+                         int32_t *idx_out, uint8_t *dist_out, void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!q_planes || !db_planes || !idx_out || !dist_out || nq <= 0 || ndb <= 0 || workspace_bytes < 0)
+    return fail(PG_E_BADARG, "pg_query_knn_hamming: bad argument");
+  if (k < 1 || k > 64) return fail(PG_E_BADARG, "pg_query_knn_hamming: k must be in 1..64");
+  if (int rc = check_bits(bits)) return rc;
+  if (int rc = check_l(l, bits)) return rc;
+  if (q_npad < nq || db_npad < ndb || db_npad % 256) return fail(PG_E_BADARG, "pg_query_knn_hamming: bad npad");
+  if (ndb >= PG_MAX_N_KNN) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: ndb must be below 2^24");
+  // pieces: the plan, bounded by the workspace the caller passed (pg_query_workspace_bytes gives the plan's size)
+  long long pieces = query_pieces(nq, ndb, k);
+  const long long fit = workspace ? workspace_bytes / ((long long)nq * k * 4) : 0;
+  if (pieces > fit) pieces = fit < 1 ? 1 : fit;
+  if (pieces > PG_QUERY_MERGE_KEYS / k) pieces = PG_QUERY_MERGE_KEYS / k;
+  QueryParams p;
+  p.qPlanes = (const uint4 *)q_planes; p.dbPlanes = (const uint4 *)db_planes;
+  p.qNpad = q_npad; p.dbNpad = db_npad; p.nq = nq; p.ndb = ndb;
+  p.k = k; p.pieces = (int)pieces;
+  const long long ntiles = (ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  p.tilesPerPiece = (ntiles + pieces - 1) / pieces;
+  p.pieces = (int)((ntiles + p.tilesPerPiece - 1) / p.tilesPerPiece);   // (no empty piece)
+  p.floorKeys = floor_keys; p.partial = (u32 *)workspace;
+  p.knnIdx = idx_out; p.knnDist = dist_out; p.lastKeys = last_keys;
+  const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
+  if (ngrp * p.pieces > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = launched(kQuery[pg_ngroups(l) - 1](bits, p, ngrp * p.pieces, s), "pg_query_knn_kernel")) return rc;
+  if (p.pieces == 1) return 0;
+  if (nq > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
+  pg_query_merge_kernel<<<dim3((unsigned)nq), dim3(PG_WG_THREADS), 0, s>>>((const u32 *)workspace, p.pieces, k, idx_out,
+                                                                             dist_out, last_keys);
+  return launched((int)hipGetLastError(), "pg_query_merge_kernel");
+}
+
 int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits, int64_t ref,
                    const uint32_t *want_dist, int pos_mode, const uint32_t *pos_mask, const uint32_t *not_mask,
                    uint8_t *dist_out, uint64_t *hist, uint8_t *flags, void *stream) {

@@ -376,6 +376,22 @@ struct KnnRowsParams {
   u32 gateMask;
 };
 
+// pg_query_knn_kernel: kNN of a query set against a database operand, ranks from 0, the database swept in column pieces
+#define PG_QUERY_RW 8               // queries per workgroup
+#define PG_QUERY_TILE 128           // columns per tile of a wave (two per lane)
+#define PG_QUERY_MERGE_KEYS 8192    // pieces x k of one query: the merge kernel holds them in LDS
+struct QueryParams {
+  const uint4 *qPlanes, *dbPlanes;
+  long long qNpad, dbNpad, nq, ndb;
+  int k, pieces;
+  long long tilesPerPiece;   // piece p sweeps column tiles [p * tilesPerPiece, (p + 1) * tilesPerPiece)
+  const u32 *floorKeys;      // NULL (first round) or per query: only keys above it are candidates
+  u32 *partial;              // pieces > 1: [nq][pieces][k] sorted keys, for pg_query_merge_kernel
+  int *knnIdx;               // pieces == 1: the results [nq][k] (and lastKeys[nq] when not NULL)
+  unsigned char *knnDist;
+  u32 *lastKeys;
+};
+
 struct CompactParams {
   NsqParams e;
   int skipOverflow;   // 1: rows beyond their slot are left to pg_eps_fill_rows instead of being recomputed here
@@ -394,7 +410,8 @@ void pg_set_error(const char *msg);   // thread-local message behind pg_last_err
   int pg_launch_dense_g##G(int bits, const DenseParams &p, hipStream_t s);                    \
   int pg_launch_compact_g##G(int bits, const CompactParams &p, hipStream_t s);                \
   int pg_launch_probe_g##G(int bits, const ProbeParams &p, hipStream_t s);                    \
-  int pg_launch_knn_rows_g##G(int bits, const KnnRowsParams &p, int grid, hipStream_t s);
+  int pg_launch_knn_rows_g##G(int bits, const KnnRowsParams &p, int grid, hipStream_t s);               \
+  int pg_launch_query_g##G(int bits, const QueryParams &p, long long grid, hipStream_t s);
 PG_DECL_G(1) PG_DECL_G(2) PG_DECL_G(3) PG_DECL_G(4) PG_DECL_G(5) PG_DECL_G(6) PG_DECL_G(7) PG_DECL_G(8)
 int pg_launch_nsq_bag(const NsqParams &p, int grid, hipStream_t s);   // pg_lev.hip
 int pg_launch_nsq_bag_sym(const NsqParams &p, int grid, hipStream_t s);

@@ -725,6 +725,113 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_rows_kernel(const KnnRow
 }
 
 // ---------------------------------------------------------------------------------------
+// kNN of QUERIES against a database operand (pg_query_knn_hamming): ranks 0..k-1 of every query's (distance, column)
+// order, k <= 64.  pg_knn_rows_kernel's sweep - eight query records staged in LDS, four waves on interleaved tiles of 128
+// columns, one load of the column records serving the eight queries, lane j = j-th smallest key, insertion = one DPP
+// shift, the four lists merged through LDS - with two changes: rank 0 is kept (threshold = lane k - 1), and the grid is
+// (query groups) x (column pieces), so that a handful of queries still fills the chip.  A workgroup sweeps only its piece
+// of the tiles; with one piece it writes the results, else its sorted list of k keys goes to `partial` and
+// pg_query_merge_kernel (pg_api.hip) makes the queries' lists of them.  floorKeys (continuation rounds, k > 64): only keys
+// above the query's floor are candidates (keys are unique: distance << 24 | column).
+// ---------------------------------------------------------------------------------------
+template <int G, int B>
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_query_knn_kernel(const QueryParams p) {
+  constexpr int Q = Rec<G, B>::Q;
+  constexpr int CR = PG_QUERY_TILE / 64;                   // columns per lane and tile
+  constexpr int RW = PG_QUERY_RW;
+  __shared__ uint4 rowrec[RW][Q];
+  __shared__ u32 lists[PG_WG_WAVES][RW][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long ngrp = (p.nq + RW - 1) / RW;
+  const long long grp = (long long)blockIdx.x % ngrp;     // consecutive workgroups: the same piece, other queries
+  const int piece = (int)((long long)blockIdx.x / ngrp);
+  const long long q0 = grp * RW;
+  const int nrw = (int)(p.nq - q0 < RW ? p.nq - q0 : RW);
+  const int kk = p.k;
+  for (int e = threadIdx.x; e < RW * Q; e += PG_WG_THREADS) {
+    const int rr = e / Q, q = e - rr * Q;
+    rowrec[rr][q] = p.qPlanes[(long long)q * p.qNpad + q0 + (rr < nrw ? rr : 0)];
+  }
+  __syncthreads();
+  const uint4 *rrec = &rowrec[0][0] + opaque_zero();       // broadcast reads, kept "divergent"
+  u32 lst[RW], thr[RW], lo[RW];                            // lo: the smallest admissible key (floor + 1)
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) {
+    lst[rr] = 0xFFFFFFFFu; thr[rr] = 0xFFFFFFFFu; lo[rr] = 0u;
+    if (p.floorKeys) {
+      const u32 f = p.floorKeys[q0 + (rr < nrw ? rr : 0)];
+      lo[rr] = f == 0xFFFFFFFFu ? 0xFFFFFFFFu : f + 1u;    // (an exhausted query admits nothing)
+    }
+  }
+  const long long ntiles = (p.ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  const long long tEnd = (piece + 1) * p.tilesPerPiece < ntiles ? (piece + 1) * p.tilesPerPiece : ntiles;
+  for (long long t = piece * p.tilesPerPiece + wv; t < tEnd; t += PG_WG_WAVES) {
+    uint4 c[CR][Q];
+#pragma unroll
+    for (int b = 0; b < CR; ++b) {
+      const long long col = t * PG_QUERY_TILE + b * 64 + lane;   // (the plane buffer is padded to 256 sequences: in bounds)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) c[b][q] = p.dbPlanes[(long long)q * p.dbNpad + col];
+    }
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+      if (rr >= nrw) break;
+      uint4 r[Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) r[q] = rrec[rr * Q + q];
+#pragma unroll
+      for (int b = 0; b < CR; ++b) {                        // (ascending columns: slices, then lanes)
+        const long long col = t * PG_QUERY_TILE + b * 64 + lane;
+        u32 key = col < p.ndb ? (mismatch<G, B>(r, c[b]) << 24) | (u32)col : 0xFFFFFFFFu;
+        key = key < lo[rr] ? 0xFFFFFFFFu : key;
+        u64 m = __builtin_amdgcn_ballot_w64(key < thr[rr]);
+        while (m) {
+          const int j = __builtin_ctzll(m);
+          m &= m - 1;
+          const u32 x = (u32)__builtin_amdgcn_readlane((int)key, j);
+          if (x < thr[rr]) {
+            const u32 prev = wave_shr1(lst[rr], 0u);
+            lst[rr] = (lst[rr] <= x) ? lst[rr] : (prev > x ? prev : x);
+            thr[rr] = (u32)__builtin_amdgcn_readlane((int)lst[rr], kk - 1);
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) lists[wv][rr][lane] = lst[rr];
+  __syncthreads();
+  for (int rr = wv; rr < nrw; rr += PG_WG_WAVES) {         // wave w merges the four lists of queries w and w + 4
+    u32 l = lists[0][rr][lane];
+    u32 t = (u32)__builtin_amdgcn_readlane((int)l, kk - 1);
+    for (int w = 1; w < PG_WG_WAVES; ++w) {
+      const u32 other = lists[w][rr][lane];
+      u64 m = __builtin_amdgcn_ballot_w64(other < t && lane < kk);
+      while (m) {
+        const int j = __builtin_ctzll(m);
+        m &= m - 1;
+        const u32 x = (u32)__builtin_amdgcn_readlane((int)other, j);
+        if (x < t) {
+          const u32 prev = wave_shr1(l, 0u);
+          l = (l <= x) ? l : (prev > x ? prev : x);
+          t = (u32)__builtin_amdgcn_readlane((int)l, kk - 1);
+        }
+      }
+    }
+    if (lane < kk) {
+      const long long qi = q0 + rr;
+      if (p.pieces > 1) {
+        p.partial[(qi * p.pieces + piece) * kk + lane] = l;
+      } else {
+        p.knnIdx[qi * kk + lane] = l == 0xFFFFFFFFu ? -1 : (int)(l & 0x00FFFFFFu);
+        p.knnDist[qi * kk + lane] = (unsigned char)(l >> 24);
+        if (p.lastKeys && lane == kk - 1) p.lastKeys[qi] = l;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // Data probe in front of a large all-pairs launch: exact distances of a few sample rows against all columns, counted
 // (see ProbeParams).  Grid: nsample * wavesPerRow waves; wave w of a sample row takes every wavesPerRow-th tile of 64
 // columns.  ~1e-3 of the launch's pair count.

@@ -115,6 +115,17 @@ int PG_CAT(pg_launch_knn_rows_g, PG_G)(int bits, const KnnRowsParams &p, int gri
   return bits == 5 ? launch_knn_rows<5>(p, grid, s) : launch_knn_rows<8>(p, grid, s);
 }
 
+template <int B>
+static int launch_query(const QueryParams &p, long long grid, hipStream_t s) {
+  if constexpr (!Cols<B>::kBuilt) return (int)hipErrorInvalidValue;
+  pg_query_knn_kernel<PG_G, B><<<dim3((unsigned)grid), dim3(PG_WG_THREADS), 0, s>>>(p);
+  return (int)hipGetLastError();
+}
+
+int PG_CAT(pg_launch_query_g, PG_G)(int bits, const QueryParams &p, long long grid, hipStream_t s) {
+  return bits == 5 ? launch_query<5>(p, grid, s) : launch_query<8>(p, grid, s);
+}
+
 int PG_CAT(pg_launch_dense_g, PG_G)(int bits, const DenseParams &p, hipStream_t s) {
   return bits == 5 ? launch_dense<5>(p, s) : launch_dense<8>(p, s);
 }

@@ -134,19 +134,24 @@ class CSRGraph:
 class KNNGraph:
     """k nearest neighbours: idx int32 (n,k), dist uint8|int16 (n,k) or fp16 Minkowski values; canonical (distance, index)
     order (descending values for Minkowski similarities).  final=True: the values are final (cosine fp32) whatever
-    their dtype."""
+    their dtype.  first: the rank of column 0 - 1 for self-graphs (rank 0 dropped, ranks beyond N-1 do not exist), 0 for
+    query results (`Prograph.search`: rank 0 kept, min(k, N) ranks)."""
 
-    def __init__(self, idx, dist, ncols, similarity=False, row0=0, final=False):
+    def __init__(self, idx, dist, ncols, similarity=False, row0=0, final=False, first=1):
         self.idx, self.dist = idx, dist
         self.ncols, self.similarity, self.row0 = int(ncols), bool(similarity), int(row0)
         self.final = bool(final)
+        self.first = int(first)
 
     @property
     def nrows(self):
         return int(self.idx.shape[0])
 
+    def _ranks(self):
+        return min(self.idx.shape[1], max(self.ncols - self.first, 0))   # ranks beyond N-1 do not exist ([:,1:k+1])
+
     def host(self):
-        kk = min(self.idx.shape[1], max(self.ncols - 1, 0))    # ranks beyond N-1 do not exist ([:,1:k+1])
+        kk = self._ranks()
         idx = self.idx[:, :kk].to(torch.int64).cpu().numpy()
         if self.final or self.dist.dtype == torch.float16:
             return idx, self.dist[:, :kk].cpu().numpy()
@@ -160,7 +165,7 @@ class KNNGraph:
 
     def as_csr(self):
         """The same graph as a CSRGraph view (k entries per row; ranks beyond N-1 do not exist)."""
-        kk = min(self.idx.shape[1], max(self.ncols - 1, 0))
+        kk = self._ranks()
         n = self.nrows
         indptr = torch.arange(0, n * kk + 1, kk, dtype=torch.int64, device=self.idx.device) if kk else \
             torch.zeros(n + 1, dtype=torch.int64, device=self.idx.device)

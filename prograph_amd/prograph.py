@@ -419,6 +419,185 @@ class Prograph:
                 seen |= set(members.index)
         return clusters
 
+    # ------------------------------------------------------------------ queries against the dataset
+    def nearest_neighbour(self, seq, distance=hamming, batch_size=8, representation="Tokenized"):
+        """(the nearest dataset row of every query, as `self[idx]`; the smallest of their distances) - the reference's
+        documented return line (prograph/prograph.py:546-569), on `search(seq, k=1)`.  `batch_size` is accepted for
+        compatibility, as in `build_graph`."""
+        res = self.search(seq, 1, distance=distance, representation=representation)
+        idx = np.array([int(i[0]) for i, _ in res], dtype=np.int64)
+        distances = np.array([w[0] for _, w in res])
+        return self[idx], np.min(distances)
+
+    def search(self, queries, k, distance=hamming, representation="Tokenized", similarity=False, output="tuples"):
+        """
+        The k nearest dataset rows of sequences or embeddings that need not be in the dataset: for the dataset
+        representation X (N rows) and the queries Y, staged as `build_graph` stages them, ranks 0..min(k, N)-1 of
+        `torch.sort(distance(X, Y, similarity=similarity), dim=1, stable=True, descending=similarity)` per query - rank
+        0 is kept (a query equal to a dataset row has that row first), ties go to the lower dataset index.
+        `queries`: a string or a list of strings (the dataset's letter table; unknown letters and padding -> 0), a 1-D or
+        2-D integer token array, or for embeddings a 1-D or 2-D float array / tensor (cast to fp16); the shorter of
+        queries and dataset is right-padded with zeros.  Returns a list of Q `(indices, weights)` tuples in rank order,
+        or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
+        Hamming runs the fused query kernel (`pg_query_knn_hamming`), sequences beyond one record the dense kernel plus
+        the fp16 selection; Minkowski and cosine the fused embedding kernels; any other `distance` the generic loop.
+        """
+        if not k:                                                          # build_graph's errors for k
+            raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
+        if not isinstance(k, int):
+            raise TypeError("K must be provided as an integer.")
+        if k < 1:
+            raise ValueError("K must be at least 1.")
+        strings = None
+        if isinstance(queries, str):
+            strings = [queries]
+        elif isinstance(queries, (list, tuple)) and len(queries) and all(isinstance(q, str) for q in queries):
+            strings = list(queries)
+        if strings is None:
+            Y = queries if isinstance(queries, torch.Tensor) else torch.as_tensor(np.asarray(queries))
+            if Y.dim() == 1:
+                Y = Y.reshape(1, -1)
+            if Y.dim() != 2 or Y.shape[0] == 0 or Y.shape[1] == 0:
+                raise ValueError("queries must be a non-empty string, list of strings or 1-D / 2-D array")
+        elif len(strings) == 0:
+            raise ValueError("queries must be a non-empty string, list of strings or 1-D / 2-D array")
+        else:
+            Y = None
+        g = None
+        if distance is hamming and k <= _native.MAX_K_ROUNDS:
+            g = self._search_hamming(strings, Y, k, similarity, representation)
+        elif distance in (minkowski, cosine) and k <= _native.MAX_K_ROUNDS and strings is None:
+            g = self._search_embedding(Y, k, similarity, representation, distance)
+        if g is None:
+            return self._search_generic(strings, Y, k, similarity, representation, distance, output)
+        return g if output == "csr" else g.to_tuples()
+
+    def _dataset_matrix(self, representation):
+        return self.tokenized if representation == "Tokenized" else np.vstack(self(representation))
+
+    def _search_hamming(self, strings, Y, k, similarity, representation):
+        """Byte-token queries on the device: the fused query kernel within one record (the dataset's cached planes when
+        they fit, else the dataset packed at the queries' width for this call), the staged dense + fp16 selection path
+        up to 2048 positions.  None when dataset or queries are not byte tokens (the generic loop then)."""
+        try:
+            X = np.asarray(self._dataset_matrix(representation))
+        except (ValueError, TypeError):
+            return None
+        raw = table = None
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            if len(self.amino_acids) > 255:
+                return None
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        if X.ndim != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not np.issubdtype(X.dtype, np.integer):
+            return None
+        if not np.issubdtype(T.dtype, np.integer) or T.min() < 0 or T.max() > 255 or X.min() < 0 or X.max() > 255:
+            return None
+        n, width = X.shape[0], max(X.shape[1], T.shape[1])
+        if n >= _native.MAX_N_KNN or width > self._LONG_MAX_L:
+            return None
+        kk = min(k, n)
+        bits = _native.BITS_5 if max(int(X.max()), int(T.max())) <= 31 else _native.BITS_8
+        limit = _native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L
+        if width > limit:
+            return self._search_hamming_long(X, T, kk, bits, similarity)
+        dp = self._planes_or_none() if representation == "Tokenized" else None
+        if dp is None or dp.l != width or dp.bits != bits:
+            dp = _native.pack(torch.from_numpy(np.ascontiguousarray(X.astype(np.uint8))), bits=bits, width=width)
+        if raw is not None:
+            wide = np.zeros((raw.shape[0], width), dtype=np.uint8)        # NUL padding: token 0, as clean_input pads
+            wide[:, :raw.shape[1]] = raw
+            qp, _ = _native.pack_bytes(wide, table.astype(np.uint8), bits=bits, want_tokens=False)
+        else:
+            qp = _native.pack(torch.from_numpy(np.ascontiguousarray(T.astype(np.uint8))), bits=bits, width=width)
+        idx, dist = _native.query_knn(qp, dp, kk)
+        return KNNGraph(idx, dist, n, similarity=similarity, first=0)
+
+    def _search_hamming_long(self, X, T, kk, bits, similarity):
+        """Sequences beyond one record (up to 2048 positions): `_build_graph_long`'s staging - the dense kernel over
+        column segments into an fp16 block per block of queries - then ranks 0..kk-1 of the block (`pg_f16_knn`,
+        first = 0; rounds beyond 64)."""
+        dev = _native.device()
+        width = max(X.shape[1], T.shape[1])
+        Xd = torch.zeros((X.shape[0], width), dtype=torch.uint8, device=dev)
+        Xd[:, :X.shape[1]] = torch.as_tensor(X.astype(np.uint8), device=dev)
+        Td = torch.zeros((T.shape[0], width), dtype=torch.uint8, device=dev)
+        Td[:, :T.shape[1]] = torch.as_tensor(T.astype(np.uint8), device=dev)
+        n, q = Xd.shape[0], Td.shape[0]
+        w = (_native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L) // 32 * 32
+        segs = [(a, min(width, a + w)) for a in range(0, width, w)]
+        xs = [_native.pack(Xd[:, a:b], bits=bits) for a, b in segs]
+        rows_per_block = max(64, min(q, (1 << 27) // n))                 # <= 256 MB of fp16 distances at a time
+        parts = []
+        for r0 in range(0, q, rows_per_block):
+            block = None
+            for (a, b), xp in zip(segs, xs):
+                block = _native.hamming_dense(xp, _native.pack(Td[r0:r0 + rows_per_block, a:b], bits=bits), out_bytes=2, out=block)
+            idx, wt = _native.f16_knn(block, kk, first=0, descending=False)
+            parts.append((idx, wt.to(torch.int16)))
+            del block
+        return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), n, similarity=similarity,
+                        first=0)
+
+    _MINK_STAGED_ROWS = 4096      # fewer Minkowski queries: dense block + selection (the fused kernel: 16 queries per CU)
+
+    def _search_embedding(self, Y, k, similarity, representation, distance):
+        """Minkowski / cosine queries on the fused kernels with first = 0 (fp16 staging of both operands, as
+        `build_graph` stages the column).  Few Minkowski queries take the staged dense + selection path instead, which
+        gives the same values bit for bit.  None (the generic loop) when an operand is not a non-empty 2-D fp16 device
+        tensor, or for cosine when one holds an inf or nan."""
+        try:
+            X = torch.as_tensor(np.vstack(self(representation)), dtype=torch.float16, device=_native.device())
+            Y = torch.as_tensor(Y, dtype=torch.float16, device=X.device)
+        except (ValueError, TypeError, RuntimeError):
+            return None
+        if X.dim() != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not X.is_cuda:
+            return None
+        if X.shape[1] != Y.shape[1]:                                     # clean_input's zero right-padding
+            d = max(X.shape[1], Y.shape[1])
+            X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
+            Y = torch.nn.functional.pad(Y, (0, d - Y.shape[1]))
+        n, kk = X.shape[0], min(k, X.shape[0])
+        if distance is minkowski:
+            xp = _native.pack_f16(X)
+            if Y.shape[0] < self._MINK_STAGED_ROWS:
+                rows = max(1, min(Y.shape[0], (1 << 27) // n))
+                parts = [_native.f16_knn(_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity),
+                                         kk, first=0, descending=similarity) for r0 in range(0, Y.shape[0], rows)]
+                idx, w = torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+            else:
+                idx, w = _native.minkowski_knn(xp, _native.pack_f16(Y), kk, first=0, similarity=similarity)
+            return KNNGraph(idx, w, n, similarity=similarity, first=0)
+        xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
+        if xc.nonfinite() or yc.nonfinite():
+            return None
+        idx, w = _native.cosine_knn(xc, yc, kk, first=0, similarity=similarity)
+        return KNNGraph(idx, w, n, similarity=similarity, final=True, first=0)
+
+    def _search_generic(self, strings, Y, k, similarity, representation, distance, output):
+        """Any `distance(X, Y, similarity=...) -> (Q, N)` operator: `_build_graph_generic`'s fp16 staging on the GPU, the
+        queries in row blocks, a stable sort, ranks 0..min(k, N)-1."""
+        dev = _native.device()
+        X = torch.as_tensor(np.vstack(self(representation)), dtype=torch.float16, device=dev)
+        if strings is not None:
+            Y = self.tokenize(strings)
+        Y = torch.as_tensor(Y if isinstance(Y, torch.Tensor) else np.asarray(Y), dtype=torch.float16, device=dev)
+        n = X.shape[0]
+        kk = min(k, n)
+        rows = max(1, min(Y.shape[0], (1 << 26) // max(n, 1)))
+        idx, wts = [], []
+        for r0 in range(0, Y.shape[0], rows):
+            s = torch.sort(distance(X, Y[r0:r0 + rows], similarity=similarity), dim=1, descending=bool(similarity), stable=True)
+            idx.append(s[1][:, :kk])
+            wts.append(s[0][:, :kk])
+        idx, wts = torch.cat(idx), torch.cat(wts)
+        if output == "csr":
+            return KNNGraph(idx.to(torch.int32), wts, n, similarity=similarity, final=True, first=0)
+        idx, wts = idx.cpu().numpy(), wts.cpu().numpy()
+        return list(zip(list(idx), list(wts)))
+
     @staticmethod
     def get_every_n(a, n=2):
         for start in range(0, a.shape[0], n):
