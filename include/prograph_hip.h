@@ -83,6 +83,10 @@ extern "C" {
 #define PG_CMP_EQ 2
 #define PG_CMP_GE 3
 #define PG_CMP_GT 4
+/* OR-ed into `cmp` of pg_f16_eps_*, pg_minkowski_eps_* and pg_cosine_eps_* (no other entry takes it): keep the pairs
+ * with d == 0 (similarities: s == 1) that those entries otherwise exclude - the rows of QUERIES, where a vector
+ * equal to the query is a hit.  Without the flag the entries behave as before.                                   */
+#define PG_CMP_KEEP_ZERO 0x10
 
 int         pg_version(void);
 const char *pg_last_error(void);
@@ -259,6 +263,29 @@ int64_t pg_query_workspace_bytes(int64_t nq, int64_t ndb, int k);
 int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb,
                          int64_t db_npad, int l, int bits, int k, const uint32_t *floor_keys, uint32_t *last_keys,
                          int32_t *idx_out, uint8_t *dist_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * pg_query_eps_count / _fill — the eps rows of QUERY sequences against a DATABASE: per query the database columns j
+ * with comp(d(query, j), eps), in ascending j, as a CSR.  Pairs with d == 0 are KEPT (a query equal to a database
+ * row finds that row), otherwise cmp and eps as in pg_eps_slots: the five PG_CMP_* codes, eps any finite number.
+ * Planes as for pg_query_knn_hamming (the same width l and bits); ndb is bounded by the int32 indices only.
+ * pg_query_knn_hamming's sweep and grid (query groups x column pieces, so that one query still fills the chip), but
+ * every wave of a workgroup takes a contiguous run of column tiles: per query the columns fall into nseg = 4 x
+ * pieces consecutive SEGMENTS.  pg_query_eps_segments(nq, ndb) is the planned nseg (0 for an empty operand); any
+ * multiple of 4 up to 4 x ceil(ndb / 128) gives the same result.  Both calls must get the same nseg.
+ *   pg_query_eps_count   seg_counts u32 [nq*nseg]: the matches of segment s of query q at [q*nseg + s]
+ *   pg_exclusive_scan    over those nq*nseg counts -> seg_indptr int64 [nq*nseg + 1]; entry q*nseg is row q's
+ *                        indptr, the last entry nnz (the one host sync of the path reads it)
+ *   pg_query_eps_fill    the sweep again: indices int32 [nnz] and weights uint8 [nnz] (the distances), every match
+ *                        at its segment's offset plus its rank in the segment.  No atomics, no sort, no overflow.
+ */
+int64_t pg_query_eps_segments(int64_t nq, int64_t ndb);
+int pg_query_eps_count(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb,
+                       int64_t db_npad, int l, int bits, int cmp, double eps, int64_t nseg, uint32_t *seg_counts,
+                       void *stream);
+int pg_query_eps_fill(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb,
+                      int64_t db_npad, int l, int bits, int cmp, double eps, int64_t nseg, const int64_t *seg_indptr,
+                      int32_t *indices, uint8_t *weights, void *stream);
 
 /*
  * pg_index_flags — the fused 1xN pass of `Prograph.indexing` (prograph/prograph.py:

@@ -21,6 +21,7 @@ ABI_VERSION = 3
 
 BITS_5, BITS_8 = 5, 8
 CMP_LE, CMP_LT, CMP_EQ, CMP_GE, CMP_GT = 0, 1, 2, 3, 4
+CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine eps entries: d = 0 (s = 1) is a hit
 MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 1023, 1 << 24, 8
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
@@ -36,6 +37,7 @@ SYMBOLS = [
     "pg_minkowski_eps_fill_rows", "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_knn_round",
     "pg_cosine_eps_slots", "pg_cosine_eps_compact", "pg_cosine_eps_fill_rows",
     "pg_query_workspace_bytes", "pg_query_knn_hamming",
+    "pg_query_eps_segments", "pg_query_eps_count", "pg_query_eps_fill",
 ]
 
 
@@ -106,6 +108,10 @@ def _load():
         lib.pg_query_workspace_bytes.argtypes = [_i64, _i64, _i32]
         lib.pg_query_knn_hamming.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                              _i64, _vp]
+        lib.pg_query_eps_segments.restype = _i64
+        lib.pg_query_eps_segments.argtypes = [_i64, _i64]
+        lib.pg_query_eps_count.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i64, _vp, _vp]
+        lib.pg_query_eps_fill.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _dbl, _i64, _vp, _vp, _vp, _vp]
         lib.pg_index_flags.argtypes = [_vp, _i64, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_compact_flags.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp]
         lib.pg_csr_row_stats.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -474,6 +480,30 @@ def query_knn(qp, dp, k):
     return idx, dist
 
 
+def query_eps(qp, dp, cmp, eps, pieces=None):
+    """The eps rows of every query row of `qp` against the database `dp` (pg_query_eps_count / _fill): the columns j with
+    comp(d(q, j), eps) in ascending j, d = 0 kept.  Returns device tensors (indptr int64 [Q+1], indices int32 [nnz],
+    weights uint8 [nnz]).  Two sweeps with a scan of the per-segment counts between them; ONE host sync (nnz) after the
+    scan.  `pieces`: column pieces per query instead of the planned number (the same result; tests and measurements)."""
+    L = lib()
+    bits = _bits2(qp, dp)
+    dev = dp.buf.device
+    nseg = int(L.pg_query_eps_segments(qp.n, dp.n)) if pieces is None else 4 * int(pieces)
+    ops = (_ptr(qp.buf), qp.n, qp.npad, _ptr(dp.buf), dp.n, dp.npad, dp.g * 32, bits, int(cmp), float(eps), nseg)
+    m = qp.n * nseg
+    counts = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    _check(L.pg_query_eps_count(*ops, _ptr(counts), _stream()), "pg_query_eps_count")
+    seg_indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
+    _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(seg_indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+    nnz = int(seg_indptr[-1].item())                                   # the one sync
+    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+    weights = torch.empty(max(nnz, 1), dtype=torch.uint8, device=dev)[:nnz]
+    if nnz:
+        _check(L.pg_query_eps_fill(*ops, _ptr(seg_indptr), _ptr(indices), _ptr(weights), _stream()), "pg_query_eps_fill")
+    return seg_indptr[::nseg].contiguous(), indices, weights
+
+
 def index_flags(planes, ref, want=None, pos_mode=0, pos_mask=None, not_mask=None, want_dist_out=True,
                 want_hist=True, want_flags=True):
     """Fused 1xN pass of Prograph.indexing; returns (dist uint8[n] | None, hist int64[256] | None, flags | None).
@@ -683,13 +713,15 @@ def f16_knn(block, k, first=1, descending=False):
     return idx, w
 
 
-def f16_eps(block, cmp, eps, similarity=False):
+def f16_eps(block, cmp, eps, similarity=False, keep_zero=False):
     """CSR of the entries of an fp16 block that satisfy comp(d, eps) & (d > 0)  [comp(eps, s) & (s < 1)].
-    `eps` is rounded to fp16 first, as torch does when an fp16 tensor meets a Python number."""
+    `eps` is rounded to fp16 first, as torch does when an fp16 tensor meets a Python number.
+    keep_zero: without the second test (rows of queries: d = 0 is a hit)."""
     L = lib()
     m, n = block.shape
     dev = block.device
     e16 = float(np.float16(eps))
+    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
     counts = torch.empty(m, dtype=torch.int32, device=dev)
     _check(L.pg_f16_eps_count(_ptr(block), m, n, block.stride(0), int(cmp), e16, 1 if similarity else 0, _ptr(counts), _stream()),
            "pg_f16_eps_count")
@@ -737,17 +769,18 @@ def minkowski_knn(xp, yp, k, first=1, similarity=False):
     return idx, w
 
 
-def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256):
+def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256, keep_zero=False):
     """f16_eps(minkowski_dense(xp, yp, similarity), cmp, eps, similarity) with ONE distance sweep per row block: exact
     counts plus up to `cap` entries per row in slots (pg_minkowski_eps_slots), scan, compaction, and a second sweep over
     just the rows with more than `cap` matches, written straight into the CSR (pg_minkowski_eps_fill_rows).  One host
-    sync per block (nnz and the number of such rows); blocks keep the slots within 256 MB.
+    sync per block (nnz and the number of such rows); blocks keep the slots within 256 MB.  keep_zero as in f16_eps.
     Returns (indptr int64 [m+1], indices int32 [nnz], weights fp16 [nnz])."""
     if xp.d != yp.d:
         raise ValueError("operands must have the same dimension")
     L = lib()
     dev = xp.buf.device
     cap = max(1, int(cap))
+    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
     e16 = float(np.float16(eps))
     sim = 1 if similarity else 0
     rows_per_block = max(64, (256 << 20) // (cap * 6))                # int32 + fp16 per slot
@@ -883,16 +916,17 @@ def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
     return idx, w
 
 
-def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256):
+def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False):
     """CSR of the entries of cosine_dense(xc, yc, similarity) with comp(d, eps) & (d > 0)  [comp(eps, s) & (s < 1)],
     `eps` rounded to fp32 first (as torch does when an fp32 tensor meets a Python number).  The minkowski_eps
     structure: one sweep into per-row slots with exact counts, scan, compaction, and a second sweep over the rows
-    with more than `cap` matches; one host sync per block of rows.
+    with more than `cap` matches; one host sync per block of rows.  keep_zero: without the d > 0 (s < 1) test.
     Returns (indptr int64 [m+1], indices int32 [nnz], weights fp32 [nnz])."""
     _cos_same_d(xc, yc)
     L = lib()
     dev = xc.packed.buf.device
     cap = max(1, int(cap))
+    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
     e32 = float(np.float32(eps))
     sim = 1 if similarity else 0
     rows_per_block = max(64, (256 << 20) // (cap * 8))                # int32 + fp32 per slot

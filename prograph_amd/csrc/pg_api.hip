@@ -350,11 +350,12 @@ static int check_bits(int b) {
   return 0;
 }
 
-// comp(d, eps) & (d > 0) as an integer interval [lo, lo+span]; an empty interval is encoded
-// so that (d - lo) <= span is false for every d in 0..255
-static void eps_interval(int cmp, double eps, u32 *lo, u32 *span) {
+// comp(d, eps) & (d >= dmin) as an integer interval [lo, lo+span]; an empty interval is encoded
+// so that (d - lo) <= span is false for every d in 0..255.  dmin = 1: the graphs (pairs with d = 0 are
+// excluded); dmin = 0: queries (pg_query_eps_*)
+static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin = 1) {
   const long long INF = 1000000;
-  long long l = 1, h = INF;
+  long long l = dmin, h = INF;
   switch (cmp) {
     case PG_CMP_LE: h = (long long)floor(eps); break;
     case PG_CMP_LT: h = (long long)ceil(eps) - 1; break;
@@ -364,7 +365,7 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span) {
     case PG_CMP_GE: l = (long long)ceil(eps); break;
     case PG_CMP_GT: l = (long long)floor(eps) + 1; break;
   }
-  if (l < 1) l = 1;
+  if (l < dmin) l = dmin;
   if (h > INF) h = INF;
   if (h < l) { *lo = 0xFFFFFF00u; *span = 0; return; }
   *lo = (u32)l;
@@ -1258,6 +1259,78 @@ int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const
   pg_query_merge_kernel<<<dim3((unsigned)nq), dim3(PG_WG_THREADS), 0, s>>>((const u32 *)workspace, p.pieces, k, idx_out,
                                                                              dist_out, last_keys);
   return launched((int)hipGetLastError(), "pg_query_merge_kernel");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// eps rows of queries (pg_query_eps_count / _fill): the piece plan of pg_query_knn_hamming without the merge kernel's LDS
+// bound.  A function of (nq, ndb) only; the caller sizes the segment tables from it (pg_query_eps_segments) and passes
+// the segment count back, so count and fill sweep the same segments.
+// ---------------------------------------------------------------------------------------
+static long long query_eps_pieces(int64_t nq, int64_t ndb) {
+  const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
+  const long long ntiles = (ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  long long p = (PG_QUERY_TARGET_WG + ngrp - 1) / ngrp;
+  const long long byTiles = (ntiles + PG_WG_WAVES - 1) / PG_WG_WAVES;   // at least one tile per wave
+  if (p > byTiles) p = byTiles;
+  return p < 1 ? 1 : p;
+}
+
+typedef int (*query_eps_fn)(int, int, const QueryEpsParams &, long long, hipStream_t);
+static const query_eps_fn kQueryEps[8] = {pg_launch_query_eps_g1, pg_launch_query_eps_g2, pg_launch_query_eps_g3,
+                                          pg_launch_query_eps_g4, pg_launch_query_eps_g5, pg_launch_query_eps_g6,
+                                          pg_launch_query_eps_g7, pg_launch_query_eps_g8};
+
+// the checks and the launch both entries share; every check runs on the host before the launch
+static int query_eps_launch(const char *who, int fill, const void *q_planes, int64_t nq, int64_t q_npad,
+                            const void *db_planes, int64_t ndb, int64_t db_npad, int l, int bits, int cmp, double eps,
+                            int64_t nseg, QueryEpsParams &p, void *stream) {
+  if (!q_planes || !db_planes || nq <= 0 || ndb <= 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT || !(eps == eps))
+    return fail(PG_E_BADARG, who);
+  if (int rc = check_bits(bits)) return rc;
+  if (int rc = check_l(l, bits)) return rc;
+  if (q_npad < nq || db_npad < ndb || db_npad % 256) return fail(PG_E_BADARG, "pg_query_eps: bad npad");
+  if (ndb > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_eps: ndb must fit int32 column indices");
+  const long long ntiles = (ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  if (nseg < PG_WG_WAVES || nseg % PG_WG_WAVES || nseg / PG_WG_WAVES > ntiles)
+    return fail(PG_E_BADARG, "pg_query_eps: nseg must be 4 x pieces, with at most one piece per column tile");
+  const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
+  const long long pieces = nseg / PG_WG_WAVES;
+  if (ngrp * pieces > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_eps: too many queries for one launch");
+  p.qPlanes = (const uint4 *)q_planes; p.dbPlanes = (const uint4 *)db_planes;
+  p.qNpad = q_npad; p.dbNpad = db_npad; p.nq = nq; p.ndb = ndb;
+  eps_interval(cmp, eps, &p.lo, &p.span, 0);
+  p.pieces = (int)pieces;
+  p.tilesPerPiece = (ntiles + pieces - 1) / pieces;        // (trailing pieces may be empty: their segments count 0)
+  return launched(kQueryEps[pg_ngroups(l) - 1](bits, fill, p, ngrp * pieces, (hipStream_t)stream),
+                  fill ? "pg_query_eps_kernel(fill)" : "pg_query_eps_kernel(count)");
+}
+
+extern "C" {
+
+int64_t pg_query_eps_segments(int64_t nq, int64_t ndb) {
+  if (nq <= 0 || ndb <= 0) return 0;
+  return query_eps_pieces(nq, ndb) * PG_WG_WAVES;
+}
+
+int pg_query_eps_count(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb, int64_t db_npad,
+                       int l, int bits, int cmp, double eps, int64_t nseg, uint32_t *seg_counts, void *stream) {
+  if (!seg_counts) return fail(PG_E_BADARG, "pg_query_eps_count: bad argument");
+  QueryEpsParams p = {};
+  p.segCounts = seg_counts;
+  return query_eps_launch("pg_query_eps_count: bad argument", 0, q_planes, nq, q_npad, db_planes, ndb, db_npad, l, bits, cmp,
+                          eps, nseg, p, stream);
+}
+
+int pg_query_eps_fill(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb, int64_t db_npad,
+                      int l, int bits, int cmp, double eps, int64_t nseg, const int64_t *seg_indptr, int32_t *indices,
+                      uint8_t *weights, void *stream) {
+  if (!seg_indptr || !indices || !weights) return fail(PG_E_BADARG, "pg_query_eps_fill: bad argument");
+  QueryEpsParams p = {};
+  p.segIndptr = (const long long *)seg_indptr; p.indices = indices; p.weights = weights;
+  return query_eps_launch("pg_query_eps_fill: bad argument", 1, q_planes, nq, q_npad, db_planes, ndb, db_npad, l, bits, cmp,
+                          eps, nseg, p, stream);
 }
 
 int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits, int64_t ref,

@@ -392,6 +392,20 @@ struct QueryParams {
   u32 *lastKeys;
 };
 
+// pg_query_eps_kernel: the queries' eps rows of the database, d = 0 admitted.  The sweep of pg_query_knn_kernel, every wave
+// on a contiguous run of its piece's tiles: (query, piece, wave) is a segment of ascending columns
+struct QueryEpsParams {
+  const uint4 *qPlanes, *dbPlanes;
+  long long qNpad, dbNpad, nq, ndb;
+  u32 lo, span;              // match: (d - lo) <= span   (eps_interval with a lower clamp of 0)
+  int pieces;                // segments per query: pieces * PG_WG_WAVES
+  long long tilesPerPiece;   // piece p sweeps column tiles [p * tilesPerPiece, (p + 1) * tilesPerPiece)
+  u32 *segCounts;            // count mode: [nq][pieces * PG_WG_WAVES] matches per segment
+  const long long *segIndptr;   // fill mode: the exclusive scan of segCounts, the offset of every segment
+  int *indices;              // fill mode: [nnz] columns, ascending within a query
+  unsigned char *weights;    //            [nnz] distances
+};
+
 struct CompactParams {
   NsqParams e;
   int skipOverflow;   // 1: rows beyond their slot are left to pg_eps_fill_rows instead of being recomputed here
@@ -411,7 +425,8 @@ void pg_set_error(const char *msg);   // thread-local message behind pg_last_err
   int pg_launch_compact_g##G(int bits, const CompactParams &p, hipStream_t s);                \
   int pg_launch_probe_g##G(int bits, const ProbeParams &p, hipStream_t s);                    \
   int pg_launch_knn_rows_g##G(int bits, const KnnRowsParams &p, int grid, hipStream_t s);               \
-  int pg_launch_query_g##G(int bits, const QueryParams &p, long long grid, hipStream_t s);
+  int pg_launch_query_g##G(int bits, const QueryParams &p, long long grid, hipStream_t s);              \
+  int pg_launch_query_eps_g##G(int bits, int fill, const QueryEpsParams &p, long long grid, hipStream_t s);
 PG_DECL_G(1) PG_DECL_G(2) PG_DECL_G(3) PG_DECL_G(4) PG_DECL_G(5) PG_DECL_G(6) PG_DECL_G(7) PG_DECL_G(8)
 int pg_launch_nsq_bag(const NsqParams &p, int grid, hipStream_t s);   // pg_lev.hip
 int pg_launch_nsq_bag_sym(const NsqParams &p, int grid, hipStream_t s);

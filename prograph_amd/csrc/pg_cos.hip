@@ -23,6 +23,9 @@
 #include "pg_common.h"
 #include "../../include/prograph_hip.h"
 
+// cmp of the eps entries: one of the five codes, with or without PG_CMP_KEEP_ZERO
+static inline bool pg_cmp_bad(int cmp) { return (cmp & ~PG_CMP_KEEP_ZERO) < PG_CMP_LE || (cmp & ~PG_CMP_KEEP_ZERO) > PG_CMP_GT; }
+
 #include <stdio.h>
 
 typedef _Float16 cs_h8 __attribute__((ext_vector_type(8)));
@@ -79,17 +82,18 @@ __device__ __forceinline__ float cs_unkey(u32 key, int descending) { return __ui
 
 //   distances:    comp(d, eps) & (d > 0)
 //   similarities: comp(eps, s) & (s < 1)
+//   cmp | PG_CMP_KEEP_ZERO: without the second test (queries)
 __device__ __forceinline__ bool cs_match(float v, float eps, int cmp, int similarity) {
   const float a = similarity ? eps : v, b = similarity ? v : eps;
   bool ok;
-  switch (cmp) {
+  switch (cmp & ~PG_CMP_KEEP_ZERO) {
     case PG_CMP_LE: ok = a <= b; break;
     case PG_CMP_LT: ok = a < b; break;
     case PG_CMP_EQ: ok = a == b; break;
     case PG_CMP_GE: ok = a >= b; break;
     default: ok = a > b; break;
   }
-  return ok && (similarity ? v < 1.0f : v > 0.0f);
+  return ok && ((cmp & PG_CMP_KEEP_ZERO) || (similarity ? v < 1.0f : v > 0.0f));
 }
 
 // ---- per-vector norms: the diagonal of cs_tile on 32 vectors against themselves --------------------------------
@@ -412,7 +416,7 @@ int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float 
                         int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w, uint32_t *counts,
                         void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !slot_idx ||
-      !slot_w || !counts || cap < 1 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+      !slot_w || !counts || cap < 1 || pg_cmp_bad(cmp))
     return cfail(PG_E_BADARG, "pg_cosine_eps_slots: bad argument");
   if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
     return cfail(PG_E_BADARG, "pg_cosine_eps_slots: too many vectors for one launch");
@@ -436,7 +440,7 @@ int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const fl
                             int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
                             const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !row_list ||
-      n_list <= 0 || !indptr || !indices || !weights || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+      n_list <= 0 || !indptr || !indices || !weights || pg_cmp_bad(cmp))
     return cfail(PG_E_BADARG, "pg_cosine_eps_fill_rows: bad argument");
   if (n > 0x7FFFFFFFll || cs_groups(n_list) > 0x7FFFFFFFll)
     return cfail(PG_E_BADARG, "pg_cosine_eps_fill_rows: too many vectors for one launch");

@@ -24,6 +24,9 @@
 #include "pg_common.h"
 #include "../../include/prograph_hip.h"
 
+// cmp of the eps entries: one of the five codes, with or without PG_CMP_KEEP_ZERO
+static inline bool pg_cmp_bad(int cmp) { return (cmp & ~PG_CMP_KEEP_ZERO) < PG_CMP_LE || (cmp & ~PG_CMP_KEEP_ZERO) > PG_CMP_GT; }
+
 #include <hip/hip_fp16.h>
 #include <stdio.h>
 
@@ -179,17 +182,18 @@ __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *_
 // epsilon selection on a distance / similarity block: count, or fill at indptr
 //   distances:    comp(d, eps) & (d > 0)      (prograph.py:736)
 //   similarities: comp(eps, s) & (s < 1)      (:734), eps already 1/(1+eps) rounded to fp16
+//   cmp | PG_CMP_KEEP_ZERO: without the second test (queries: a vector equal to the query is a hit)
 __device__ __forceinline__ bool mk_match(float v, float eps, int cmp, int similarity) {
   const float a = similarity ? eps : v, b = similarity ? v : eps;
   bool ok;
-  switch (cmp) {
+  switch (cmp & ~PG_CMP_KEEP_ZERO) {
     case PG_CMP_LE: ok = a <= b; break;
     case PG_CMP_LT: ok = a < b; break;
     case PG_CMP_EQ: ok = a == b; break;
     case PG_CMP_GE: ok = a >= b; break;
     default: ok = a > b; break;
   }
-  return ok && (similarity ? v < 1.0f : v > 0.0f);
+  return ok && ((cmp & PG_CMP_KEEP_ZERO) || (similarity ? v < 1.0f : v > 0.0f));
 }
 
 __global__ __launch_bounds__(256) void pg_f16_eps_kernel(const __half *__restrict__ dist, long long m, long long n, long long ld,
@@ -466,7 +470,7 @@ int pg_f16_knn_round(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int
 
 int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                      uint32_t *counts, void *stream) {
-  if (!dist_f16 || !counts || m <= 0 || n <= 0 || ld < n || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+  if (!dist_f16 || !counts || m <= 0 || n <= 0 || ld < n || pg_cmp_bad(cmp))
     return mfail(PG_E_BADARG, "pg_f16_eps_count: bad argument");
   pg_f16_eps_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const __half *)dist_f16, m, n, ld, cmp, eps_f16, similarity ? 1 : 0, counts, nullptr, nullptr, nullptr);
@@ -475,7 +479,7 @@ int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int
 
 int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                     const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
-  if (!dist_f16 || !indptr || !indices || !weights_f16 || m <= 0 || n <= 0 || ld < n || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+  if (!dist_f16 || !indptr || !indices || !weights_f16 || m <= 0 || n <= 0 || ld < n || pg_cmp_bad(cmp))
     return mfail(PG_E_BADARG, "pg_f16_eps_fill: bad argument");
   pg_f16_eps_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const __half *)dist_f16, m, n, ld, cmp, eps_f16, similarity ? 1 : 0, nullptr, (const long long *)indptr, indices,
@@ -519,7 +523,7 @@ int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, cons
                            int d, int similarity, int cmp, float eps_f16, int cap, int32_t *slot_idx, void *slot_w_f16,
                            uint32_t *counts, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !slot_idx || !slot_w_f16 || !counts || cap < 1 ||
-      cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+      pg_cmp_bad(cmp))
     return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: bad argument");
   if (n > 0x7FFFFFFFll || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
     return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: too many vectors for one launch");
@@ -543,7 +547,7 @@ int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, 
                                int d, int similarity, int cmp, float eps_f16, const int64_t *row_list, int64_t n_list,
                                const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !row_list || n_list <= 0 || !indptr || !indices ||
-      !weights_f16 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
+      !weights_f16 || pg_cmp_bad(cmp))
     return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: bad argument");
   if (n > 0x7FFFFFFFll || (n_list + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
     return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: too many vectors for one launch");

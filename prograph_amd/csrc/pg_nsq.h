@@ -832,6 +832,80 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_query_knn_kernel(const Query
 }
 
 // ---------------------------------------------------------------------------------------
+// eps rows of QUERIES against a database operand (pg_query_eps_count / _fill): per query the columns with (d - lo) <= span
+// in ascending order, d = 0 admitted.  pg_query_knn_kernel's sweep and grid - eight query records in LDS, four waves, tiles
+// of 128 columns, one load of the column records serving the eight queries, (query groups) x (column pieces) - but every
+// wave takes a CONTIGUOUS run of its piece's tiles, so a (query, piece, wave) triple is a contiguous column range, a
+// segment, and segments in (piece, wave) order are ascending columns: no sort, no atomics, no slots.  Count mode writes
+// the matches of every segment (ballot + popcount, wave-uniform); the caller's exclusive scan of them gives every
+// segment's offset (entry q * nseg: row q's indptr).  Fill mode repeats the sweep and writes each match at its segment's
+// running offset plus its rank in the ballot mask.
+// ---------------------------------------------------------------------------------------
+template <int G, int B, bool FILL>
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_query_eps_kernel(const QueryEpsParams p) {
+  constexpr int Q = Rec<G, B>::Q;
+  constexpr int CR = PG_QUERY_TILE / 64;                   // columns per lane and tile
+  constexpr int RW = PG_QUERY_RW;
+  __shared__ uint4 rowrec[RW][Q];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long ngrp = (p.nq + RW - 1) / RW;
+  const long long grp = (long long)blockIdx.x % ngrp;     // consecutive workgroups: the same piece, other queries
+  const int piece = (int)((long long)blockIdx.x / ngrp);
+  const long long q0 = grp * RW;
+  const int nrw = (int)(p.nq - q0 < RW ? p.nq - q0 : RW);
+  for (int e = threadIdx.x; e < RW * Q; e += PG_WG_THREADS) {
+    const int rr = e / Q, q = e - rr * Q;
+    rowrec[rr][q] = p.qPlanes[(long long)q * p.qNpad + q0 + (rr < nrw ? rr : 0)];
+  }
+  __syncthreads();
+  const uint4 *rrec = &rowrec[0][0] + opaque_zero();       // broadcast reads, kept "divergent"
+  const long long nseg = (long long)p.pieces * PG_WG_WAVES;
+  const long long seg = (long long)piece * PG_WG_WAVES + wv;
+  long long run[RW];                                       // count: matches so far; fill: the next offset (wave-uniform)
+#pragma unroll
+  for (int rr = 0; rr < RW; ++rr) run[rr] = FILL && rr < nrw ? p.segIndptr[(q0 + rr) * nseg + seg] : 0;
+  const long long ntiles = (p.ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
+  const long long pEnd = (piece + 1) * p.tilesPerPiece < ntiles ? (piece + 1) * p.tilesPerPiece : ntiles;
+  const long long perWave = (p.tilesPerPiece + PG_WG_WAVES - 1) / PG_WG_WAVES;
+  const long long t0 = piece * p.tilesPerPiece + wv * perWave;
+  const long long t1 = t0 + perWave < pEnd ? t0 + perWave : pEnd;
+  for (long long t = t0; t < t1; ++t) {
+    uint4 c[CR][Q];
+#pragma unroll
+    for (int b = 0; b < CR; ++b) {
+      const long long col = t * PG_QUERY_TILE + b * 64 + lane;   // (the plane buffer is padded to 256 sequences: in bounds)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) c[b][q] = p.dbPlanes[(long long)q * p.dbNpad + col];
+    }
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr) {
+      if (rr >= nrw) break;
+      uint4 r[Q];
+#pragma unroll
+      for (int q = 0; q < Q; ++q) r[q] = rrec[rr * Q + q];
+#pragma unroll
+      for (int b = 0; b < CR; ++b) {                        // (ascending columns: slices, then lanes)
+        const long long col = t * PG_QUERY_TILE + b * 64 + lane;
+        const u32 d = mismatch<G, B>(r, c[b]);
+        const bool hit = col < p.ndb && d - p.lo <= p.span;
+        const u64 mask = __builtin_amdgcn_ballot_w64(hit);
+        if (FILL && hit) {
+          const long long o = run[rr] + mask_rank(mask);
+          p.indices[o] = (int)col;
+          p.weights[o] = (unsigned char)d;
+        }
+        run[rr] += __popcll(mask);
+      }
+    }
+  }
+  if (!FILL && lane == 0) {
+#pragma unroll
+    for (int rr = 0; rr < RW; ++rr)
+      if (rr < nrw) p.segCounts[(q0 + rr) * nseg + seg] = (u32)run[rr];
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // Data probe in front of a large all-pairs launch: exact distances of a few sample rows against all columns, counted
 // (see ProbeParams).  Grid: nsample * wavesPerRow waves; wave w of a sample row takes every wavesPerRow-th tile of 64
 // columns.  ~1e-3 of the launch's pair count.

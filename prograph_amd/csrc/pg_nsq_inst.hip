@@ -126,6 +126,20 @@ int PG_CAT(pg_launch_query_g, PG_G)(int bits, const QueryParams &p, long long gr
   return bits == 5 ? launch_query<5>(p, grid, s) : launch_query<8>(p, grid, s);
 }
 
+template <int B>
+static int launch_query_eps(int fill, const QueryEpsParams &p, long long grid, hipStream_t s) {
+  if constexpr (!Cols<B>::kBuilt) return (int)hipErrorInvalidValue;
+  if (fill)
+    pg_query_eps_kernel<PG_G, B, true><<<dim3((unsigned)grid), dim3(PG_WG_THREADS), 0, s>>>(p);
+  else
+    pg_query_eps_kernel<PG_G, B, false><<<dim3((unsigned)grid), dim3(PG_WG_THREADS), 0, s>>>(p);
+  return (int)hipGetLastError();
+}
+
+int PG_CAT(pg_launch_query_eps_g, PG_G)(int bits, int fill, const QueryEpsParams &p, long long grid, hipStream_t s) {
+  return bits == 5 ? launch_query_eps<5>(fill, p, grid, s) : launch_query_eps<8>(fill, p, grid, s);
+}
+
 int PG_CAT(pg_launch_dense_g, PG_G)(int bits, const DenseParams &p, hipStream_t s) {
   return bits == 5 ? launch_dense<5>(p, s) : launch_dense<8>(p, s);
 }

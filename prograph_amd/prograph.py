@@ -402,7 +402,12 @@ class Prograph:
         return np.where(comp(d, eps))[1]
 
     def neighbourhood(self, seq, eps, distance=hamming):
-        """All rows within `eps` of `seq`, the row itself included (reference :571-588)."""
+        """All rows within `eps` of `seq`, the row itself included (reference :571-588).  A string that is not in the
+        dataset is answered by `search(seq, eps=eps)`: the dataset rows within `eps` of it."""
+        if isinstance(seq, str) and seq not in self.seq_idxs:
+            hit = np.zeros(len(self), dtype=bool)
+            hit[self.search(seq, eps=eps)[0][0]] = True
+            return self[hit]
         planes = self._planes_or_none()
         if planes is None:
             dist = self._row_distances_long(int(self.query(seq)))
@@ -429,25 +434,43 @@ class Prograph:
         distances = np.array([w[0] for _, w in res])
         return self[idx], np.min(distances)
 
-    def search(self, queries, k, distance=hamming, representation="Tokenized", similarity=False, output="tuples"):
+    def search(self, queries, k=None, eps=None, distance=hamming, representation="Tokenized", similarity=False,
+               output="tuples", comp=operator.le):
         """
-        The k nearest dataset rows of sequences or embeddings that need not be in the dataset: for the dataset
+        The k nearest dataset rows (`k`), or the dataset rows within a radius (`eps`), of sequences or embeddings that
+        need not be in the dataset; exactly one of the two.
+        `k`: for the dataset
         representation X (N rows) and the queries Y, staged as `build_graph` stages them, ranks 0..min(k, N)-1 of
         `torch.sort(distance(X, Y, similarity=similarity), dim=1, stable=True, descending=similarity)` per query - rank
         0 is kept (a query equal to a dataset row has that row first), ties go to the lower dataset index.
+        `eps` (0 is a valid radius: exact matches): per query the dataset rows j with `comp(distance(X, Y)[q, j], eps)` in
+        ascending j, the order `torch.where` yields; no pair is excluded for d = 0.  With `similarity=True` the test is
+        `comp(1/(1+eps), s)` as in `build_graph` and the weights are the similarities.  The five orderings of `operator`
+        run on the device, any other `comp` takes the generic loop.  Returns a list of Q `(indices, weights)` tuples with
+        the dtypes of `build_graph(eps=)` (queries without a hit share one empty pair), or with `output="csr"` a device
+        `CSRGraph` with Q rows and `ncols = N`.
         `queries`: a string or a list of strings (the dataset's letter table; unknown letters and padding -> 0), a 1-D or
         2-D integer token array, or for embeddings a 1-D or 2-D float array / tensor (cast to fp16); the shorter of
         queries and dataset is right-padded with zeros.  Returns a list of Q `(indices, weights)` tuples in rank order,
         or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
-        Hamming runs the fused query kernel (`pg_query_knn_hamming`), sequences beyond one record the dense kernel plus
-        the fp16 selection; Minkowski and cosine the fused embedding kernels; any other `distance` the generic loop.
+        Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
+        dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; any other `distance` the
+        generic loop.
         """
-        if not k:                                                          # build_graph's errors for k
-            raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
-        if not isinstance(k, int):
-            raise TypeError("K must be provided as an integer.")
-        if k < 1:
-            raise ValueError("K must be at least 1.")
+        if eps is None:
+            if not k:                                                      # build_graph's errors for k
+                raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
+            if not isinstance(k, int):
+                raise TypeError("K must be provided as an integer.")
+            if k < 1:
+                raise ValueError("K must be at least 1.")
+        else:
+            if k is not None:
+                raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
+            if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
+                raise TypeError("Epsilon must be provided as a number.")
+            if eps != eps:
+                raise ValueError("Epsilon must not be NaN.")
         strings = None
         if isinstance(queries, str):
             strings = [queries]
@@ -464,6 +487,14 @@ class Prograph:
         else:
             Y = None
         g = None
+        if eps is not None:
+            if distance is hamming and comp in _CMP_CODE:
+                g = self._search_eps_hamming(strings, Y, eps, comp, similarity, representation)
+            elif distance in (minkowski, cosine) and comp in _CMP_CODE and strings is None:
+                g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
+            if g is None:
+                g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
+            return g if output == "csr" else g.to_tuples()
         if distance is hamming and k <= _native.MAX_K_ROUNDS:
             g = self._search_hamming(strings, Y, k, similarity, representation)
         elif distance in (minkowski, cosine) and k <= _native.MAX_K_ROUNDS and strings is None:
@@ -476,9 +507,23 @@ class Prograph:
         return self.tokenized if representation == "Tokenized" else np.vstack(self(representation))
 
     def _search_hamming(self, strings, Y, k, similarity, representation):
-        """Byte-token queries on the device: the fused query kernel within one record (the dataset's cached planes when
-        they fit, else the dataset packed at the queries' width for this call), the staged dense + fp16 selection path
-        up to 2048 positions.  None when dataset or queries are not byte tokens (the generic loop then)."""
+        """Byte-token queries on the device: the fused query kernel within one record, the staged dense + fp16 selection
+        path up to 2048 positions.  None when dataset or queries are not byte tokens (the generic loop then)."""
+        ops = self._hamming_operands(strings, Y, representation, _native.MAX_N_KNN)
+        if ops is None:
+            return None
+        n, bits, X, T, qp, dp = ops
+        kk = min(k, n)
+        if qp is None:
+            return self._search_hamming_long(X, T, kk, bits, similarity)
+        idx, dist = _native.query_knn(qp, dp, kk)
+        return KNNGraph(idx, dist, n, similarity=similarity, first=0)
+
+    def _hamming_operands(self, strings, Y, representation, max_n):
+        """The staging of byte-token queries: (n, bits, X, T, query planes, dataset planes) within one record (the
+        dataset's cached planes when they fit, else the dataset packed at the queries' width for this call), planes of
+        None for the staged path up to 2048 positions.  None when dataset or queries are not byte tokens, or the
+        dataset has `max_n` rows or more (the generic loop then)."""
         try:
             X = np.asarray(self._dataset_matrix(representation))
         except (ValueError, TypeError):
@@ -496,13 +541,12 @@ class Prograph:
         if not np.issubdtype(T.dtype, np.integer) or T.min() < 0 or T.max() > 255 or X.min() < 0 or X.max() > 255:
             return None
         n, width = X.shape[0], max(X.shape[1], T.shape[1])
-        if n >= _native.MAX_N_KNN or width > self._LONG_MAX_L:
+        if n >= max_n or width > self._LONG_MAX_L:
             return None
-        kk = min(k, n)
         bits = _native.BITS_5 if max(int(X.max()), int(T.max())) <= 31 else _native.BITS_8
         limit = _native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L
         if width > limit:
-            return self._search_hamming_long(X, T, kk, bits, similarity)
+            return n, bits, X, T, None, None
         dp = self._planes_or_none() if representation == "Tokenized" else None
         if dp is None or dp.l != width or dp.bits != bits:
             dp = _native.pack(torch.from_numpy(np.ascontiguousarray(X.astype(np.uint8))), bits=bits, width=width)
@@ -512,13 +556,21 @@ class Prograph:
             qp, _ = _native.pack_bytes(wide, table.astype(np.uint8), bits=bits, want_tokens=False)
         else:
             qp = _native.pack(torch.from_numpy(np.ascontiguousarray(T.astype(np.uint8))), bits=bits, width=width)
-        idx, dist = _native.query_knn(qp, dp, kk)
-        return KNNGraph(idx, dist, n, similarity=similarity, first=0)
+        return n, bits, X, T, qp, dp
 
     def _search_hamming_long(self, X, T, kk, bits, similarity):
-        """Sequences beyond one record (up to 2048 positions): `_build_graph_long`'s staging - the dense kernel over
-        column segments into an fp16 block per block of queries - then ranks 0..kk-1 of the block (`pg_f16_knn`,
-        first = 0; rounds beyond 64)."""
+        """Sequences beyond one record (up to 2048 positions): ranks 0..kk-1 of every fp16 block of
+        `_hamming_long_blocks` (`pg_f16_knn`, first = 0; rounds beyond 64)."""
+        parts = []
+        for block in self._hamming_long_blocks(X, T, bits):
+            idx, wt = _native.f16_knn(block, kk, first=0, descending=False)
+            parts.append((idx, wt.to(torch.int16)))
+        return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), X.shape[0],
+                        similarity=similarity, first=0)
+
+    def _hamming_long_blocks(self, X, T, bits):
+        """`_build_graph_long`'s staging for queries: the dense kernel over column segments of whole records into an
+        fp16 block (Q', N) per block of queries, one block alive at a time."""
         dev = _native.device()
         width = max(X.shape[1], T.shape[1])
         Xd = torch.zeros((X.shape[0], width), dtype=torch.uint8, device=dev)
@@ -530,16 +582,11 @@ class Prograph:
         segs = [(a, min(width, a + w)) for a in range(0, width, w)]
         xs = [_native.pack(Xd[:, a:b], bits=bits) for a, b in segs]
         rows_per_block = max(64, min(q, (1 << 27) // n))                 # <= 256 MB of fp16 distances at a time
-        parts = []
         for r0 in range(0, q, rows_per_block):
             block = None
             for (a, b), xp in zip(segs, xs):
                 block = _native.hamming_dense(xp, _native.pack(Td[r0:r0 + rows_per_block, a:b], bits=bits), out_bytes=2, out=block)
-            idx, wt = _native.f16_knn(block, kk, first=0, descending=False)
-            parts.append((idx, wt.to(torch.int16)))
-            del block
-        return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), n, similarity=similarity,
-                        first=0)
+            yield block
 
     _MINK_STAGED_ROWS = 4096      # fewer Minkowski queries: dense block + selection (the fused kernel: 16 queries per CU)
 
@@ -548,17 +595,10 @@ class Prograph:
         `build_graph` stages the column).  Few Minkowski queries take the staged dense + selection path instead, which
         gives the same values bit for bit.  None (the generic loop) when an operand is not a non-empty 2-D fp16 device
         tensor, or for cosine when one holds an inf or nan."""
-        try:
-            X = torch.as_tensor(np.vstack(self(representation)), dtype=torch.float16, device=_native.device())
-            Y = torch.as_tensor(Y, dtype=torch.float16, device=X.device)
-        except (ValueError, TypeError, RuntimeError):
+        ops = self._embedding_operands(Y, representation)
+        if ops is None:
             return None
-        if X.dim() != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not X.is_cuda:
-            return None
-        if X.shape[1] != Y.shape[1]:                                     # clean_input's zero right-padding
-            d = max(X.shape[1], Y.shape[1])
-            X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
-            Y = torch.nn.functional.pad(Y, (0, d - Y.shape[1]))
+        X, Y = ops
         n, kk = X.shape[0], min(k, X.shape[0])
         if distance is minkowski:
             xp = _native.pack_f16(X)
@@ -575,6 +615,107 @@ class Prograph:
             return None
         idx, w = _native.cosine_knn(xc, yc, kk, first=0, similarity=similarity)
         return KNNGraph(idx, w, n, similarity=similarity, final=True, first=0)
+
+    def _embedding_operands(self, Y, representation):
+        """The fp16 device staging of dataset and queries (X, Y), the narrower one right-padded with zeros; None when the
+        dataset is not a non-empty 2-D fp16 device tensor."""
+        try:
+            X = torch.as_tensor(np.vstack(self(representation)), dtype=torch.float16, device=_native.device())
+            Y = torch.as_tensor(Y, dtype=torch.float16, device=X.device)
+        except (ValueError, TypeError, RuntimeError):
+            return None
+        if X.dim() != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not X.is_cuda:
+            return None
+        if X.shape[1] != Y.shape[1]:                                     # clean_input's zero right-padding
+            d = max(X.shape[1], Y.shape[1])
+            X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
+            Y = torch.nn.functional.pad(Y, (0, d - Y.shape[1]))
+        return X, Y
+
+    # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
+    @staticmethod
+    def _cat_csr(parts, dev):
+        if len(parts) == 1:
+            return parts[0]
+        base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
+        for indptr, _, _ in parts:
+            ptrs.append(indptr[1:] + base)
+            base += int(indptr[-1].item())
+        return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
+
+    def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
+        """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
+        the staged blocks and the fp16 selection with d = 0 kept (int16 weights, as `_build_graph_long` gives them).
+        Similarities: comp(1/(1+eps), 1/(1+d)) is the same integer test on d (as in `build_graph`); the container forms
+        the similarities.  None when dataset or queries are not byte tokens (the generic loop then)."""
+        ops = self._hamming_operands(strings, Y, representation, 1 << 31)
+        if ops is None:
+            return None
+        n, bits, X, T, qp, dp = ops
+        cmp = _CMP_CODE[comp]
+        eps = min(max(float(eps), -1.0), 4096.0)                         # (the same test on every d in 0..2048)
+        if qp is not None:
+            indptr, indices, wts = _native.query_eps(qp, dp, cmp, eps)
+        else:
+            thr = self._integer_threshold(cmp, eps)
+            parts = []
+            for block in self._hamming_long_blocks(X, T, bits):
+                ip, ix, w = _native.f16_eps(block, cmp, thr, similarity=False, keep_zero=True)
+                parts.append((ip, ix, w.to(torch.int16)))
+            indptr, indices, wts = self._cat_csr(parts, _native.device())
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
+    def _search_eps_embedding(self, Y, eps, comp, similarity, representation, distance):
+        """Minkowski / cosine queries on the fused eps kernels with d = 0 (s = 1) kept; fewer than `_MINK_STAGED_ROWS`
+        Minkowski queries take the dense block + fp16 selection, which gives the same CSR bit for bit.  None (the
+        generic loop) as in `_search_embedding`."""
+        ops = self._embedding_operands(Y, representation)
+        if ops is None:
+            return None
+        X, Y = ops
+        n, cmp = X.shape[0], _CMP_CODE[comp]
+        if similarity:
+            eps = 1 / (1 + eps)                                          # :720-721
+        if distance is minkowski:
+            xp = _native.pack_f16(X)
+            if Y.shape[0] < self._MINK_STAGED_ROWS:
+                rows = max(1, min(Y.shape[0], (1 << 27) // n))
+                parts = [_native.f16_eps(_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity),
+                                         cmp, eps, similarity=similarity, keep_zero=True) for r0 in range(0, Y.shape[0], rows)]
+                indptr, indices, wts = self._cat_csr(parts, X.device)
+            else:
+                indptr, indices, wts = _native.minkowski_eps(xp, _native.pack_f16(Y), cmp, eps, similarity=similarity,
+                                                             keep_zero=True)
+            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
+        if xc.nonfinite() or yc.nonfinite():
+            return None
+        indptr, indices, wts = _native.cosine_eps(xc, yc, cmp, eps, similarity=similarity, keep_zero=True)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
+
+    def _search_eps_generic(self, strings, Y, eps, comp, similarity, representation, distance):
+        """Any `distance(X, Y, similarity=...) -> (Q, N)` operator and any `comp`: `_search_generic`'s staging, the queries
+        in row blocks, `torch.where(comp(d, eps))` (similarities: `comp(1/(1+eps), s)`), no pair excluded.  The
+        weights are the operator's values as they are."""
+        dev = _native.device()
+        X = torch.as_tensor(np.vstack(self(representation)), dtype=torch.float16, device=dev)
+        if strings is not None:
+            Y = self.tokenize(strings)
+        Y = torch.as_tensor(Y if isinstance(Y, torch.Tensor) else np.asarray(Y), dtype=torch.float16, device=dev)
+        n = X.shape[0]
+        if similarity:
+            eps = 1 / (1 + eps)
+        rows = max(1, min(Y.shape[0], (1 << 26) // max(n, 1)))
+        parts = []
+        for r0 in range(0, Y.shape[0], rows):
+            d = distance(X, Y[r0:r0 + rows], similarity=similarity)
+            keep = comp(eps, d) if similarity else comp(d, eps)
+            loc = torch.where(keep)
+            indptr = torch.zeros(d.shape[0] + 1, dtype=torch.int64, device=d.device)
+            indptr[1:] = torch.cumsum(torch.bincount(loc[0], minlength=d.shape[0]), 0)
+            parts.append((indptr, loc[1].to(torch.int32), d[loc]))
+        indptr, indices, wts = self._cat_csr(parts, parts[0][0].device)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
 
     def _search_generic(self, strings, Y, k, similarity, representation, distance, output):
         """Any `distance(X, Y, similarity=...) -> (Q, N)` operator: `_build_graph_generic`'s fp16 staging on the GPU, the
@@ -691,6 +832,15 @@ class Prograph:
 
     _LONG_MAX_L = 2048                               # integers up to here are exact in fp16
 
+    @staticmethod
+    def _integer_threshold(cmp, eps):
+        """comp(d, eps) on integer distances d in 0..2048 as the same comparison with an integer threshold, which is
+        exact in fp16 whatever eps is (-1: an `==` that nothing satisfies)."""
+        e = float(eps)
+        lo, hi = int(np.floor(e)), int(np.ceil(e))
+        thr = {_native.CMP_LE: lo, _native.CMP_LT: hi, _native.CMP_GE: hi, _native.CMP_GT: lo}.get(cmp, lo if lo == hi else -1)
+        return float(min(max(thr, -1), 4096))
+
     def _build_graph_long(self, idxs, eps, k, similarity, representation, comp):
         """
         Graphs of byte-token sequences LONGER than one record of the fused engines (more than 255 positions,
@@ -725,10 +875,7 @@ class Prograph:
         # similarity graphs: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the same test on d (:720-721, :734)
         cmp = _CMP_CODE[comp]
         if eps:
-            e = float(eps)
-            lo, hi = int(np.floor(e)), int(np.ceil(e))
-            thr = {_native.CMP_LE: lo, _native.CMP_LT: hi, _native.CMP_GE: hi, _native.CMP_GT: lo}.get(cmp, lo if lo == hi else -1)
-            thr = float(min(max(thr, -1), 4096))
+            thr = self._integer_threshold(cmp, eps)
         rows_per_block = max(64, min(n, (1 << 27) // n))                  # <= 256 MB of fp16 distances at a time
         kk = min(k, n - 1) if k else 0
         parts = []
