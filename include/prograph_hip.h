@@ -342,6 +342,40 @@ int pg_lev_knn(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *
                void *stream);
 
 /*
+ * Exact Levenshtein distance — BUILD DEFINED like the banded kNN above, but without band or cap: unit cost
+ * edit distance of the non-zero prefixes of zero-right-padded token rows (tokens 1..31, at most 128 positions;
+ * what pg_lev_profile validates).  Operands are the rows packed with pg_pack_planes(bits = 5) at width
+ * l = 128 (chunk p = bit plane p) plus their lengths (pg_lev_profile's lens).
+ *   pg_levenshtein_dense  out[r * ldo + c] = d(Y row r, X row c) for all m x n pairs (Myers' bit-vector
+ *                      recurrence on a 128-bit pattern, one X row per lane); out_elem_bytes 8 = int64,
+ *                      2 = fp16 (distances are at most 128: exact), the block format of pg_f16_knn /
+ *                      pg_f16_eps_*; l = width of the token rows (1..128), lengths are clamped to it.
+ *                      A Y operand that starts at row r0 of a packed matrix is y_planes128 + 16 * r0 bytes,
+ *                      y_lens + r0, with the matrix's npad.
+ *   Epsilon graph of all rows (d > 0, comp(d, thr), comp = PG_CMP_LE / LT / EQ, thr in 0..8): after
+ *   pg_lev_profile and pg_lev_candidates_sym with band >= thr (re-run with a larger cap while
+ *   max(up + lo) > cap),
+ *   pg_lev_eps_pairs   evaluates every candidate PAIR once - the banded distance min(d, band + 1), exact
+ *                      where it is <= band - and stores it with both entries in slot_w;
+ *   pg_lev_eps_count   counts_out[row] = number of kept entries; cmp | PG_CMP_KEEP_ZERO also keeps d = 0;
+ *   pg_lev_eps_fill    after pg_exclusive_scan of those counts: int32 columns ascending within a row,
+ *                      uint8 distances.  Same n, cap, cmp, thr and slots as the count.
+ */
+int pg_levenshtein_dense(const void *x_planes128, int64_t n, int64_t x_npad, const int32_t *x_lens,
+                         const void *y_planes128, int64_t m, int64_t y_npad, const int32_t *y_lens, int l,
+                         void *out, int out_elem_bytes, int64_t ldo, void *stream);
+int pg_lev_eps_pairs(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *planes128,
+                     int64_t npad, const int32_t *lens, int band, int cap, const int32_t *slot_idx,
+                     uint8_t *slot_w, const int32_t *slot_aux, const uint32_t *counts_up,
+                     const uint32_t *counts_lo, void *stream);
+int pg_lev_eps_count(int64_t n, int cap, int cmp, int thr, const uint8_t *slot_w,
+                     const uint32_t *counts_up, const uint32_t *counts_lo, uint32_t *counts_out,
+                     void *stream);
+int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_idx, const uint8_t *slot_w,
+                    const uint32_t *counts_up, const uint32_t *counts_lo, const int64_t *indptr,
+                    int32_t *indices, uint8_t *weights, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

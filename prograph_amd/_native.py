@@ -31,6 +31,7 @@ SYMBOLS = [
     "pg_hamming_dense", "pg_eps_slots", "pg_scan_scratch_bytes", "pg_exclusive_scan",
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
+    "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -120,6 +121,10 @@ def _load():
         lib.pg_lev_candidates_sym.argtypes = [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_lev_knn.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp]
+        lib.pg_levenshtein_dense.argtypes = [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp]
+        lib.pg_lev_eps_pairs.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_lev_eps_count.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_lev_eps_fill.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -618,6 +623,109 @@ def levenshtein_knn(tokens, k, band=8, row0=0, nrows=None, cap=512, return_stats
         ncand = int(counts.to(torch.int64).sum().item()) + (int(counts_lo.to(torch.int64).sum().item()) if sym else 0)
         return idx, dist, {"candidates": ncand, "cap": cap, "filter_passes": passes, "symmetric": bool(sym)}
     return idx, dist
+
+
+class LevOperand:
+    """A token matrix staged for the exact Levenshtein kernels: `tokens` (n, l <= 128) uint8 on the device, `planes` (5 bit
+    planes at width 128), `lens` int32 [n], `prof` (pg_lev_profile's bag profiles) and the two validity words."""
+    __slots__ = ("tokens", "planes", "lens", "prof", "flags", "n", "l")
+
+    def __init__(self, tokens, planes, lens, prof, flags):
+        self.tokens, self.planes, self.lens, self.prof, self.flags = tokens, planes, lens, prof, flags
+        self.n, self.l = int(tokens.shape[0]), int(tokens.shape[1])
+
+    def bad_word(self):
+        """Device int64 scalar, non-zero when a token is above 31 or a zero is not trailing padding."""
+        return (self.flags[0] | self.planes.flags[0]).to(torch.int64)
+
+    def valid(self):
+        """One host sync: do the kernels' preconditions hold?"""
+        return int(self.bad_word().item()) == 0
+
+
+def lev_operand(tokens):
+    """(N, L <= 128) uint8 tokens -> LevOperand (pg_lev_profile + pg_pack_planes at width 128).  No host sync: ask
+    `valid()` before trusting a result computed from it (the kernels mask symbols and clamp lengths, so an invalid
+    operand gives wrong numbers, never an out-of-bounds access)."""
+    L = lib()
+    dev = device()
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dtype != torch.uint8 or tokens.dim() != 2 or tokens.shape[0] == 0 or tokens.shape[1] == 0:
+        raise TypeError("lev_operand expects a non-empty 2-D uint8 token matrix")
+    if tokens.shape[1] > 128:
+        raise ValueError("lev_operand: at most 128 tokens per sequence")
+    tokens = tokens.to(dev).contiguous()
+    n, l = tokens.shape
+    np_ = npad(n)
+    prof = torch.empty(3 * np_ * 16, dtype=torch.uint8, device=dev)
+    lens = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(L.pg_lev_profile(_ptr(tokens), n, l, tokens.stride(0), _ptr(prof), np_, _ptr(lens), _ptr(flags), _stream()),
+           "pg_lev_profile")
+    planes = pack(tokens, bits=BITS_5, width=128, check=False)   # chunk p of a record = bit plane p (128 bits)
+    return LevOperand(tokens, planes, lens, prof, flags)
+
+
+def levenshtein_dense(xo, yo, out_bytes=8, rows=None):
+    """(M, N) exact edit distances of the rows of LevOperand `yo` (rows = (r0, r1): only those) against every row of `xo`
+    (pg_levenshtein_dense): int64 (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2)."""
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.tokens.device)
+    _check(lib().pg_levenshtein_dense(_ptr(xo.planes.buf), xo.n, xo.planes.npad, _ptr(xo.lens),
+                                      ctypes.c_void_p(yo.planes.buf.data_ptr() + 16 * r0), r1 - r0, yo.planes.npad,
+                                      ctypes.c_void_p(yo.lens.data_ptr() + 4 * r0), max(xo.l, yo.l), _ptr(out), out_bytes,
+                                      out.stride(0), _stream()), "pg_levenshtein_dense")
+    return out
+
+
+def levenshtein_eps(op, cmp, thr, cap=512, keep_zero=False):
+    """Epsilon graph of all rows of a LevOperand under the exact edit distance: the entries with comp(d, thr) and d > 0
+    (d >= 0 with keep_zero), comp = CMP_LE / CMP_LT / CMP_EQ, integer thr in 0..LEV_MAX_BAND.  The bag filter with
+    band = thr over every unordered pair, the banded distance of every candidate pair once (exact where it is within the
+    band), then count / scan / fill.  Two host syncs: the filter's largest candidate count with the token check (a row
+    with more candidates than `cap` reruns the filter with room), and the CSR size.
+    Returns (indptr int64 [n+1], indices int32 ascending within a row, weights uint8).  ValueError for invalid tokens."""
+    L = lib()
+    if cmp not in (CMP_LE, CMP_LT, CMP_EQ) or int(thr) != thr or not 0 <= thr <= LEV_MAX_BAND:
+        raise ValueError("levenshtein_eps: comp le / lt / eq with an integer threshold in 0..8")
+    n, thr, cap = op.n, int(thr), int(cap)
+    if n >= (1 << 27):
+        raise ValueError("levenshtein_eps: n must be below 2^27")
+    dev = op.tokens.device
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    counts_lo = torch.empty(n, dtype=torch.int32, device=dev)
+    while True:
+        slot_idx = torch.empty(n * cap, dtype=torch.int32, device=dev)
+        slot_w = torch.empty(n * cap, dtype=torch.uint8, device=dev)
+        slot_aux = torch.empty(n * cap, dtype=torch.int32, device=dev)
+        _check(L.pg_lev_candidates_sym(_ptr(op.prof), op.planes.npad, n, thr, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(slot_aux),
+                                       _ptr(counts), _ptr(counts_lo), _stream()), "pg_lev_candidates_sym")
+        bad, mx = (int(v) for v in torch.stack([op.bad_word(), (counts + counts_lo).max().to(torch.int64)]).cpu())
+        if bad:
+            raise ValueError("levenshtein_eps: tokens must be 1..31 with zeros only as right padding")
+        if mx <= cap:
+            break
+        cap = ((mx + 63) // 64) * 64          # some row has more candidates than slots: redo with room
+    _check(L.pg_lev_eps_pairs(_ptr(op.tokens), n, op.l, op.tokens.stride(0), _ptr(op.planes.buf), op.planes.npad, _ptr(op.lens),
+                              thr, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(slot_aux), _ptr(counts), _ptr(counts_lo), _stream()),
+           "pg_lev_eps_pairs")
+    code = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
+    kept = torch.empty(n, dtype=torch.int32, device=dev)
+    _check(L.pg_lev_eps_count(n, cap, code, thr, _ptr(slot_w), _ptr(counts), _ptr(counts_lo), _ptr(kept), _stream()),
+           "pg_lev_eps_count")
+    indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(L.pg_scan_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    _check(L.pg_exclusive_scan(_ptr(kept), n, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+    nnz = int(indptr[-1].item())
+    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+    weights = torch.empty(max(nnz, 1), dtype=torch.uint8, device=dev)[:nnz]
+    if nnz:
+        _check(L.pg_lev_eps_fill(n, cap, code, thr, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(counts_lo), _ptr(indptr),
+                                 _ptr(indices), _ptr(weights), _stream()), "pg_lev_eps_fill")
+    return indptr, indices, weights
 
 
 def csr_row_stats(indptr, indices, weights, f=None, want=("deg",), row0=0, ncols=None):

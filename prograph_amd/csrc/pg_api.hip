@@ -1428,6 +1428,63 @@ int pg_lev_knn(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *
                                        slot_aux, counts, counts_lo, idx_out, dist_out, (hipStream_t)stream), "pg_lev_select_kernel");
 }
 
+// ---------------------------------------------------------------------------------------
+// exact Levenshtein: dense matrix and the epsilon graph over symmetric candidate slots (pg_lev.hip)
+// ---------------------------------------------------------------------------------------
+int pg_levenshtein_dense(const void *x_planes128, int64_t n, int64_t x_npad, const int32_t *x_lens, const void *y_planes128,
+                         int64_t m, int64_t y_npad, const int32_t *y_lens, int l, void *out, int out_elem_bytes, int64_t ldo,
+                         void *stream) {
+  if (!x_planes128 || !x_lens || !y_planes128 || !y_lens || !out || n <= 0 || m <= 0 || ldo < n)
+    return fail(PG_E_BADARG, "pg_levenshtein_dense: bad argument");
+  if (l < 1 || l > PG_MAX_L) return fail(PG_E_BADARG, "pg_levenshtein_dense: l must be in 1..128");
+  if (out_elem_bytes != 2 && out_elem_bytes != 8) return fail(PG_E_BADARG, "pg_levenshtein_dense: out_elem_bytes must be 2 or 8");
+  if (x_npad < n || x_npad % 256 || y_npad < m) return fail(PG_E_BADARG, "pg_levenshtein_dense: bad npad");
+  if (((n + PG_WG_THREADS - 1) / PG_WG_THREADS) * ((m + PG_LEVD_ROWS - 1) / PG_LEVD_ROWS) > 0x7fffffffLL)
+    return fail(PG_E_TOOMANY, "pg_levenshtein_dense: too many blocks for one launch");
+  return launched(pg_launch_levenshtein_dense((const uint4 *)x_planes128, x_npad, n, x_lens, (const uint4 *)y_planes128, y_npad, m,
+                                              y_lens, l, out, out_elem_bytes, ldo, (hipStream_t)stream),
+                  "pg_levenshtein_dense_kernel");
+}
+
+int pg_lev_eps_pairs(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *planes128, int64_t npad,
+                     const int32_t *lens, int band, int cap, const int32_t *slot_idx, uint8_t *slot_w, const int32_t *slot_aux,
+                     const uint32_t *counts_up, const uint32_t *counts_lo, void *stream) {
+  if (!tokens || !planes128 || !lens || !slot_idx || !slot_w || !slot_aux || !counts_up || !counts_lo || n <= 0 || ld < l ||
+      cap < 0 || npad < n || npad % 256)
+    return fail(PG_E_BADARG, "pg_lev_eps_pairs: bad argument");
+  if (l < 1 || l > PG_MAX_L) return fail(PG_E_BADARG, "pg_lev_eps_pairs: l must be in 1..128");
+  if (band < 0 || band > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_eps_pairs: band must be in 0..8");
+  return launched(pg_launch_lev_pairs(tokens, n, l, ld, (const uint4 *)planes128, npad, lens, band, (u32)cap, slot_idx, slot_w,
+                                      slot_aux, counts_up, counts_lo, (hipStream_t)stream), "pg_lev_select_kernel<1>");
+}
+
+static int lev_eps_args(int64_t n, int cap, int cmp, int thr, const char *who) {
+  const int c = cmp & ~PG_CMP_KEEP_ZERO;
+  if (n <= 0 || cap < 0 || (c != PG_CMP_LE && c != PG_CMP_LT && c != PG_CMP_EQ)) return fail(PG_E_BADARG, who);
+  if (thr < 0 || thr > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_eps: the threshold must be in 0..8 (the band of the pairs)");
+  return 0;
+}
+
+int pg_lev_eps_count(int64_t n, int cap, int cmp, int thr, const uint8_t *slot_w, const uint32_t *counts_up,
+                     const uint32_t *counts_lo, uint32_t *counts_out, void *stream) {
+  if (!slot_w || !counts_up || !counts_lo || !counts_out) return fail(PG_E_BADARG, "pg_lev_eps_count: bad argument");
+  if (int rc = lev_eps_args(n, cap, cmp, thr, "pg_lev_eps_count: bad argument")) return rc;
+  return launched(pg_launch_lev_eps(0, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, nullptr,
+                                    slot_w, counts_up, counts_lo, counts_out, nullptr, nullptr, nullptr, (hipStream_t)stream),
+                  "pg_lev_eps_kernel<0>");
+}
+
+int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_idx, const uint8_t *slot_w,
+                    const uint32_t *counts_up, const uint32_t *counts_lo, const int64_t *indptr, int32_t *indices,
+                    uint8_t *weights, void *stream) {
+  if (!slot_idx || !slot_w || !counts_up || !counts_lo || !indptr || !indices || !weights)
+    return fail(PG_E_BADARG, "pg_lev_eps_fill: bad argument");
+  if (int rc = lev_eps_args(n, cap, cmp, thr, "pg_lev_eps_fill: bad argument")) return rc;
+  return launched(pg_launch_lev_eps(1, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, slot_idx,
+                                    slot_w, counts_up, counts_lo, nullptr, (const long long *)indptr, indices, weights,
+                                    (hipStream_t)stream), "pg_lev_eps_kernel<1>");
+}
+
 int pg_csr_row_stats(const int64_t *indptr, const int32_t *indices, const uint8_t *weights_u8, const float *weights_f32,
                      int64_t nrows, int64_t row0, const double *f, double *deg, double *sum_f, double *sum_wf,
                      double *self_w, double *col_sum, void *stream) {

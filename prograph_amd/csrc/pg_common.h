@@ -437,3 +437,13 @@ int pg_launch_lev_select(const unsigned char *tok, long long n, int l, long long
                          long long npad, const int *lens, long long row0,
                          long long nrows, int band, int k, u32 cap, const int *slotIdx, unsigned char *slotW, const int *slotAux, const u32 *counts, const u32 *countsLo,
                          int *knnIdx, unsigned char *knnDist, hipStream_t s);
+int pg_launch_lev_pairs(const unsigned char *tok, long long n, int l, long long ld, const uint4 *planes, long long npad,
+                        const int *lens, int band, u32 cap, const int *slotIdx, unsigned char *slotW, const int *slotAux,
+                        const u32 *counts, const u32 *countsLo, hipStream_t s);
+int pg_launch_lev_eps(int fill, long long n, u32 cap, int cmp, u32 thr, u32 dmin, const int *slotIdx,
+                      const unsigned char *slotW, const u32 *counts, const u32 *countsLo, u32 *kept,
+                      const long long *indptr, int *indices, unsigned char *weights, hipStream_t s);
+#define PG_LEVD_ROWS 16      // Y rows per wave of pg_levenshtein_dense_kernel
+int pg_launch_levenshtein_dense(const uint4 *xPlanes, long long xNpad, long long n, const int *xLens, const uint4 *yPlanes,
+                                long long yNpad, long long m, const int *yLens, int l, void *out, int outBytes,
+                                long long ldo, hipStream_t s);

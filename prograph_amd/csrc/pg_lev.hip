@@ -17,6 +17,10 @@
 //     pair per lane, ~24 VALU ops per text character instead of 4 per DP cell x 17 cells), sorted
 //     insertion of (d << 24 | column) keys into the 64-lane register list, then the ranks that no
 //     candidate within the band fills are taken by the smallest column indices at distance band+1.
+//
+// The same file holds the two exact (uncapped) users of these pieces: pg_levenshtein_dense_kernel, the (M, N)
+// edit-distance matrix by Myers' full bit-vector recurrence on a 128-bit pattern, and the epsilon graph
+// (pg_lev_eps_kernel) that turns the pair-once distances of PHASE 1 into a CSR.
 #include "pg_nsq.h"
 
 #define PG_LEV_MAXL 128
@@ -292,5 +296,214 @@ int pg_launch_lev_select(const unsigned char *tok, long long n, int l, long long
   } else {
     pg_lev_select_kernel<0><<<grid, block, 0, s>>>(p);
   }
+  return (int)hipGetLastError();
+}
+
+int pg_launch_lev_pairs(const unsigned char *tok, long long n, int l, long long ld, const uint4 *planes, long long npad,
+                        const int *lens, int band, u32 cap, const int *slotIdx, unsigned char *slotW, const int *slotAux,
+                        const u32 *counts, const u32 *countsLo, hipStream_t s) {
+  LevParams p;
+  p.tok = tok; p.n = n; p.ld = ld; p.l = l; p.planes = planes; p.npad = npad; p.lens = lens; p.row0 = 0; p.nrows = n;
+  p.band = band; p.k = 0; p.cap = cap; p.slotIdx = slotIdx; p.slotW = slotW; p.slotAux = slotAux; p.counts = counts;
+  p.countsLo = countsLo; p.knnIdx = nullptr; p.knnDist = nullptr;
+  pg_lev_select_kernel<1><<<dim3((unsigned)((n + PG_WG_WAVES - 1) / PG_WG_WAVES)), dim3(PG_WG_THREADS), 0, s>>>(p);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// epsilon graph from symmetric candidate slots whose distances PHASE 1 has stored: one wave per row.
+// An entry is kept when comp(d, thr) and d >= dmin (1; 0 with PG_CMP_KEEP_ZERO).  A stored value is
+// min(d, band+1) and thr <= band, so every kept value is the exact distance.  FILL = 0 counts the kept
+// entries; FILL = 1 writes them at indptr[row] + rank, rank = number of kept entries of the row with a
+// smaller column (columns are distinct within a row: every pair is a candidate once), which orders the
+// back half of the slot - filled through atomics in arbitrary order - and the front half alike.
+// ---------------------------------------------------------------------------------------
+struct LevEpsParams {
+  long long n;
+  u32 cap, thr, dmin;
+  int cmp;
+  const int *slotIdx;
+  const unsigned char *slotW;
+  const u32 *counts, *countsLo;
+  u32 *kept;                 // FILL = 0
+  const long long *indptr;   // FILL = 1
+  int *indices;
+  unsigned char *weights;
+};
+
+template <int FILL>
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_lev_eps_kernel(const LevEpsParams p) {
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long row = (long long)blockIdx.x * PG_WG_WAVES + wv;
+  if (row >= p.n) return;
+  const u32 up = p.counts[row];
+  const u32 all = up + p.countsLo[row];
+  const u32 tot = all < p.cap ? all : p.cap;              // host guarantees all <= cap (re-runs otherwise)
+  const long long base = row * (long long)p.cap;
+  // entry e of the row: front part in slots [0, up), back part downwards from slot cap-1; a column that is
+  // not kept reads as 0x7FFFFFFF, above every real column
+  auto entry = [&](u32 e, u32 &d) -> u32 {
+    d = 0;
+    if (e >= tot) return 0x7FFFFFFFu;
+    const long long o = base + (e < up ? e : p.cap - 1u - (e - up));
+    d = p.slotW[o];
+    const bool c = p.cmp == 0 ? d <= p.thr : (p.cmp == 1 ? d < p.thr : d == p.thr);
+    return (c && d >= p.dmin) ? (FILL ? (u32)p.slotIdx[o] : 0u) : 0x7FFFFFFFu;   // counting needs no column
+  };
+  if constexpr (FILL == 0) {
+    u32 cnt = 0;
+    for (u32 e0 = 0; e0 < tot; e0 += 64) {
+      u32 d;
+      cnt += (u32)__popcll(__builtin_amdgcn_ballot_w64(entry(e0 + lane, d) != 0x7FFFFFFFu));
+    }
+    if (lane == 0) p.kept[row] = cnt;
+  } else {
+    const long long dst = p.indptr[row];
+    if (p.indptr[row + 1] == dst) return;
+    for (u32 e0 = 0; e0 < tot; e0 += 64) {
+      u32 d;
+      const u32 col = entry(e0 + lane, d);
+      if (__builtin_amdgcn_ballot_w64(col != 0x7FFFFFFFu) == 0) continue;
+      u32 rank = 0;
+      for (u32 f0 = 0; f0 < tot; f0 += 64) {
+        u32 df;
+        const u32 cf = entry(f0 + lane, df);
+        const int nf = (int)(tot - f0 < 64u ? tot - f0 : 64u);
+        for (int t = 0; t < nf; ++t) rank += (u32)__builtin_amdgcn_readlane(cf, t) < col ? 1u : 0u;
+      }
+      if (col != 0x7FFFFFFFu) {
+        p.indices[dst + rank] = (int)col;
+        p.weights[dst + rank] = (unsigned char)d;
+      }
+    }
+  }
+}
+
+int pg_launch_lev_eps(int fill, long long n, u32 cap, int cmp, u32 thr, u32 dmin, const int *slotIdx,
+                      const unsigned char *slotW, const u32 *counts, const u32 *countsLo, u32 *kept,
+                      const long long *indptr, int *indices, unsigned char *weights, hipStream_t s) {
+  LevEpsParams p;
+  p.n = n; p.cap = cap; p.thr = thr; p.dmin = dmin; p.cmp = cmp; p.slotIdx = slotIdx; p.slotW = slotW; p.counts = counts;
+  p.countsLo = countsLo; p.kept = kept; p.indptr = indptr; p.indices = indices; p.weights = weights;
+  const dim3 grid((unsigned)((n + PG_WG_WAVES - 1) / PG_WG_WAVES)), block(PG_WG_THREADS);
+  if (fill) pg_lev_eps_kernel<1><<<grid, block, 0, s>>>(p);
+  else pg_lev_eps_kernel<0><<<grid, block, 0, s>>>(p);
+  return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// dense exact edit distance: out[row][col] = d(Y[row], X[col]), no band, no cap.
+// Myers' bit-vector recurrence in Hyyro's form, the X sequence b as the 128-bit pattern of one lane (five
+// planes, four dwords each, kept in registers over PG_LEVD_ROWS rows of Y), the Y row a as the wave-uniform
+// text, its per-position plane masks in LDS as in the banded kernel.  Per text position and dword
+//     Eq = (b[i] == a[j])                                      v_xnor + 4 x v_bitop3
+//     D0 = (((Eq & VP) + VP) ^ VP) | Eq | VN                   the + carries through the four dwords
+//     HP = VN | ~(D0 | VP);   HN = D0 & VP
+//     HP' = (HP << 1) | 1;  HN' = HN << 1                      shifts carry too; the 1 is D[0][j] - D[0][j-1]
+//     VP = HN' | ~(D0 | HP');   VN = HP' & D0
+// from VP = ~0, VN = 0 (D[i][0] = i).  Bit i depends on lower bits only, so pattern bits at and above lb (the
+// padding, token 0, which no text symbol equals) never reach the rows that count, and the distance is read
+// off the last column:  D[lb][la] = la + popcount(VP & rows) - popcount(VN & rows),  rows = bits below lb.
+// The loop has no lane-dependent branch: its trip count is the text length.
+// ---------------------------------------------------------------------------------------
+struct LevDenseParams {
+  const uint4 *xPlanes;
+  long long xNpad, n;
+  const int *xLens;
+  const uint4 *yPlanes;
+  long long yNpad, m;
+  const int *yLens;
+  int l;
+  void *out;
+  long long ldo, colTiles;
+};
+
+template <typename OUT>
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_levenshtein_dense_kernel(const LevDenseParams p) {
+  __shared__ uint4 amask[PG_WG_WAVES][PG_LEV_MAXL][2];   // per text position: masks of planes 0..3 | plane 4
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long ct = (long long)blockIdx.x % p.colTiles, rg = (long long)blockIdx.x / p.colTiles;
+  const long long col = (ct * PG_WG_WAVES + wv) * 64 + lane;      // < colTiles * 256 <= xNpad
+  const bool have = col < p.n;
+  int lb = have ? p.xLens[col] : 0;
+  lb = lb < 0 ? 0 : (lb > p.l ? p.l : lb);
+  u32 P[5][4], rows[4];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const uint4 v = p.xPlanes[(long long)q * p.xNpad + col];
+    P[q][0] = v.x; P[q][1] = v.y; P[q][2] = v.z; P[q][3] = v.w;
+  }
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const int nb = lb - 32 * w;
+    rows[w] = nb >= 32 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : (1u << nb) - 1u);
+  }
+  const uint4 *am = &amask[wv][0][0] + opaque_zero();
+
+  for (int r = 0; r < PG_LEVD_ROWS; ++r) {
+    const long long row = rg * PG_LEVD_ROWS + r;
+    if (row >= p.m) break;
+    int la = __builtin_amdgcn_readfirstlane(p.yLens[row]);
+    la = la < 0 ? 0 : (la > p.l ? p.l : la);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the previous row's reads are done
+    __builtin_amdgcn_wave_barrier();
+    for (int j = lane; j < PG_LEV_MAXL; j += 64) {
+      u32 mk[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        const u32 *yw = (const u32 *)(p.yPlanes + (long long)q * p.yNpad + row);
+        mk[q] = 0u - ((yw[j >> 5] >> (j & 31)) & 1u);
+      }
+      amask[wv][j][0] = make_uint4(mk[0], mk[1], mk[2], mk[3]);
+      amask[wv][j][1] = make_uint4(mk[4], 0u, 0u, 0u);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    u32 VP[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, VN[4] = {0u, 0u, 0u, 0u};
+    for (int j = 0; j < la; ++j) {
+      const uint4 m03 = am[j * 2];
+      const u32 m4 = am[j * 2 + 1].x;
+      u32 D0[4], HP[4], HN[4], carry = 0u;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        u32 Eq = ~(P[0][w] ^ m03.x);
+        Eq = __builtin_amdgcn_bitop3_b32(Eq, P[1][w], m03.y, 0x90);        // Eq & ~(plane ^ mask)
+        Eq = __builtin_amdgcn_bitop3_b32(Eq, P[2][w], m03.z, 0x90);
+        Eq = __builtin_amdgcn_bitop3_b32(Eq, P[3][w], m03.w, 0x90);
+        Eq = __builtin_amdgcn_bitop3_b32(Eq, P[4][w], m4, 0x90);
+        const u32 t = __builtin_addc(Eq & VP[w], VP[w], carry, &carry);
+        D0[w] = __builtin_amdgcn_bitop3_b32(t, VP[w], Eq, 0xBE) | VN[w];   // ((t ^ VP) | Eq) | VN
+        HP[w] = __builtin_amdgcn_bitop3_b32(VN[w], D0[w], VP[w], 0xF1);    // VN | ~(D0 | VP)
+        HN[w] = D0[w] & VP[w];
+      }
+#pragma unroll
+      for (int w = 3; w >= 0; --w) {
+        const u32 hp = w ? __builtin_amdgcn_alignbit(HP[w], HP[w - 1], 31) : ((HP[0] << 1) | 1u);
+        const u32 hn = w ? __builtin_amdgcn_alignbit(HN[w], HN[w - 1], 31) : (HN[0] << 1);
+        VP[w] = __builtin_amdgcn_bitop3_b32(hn, D0[w], hp, 0xF1);          // HN' | ~(D0 | HP')
+        VN[w] = hp & D0[w];
+      }
+    }
+    int d = la;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) d += __popc(VP[w] & rows[w]) - __popc(VN[w] & rows[w]);
+    if (have) ((OUT *)p.out)[row * p.ldo + col] = (OUT)d;
+  }
+}
+
+int pg_launch_levenshtein_dense(const uint4 *xPlanes, long long xNpad, long long n, const int *xLens, const uint4 *yPlanes,
+                                long long yNpad, long long m, const int *yLens, int l, void *out, int outBytes,
+                                long long ldo, hipStream_t s) {
+  LevDenseParams p;
+  p.xPlanes = xPlanes; p.xNpad = xNpad; p.n = n; p.xLens = xLens; p.yPlanes = yPlanes; p.yNpad = yNpad; p.m = m;
+  p.yLens = yLens; p.l = l; p.out = out; p.ldo = ldo;
+  p.colTiles = (n + PG_WG_THREADS - 1) / PG_WG_THREADS;
+  const long long blocks = p.colTiles * ((m + PG_LEVD_ROWS - 1) / PG_LEVD_ROWS);      // checked by pg_levenshtein_dense
+  if (outBytes == 2) pg_levenshtein_dense_kernel<_Float16><<<dim3((unsigned)blocks), dim3(PG_WG_THREADS), 0, s>>>(p);
+  else pg_levenshtein_dense_kernel<long long><<<dim3((unsigned)blocks), dim3(PG_WG_THREADS), 0, s>>>(p);
   return (int)hipGetLastError();
 }

@@ -1,4 +1,5 @@
 from .cosine import cosine
 from .hamming import hamming
+from .levenshtein import levenshtein, levenshtein_knn
 from .minkowski import minkowski
 from .utils import clean_input

@@ -33,7 +33,7 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import cosine, hamming, minkowski
+from .distance import cosine, hamming, levenshtein, minkowski
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
@@ -222,7 +222,10 @@ class Prograph:
         return self.tokenized != self.tokenized[self.query(seq)]
 
     def calc_mutated_positions(self):
-        varies = ~np.all(self.tokenized == self.tokenize(self.seed.Sequence), axis=0)
+        seed = self.tokenize(self.seed.Sequence)
+        if seed.shape[1] < self.tokenized.shape[1]:                      # variable-length data: the seed is padded like every row
+            seed = np.pad(seed, ((0, 0), (0, self.tokenized.shape[1] - seed.shape[1])))
+        varies = ~np.all(self.tokenized == seed, axis=0)
         return np.nonzero(varies[: len(self.seed)])[0]
 
     def coloured_seed_string(self):
@@ -398,12 +401,19 @@ class Prograph:
             _, _, flags = _native.index_flags(planes, int(self.query(seq)), want=want,
                                               want_dist_out=False, want_hist=False)
             return _native.compact_flags(flags).cpu().numpy()
+        if distance is levenshtein and comp in _CMP_CODE:
+            return self.search(self._lev_query(seq), eps=eps, distance=levenshtein, comp=comp)[0][0]
         d = distance(self.tokenized, self.tokenized[self.query(seq)].reshape(1, -1))
         return np.where(comp(d, eps))[1]
 
     def neighbourhood(self, seq, eps, distance=hamming):
         """All rows within `eps` of `seq`, the row itself included (reference :571-588).  A string that is not in the
-        dataset is answered by `search(seq, eps=eps)`: the dataset rows within `eps` of it."""
+        dataset is answered by `search(seq, eps=eps)`: the dataset rows within `eps` of it.  `distance=levenshtein`: the rows
+        within `eps` edits, for a string of any length up to 128."""
+        if distance is levenshtein:
+            hit = np.zeros(len(self), dtype=bool)
+            hit[self.search(self._lev_query(seq), eps=eps, distance=levenshtein)[0][0]] = True
+            return self[hit]
         if isinstance(seq, str) and seq not in self.seq_idxs:
             hit = np.zeros(len(self), dtype=bool)
             hit[self.search(seq, eps=eps)[0][0]] = True
@@ -414,6 +424,10 @@ class Prograph:
         else:
             dist, _, _ = _native.index_flags(planes, int(self.query(seq)), want_hist=False, want_flags=False)
         return self[(dist <= eps).cpu().numpy().flatten()]
+
+    def _lev_query(self, seq):
+        """A sequence as `search` takes it: a string as it is, anything `query` resolves as that row's tokens."""
+        return seq if isinstance(seq, str) else np.asarray(self.tokenized[self.query(seq)])
 
     def neighbourhood_clustering(self, eps, distance=hamming):
         clusters, seen = {}, set()
@@ -454,8 +468,9 @@ class Prograph:
         queries and dataset is right-padded with zeros.  Returns a list of Q `(indices, weights)` tuples in rank order,
         or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
         Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
-        dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; any other `distance` the
-        generic loop.
+        dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; Levenshtein (queries of
+        any length up to 128, not only the dataset's) blocks of `pg_levenshtein_dense` plus the fp16 selection; any other
+        `distance` the generic loop.
         """
         if eps is None:
             if not k:                                                      # build_graph's errors for k
@@ -492,6 +507,8 @@ class Prograph:
                 g = self._search_eps_hamming(strings, Y, eps, comp, similarity, representation)
             elif distance in (minkowski, cosine) and comp in _CMP_CODE and strings is None:
                 g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
+            elif distance is levenshtein and comp in _CMP_CODE:
+                g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
             if g is None:
                 g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
             return g if output == "csr" else g.to_tuples()
@@ -499,6 +516,8 @@ class Prograph:
             g = self._search_hamming(strings, Y, k, similarity, representation)
         elif distance in (minkowski, cosine) and k <= _native.MAX_K_ROUNDS and strings is None:
             g = self._search_embedding(Y, k, similarity, representation, distance)
+        elif distance is levenshtein and k <= _native.MAX_K_ROUNDS:
+            g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
         if g is None:
             return self._search_generic(strings, Y, k, similarity, representation, distance, output)
         return g if output == "csr" else g.to_tuples()
@@ -631,6 +650,50 @@ class Prograph:
             X = torch.nn.functional.pad(X, (0, d - X.shape[1]))
             Y = torch.nn.functional.pad(Y, (0, d - Y.shape[1]))
         return X, Y
+
+    @staticmethod
+    def _lev_operand(mat):
+        """LevOperand of an integer token matrix the exact Levenshtein kernels take (at most 128 positions, tokens up to
+        31, zeros only as trailing padding; one host sync for the last two), else None."""
+        mat = np.asarray(mat)
+        if mat.ndim != 2 or mat.shape[0] == 0 or not 1 <= mat.shape[1] <= 128 or not np.issubdtype(mat.dtype, np.integer):
+            return None
+        if mat.min() < 0 or mat.max() > 31:
+            return None
+        op = _native.lev_operand(torch.from_numpy(np.ascontiguousarray(mat.astype(np.uint8))))
+        return op if op.valid() else None
+
+    def _search_levenshtein(self, strings, Y, k, eps, comp, similarity, representation):
+        """Edit-distance queries: Q x N blocks of `pg_levenshtein_dense` (fp16: distances are at most 128) and the fp16
+        selection with rank 0 / d = 0 kept.  Strings are tokenised with the dataset's letter table at their own width.
+        None (the generic loop with the operator) when dataset or queries are not what the kernel takes."""
+        try:
+            xo = self._lev_operand(self._dataset_matrix(representation))
+        except (ValueError, TypeError):
+            return None
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        qo = self._lev_operand(T) if xo is not None else None
+        if qo is None:
+            return None
+        n, q = xo.n, qo.n
+        rows = max(1, min(q, (1 << 27) // n))                            # <= 256 MB of fp16 distances at a time
+        blocks = (_native.levenshtein_dense(xo, qo, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+        if k is not None:
+            parts = [_native.f16_knn(block, min(k, n), first=0, descending=False) for block in blocks]
+            return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]).to(torch.uint8), n,
+                            similarity=similarity, first=0)
+        cmp = _CMP_CODE[comp]
+        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
+        parts = []
+        for block in blocks:
+            ip, ix, w = _native.f16_eps(block, cmp, thr, similarity=False, keep_zero=True)
+            parts.append((ip, ix, w.to(torch.uint8)))
+        indptr, indices, wts = self._cat_csr(parts, _native.device())
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     @staticmethod
@@ -791,6 +854,8 @@ class Prograph:
             g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
         if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
+        if distance is levenshtein and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+            g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:
@@ -972,6 +1037,70 @@ class Prograph:
             return KNNGraph(idx, w, n, similarity=similarity, final=True)
         indptr, indices, wts = _native.cosine_eps(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
+
+    _LEV_FUSED_MAX = _native.LEV_MAX_BAND            # thresholds the fused epsilon graph (and the banded first kNN pass) cover
+
+    def _build_graph_levenshtein(self, idxs, eps, k, similarity, representation, comp, cap=256):
+        """
+        `build_graph(distance=levenshtein)` on the HIP kernels, for token matrices they take (at most 128 positions,
+        tokens up to 31, zeros only as trailing padding; else None: the generic loop with the operator).
+        eps, comp le / lt / eq with an integer threshold of 1..8: the fused graph (`_native.levenshtein_eps`: bag
+        filter, every candidate pair's banded distance once, count / scan / fill).  Any other threshold or ordering:
+        row blocks of `pg_levenshtein_dense` in fp16 and the thresholded CSR of `pg_f16_eps_*`.
+        k: ranks 1..k of the (d, column) order of exact distances.  Up to k = 63 the banded kNN (band 8) runs first: it
+        lists every column within the band in canonical order, so a row whose k-th entry is within the band has its
+        exact ranks; the other rows (all rows beyond k = 63) are Y rows of the dense kernel + `pg_f16_knn`.
+        PG_LEV_ROUTE=dense takes the dense kernel for everything (A/B comparisons; the graphs are identical).
+        Returns a CSRGraph / KNNGraph with uint8 weights whichever route ran; similarities as for Hamming: the same
+        integer test on d, formed by the container.
+        """
+        try:
+            mat = np.asarray(self._dataset_matrix(representation))
+            if idxs is not None:
+                mat = mat[np.asarray(idxs)]
+            op = self._lev_operand(mat)
+        except (ValueError, TypeError):
+            return None
+        if op is None or op.n >= (1 << 27):
+            return None
+        n, dev = op.n, op.tokens.device
+        dense_only = os.environ.get("PG_LEV_ROUTE", "") == "dense"
+        block_rows = max(64, min(n, (1 << 27) // n))                     # <= 256 MB of fp16 distances at a time
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=dev), torch.zeros((n, 0), dtype=torch.uint8, device=dev),
+                                n, similarity=similarity)
+            if kk <= _native.MAX_K and n <= _native.MAX_N_KNN and not dense_only:
+                idx, dist = _native.levenshtein_knn(op.tokens, kk, band=self._LEV_FUSED_MAX)
+                todo = torch.nonzero(dist[:, kk - 1] > self._LEV_FUSED_MAX).reshape(-1)
+                yo = _native.lev_operand(op.tokens[todo]) if 0 < todo.numel() < n else op
+            else:
+                idx = torch.empty((n, kk), dtype=torch.int32, device=dev)
+                dist = torch.empty((n, kk), dtype=torch.uint8, device=dev)
+                todo, yo = None, op
+            m = yo.n if (todo is None or todo.numel()) else 0
+            for r0 in range(0, m, block_rows):
+                r1 = min(m, r0 + block_rows)
+                bi, bw = _native.f16_knn(_native.levenshtein_dense(op, yo, out_bytes=2, rows=(r0, r1)), kk, first=1, descending=False)
+                where = slice(r0, r1) if todo is None else todo[r0:r1]
+                idx[where], dist[where] = bi, bw.to(torch.uint8)
+            return KNNGraph(idx, dist, n, similarity=similarity)
+        cmp = _CMP_CODE[comp]
+        thr = int(self._integer_threshold(cmp, eps))
+        if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr - (cmp == _native.CMP_LT) < 1:   # nothing in 1..thr
+            return CSRGraph(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                            torch.zeros(0, dtype=torch.uint8, device=dev), n, similarity=similarity)
+        if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr <= self._LEV_FUSED_MAX and not dense_only:
+            indptr, indices, wts = _native.levenshtein_eps(op, cmp, thr, cap=max(int(cap), 64))
+            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        parts = []
+        for r0 in range(0, n, block_rows):
+            ip, ix, w = _native.f16_eps(_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))), cmp, thr,
+                                        similarity=False)
+            parts.append((ip, ix, w.to(torch.uint8)))
+        indptr, indices, wts = self._cat_csr(parts, dev)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
         """
