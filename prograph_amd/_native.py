@@ -344,6 +344,36 @@ def _bits2(rp, cp):
     return rp.bits
 
 
+def _csr_alloc(counts, wdtype, extra=None):
+    """Per-row (or per-segment) int32 device counts -> (indptr int64 [m+1], indices int32 [nnz], weights wdtype [nnz]):
+    the exclusive scan, ONE host sync that reads nnz, and the two allocations.  `extra`: a device scalar read in the
+    same sync; then its value is returned fourth."""
+    L = lib()
+    m, dev = counts.numel(), counts.device
+    indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
+    _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+    if extra is None:
+        nnz, also = int(indptr[-1].item()), ()
+    else:
+        nnz, *also = (int(v) for v in torch.stack([indptr[-1], extra]).cpu())
+    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
+    weights = torch.empty(max(nnz, 1), dtype=wdtype, device=dev)[:nnz]
+    return (indptr, indices, weights, *also)
+
+
+def cat_csr(parts):
+    """Row blocks of one CSR, each (indptr, indices, weights) counting from 0 -> the whole (pure torch).  A single
+    part comes back as it is."""
+    if len(parts) == 1:
+        return parts[0]
+    base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=parts[0][0].device)]
+    for indptr, _, _ in parts:
+        ptrs.append(indptr[1:] + base)
+        base += int(indptr[-1].item())
+    return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
+
+
 def eps_graph(rp, cp, cmp, eps, row0=0, nrows=None, cap=256):
     """
     Epsilon-neighbourhood CSR of rows [row0, row0+nrows) of `rp` against all of `cp`.
@@ -364,8 +394,6 @@ def eps_graph(rp, cp, cmp, eps, row0=0, nrows=None, cap=256):
            and (symenv == "1" or rp.n >= 32768))          # whole square graph: every unordered pair once
     counts = torch.empty(nrows, dtype=torch.int32, device=dev)
     counts_lo = torch.empty(nrows, dtype=torch.int32, device=dev) if sym else None
-    indptr = torch.empty(nrows + 1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(L.pg_scan_scratch_bytes(nrows)), dtype=torch.uint8, device=dev)
     slot_idx = torch.empty(nrows * cap, dtype=torch.int32, device=dev)
     slot_w = torch.empty(nrows * cap, dtype=torch.uint8, device=dev)
     if sym:
@@ -380,11 +408,8 @@ def eps_graph(rp, cp, cmp, eps, row0=0, nrows=None, cap=256):
         _check(L.pg_eps_slots(*args, _ptr(workspace(nrows, dev)), _stream()), "pg_eps_slots")
         total = counts
         over = total > cap
-    _check(L.pg_exclusive_scan(_ptr(total), nrows, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-    nnz, n_over = (int(v) for v in torch.stack([indptr[-1], over.sum()]).cpu())     # the one sync
-    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-    weights = torch.empty(max(nnz, 1), dtype=torch.uint8, device=dev)[:nnz]
-    if nnz:
+    indptr, indices, weights, n_over = _csr_alloc(total, torch.uint8, extra=over.sum())     # the one sync
+    if indices.numel():
         fill = n_over > int(os.environ.get("PG_FILL_MIN_ROWS", "8"))
         if sym:
             _check(L.pg_eps_compact_sym(*args, _ptr(indptr), _ptr(indices), _ptr(weights), 1 if fill else 0, _stream()),
@@ -498,13 +523,8 @@ def query_eps(qp, dp, cmp, eps, pieces=None):
     m = qp.n * nseg
     counts = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
     _check(L.pg_query_eps_count(*ops, _ptr(counts), _stream()), "pg_query_eps_count")
-    seg_indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
-    _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(seg_indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-    nnz = int(seg_indptr[-1].item())                                   # the one sync
-    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-    weights = torch.empty(max(nnz, 1), dtype=torch.uint8, device=dev)[:nnz]
-    if nnz:
+    seg_indptr, indices, weights = _csr_alloc(counts[:m], torch.uint8)          # the one sync
+    if indices.numel():
         _check(L.pg_query_eps_fill(*ops, _ptr(seg_indptr), _ptr(indices), _ptr(weights), _stream()), "pg_query_eps_fill")
     return seg_indptr[::nseg].contiguous(), indices, weights
 
@@ -716,13 +736,8 @@ def levenshtein_eps(op, cmp, thr, cap=512, keep_zero=False):
     kept = torch.empty(n, dtype=torch.int32, device=dev)
     _check(L.pg_lev_eps_count(n, cap, code, thr, _ptr(slot_w), _ptr(counts), _ptr(counts_lo), _ptr(kept), _stream()),
            "pg_lev_eps_count")
-    indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(L.pg_scan_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-    _check(L.pg_exclusive_scan(_ptr(kept), n, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-    nnz = int(indptr[-1].item())
-    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-    weights = torch.empty(max(nnz, 1), dtype=torch.uint8, device=dev)[:nnz]
-    if nnz:
+    indptr, indices, weights = _csr_alloc(kept, torch.uint8)
+    if indices.numel():
         _check(L.pg_lev_eps_fill(n, cap, code, thr, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(counts_lo), _ptr(indptr),
                                  _ptr(indices), _ptr(weights), _stream()), "pg_lev_eps_fill")
     return indptr, indices, weights
@@ -833,13 +848,8 @@ def f16_eps(block, cmp, eps, similarity=False, keep_zero=False):
     counts = torch.empty(m, dtype=torch.int32, device=dev)
     _check(L.pg_f16_eps_count(_ptr(block), m, n, block.stride(0), int(cmp), e16, 1 if similarity else 0, _ptr(counts), _stream()),
            "pg_f16_eps_count")
-    indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-    scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
-    _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-    nnz = int(indptr[-1].item())
-    indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-    weights = torch.empty(max(nnz, 1), dtype=torch.float16, device=dev)[:nnz]
-    if nnz:
+    indptr, indices, weights = _csr_alloc(counts, torch.float16)
+    if indices.numel():
         _check(L.pg_f16_eps_fill(_ptr(block), m, n, block.stride(0), int(cmp), e16, 1 if similarity else 0, _ptr(indptr),
                                  _ptr(indices), _ptr(weights), _stream()), "pg_f16_eps_fill")
     return indptr, indices, weights
@@ -877,53 +887,56 @@ def minkowski_knn(xp, yp, k, first=1, similarity=False):
     return idx, w
 
 
-def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256, keep_zero=False):
+def _slots_eps(m_all, rows, slots, compact, fill_rows, wdtype, cap, rows_per_block, dev):
+    """The slots -> CSR host loop of minkowski_eps / cosine_eps over blocks of rows_per_block Y rows (None: blocks that
+    keep the slots within 256 MB).  Per block: ops = rows(r0, r1) stages the block's operands; slots(ops, slot_idx,
+    slot_w, counts) is the one distance sweep (exact counts, up to `cap` entries per row); scan and the block's ONE
+    host sync (nnz and the number of rows beyond `cap`); compact(<the C entry's arguments>) moves the rows within `cap`
+    into the CSR and fill_rows(ops, row list, its length, indptr, indices, weights) sweeps the others once more,
+    straight into it.  ops[-1] is the block's row count."""
+    if rows_per_block is None:
+        rows_per_block = max(64, (256 << 20) // (cap * (4 + torch.finfo(wdtype).bits // 8)))     # int32 + weight per slot
+    parts = []
+    for r0 in range(0, m_all, rows_per_block):
+        ops = rows(r0, min(m_all, r0 + rows_per_block))
+        m = ops[-1]
+        counts = torch.empty(m, dtype=torch.int32, device=dev)
+        slot_idx = torch.empty(m * cap, dtype=torch.int32, device=dev)
+        slot_w = torch.empty(m * cap, dtype=wdtype, device=dev)
+        slots(ops, slot_idx, slot_w, counts)
+        over = counts > cap
+        indptr, indices, weights, n_over = _csr_alloc(counts, wdtype, extra=over.sum())     # the one sync
+        if indices.numel():
+            compact(m, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(indptr), _ptr(indices), _ptr(weights), _stream())
+        if n_over:
+            fill_rows(ops, compact_flags(over.to(torch.uint8), count=n_over), n_over, indptr, indices, weights)
+        del slot_idx, slot_w
+        parts.append((indptr, indices, weights))
+    return cat_csr(parts)
+
+
+def minkowski_eps(xp, yp, cmp, eps, similarity=False, cap=256, keep_zero=False, rows_per_block=None):
     """f16_eps(minkowski_dense(xp, yp, similarity), cmp, eps, similarity) with ONE distance sweep per row block: exact
     counts plus up to `cap` entries per row in slots (pg_minkowski_eps_slots), scan, compaction, and a second sweep over
     just the rows with more than `cap` matches, written straight into the CSR (pg_minkowski_eps_fill_rows).  One host
-    sync per block (nnz and the number of such rows); blocks keep the slots within 256 MB.  keep_zero as in f16_eps.
-    Returns (indptr int64 [m+1], indices int32 [nnz], weights fp16 [nnz])."""
+    sync per block (nnz and the number of such rows); blocks keep the slots within 256 MB (_slots_eps).  keep_zero as in
+    f16_eps.  Returns (indptr int64 [m+1], indices int32 [nnz], weights fp16 [nnz])."""
     if xp.d != yp.d:
         raise ValueError("operands must have the same dimension")
     L = lib()
-    dev = xp.buf.device
     cap = max(1, int(cap))
-    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
-    e16 = float(np.float16(eps))
-    sim = 1 if similarity else 0
-    rows_per_block = max(64, (256 << 20) // (cap * 6))                # int32 + fp16 per slot
-    parts = []
-    for r0 in range(0, yp.n, rows_per_block):
-        y, m = _f16_rows(yp, r0, min(yp.n, r0 + rows_per_block))
-        counts = torch.empty(m, dtype=torch.int32, device=dev)
-        slot_idx = torch.empty(m * cap, dtype=torch.int32, device=dev)
-        slot_w = torch.empty(m * cap, dtype=torch.float16, device=dev)
-        _check(L.pg_minkowski_eps_slots(_ptr(xp.buf), xp.n, xp.npad, y, m, yp.npad, xp.d, sim, int(cmp), e16, cap,
-                                        _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _stream()), "pg_minkowski_eps_slots")
-        indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
-        _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-        over = counts > cap
-        nnz, n_over = (int(v) for v in torch.stack([indptr[-1], over.sum()]).cpu())     # the one sync
-        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-        weights = torch.empty(max(nnz, 1), dtype=torch.float16, device=dev)[:nnz]
-        if nnz:
-            _check(L.pg_minkowski_eps_compact(m, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(indptr), _ptr(indices),
-                                              _ptr(weights), _stream()), "pg_minkowski_eps_compact")
-        if n_over:
-            rows = compact_flags(over.to(torch.uint8), count=n_over)
-            _check(L.pg_minkowski_eps_fill_rows(_ptr(xp.buf), xp.n, xp.npad, y, m, yp.npad, xp.d, sim, int(cmp), e16, _ptr(rows),
-                                                n_over, _ptr(indptr), _ptr(indices), _ptr(weights), _stream()),
-                   "pg_minkowski_eps_fill_rows")
-        del slot_idx, slot_w
-        parts.append((indptr, indices, weights))
-    if len(parts) == 1:
-        return parts[0]
-    base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
-    for indptr, _, _ in parts:
-        ptrs.append(indptr[1:] + base)
-        base += int(indptr[-1].item())
-    return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
+    sel = (1 if similarity else 0, int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0), float(np.float16(eps)))
+
+    def call(fn, name, ops, *args):
+        _check(fn(_ptr(xp.buf), xp.n, xp.npad, ops[0], ops[1], yp.npad, xp.d, *sel, *args, _stream()), name)
+
+    return _slots_eps(
+        yp.n, lambda r0, r1: _f16_rows(yp, r0, r1),
+        lambda ops, si, sw, cnt: call(L.pg_minkowski_eps_slots, "pg_minkowski_eps_slots", ops, cap, _ptr(si), _ptr(sw), _ptr(cnt)),
+        lambda *a: _check(L.pg_minkowski_eps_compact(*a), "pg_minkowski_eps_compact"),
+        lambda ops, rows, n_over, ip, ix, w: call(L.pg_minkowski_eps_fill_rows, "pg_minkowski_eps_fill_rows", ops, _ptr(rows),
+                                                  n_over, _ptr(ip), _ptr(ix), _ptr(w)),
+        torch.float16, cap, rows_per_block, xp.buf.device)
 
 
 class CosineOperand:
@@ -1024,52 +1037,27 @@ def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
     return idx, w
 
 
-def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False):
+def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False, rows_per_block=None):
     """CSR of the entries of cosine_dense(xc, yc, similarity) with comp(d, eps) & (d > 0)  [comp(eps, s) & (s < 1)],
     `eps` rounded to fp32 first (as torch does when an fp32 tensor meets a Python number).  The minkowski_eps
-    structure: one sweep into per-row slots with exact counts, scan, compaction, and a second sweep over the rows
-    with more than `cap` matches; one host sync per block of rows.  keep_zero: without the d > 0 (s < 1) test.
+    structure (_slots_eps): one sweep into per-row slots with exact counts, scan, compaction, and a second sweep over
+    the rows with more than `cap` matches; one host sync per block of rows.  keep_zero: without the d > 0 (s < 1) test.
     Returns (indptr int64 [m+1], indices int32 [nnz], weights fp32 [nnz])."""
     _cos_same_d(xc, yc)
     L = lib()
-    dev = xc.packed.buf.device
     cap = max(1, int(cap))
-    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
-    e32 = float(np.float32(eps))
-    sim = 1 if similarity else 0
-    rows_per_block = max(64, (256 << 20) // (cap * 8))                # int32 + fp32 per slot
-    parts = []
-    for r0 in range(0, yc.n, rows_per_block):
-        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
-        ops = _cos_ops(xc, y, yn, yr, m, yc.packed.npad)
-        counts = torch.empty(m, dtype=torch.int32, device=dev)
-        slot_idx = torch.empty(m * cap, dtype=torch.int32, device=dev)
-        slot_w = torch.empty(m * cap, dtype=torch.float32, device=dev)
-        _check(L.pg_cosine_eps_slots(*ops, sim, int(cmp), e32, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _stream()),
-               "pg_cosine_eps_slots")
-        indptr = torch.empty(m + 1, dtype=torch.int64, device=dev)
-        scratch = torch.empty(int(L.pg_scan_scratch_bytes(m)), dtype=torch.uint8, device=dev)
-        _check(L.pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
-        over = counts > cap
-        nnz, n_over = (int(v) for v in torch.stack([indptr[-1], over.sum()]).cpu())     # the one sync
-        indices = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz]
-        weights = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)[:nnz]
-        if nnz:
-            _check(L.pg_cosine_eps_compact(m, cap, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(indptr), _ptr(indices),
-                                           _ptr(weights), _stream()), "pg_cosine_eps_compact")
-        if n_over:
-            rows = compact_flags(over.to(torch.uint8), count=n_over)
-            _check(L.pg_cosine_eps_fill_rows(*ops, sim, int(cmp), e32, _ptr(rows), n_over, _ptr(indptr), _ptr(indices),
-                                             _ptr(weights), _stream()), "pg_cosine_eps_fill_rows")
-        del slot_idx, slot_w
-        parts.append((indptr, indices, weights))
-    if len(parts) == 1:
-        return parts[0]
-    base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
-    for indptr, _, _ in parts:
-        ptrs.append(indptr[1:] + base)
-        base += int(indptr[-1].item())
-    return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
+    sel = (1 if similarity else 0, int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0), float(np.float32(eps)))
+
+    def call(fn, name, ops, *args):
+        _check(fn(*_cos_ops(xc, *ops, yc.packed.npad), *sel, *args, _stream()), name)
+
+    return _slots_eps(
+        yc.n, yc.rows,
+        lambda ops, si, sw, cnt: call(L.pg_cosine_eps_slots, "pg_cosine_eps_slots", ops, cap, _ptr(si), _ptr(sw), _ptr(cnt)),
+        lambda *a: _check(L.pg_cosine_eps_compact(*a), "pg_cosine_eps_compact"),
+        lambda ops, rows, n_over, ip, ix, w: call(L.pg_cosine_eps_fill_rows, "pg_cosine_eps_fill_rows", ops, _ptr(rows), n_over,
+                                                  _ptr(ip), _ptr(ix), _ptr(w)),
+        torch.float32, cap, rows_per_block, xc.packed.buf.device)
 
 
 COMM_ID_BYTES = 128

@@ -16,18 +16,6 @@
 static thread_local char g_err[256] = "";
 
 void pg_set_error(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
-static int fail(int code, const char *msg) {
-  snprintf(g_err, sizeof(g_err), "%s", msg);
-  return code;
-}
-static int hipfail(hipError_t e, const char *where) {
-  snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
-  return (int)e;
-}
-static int launched(int rc, const char *where) {
-  if (rc != 0) return hipfail((hipError_t)rc, where);
-  return 0;
-}
 
 // stage-1 lower-bound filter of the engine: adaptive by default; PG_LB_FILTER=0 disables, =2 forces it on
 static int lb_filter_mode() { return getenv("PG_LB_FILTER") ? atoi(getenv("PG_LB_FILTER")) : 1; }
@@ -64,9 +52,9 @@ int pg_device_info(int *cus, int *wave, char *arch, int arch_len) {
   int dev = 0;
   hipDeviceProp_t prop;
   hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hipfail(e, "hipGetDevice");
+  if (e != hipSuccess) return pg_launched((int)e, "hipGetDevice");
   e = hipGetDeviceProperties(&prop, dev);
-  if (e != hipSuccess) return hipfail(e, "hipGetDeviceProperties");
+  if (e != hipSuccess) return pg_launched((int)e, "hipGetDeviceProperties");
   if (cus) *cus = prop.multiProcessorCount;
   if (wave) *wave = prop.warpSize;
   if (arch && arch_len > 0) snprintf(arch, (size_t)arch_len, "%s", prop.gcnArchName);
@@ -339,14 +327,14 @@ __global__ __launch_bounds__(256) void pg_csr_row_stats_kernel(const long long *
 // `l` may be the packed width rounded up to whole 32-token groups (256 for 8 groups); only
 // pg_pack_planes, which sees the real tokens, enforces L <= 255 (a distance must fit uint8).
 static int check_l(int l, int bits = 8, bool exact = false) {
-  if (l <= 0) return fail(PG_E_BADARG, "sequence length must be positive");
+  if (l <= 0) return pg_fail(PG_E_BADARG, "sequence length must be positive");
   const int maxg = bits == 5 ? PG_MAX_L_5BIT / 32 + 1 : PG_MAX_L / 32;
   if ((l + 31) / 32 > maxg || (exact && l > (bits == 5 ? PG_MAX_L_5BIT : PG_MAX_L)))
-    return fail(PG_E_TOOLONG, "sequence length exceeds the native limit (128 tokens, 255 with 5 bit planes)");
+    return pg_fail(PG_E_TOOLONG, "sequence length exceeds the native limit (128 tokens, 255 with 5 bit planes)");
   return 0;
 }
 static int check_bits(int b) {
-  if (b != PG_BITS_5 && b != PG_BITS_8) return fail(PG_E_BADARG, "bits must be 5 or 8");
+  if (b != PG_BITS_5 && b != PG_BITS_8) return pg_fail(PG_E_BADARG, "bits must be 5 or 8");
   return 0;
 }
 
@@ -484,7 +472,7 @@ static bool probe_enabled() {
 // zeroes and fills workspace[64, ...): returns the gate words through *gate
 static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 span, u32 need, void *workspace, hipStream_t s,
                      const u32 **gate) {
-  if (!workspace) return fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
+  if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
   u32 *gates = (u32 *)((char *)workspace + PG_WS_GATES), *counts = (u32 *)((char *)workspace + PG_WS_COUNTS);
   static_assert(PG_WS_COUNTS + 8 * PG_PROBE_ROWS * PG_PROBE_WAVES <= PG_WS_PARTIAL, "pg_workspace_bytes");
   ProbeParams pp;
@@ -495,11 +483,11 @@ static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 
   if (const char *es = getenv("PG_PROBE_S")) { if (atoi(es) > 0 && atoi(es) <= PG_PROBE_ROWS) pp.nsample = atoi(es); }   // (experiments)
   if (const char *ew = getenv("PG_PROBE_W")) { if (atoi(ew) > 0 && atoi(ew) <= PG_PROBE_WAVES) pp.wavesPerRow = atoi(ew); }
   pp.near = near; pp.lo = lo; pp.span = span; pp.counts = counts;
-  if (int rc = launched(kProbe[pg_ngroups(l) - 1](bits, pp, s), "pg_probe_kernel")) return rc;
+  if (int rc = pg_launched(kProbe[pg_ngroups(l) - 1](bits, pp, s), "pg_probe_kernel")) return rc;
   const int force = getenv("PG_GATE_FORCE") ? atoi(getenv("PG_GATE_FORCE")) : -1;
   // (counts of a short sample: pg_decide_kernel reads counts[nsample + s] - same layout as the probe wrote)
   pg_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates);   // (PG_PROBE_ROWS <= 64)
-  if (int rc = launched((int)hipGetLastError(), "pg_decide_kernel")) return rc;
+  if (int rc = pg_launched("pg_decide_kernel")) return rc;
   *gate = gates;
   return 0;
 }
@@ -550,7 +538,7 @@ static const compact_fn kCompact[8] = {pg_launch_compact_g1, pg_launch_compact_g
 // (capped at 4x) and 1.21e-11 s per makespan unit and column.
 static int plan_rows(int64_t nrows, NsqParams *p, int *grid, int occ, double recBytes, int maxRows = PG_RB) {
   const int cus = cu_count();
-  if (cus <= 0) return fail(PG_E_NODEV, "no HIP device");
+  if (cus <= 0) return pg_fail(PG_E_NODEV, "no HIP device");
   long long rpw = 4;
   if (getenv("PG_WAVES_PER_CU")) {
     const long long maxWaves = (long long)cus * waves_per_cu();
@@ -593,14 +581,14 @@ extern "C" {
 
 int pg_pack_planes(const void *src, int elem_bytes, int64_t n, int l, int64_t ld, const int64_t *rows, int bits,
                    void *planes, int64_t npad, uint32_t *flags, void *stream) {
-  if (!src || !planes || !flags || n < 0 || ld < l) return fail(PG_E_BADARG, "pg_pack_planes: bad argument");
+  if (!src || !planes || !flags || n < 0 || ld < l) return pg_fail(PG_E_BADARG, "pg_pack_planes: bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits, true)) return rc;
-  if (npad < n || npad % 256) return fail(PG_E_BADARG, "pg_pack_planes: npad must be pg_npad(n)");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_pack_planes: npad must be pg_npad(n)");
   const int ng = pg_ngroups(l), nq = pg_nchunks(l, bits);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s);
-  if (e != hipSuccess) return hipfail(e, "hipMemsetAsync");
+  if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
   const dim3 grid((unsigned)((npad + 255) / 256)), block(256);
   const long long *r = (const long long *)rows;
   u32 *pl = (u32 *)planes;
@@ -614,22 +602,22 @@ int pg_pack_planes(const void *src, int elem_bytes, int64_t n, int l, int64_t ld
     case 2: PG_PACK(short); break;
     case 4: PG_PACK(int); break;
     case 8: PG_PACK(long long); break;
-    default: return fail(PG_E_BADARG, "pg_pack_planes: elem_bytes must be 1, 2, 4 or 8");
+    default: return pg_fail(PG_E_BADARG, "pg_pack_planes: elem_bytes must be 1, 2, 4 or 8");
   }
 #undef PG_PACK
-  return launched((int)hipGetLastError(), "pg_pack_kernel");
+  return pg_launched("pg_pack_kernel");
 }
 
 int pg_pack_bytes(const uint8_t *src, int64_t n, int width, int64_t ld, const int64_t *rows, const uint8_t *lut256, int bits,
                   void *planes, int64_t npad, uint8_t *tokens_out, uint32_t *flags, void *stream) {
-  if (!src || !lut256 || !planes || !flags || n < 0 || ld < width) return fail(PG_E_BADARG, "pg_pack_bytes: bad argument");
+  if (!src || !lut256 || !planes || !flags || n < 0 || ld < width) return pg_fail(PG_E_BADARG, "pg_pack_bytes: bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(width, bits, true)) return rc;
-  if (npad < n || npad % 256) return fail(PG_E_BADARG, "pg_pack_bytes: npad must be pg_npad(n)");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_pack_bytes: npad must be pg_npad(n)");
   const int ng = pg_ngroups(width), nq = pg_nchunks(width, bits);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s);
-  if (e != hipSuccess) return hipfail(e, "hipMemsetAsync");
+  if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
   const dim3 grid((unsigned)((npad + 255) / 256)), block(256);
   if (bits == 5)
     pg_pack_kernel<unsigned char, 5><<<grid, block, 0, s>>>(src, n, width, ld, (const long long *)rows, (u32 *)planes, npad, ng, nq,
@@ -637,33 +625,33 @@ int pg_pack_bytes(const uint8_t *src, int64_t n, int width, int64_t ld, const in
   else
     pg_pack_kernel<unsigned char, 8><<<grid, block, 0, s>>>(src, n, width, ld, (const long long *)rows, (u32 *)planes, npad, ng, nq,
                                                             flags, lut256, tokens_out);
-  return launched((int)hipGetLastError(), "pg_pack_kernel(bytes)");
+  return pg_launched("pg_pack_kernel(bytes)");
 }
 
 int pg_hamming_dense(const void *x_planes, int64_t n, int64_t x_npad, const void *y_planes, int64_t m, int64_t y_npad,
                      int l, int bits, void *out, int out_elem_bytes, int64_t ldo, int accumulate, void *stream) {
   if (!x_planes || !y_planes || !out || n <= 0 || m <= 0 || ldo < n)
-    return fail(PG_E_BADARG, "pg_hamming_dense: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_hamming_dense: bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
   if (out_elem_bytes != 1 && out_elem_bytes != 2 && out_elem_bytes != 4 && out_elem_bytes != 8)
-    return fail(PG_E_BADARG, "pg_hamming_dense: out_elem_bytes must be 1, 2, 4 or 8");
-  if (x_npad < n || x_npad % 256 || y_npad < m) return fail(PG_E_BADARG, "pg_hamming_dense: bad npad");
-  if ((m + PG_RBD - 1) / PG_RBD > 65535) return fail(PG_E_BADARG, "pg_hamming_dense: m too large for one launch");
+    return pg_fail(PG_E_BADARG, "pg_hamming_dense: out_elem_bytes must be 1, 2, 4 or 8");
+  if (x_npad < n || x_npad % 256 || y_npad < m) return pg_fail(PG_E_BADARG, "pg_hamming_dense: bad npad");
+  if ((m + PG_RBD - 1) / PG_RBD > 65535) return pg_fail(PG_E_BADARG, "pg_hamming_dense: m too large for one launch");
   DenseParams p;
   p.xPlanes = (const uint4 *)x_planes; p.xNpad = x_npad; p.n = n;
   p.yPlanes = (const uint4 *)y_planes; p.yNpad = y_npad; p.m = m;
   p.out = out; p.ldo = ldo; p.outBytes = out_elem_bytes; p.accumulate = accumulate ? 1 : 0;
-  return launched(kDense[pg_ngroups(l) - 1](bits, p, (hipStream_t)stream), "pg_dense_kernel");
+  return pg_launched(kDense[pg_ngroups(l) - 1](bits, p, (hipStream_t)stream), "pg_dense_kernel");
 }
 
 static int fill_nsq(NsqParams *p, const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows,
                     const void *col_planes, int64_t col_npad, int64_t ncols, int l, int bits) {
-  if (!row_planes || !col_planes || row0 < 0 || nrows <= 0 || ncols <= 0) return fail(PG_E_BADARG, "bad argument");
+  if (!row_planes || !col_planes || row0 < 0 || nrows <= 0 || ncols <= 0) return pg_fail(PG_E_BADARG, "bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
-  if (col_npad < ncols || col_npad % 256 || row_npad < row0 + nrows) return fail(PG_E_BADARG, "bad npad");
-  if (ncols > 0x7fffffffLL) return fail(PG_E_TOOMANY, "ncols exceeds int32 indices");
+  if (col_npad < ncols || col_npad % 256 || row_npad < row0 + nrows) return pg_fail(PG_E_BADARG, "bad npad");
+  if (ncols > 0x7fffffffLL) return pg_fail(PG_E_TOOMANY, "ncols exceeds int32 indices");
   memset(p, 0, sizeof(*p));
   p->filter = lb_filter_mode();
   p->rowPlanes = (const uint4 *)row_planes; p->rowNpad = row_npad; p->row0 = row0; p->nrows = nrows;
@@ -789,10 +777,10 @@ static void plan_mm(int64_t nrows, NsqParams *p, int *grid, int rb = PG_MM_RB, i
 // right before the kernel.  Launch-private by contract, so concurrent launches - other streams, other devices,
 // any number of them - never share a word (the static ring of counters this replaces did after 256 launches).
 static int pass_counter(NsqParams *p, void *workspace, hipStream_t s) {
-  if (!workspace) return fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
+  if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
   unsigned *c = (unsigned *)workspace;
   const hipError_t e = hipMemsetAsync(c, 0, PG_WS_GATES, s);   // (the counters and the row-block flags of a launch in column pieces)
-  if (e != hipSuccess) return hipfail(e, "workspace: hipMemsetAsync");
+  if (e != hipSuccess) return pg_launched((int)e, "workspace: hipMemsetAsync");
   p->mmPassCounter = c;
   return 0;
 }
@@ -803,7 +791,7 @@ int pg_eps_slots(const void *row_planes, int64_t row_npad, int64_t row0, int64_t
   NsqParams p;
   if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
   if (!slot_idx || !slot_w || !counts || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
-    return fail(PG_E_BADARG, "pg_eps_slots: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_eps_slots: bad argument");
   eps_interval(cmp, eps, &p.lo, &p.span);
   p.hi1 = (p.lo > 0xFFFFFF00u - 1u) ? 0u : p.lo + p.span + 1u;   // empty interval: nothing can match
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.counts = counts;
@@ -812,10 +800,10 @@ int pg_eps_slots(const void *row_planes, int64_t row_npad, int64_t row0, int64_t
   if (use_mm_engine(nrows, l, false)) {
     plan_mm(nrows, &p, &grid);
     if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
-    return launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps)");
+    return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps)");
   }
   if (int rc = plan_rows(nrows, &p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits))) return rc;
-  return launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps)");
+  return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps)");
 }
 
 // Square self-graph, every unordered pair evaluated once (Hamming and the comparators are symmetric):
@@ -827,13 +815,13 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
   NsqParams p;
   if (int rc = fill_nsq(&p, planes, npad, 0, n, planes, npad, n, l, bits)) return rc;
   if (!slot_idx || !slot_w || !counts_up || !counts_lo || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
-    return fail(PG_E_BADARG, "pg_eps_slots_sym: bad argument");
-  if (n >= (1ll << 27)) return fail(PG_E_TOOMANY, "pg_eps_slots_sym: n must be below 2^27");
+    return pg_fail(PG_E_BADARG, "pg_eps_slots_sym: bad argument");
+  if (n >= (1ll << 27)) return pg_fail(PG_E_TOOMANY, "pg_eps_slots_sym: n must be below 2^27");
   eps_interval(cmp, eps, &p.lo, &p.span);
   p.hi1 = (p.lo > 0xFFFFFF00u - 1u) ? 0u : p.lo + p.span + 1u;
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.counts = counts_up; p.countsLo = counts_lo;
   hipError_t e = hipMemsetAsync(counts_lo, 0, (size_t)n * sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return hipfail(e, "hipMemsetAsync");
+  if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
   int grid = 0;
   // Large graphs: the data decide (probe above) between this path and a plain rectangular sweep on the VALU engine,
   // which writes the same slots (every match at the front of its row, counts_lo stays zero): dense graphs.
@@ -845,7 +833,7 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
     r.gate = gate + 1; r.gateMask = 1u << 1;
     int rgrid = 0;
     if (int rc = plan_rows(n, &r, &rgrid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits))) return rc;
-    if (int rc = launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, r, rgrid, (hipStream_t)stream), "pg_nsq_kernel(eps, gated)")) return rc;
+    if (int rc = pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, r, rgrid, (hipStream_t)stream), "pg_nsq_kernel(eps, gated)")) return rc;
     p.gate = gate + 1; p.gateMask = 1u << 0;
   }
   // Rows near the top sweep almost everything, rows near the bottom almost nothing; workgroups are
@@ -864,7 +852,7 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
     const bool fine = pg_nchunks(l, bits) <= 3 && !(getenv("PG_MM_PLAN") && atoi(getenv("PG_MM_PLAN")) == 2);
     plan_mm(n, &p, &grid, PG_MM_RB, 4, false, fine ? (int)rs : 0);
     if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
-    return launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps sym)");
+    return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps sym)");
   }
   if (!getenv("PG_ROWS_PER_WAVE") && !getenv("PG_WAVES_PER_CU")) {
     const long long r = n >= 80000 ? 16 : 8;
@@ -873,7 +861,7 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
   } else if (int rc = plan_rows(n, &p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS_SYM, bits), 16.0 * pg_nchunks(l, bits), 16)) {
     return rc;
   }
-  return launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps sym)");
+  return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps sym)");
 }
 
 int pg_eps_compact_sym(const void *planes, int64_t npad, int64_t n, int l, int bits, int cmp, double eps, int cap,
@@ -884,7 +872,7 @@ int pg_eps_compact_sym(const void *planes, int64_t npad, int64_t n, int l, int b
   c.skipOverflow = leave_overflow ? 1 : 0;
   if (int rc = fill_nsq(&c.e, planes, npad, 0, n, planes, npad, n, l, bits)) return rc;
   if (!slot_idx || !slot_w || !counts_up || !counts_lo || !indptr || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
-    return fail(PG_E_BADARG, "pg_eps_compact_sym: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_eps_compact_sym: bad argument");
   eps_interval(cmp, eps, &c.e.lo, &c.e.span);
   c.e.hi1 = c.e.lo + c.e.span + 1u;
   c.e.cap = (u32)cap;
@@ -893,7 +881,7 @@ int pg_eps_compact_sym(const void *planes, int64_t npad, int64_t n, int l, int b
   c.e.counts = const_cast<u32 *>(counts_up);
   c.e.countsLo = const_cast<u32 *>(counts_lo);
   c.indptr = (const long long *)indptr; c.indices = indices; c.weights = weights;
-  return launched(kCompact[pg_ngroups(l) - 1](bits, c, (hipStream_t)stream), "pg_compact_kernel(sym)");
+  return pg_launched(kCompact[pg_ngroups(l) - 1](bits, c, (hipStream_t)stream), "pg_compact_kernel(sym)");
 }
 
 int64_t pg_scan_scratch_bytes(int64_t n) {
@@ -902,14 +890,14 @@ int64_t pg_scan_scratch_bytes(int64_t n) {
 }
 
 int pg_exclusive_scan(const uint32_t *counts, int64_t n, int64_t *indptr, void *scratch, void *stream) {
-  if (!counts || !indptr || !scratch || n <= 0) return fail(PG_E_BADARG, "pg_exclusive_scan: bad argument");
+  if (!counts || !indptr || !scratch || n <= 0) return pg_fail(PG_E_BADARG, "pg_exclusive_scan: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const long long nb = (n + PG_SCAN_TILE - 1) / PG_SCAN_TILE;
   long long *part = (long long *)scratch;
   pg_scan_partials<u32><<<dim3((unsigned)nb), dim3(256), 0, s>>>(counts, n, part);
   pg_scan_single<<<dim3(1), dim3(256), 0, s>>>(part, nb);
   pg_scan_apply<u32, 0><<<dim3((unsigned)nb), dim3(256), 0, s>>>(counts, n, part, nb, (long long *)indptr, nullptr);
-  return launched((int)hipGetLastError(), "pg_scan");
+  return pg_launched("pg_scan");
 }
 
 int pg_eps_compact(const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows, const void *col_planes,
@@ -920,7 +908,7 @@ int pg_eps_compact(const void *row_planes, int64_t row_npad, int64_t row0, int64
   c.skipOverflow = leave_overflow ? 1 : 0;
   if (int rc = fill_nsq(&c.e, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
   if (!slot_idx || !slot_w || !counts || !indptr || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
-    return fail(PG_E_BADARG, "pg_eps_compact: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_eps_compact: bad argument");
   eps_interval(cmp, eps, &c.e.lo, &c.e.span);
   c.e.hi1 = c.e.lo + c.e.span + 1u;
   c.e.cap = (u32)cap;
@@ -928,7 +916,7 @@ int pg_eps_compact(const void *row_planes, int64_t row_npad, int64_t row0, int64
   c.e.slotW = const_cast<unsigned char *>(slot_w);
   c.e.counts = const_cast<u32 *>(counts);
   c.indptr = (const long long *)indptr; c.indices = indices; c.weights = weights;
-  return launched(kCompact[pg_ngroups(l) - 1](bits, c, (hipStream_t)stream), "pg_compact_kernel");
+  return pg_launched(kCompact[pg_ngroups(l) - 1](bits, c, (hipStream_t)stream), "pg_compact_kernel");
 }
 
 // Rows whose matches did not fit their slot: the all-pairs engine runs once more over just those rows
@@ -939,10 +927,10 @@ int pg_eps_fill_rows(const void *row_planes, int64_t row_npad, int64_t row0, con
                      const int64_t *indptr, int32_t *indices, uint8_t *weights, uint32_t *scratch_counts, void *workspace,
                      void *stream) {
   NsqParams p;
-  if (!row_list || n_list <= 0) return fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
+  if (!row_list || n_list <= 0) return pg_fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
   if (int rc = fill_nsq(&p, row_planes, row_npad, row0, n_list, col_planes, col_npad, ncols, l, bits)) return rc;
   if (!indptr || !indices || !weights || !scratch_counts || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
-    return fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
   eps_interval(cmp, eps, &p.lo, &p.span);
   p.hi1 = (p.lo > 0xFFFFFF00u - 1u) ? 0u : p.lo + p.span + 1u;
   p.cap = 0xFFFFFFFFu;                                     // a row's place in the CSR holds all of its matches
@@ -951,7 +939,7 @@ int pg_eps_fill_rows(const void *row_planes, int64_t row_npad, int64_t row0, con
   int grid = 0;
   plan_mm(n_list, &p, &grid);
   if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
-  return launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps fill)");
+  return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps fill)");
 }
 
 // What a kNN launch of `nrows` rows x `ncols` columns takes (ms) on the 32-row (rb = 32) or the 64-row (rb = 64) short-list
@@ -1000,9 +988,9 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
                       uint32_t *last_keys, int32_t *idx_out, uint8_t *dist_out, void *workspace, void *stream) {
   NsqParams p;
   if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
-  if (!idx_out || !dist_out) return fail(PG_E_BADARG, "pg_knn_hamming: bad argument");
-  if (k < 1 || first < 0 || first > 1 || first + k > 64) return fail(PG_E_BADARG, "pg_knn_hamming: k out of range");
-  if (ncols > PG_MAX_N_KNN) return fail(PG_E_TOOMANY, "pg_knn_hamming: ncols exceeds 2^24");
+  if (!idx_out || !dist_out) return pg_fail(PG_E_BADARG, "pg_knn_hamming: bad argument");
+  if (k < 1 || first < 0 || first > 1 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_knn_hamming: k out of range");
+  if (ncols > PG_MAX_N_KNN) return pg_fail(PG_E_TOOMANY, "pg_knn_hamming: ncols exceeds 2^24");
   p.k = k; p.knnFirst = first; p.floorKeys = floor_keys; p.lastKeys = last_keys;
   // optimistic stage-1 cap.  pg_nsq.h: 8 = half of what unrelated sequences show in its 32-bit plane-0 bound.
   // pg_mm.h: 10 with the 54-bit signature (L > 32) - unrelated pairs below it are one in 3e6, kNN time is flat from
@@ -1017,7 +1005,7 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
   auto launch_valu = [&](NsqParams &q) -> int {
     int g = 0;
     if (int rc = plan_rows(nrows, &q, &g, nsq_occupancy(pg_ngroups(l), PG_MODE_KNN, bits), 16.0 * pg_nchunks(l, bits), PG_RB_KNN)) return rc;
-    return launched(kNsq[pg_ngroups(l) - 1](PG_MODE_KNN, bits, q, g, (hipStream_t)stream), "pg_nsq_kernel(knn)");
+    return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_KNN, bits, q, g, (hipStream_t)stream), "pg_nsq_kernel(knn)");
   };
   if (mm) {
     // Large launches: the data decide between the engines (probe above): unclustered data -> the VALU engine
@@ -1079,7 +1067,7 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
       kr.count = p.mmEvict; kr.rows = p.mmEvictRows; kr.baseRow = row0; kr.k = k;
       kr.knnIdx = idx_out; kr.knnDist = dist_out; kr.gate = p.gate; kr.gateMask = p.gateMask;
       const long long cap = (long long)(cu_count() > 0 ? cu_count() : 256) * 8;   // (one workgroup per row, the rows in turns)
-      return launched(kKnnRows[ng - 1](bits, kr, (int)(nrows < cap ? nrows : cap), (hipStream_t)stream), "pg_knn_rows_kernel");
+      return pg_launched(kKnnRows[ng - 1](bits, kr, (int)(nrows < cap ? nrows : cap), (hipStream_t)stream), "pg_knn_rows_kernel");
     };
     if (mainRows < nrows) {
       const long long rem = nrows - mainRows, nb = (rem + rbm - 1) / rbm;
@@ -1101,11 +1089,11 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
         p.mmGridWaves = (p.mmPasses + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
         grid = (int)(p.mmGridWaves / PG_WG_WAVES);
       }
-      if (int rc = launched(kMm[ng - 1](modeM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(knn + column pieces)")) return rc;
+      if (int rc = pg_launched(kMm[ng - 1](modeM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(knn + column pieces)")) return rc;
       pg_knn_merge_kernel<<<dim3((unsigned)((rem + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES))), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
           p.mmPartial, rem, pieces, k, idx_out + mainRows * k, dist_out + mainRows * k, p.knnGuess, p.mmEvict, p.mmEvictRows,
           (long long)row0 + mainRows, p.gate, p.gateMask);
-      if (int rc = launched((int)hipGetLastError(), "pg_knn_merge_kernel")) return rc;
+      if (int rc = pg_launched("pg_knn_merge_kernel")) return rc;
       p.nrows = nrows;                                      // (the gated 32-row alternative below covers all rows)
     }
     if (alt32) {
@@ -1117,10 +1105,10 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
       plan_mm(nrows, &q, &qgrid, PG_MM_RB, occ1, true);
       q.mmPassCounter = p.mmPassCounter + 8;
       q.gateMask = 1u << 2;
-      if (int rc = launched(kMm[pg_ngroups(l) - 1](PG_MODE_KNN_SHORT, bits, q, qgrid, (hipStream_t)stream), "pg_mm_kernel(knn, 32-row passes, gated)")) return rc;
+      if (int rc = pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_KNN_SHORT, bits, q, qgrid, (hipStream_t)stream), "pg_mm_kernel(knn, 32-row passes, gated)")) return rc;
     }
     if (mainRows < nrows) return finish_evicted();          // (the main launch and the pieces are out already)
-    if (int rc = launched(kMm[pg_ngroups(l) - 1](two ? PG_MODE_KNN_SHORT2 : (shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN), bits, p, grid,
+    if (int rc = pg_launched(kMm[pg_ngroups(l) - 1](two ? PG_MODE_KNN_SHORT2 : (shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN), bits, p, grid,
                                                  (hipStream_t)stream), "pg_mm_kernel(knn)")) return rc;
     return finish_evicted();
   }
@@ -1130,7 +1118,7 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
 int pg_knn_hamming(const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows, const void *col_planes,
                    int64_t col_npad, int64_t ncols, int l, int bits, int k, int32_t *idx_out, uint8_t *dist_out,
                    void *workspace, void *stream) {
-  if (k < 1 || k > PG_MAX_K) return fail(PG_E_BADARG, "pg_knn_hamming: k must be in 1..63");
+  if (k < 1 || k > PG_MAX_K) return pg_fail(PG_E_BADARG, "pg_knn_hamming: k must be in 1..63");
   return knn_launch(row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits, k, 1, nullptr, nullptr,
                     idx_out, dist_out, workspace, stream);
 }
@@ -1139,7 +1127,7 @@ int pg_knn_hamming_round(const void *row_planes, int64_t row_npad, int64_t row0,
                          int64_t col_npad, int64_t ncols, int l, int bits, int k, int first_round,
                          const uint32_t *floor_keys, uint32_t *last_keys, int32_t *idx_out, uint8_t *dist_out,
                          void *workspace, void *stream) {
-  if (!last_keys || (!first_round && !floor_keys)) return fail(PG_E_BADARG, "pg_knn_hamming_round: key arrays required");
+  if (!last_keys || (!first_round && !floor_keys)) return pg_fail(PG_E_BADARG, "pg_knn_hamming_round: key arrays required");
   return knn_launch(row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits, k, first_round ? 1 : 0,
                     first_round ? nullptr : floor_keys, last_keys, idx_out, dist_out, workspace, stream);
 }
@@ -1230,12 +1218,12 @@ int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const
                          int64_t db_npad, int l, int bits, int k, const uint32_t *floor_keys, uint32_t *last_keys,
                          int32_t *idx_out, uint8_t *dist_out, void *workspace, int64_t workspace_bytes, void *stream) {
   if (!q_planes || !db_planes || !idx_out || !dist_out || nq <= 0 || ndb <= 0 || workspace_bytes < 0)
-    return fail(PG_E_BADARG, "pg_query_knn_hamming: bad argument");
-  if (k < 1 || k > 64) return fail(PG_E_BADARG, "pg_query_knn_hamming: k must be in 1..64");
+    return pg_fail(PG_E_BADARG, "pg_query_knn_hamming: bad argument");
+  if (k < 1 || k > 64) return pg_fail(PG_E_BADARG, "pg_query_knn_hamming: k must be in 1..64");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
-  if (q_npad < nq || db_npad < ndb || db_npad % 256) return fail(PG_E_BADARG, "pg_query_knn_hamming: bad npad");
-  if (ndb >= PG_MAX_N_KNN) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: ndb must be below 2^24");
+  if (q_npad < nq || db_npad < ndb || db_npad % 256) return pg_fail(PG_E_BADARG, "pg_query_knn_hamming: bad npad");
+  if (ndb >= PG_MAX_N_KNN) return pg_fail(PG_E_TOOMANY, "pg_query_knn_hamming: ndb must be below 2^24");
   // pieces: the plan, bounded by the workspace the caller passed (pg_query_workspace_bytes gives the plan's size)
   long long pieces = query_pieces(nq, ndb, k);
   const long long fit = workspace ? workspace_bytes / ((long long)nq * k * 4) : 0;
@@ -1251,14 +1239,14 @@ int pg_query_knn_hamming(const void *q_planes, int64_t nq, int64_t q_npad, const
   p.floorKeys = floor_keys; p.partial = (u32 *)workspace;
   p.knnIdx = idx_out; p.knnDist = dist_out; p.lastKeys = last_keys;
   const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
-  if (ngrp * p.pieces > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
+  if (ngrp * p.pieces > 0x7FFFFFFFll) return pg_fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = launched(kQuery[pg_ngroups(l) - 1](bits, p, ngrp * p.pieces, s), "pg_query_knn_kernel")) return rc;
+  if (int rc = pg_launched(kQuery[pg_ngroups(l) - 1](bits, p, ngrp * p.pieces, s), "pg_query_knn_kernel")) return rc;
   if (p.pieces == 1) return 0;
-  if (nq > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
+  if (nq > 0x7FFFFFFFll) return pg_fail(PG_E_TOOMANY, "pg_query_knn_hamming: too many queries for one launch");
   pg_query_merge_kernel<<<dim3((unsigned)nq), dim3(PG_WG_THREADS), 0, s>>>((const u32 *)workspace, p.pieces, k, idx_out,
                                                                              dist_out, last_keys);
-  return launched((int)hipGetLastError(), "pg_query_merge_kernel");
+  return pg_launched("pg_query_merge_kernel");
 }
 
 }  // extern "C"
@@ -1287,23 +1275,23 @@ static int query_eps_launch(const char *who, int fill, const void *q_planes, int
                             const void *db_planes, int64_t ndb, int64_t db_npad, int l, int bits, int cmp, double eps,
                             int64_t nseg, QueryEpsParams &p, void *stream) {
   if (!q_planes || !db_planes || nq <= 0 || ndb <= 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT || !(eps == eps))
-    return fail(PG_E_BADARG, who);
+    return pg_fail(PG_E_BADARG, who);
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
-  if (q_npad < nq || db_npad < ndb || db_npad % 256) return fail(PG_E_BADARG, "pg_query_eps: bad npad");
-  if (ndb > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_eps: ndb must fit int32 column indices");
+  if (q_npad < nq || db_npad < ndb || db_npad % 256) return pg_fail(PG_E_BADARG, "pg_query_eps: bad npad");
+  if (ndb > 0x7FFFFFFFll) return pg_fail(PG_E_TOOMANY, "pg_query_eps: ndb must fit int32 column indices");
   const long long ntiles = (ndb + PG_QUERY_TILE - 1) / PG_QUERY_TILE;
   if (nseg < PG_WG_WAVES || nseg % PG_WG_WAVES || nseg / PG_WG_WAVES > ntiles)
-    return fail(PG_E_BADARG, "pg_query_eps: nseg must be 4 x pieces, with at most one piece per column tile");
+    return pg_fail(PG_E_BADARG, "pg_query_eps: nseg must be 4 x pieces, with at most one piece per column tile");
   const long long ngrp = (nq + PG_QUERY_RW - 1) / PG_QUERY_RW;
   const long long pieces = nseg / PG_WG_WAVES;
-  if (ngrp * pieces > 0x7FFFFFFFll) return fail(PG_E_TOOMANY, "pg_query_eps: too many queries for one launch");
+  if (ngrp * pieces > 0x7FFFFFFFll) return pg_fail(PG_E_TOOMANY, "pg_query_eps: too many queries for one launch");
   p.qPlanes = (const uint4 *)q_planes; p.dbPlanes = (const uint4 *)db_planes;
   p.qNpad = q_npad; p.dbNpad = db_npad; p.nq = nq; p.ndb = ndb;
   eps_interval(cmp, eps, &p.lo, &p.span, 0);
   p.pieces = (int)pieces;
   p.tilesPerPiece = (ntiles + pieces - 1) / pieces;        // (trailing pieces may be empty: their segments count 0)
-  return launched(kQueryEps[pg_ngroups(l) - 1](bits, fill, p, ngrp * pieces, (hipStream_t)stream),
+  return pg_launched(kQueryEps[pg_ngroups(l) - 1](bits, fill, p, ngrp * pieces, (hipStream_t)stream),
                   fill ? "pg_query_eps_kernel(fill)" : "pg_query_eps_kernel(count)");
 }
 
@@ -1316,7 +1304,7 @@ int64_t pg_query_eps_segments(int64_t nq, int64_t ndb) {
 
 int pg_query_eps_count(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb, int64_t db_npad,
                        int l, int bits, int cmp, double eps, int64_t nseg, uint32_t *seg_counts, void *stream) {
-  if (!seg_counts) return fail(PG_E_BADARG, "pg_query_eps_count: bad argument");
+  if (!seg_counts) return pg_fail(PG_E_BADARG, "pg_query_eps_count: bad argument");
   QueryEpsParams p = {};
   p.segCounts = seg_counts;
   return query_eps_launch("pg_query_eps_count: bad argument", 0, q_planes, nq, q_npad, db_planes, ndb, db_npad, l, bits, cmp,
@@ -1326,7 +1314,7 @@ int pg_query_eps_count(const void *q_planes, int64_t nq, int64_t q_npad, const v
 int pg_query_eps_fill(const void *q_planes, int64_t nq, int64_t q_npad, const void *db_planes, int64_t ndb, int64_t db_npad,
                       int l, int bits, int cmp, double eps, int64_t nseg, const int64_t *seg_indptr, int32_t *indices,
                       uint8_t *weights, void *stream) {
-  if (!seg_indptr || !indices || !weights) return fail(PG_E_BADARG, "pg_query_eps_fill: bad argument");
+  if (!seg_indptr || !indices || !weights) return pg_fail(PG_E_BADARG, "pg_query_eps_fill: bad argument");
   QueryEpsParams p = {};
   p.segIndptr = (const long long *)seg_indptr; p.indices = indices; p.weights = weights;
   return query_eps_launch("pg_query_eps_fill: bad argument", 1, q_planes, nq, q_npad, db_planes, ndb, db_npad, l, bits, cmp,
@@ -1336,11 +1324,11 @@ int pg_query_eps_fill(const void *q_planes, int64_t nq, int64_t q_npad, const vo
 int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits, int64_t ref,
                    const uint32_t *want_dist, int pos_mode, const uint32_t *pos_mask, const uint32_t *not_mask,
                    uint8_t *dist_out, uint64_t *hist, uint8_t *flags, void *stream) {
-  if (!planes || n <= 0 || npad < n || ref < 0 || ref >= n) return fail(PG_E_BADARG, "pg_index_flags: bad argument");
+  if (!planes || n <= 0 || npad < n || ref < 0 || ref >= n) return pg_fail(PG_E_BADARG, "pg_index_flags: bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
   if (pos_mode < 0 || pos_mode > 2 || (pos_mode && (!pos_mask || !not_mask)))
-    return fail(PG_E_BADARG, "pg_index_flags: bad position mode / masks");
+    return pg_fail(PG_E_BADARG, "pg_index_flags: bad position mode / masks");
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
   if (bits == 5)
@@ -1349,7 +1337,7 @@ int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits,
   else
     pg_index_kernel<8><<<grid, block, 0, s>>>((const u32 *)planes, n, npad, pg_ngroups(l), ref, want_dist, pos_mode,
                                               pos_mask, not_mask, dist_out, (u64 *)hist, flags);
-  return launched((int)hipGetLastError(), "pg_index_kernel");
+  return pg_launched("pg_index_kernel");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1357,22 +1345,22 @@ int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits,
 // ---------------------------------------------------------------------------------------
 int pg_lev_profile(const uint8_t *tokens, int64_t n, int l, int64_t ld, void *profiles, int64_t npad, int32_t *lens,
                    uint32_t *flags, void *stream) {
-  if (!tokens || !profiles || !lens || !flags || n <= 0 || ld < l) return fail(PG_E_BADARG, "pg_lev_profile: bad argument");
+  if (!tokens || !profiles || !lens || !flags || n <= 0 || ld < l) return pg_fail(PG_E_BADARG, "pg_lev_profile: bad argument");
   if (int rc = check_l(l)) return rc;
-  if (npad < n || npad % 256) return fail(PG_E_BADARG, "pg_lev_profile: npad must be pg_npad(n)");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_lev_profile: npad must be pg_npad(n)");
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s);
-  if (e != hipSuccess) return hipfail(e, "hipMemsetAsync");
-  return launched(pg_launch_lev_profile(tokens, n, l, ld, (u32 *)profiles, npad, lens, flags, s), "pg_lev_profile_kernel");
+  if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
+  return pg_launched(pg_launch_lev_profile(tokens, n, l, ld, (u32 *)profiles, npad, lens, flags, s), "pg_lev_profile_kernel");
 }
 
 int pg_lev_candidates(const void *profiles, int64_t npad, int64_t n, int64_t row0, int64_t nrows, int band, int cap,
                       int32_t *slot_idx, uint8_t *slot_w, uint32_t *counts, void *stream) {
   if (!profiles || !slot_idx || !slot_w || !counts || n <= 0 || nrows <= 0 || row0 < 0 || row0 + nrows > n || cap < 0)
-    return fail(PG_E_BADARG, "pg_lev_candidates: bad argument");
-  if (band < 0 || band > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_candidates: band must be in 0..8");
-  if (npad < n || npad % 256) return fail(PG_E_BADARG, "pg_lev_candidates: bad npad");
-  if (n > 0x7fffffffLL) return fail(PG_E_TOOMANY, "n exceeds int32 indices");
+    return pg_fail(PG_E_BADARG, "pg_lev_candidates: bad argument");
+  if (band < 0 || band > PG_LEV_MAX_BAND) return pg_fail(PG_E_BADARG, "pg_lev_candidates: band must be in 0..8");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_lev_candidates: bad npad");
+  if (n > 0x7fffffffLL) return pg_fail(PG_E_TOOMANY, "n exceeds int32 indices");
   NsqParams p;
   memset(&p, 0, sizeof(p));
   p.rowPlanes = (const uint4 *)profiles; p.rowNpad = npad; p.row0 = row0; p.nrows = nrows;
@@ -1384,7 +1372,7 @@ int pg_lev_candidates(const void *profiles, int64_t npad, int64_t n, int64_t row
   static int bag_occ = 0;
   if (!bag_occ) { bag_occ = pg_occ_nsq_bag(); if (bag_occ < 1) bag_occ = 4; }
   if (int rc = plan_rows(nrows, &p, &grid, bag_occ, 48.0)) return rc;
-  return launched(pg_launch_nsq_bag(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag)");
+  return pg_launched(pg_launch_nsq_bag(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag)");
 }
 
 // Symmetric candidate generation (all rows against the same profiles): every unordered pair once,
@@ -1392,10 +1380,10 @@ int pg_lev_candidates(const void *profiles, int64_t npad, int64_t n, int64_t row
 int pg_lev_candidates_sym(const void *profiles, int64_t npad, int64_t n, int band, int cap, int32_t *slot_idx,
                           uint8_t *slot_w, int32_t *slot_aux, uint32_t *counts_up, uint32_t *counts_lo, void *stream) {
   if (!profiles || !slot_idx || !slot_w || !counts_up || !counts_lo || n <= 0 || cap < 0)
-    return fail(PG_E_BADARG, "pg_lev_candidates_sym: bad argument");
-  if (band < 0 || band > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_candidates_sym: band must be in 0..8");
-  if (npad < n || npad % 256) return fail(PG_E_BADARG, "pg_lev_candidates_sym: bad npad");
-  if (n >= (1ll << 27)) return fail(PG_E_TOOMANY, "pg_lev_candidates_sym: n must be below 2^27");
+    return pg_fail(PG_E_BADARG, "pg_lev_candidates_sym: bad argument");
+  if (band < 0 || band > PG_LEV_MAX_BAND) return pg_fail(PG_E_BADARG, "pg_lev_candidates_sym: band must be in 0..8");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_lev_candidates_sym: bad npad");
+  if (n >= (1ll << 27)) return pg_fail(PG_E_TOOMANY, "pg_lev_candidates_sym: n must be below 2^27");
   NsqParams p;
   memset(&p, 0, sizeof(p));
   p.rowPlanes = (const uint4 *)profiles; p.rowNpad = npad; p.row0 = 0; p.nrows = n;
@@ -1404,12 +1392,12 @@ int pg_lev_candidates_sym(const void *profiles, int64_t npad, int64_t n, int ban
   p.filter = lb_filter_mode();
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.slotAux = slot_aux; p.counts = counts_up; p.countsLo = counts_lo;
   hipError_t e = hipMemsetAsync(counts_lo, 0, (size_t)n * sizeof(uint32_t), (hipStream_t)stream);
-  if (e != hipSuccess) return hipfail(e, "hipMemsetAsync");
+  if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
   long long r = n >= 80000 ? 16 : 8;                        // as pg_eps_slots_sym
   if (const char *ev = getenv("PG_ROWS_PER_WAVE")) { if (atoi(ev) > 0) r = atoi(ev); }
   p.rowsPerWave = (int)r; p.rowsPerPass = (int)(r > PG_RB ? PG_RB : r);
   const int grid = (int)(((n + r - 1) / r + PG_WG_WAVES - 1) / PG_WG_WAVES);
-  return launched(pg_launch_nsq_bag_sym(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag sym)");
+  return pg_launched(pg_launch_nsq_bag_sym(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag sym)");
 }
 
 int pg_lev_knn(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *planes128, int64_t npad,
@@ -1418,13 +1406,13 @@ int pg_lev_knn(const uint8_t *tokens, int64_t n, int l, int64_t ld, const void *
                const uint32_t *counts, const uint32_t *counts_lo, int32_t *idx_out, uint8_t *dist_out, void *stream) {
   if (!tokens || !planes128 || npad < n || npad % 256 || !lens || !slot_idx || !counts || !idx_out || !dist_out || n <= 0 || nrows <= 0 || row0 < 0 ||
       row0 + nrows > n || ld < l || cap < 0)
-    return fail(PG_E_BADARG, "pg_lev_knn: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_lev_knn: bad argument");
   if (int rc = check_l(l)) return rc;
-  if (band < 0 || band > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_knn: band must be in 0..8");
-  if (k < 1 || k > PG_MAX_K) return fail(PG_E_BADARG, "pg_lev_knn: k must be in 1..63");
-  if (n > PG_MAX_N_KNN) return fail(PG_E_TOOMANY, "pg_lev_knn: n exceeds 2^24");
-  if (counts_lo && (row0 != 0 || nrows != n)) return fail(PG_E_BADARG, "pg_lev_knn: symmetric slots cover all rows");
-  return launched(pg_launch_lev_select(tokens, n, l, ld, (const uint4 *)planes128, npad, lens, row0, nrows, band, k, (u32)cap, slot_idx, slot_w,
+  if (band < 0 || band > PG_LEV_MAX_BAND) return pg_fail(PG_E_BADARG, "pg_lev_knn: band must be in 0..8");
+  if (k < 1 || k > PG_MAX_K) return pg_fail(PG_E_BADARG, "pg_lev_knn: k must be in 1..63");
+  if (n > PG_MAX_N_KNN) return pg_fail(PG_E_TOOMANY, "pg_lev_knn: n exceeds 2^24");
+  if (counts_lo && (row0 != 0 || nrows != n)) return pg_fail(PG_E_BADARG, "pg_lev_knn: symmetric slots cover all rows");
+  return pg_launched(pg_launch_lev_select(tokens, n, l, ld, (const uint4 *)planes128, npad, lens, row0, nrows, band, k, (u32)cap, slot_idx, slot_w,
                                        slot_aux, counts, counts_lo, idx_out, dist_out, (hipStream_t)stream), "pg_lev_select_kernel");
 }
 
@@ -1435,13 +1423,13 @@ int pg_levenshtein_dense(const void *x_planes128, int64_t n, int64_t x_npad, con
                          int64_t m, int64_t y_npad, const int32_t *y_lens, int l, void *out, int out_elem_bytes, int64_t ldo,
                          void *stream) {
   if (!x_planes128 || !x_lens || !y_planes128 || !y_lens || !out || n <= 0 || m <= 0 || ldo < n)
-    return fail(PG_E_BADARG, "pg_levenshtein_dense: bad argument");
-  if (l < 1 || l > PG_MAX_L) return fail(PG_E_BADARG, "pg_levenshtein_dense: l must be in 1..128");
-  if (out_elem_bytes != 2 && out_elem_bytes != 8) return fail(PG_E_BADARG, "pg_levenshtein_dense: out_elem_bytes must be 2 or 8");
-  if (x_npad < n || x_npad % 256 || y_npad < m) return fail(PG_E_BADARG, "pg_levenshtein_dense: bad npad");
+    return pg_fail(PG_E_BADARG, "pg_levenshtein_dense: bad argument");
+  if (l < 1 || l > PG_MAX_L) return pg_fail(PG_E_BADARG, "pg_levenshtein_dense: l must be in 1..128");
+  if (out_elem_bytes != 2 && out_elem_bytes != 8) return pg_fail(PG_E_BADARG, "pg_levenshtein_dense: out_elem_bytes must be 2 or 8");
+  if (x_npad < n || x_npad % 256 || y_npad < m) return pg_fail(PG_E_BADARG, "pg_levenshtein_dense: bad npad");
   if (((n + PG_WG_THREADS - 1) / PG_WG_THREADS) * ((m + PG_LEVD_ROWS - 1) / PG_LEVD_ROWS) > 0x7fffffffLL)
-    return fail(PG_E_TOOMANY, "pg_levenshtein_dense: too many blocks for one launch");
-  return launched(pg_launch_levenshtein_dense((const uint4 *)x_planes128, x_npad, n, x_lens, (const uint4 *)y_planes128, y_npad, m,
+    return pg_fail(PG_E_TOOMANY, "pg_levenshtein_dense: too many blocks for one launch");
+  return pg_launched(pg_launch_levenshtein_dense((const uint4 *)x_planes128, x_npad, n, x_lens, (const uint4 *)y_planes128, y_npad, m,
                                               y_lens, l, out, out_elem_bytes, ldo, (hipStream_t)stream),
                   "pg_levenshtein_dense_kernel");
 }
@@ -1451,25 +1439,25 @@ int pg_lev_eps_pairs(const uint8_t *tokens, int64_t n, int l, int64_t ld, const 
                      const uint32_t *counts_up, const uint32_t *counts_lo, void *stream) {
   if (!tokens || !planes128 || !lens || !slot_idx || !slot_w || !slot_aux || !counts_up || !counts_lo || n <= 0 || ld < l ||
       cap < 0 || npad < n || npad % 256)
-    return fail(PG_E_BADARG, "pg_lev_eps_pairs: bad argument");
-  if (l < 1 || l > PG_MAX_L) return fail(PG_E_BADARG, "pg_lev_eps_pairs: l must be in 1..128");
-  if (band < 0 || band > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_eps_pairs: band must be in 0..8");
-  return launched(pg_launch_lev_pairs(tokens, n, l, ld, (const uint4 *)planes128, npad, lens, band, (u32)cap, slot_idx, slot_w,
+    return pg_fail(PG_E_BADARG, "pg_lev_eps_pairs: bad argument");
+  if (l < 1 || l > PG_MAX_L) return pg_fail(PG_E_BADARG, "pg_lev_eps_pairs: l must be in 1..128");
+  if (band < 0 || band > PG_LEV_MAX_BAND) return pg_fail(PG_E_BADARG, "pg_lev_eps_pairs: band must be in 0..8");
+  return pg_launched(pg_launch_lev_pairs(tokens, n, l, ld, (const uint4 *)planes128, npad, lens, band, (u32)cap, slot_idx, slot_w,
                                       slot_aux, counts_up, counts_lo, (hipStream_t)stream), "pg_lev_select_kernel<1>");
 }
 
 static int lev_eps_args(int64_t n, int cap, int cmp, int thr, const char *who) {
   const int c = cmp & ~PG_CMP_KEEP_ZERO;
-  if (n <= 0 || cap < 0 || (c != PG_CMP_LE && c != PG_CMP_LT && c != PG_CMP_EQ)) return fail(PG_E_BADARG, who);
-  if (thr < 0 || thr > PG_LEV_MAX_BAND) return fail(PG_E_BADARG, "pg_lev_eps: the threshold must be in 0..8 (the band of the pairs)");
+  if (n <= 0 || cap < 0 || (c != PG_CMP_LE && c != PG_CMP_LT && c != PG_CMP_EQ)) return pg_fail(PG_E_BADARG, who);
+  if (thr < 0 || thr > PG_LEV_MAX_BAND) return pg_fail(PG_E_BADARG, "pg_lev_eps: the threshold must be in 0..8 (the band of the pairs)");
   return 0;
 }
 
 int pg_lev_eps_count(int64_t n, int cap, int cmp, int thr, const uint8_t *slot_w, const uint32_t *counts_up,
                      const uint32_t *counts_lo, uint32_t *counts_out, void *stream) {
-  if (!slot_w || !counts_up || !counts_lo || !counts_out) return fail(PG_E_BADARG, "pg_lev_eps_count: bad argument");
+  if (!slot_w || !counts_up || !counts_lo || !counts_out) return pg_fail(PG_E_BADARG, "pg_lev_eps_count: bad argument");
   if (int rc = lev_eps_args(n, cap, cmp, thr, "pg_lev_eps_count: bad argument")) return rc;
-  return launched(pg_launch_lev_eps(0, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, nullptr,
+  return pg_launched(pg_launch_lev_eps(0, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, nullptr,
                                     slot_w, counts_up, counts_lo, counts_out, nullptr, nullptr, nullptr, (hipStream_t)stream),
                   "pg_lev_eps_kernel<0>");
 }
@@ -1478,9 +1466,9 @@ int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_id
                     const uint32_t *counts_up, const uint32_t *counts_lo, const int64_t *indptr, int32_t *indices,
                     uint8_t *weights, void *stream) {
   if (!slot_idx || !slot_w || !counts_up || !counts_lo || !indptr || !indices || !weights)
-    return fail(PG_E_BADARG, "pg_lev_eps_fill: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_lev_eps_fill: bad argument");
   if (int rc = lev_eps_args(n, cap, cmp, thr, "pg_lev_eps_fill: bad argument")) return rc;
-  return launched(pg_launch_lev_eps(1, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, slot_idx,
+  return pg_launched(pg_launch_lev_eps(1, n, (u32)cap, cmp & ~PG_CMP_KEEP_ZERO, (u32)thr, (cmp & PG_CMP_KEEP_ZERO) ? 0u : 1u, slot_idx,
                                     slot_w, counts_up, counts_lo, nullptr, (const long long *)indptr, indices, weights,
                                     (hipStream_t)stream), "pg_lev_eps_kernel<1>");
 }
@@ -1488,16 +1476,16 @@ int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_id
 int pg_csr_row_stats(const int64_t *indptr, const int32_t *indices, const uint8_t *weights_u8, const float *weights_f32,
                      int64_t nrows, int64_t row0, const double *f, double *deg, double *sum_f, double *sum_wf,
                      double *self_w, double *col_sum, void *stream) {
-  if (!indptr || !indices || nrows <= 0 || row0 < 0) return fail(PG_E_BADARG, "pg_csr_row_stats: bad argument");
-  if ((sum_f || sum_wf) && !f) return fail(PG_E_BADARG, "pg_csr_row_stats: node values required");
+  if (!indptr || !indices || nrows <= 0 || row0 < 0) return pg_fail(PG_E_BADARG, "pg_csr_row_stats: bad argument");
+  if ((sum_f || sum_wf) && !f) return pg_fail(PG_E_BADARG, "pg_csr_row_stats: node values required");
   pg_csr_row_stats_kernel<<<dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const long long *)indptr, indices, weights_u8, weights_f32, nrows, row0, f, deg, sum_f, sum_wf, self_w, col_sum);
-  return launched((int)hipGetLastError(), "pg_csr_row_stats_kernel");
+  return pg_launched("pg_csr_row_stats_kernel");
 }
 
 int pg_compact_flags(const uint8_t *flags, int64_t n, int64_t *out_idx, int64_t *out_count, void *scratch,
                      void *stream) {
-  if (!flags || !out_idx || !out_count || !scratch || n <= 0) return fail(PG_E_BADARG, "pg_compact_flags: bad argument");
+  if (!flags || !out_idx || !out_count || !scratch || n <= 0) return pg_fail(PG_E_BADARG, "pg_compact_flags: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const long long nb = (n + PG_SCAN_TILE - 1) / PG_SCAN_TILE;
   long long *part = (long long *)scratch;
@@ -1505,7 +1493,7 @@ int pg_compact_flags(const uint8_t *flags, int64_t n, int64_t *out_idx, int64_t 
   pg_scan_single<<<dim3(1), dim3(256), 0, s>>>(part, nb);
   pg_scan_apply<unsigned char, 1><<<dim3((unsigned)nb), dim3(256), 0, s>>>(flags, n, part, nb, (long long *)out_idx,
                                                                           (long long *)out_count);
-  return launched((int)hipGetLastError(), "pg_compact_flags");
+  return pg_launched("pg_compact_flags");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1550,8 +1538,8 @@ int pg_comm_available(void) { return rccl() ? 1 : 0; }   // local, not a collect
 
 int pg_comm_unique_id(void *id128) {
   RcclApi *r = rccl();
-  if (!r) return fail(PG_E_COMM, "pg_comm_unique_id: librccl.so not found");
-  if (!id128) return fail(PG_E_BADARG, "pg_comm_unique_id: bad argument");
+  if (!r) return pg_fail(PG_E_COMM, "pg_comm_unique_id: librccl.so not found");
+  if (!id128) return pg_fail(PG_E_BADARG, "pg_comm_unique_id: bad argument");
   ncclUniqueId id;
   ncclResult_t e = r->GetUniqueId(&id);
   if (e != ncclSuccess) return rcclfail(r, e, "ncclGetUniqueId");
@@ -1562,8 +1550,8 @@ int pg_comm_unique_id(void *id128) {
 
 int pg_comm_init(void **comm, int nranks, int rank, const void *id128) {
   RcclApi *r = rccl();
-  if (!r) return fail(PG_E_COMM, "pg_comm_init: librccl.so not found");
-  if (!comm || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(PG_E_BADARG, "pg_comm_init: bad argument");
+  if (!r) return pg_fail(PG_E_COMM, "pg_comm_init: librccl.so not found");
+  if (!comm || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return pg_fail(PG_E_BADARG, "pg_comm_init: bad argument");
   ncclUniqueId id;
   memcpy(&id, id128, sizeof(id));
   ncclComm_t c = nullptr;
@@ -1575,15 +1563,15 @@ int pg_comm_init(void **comm, int nranks, int rank, const void *id128) {
 
 int pg_comm_destroy(void *comm) {
   RcclApi *r = rccl();
-  if (!r || !comm) return fail(PG_E_BADARG, "pg_comm_destroy: bad argument");
+  if (!r || !comm) return pg_fail(PG_E_BADARG, "pg_comm_destroy: bad argument");
   ncclResult_t e = r->CommDestroy((ncclComm_t)comm);
   return e == ncclSuccess ? 0 : rcclfail(r, e, "ncclCommDestroy");
 }
 
 int pg_allgather_tokens(void *comm, const void *shard, int64_t rows_per_rank, int l, void *full, void *stream) {
   RcclApi *r = rccl();
-  if (!r) return fail(PG_E_COMM, "pg_allgather_tokens: librccl.so not found");
-  if (!comm || !shard || !full || rows_per_rank <= 0 || l <= 0) return fail(PG_E_BADARG, "pg_allgather_tokens: bad argument");
+  if (!r) return pg_fail(PG_E_COMM, "pg_allgather_tokens: librccl.so not found");
+  if (!comm || !shard || !full || rows_per_rank <= 0 || l <= 0) return pg_fail(PG_E_BADARG, "pg_allgather_tokens: bad argument");
   ncclResult_t e = r->AllGather(shard, full, (size_t)rows_per_rank * (size_t)l, ncclUint8, (ncclComm_t)comm, (hipStream_t)stream);
   return e == ncclSuccess ? 0 : rcclfail(r, e, "ncclAllGather");
 }

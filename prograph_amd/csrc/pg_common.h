@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 typedef unsigned int u32;
 typedef unsigned long long u64;
@@ -415,6 +416,20 @@ struct CompactParams {
 };
 
 void pg_set_error(const char *msg);   // thread-local message behind pg_last_error() (pg_api.hip)
+// set the message and return `code`
+static inline int pg_fail(int code, const char *msg) {
+  pg_set_error(msg);
+  return code;
+}
+// rc of a launcher or a HIP call: 0, or the message "where: <HIP error>" and rc
+static inline int pg_launched(int rc, const char *where) {
+  if (rc == 0) return 0;
+  char buf[200];
+  snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString((hipError_t)rc));
+  return pg_fail(rc, buf);
+}
+// the same for the kernel launch just made
+static inline int pg_launched(const char *where) { return pg_launched((int)hipGetLastError(), where); }
 
 // per-(G,B) launchers (pg_nsq_inst.hip is compiled once per group count G = 1..4)
 #define PG_DECL_G(G)                                                                          \

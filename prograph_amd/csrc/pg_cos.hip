@@ -20,13 +20,7 @@
 // The 32x32 result has the X column on the lane (l&31) and the Y rows in the 16 registers: register r of lane
 // half h is row (r&3) + 8(r>>2) + 4h.  The dense kernel writes it out; the fused kernels select from it in
 // registers.  Both call cs_tile and cs_finish, so the fused graphs are exactly the selection over the dense block.
-#include "pg_common.h"
-#include "../../include/prograph_hip.h"
-
-// cmp of the eps entries: one of the five codes, with or without PG_CMP_KEEP_ZERO
-static inline bool pg_cmp_bad(int cmp) { return (cmp & ~PG_CMP_KEEP_ZERO) < PG_CMP_LE || (cmp & ~PG_CMP_KEEP_ZERO) > PG_CMP_GT; }
-
-#include <stdio.h>
+#include "pg_select.h"
 
 typedef _Float16 cs_h8 __attribute__((ext_vector_type(8)));
 typedef float cs_f16 __attribute__((ext_vector_type(16)));
@@ -79,22 +73,6 @@ __device__ __forceinline__ u32 cs_key(float v, int descending) {
   return descending ? ~b : b;
 }
 __device__ __forceinline__ float cs_unkey(u32 key, int descending) { return __uint_as_float(descending ? ~key : key); }
-
-//   distances:    comp(d, eps) & (d > 0)
-//   similarities: comp(eps, s) & (s < 1)
-//   cmp | PG_CMP_KEEP_ZERO: without the second test (queries)
-__device__ __forceinline__ bool cs_match(float v, float eps, int cmp, int similarity) {
-  const float a = similarity ? eps : v, b = similarity ? v : eps;
-  bool ok;
-  switch (cmp & ~PG_CMP_KEEP_ZERO) {
-    case PG_CMP_LE: ok = a <= b; break;
-    case PG_CMP_LT: ok = a < b; break;
-    case PG_CMP_EQ: ok = a == b; break;
-    case PG_CMP_GE: ok = a >= b; break;
-    default: ok = a > b; break;
-  }
-  return ok && ((cmp & PG_CMP_KEEP_ZERO) || (similarity ? v < 1.0f : v > 0.0f));
-}
 
 // ---- per-vector norms: the diagonal of cs_tile on 32 vectors against themselves --------------------------------
 __global__ __launch_bounds__(256) void pg_cos_prep_kernel(const uint4 *__restrict__ xp, long long n, long long npad, int nq,
@@ -168,24 +146,7 @@ __device__ __forceinline__ long long cs_wave_row(int i, long long m, const long 
 // Row i's list is (lk[i], lc[i]): lane j = j-th smallest (key, column), and (tk[i], tc[i]) is its entry at rank
 // `last` = the running threshold.  A tile value is a candidate only below the threshold of its register's row
 // (one compare for most pairs); the candidates of a register go through a ballot and are inserted in lane order,
-// the pg_minkowski_knn insertion, into the list of row cs_row(r, 0) (lanes 0-31) or cs_row(r, 1) (lanes 32-63).
-__device__ __forceinline__ void cs_insert(u32 &lk, u32 &lc, u32 &tk, u32 &tc, u32 mask, u32 key, int boff, long long x0,
-                                          int last) {
-  while (mask) {
-    const int b = __builtin_ctz(mask);
-    mask &= mask - 1;
-    const u32 xk = __builtin_amdgcn_readlane(key, b + boff), xc = (u32)(x0 + b);
-    if (xk < tk || (xk == tk && xc < tc)) {
-      const bool keep = lk < xk || (lk == xk && lc <= xc);           // entries not after x stay
-      const u32 pk = wave_shr1(lk, 0u), pc = wave_shr1(lc, 0u);
-      const bool prev_after = pk > xk || (pk == xk && pc > xc);      // lane-1's entry also moves, else x lands here
-      lk = keep ? lk : (prev_after ? pk : xk);
-      lc = keep ? lc : (prev_after ? pc : xc);
-      tk = __builtin_amdgcn_readlane(lk, last);
-      tc = __builtin_amdgcn_readlane(lc, last);
-    }
-  }
-}
+// by knn_insert (pg_select.h) into the list of row cs_row(r, 0) (lanes 0-31) or cs_row(r, 1) (lanes 32-63).
 
 // FLOOR (pg_cosine_knn_round, first = 0): only pairs after each row's floor are candidates, rows written ldo elements
 // apart.  The floors sit lane-per-row in one VGPR pair (lane i and i + 32: row slot i, the cs_wave_row order) and are
@@ -232,8 +193,8 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
         cand = cand && knn_after(key, (u32)col, h ? f1k : f0k, h ? f1c : f0c);
       }
       const u64 mask = __builtin_amdgcn_ballot_w64(cand);
-      if ((u32)mask) cs_insert(lk[i0], lc[i0], tk[i0], tc[i0], (u32)mask, key, 0, x0, last);
-      if ((u32)(mask >> 32)) cs_insert(lk[i1], lc[i1], tk[i1], tc[i1], (u32)(mask >> 32), key, 32, x0, last);
+      if ((u32)mask) knn_insert(lk[i0], lc[i0], tk[i0], tc[i0], (u32)mask, key, 0, x0, last);
+      if ((u32)(mask >> 32)) knn_insert(lk[i1], lc[i1], tk[i1], tc[i1], (u32)(mask >> 32), key, 32, x0, last);
     }
   }
 #pragma unroll
@@ -289,7 +250,7 @@ __global__ __launch_bounds__(256) void pg_cos_eps_kernel(const uint4 *__restrict
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const float v = cs_finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity);
-      const bool hit = cok && rok[r] && cs_match(v, eps, cmp, similarity);
+      const bool hit = cok && rok[r] && pg_match(v, eps, cmp, similarity);
       const u64 mask = __builtin_amdgcn_ballot_w64(hit);
       if (!mask) continue;                                           // wave-uniform
       const u64 mine = h ? (mask & 0xFFFFFFFF00000000ull) : (mask & 0xFFFFFFFFull);
@@ -315,38 +276,6 @@ __global__ __launch_bounds__(256) void pg_cos_eps_kernel(const uint4 *__restrict
   }
 }
 
-// slots -> CSR for the rows that kept all their matches (count <= cap); one wave per row
-__global__ __launch_bounds__(256) void pg_cos_eps_compact_kernel(long long m, int cap, const int *__restrict__ slot_idx,
-                                                                 const float *__restrict__ slot_w, const u32 *__restrict__ counts,
-                                                                 const long long *__restrict__ indptr, int *__restrict__ indices,
-                                                                 float *__restrict__ weights) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= m) return;
-  const u32 cnt = counts[row];
-  if (cnt > (u32)cap) return;                                        // pg_cosine_eps_fill_rows writes this row
-  const long long o = indptr[row], s = row * (long long)cap;
-  for (u32 i = lane; i < cnt; i += 64) {
-    indices[o + i] = slot_idx[s + i];
-    weights[o + i] = slot_w[s + i];
-  }
-}
-
-static int cfail(int code, const char *msg) {
-  pg_set_error(msg);
-  return code;
-}
-static int claunched(const char *where) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString(e));
-    pg_set_error(buf);
-    return (int)e;
-  }
-  return 0;
-}
-
 static int cs_nq(int d) { return (d + 7) / 8; }
 
 static int cs_operands_bad(const void *xp, const float *xn, const float *xr, int64_t n, int64_t x_npad, const void *yp,
@@ -362,37 +291,37 @@ extern "C" {
 int pg_cosine_prep(const void *packed, int64_t n, int64_t npad, int d, float *norms, float *rnorms, uint32_t *flags,
                    void *stream) {
   if (!packed || !norms || !rnorms || !flags || n < 0 || d <= 0 || npad < n || npad <= 0 || npad % 256)
-    return cfail(PG_E_BADARG, "pg_cosine_prep: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_cosine_prep: bad argument");
   pg_cos_prep_kernel<<<dim3((unsigned)(npad / (CS_T * CS_WAVES))), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)packed, n, npad, cs_nq(d), norms, rnorms, flags);
-  return claunched("pg_cos_prep_kernel");
+  return pg_launched("pg_cos_prep_kernel");
 }
 
 int pg_cosine_dense(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
                     const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
                     int similarity, float *out, int64_t ldo, void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !out || ldo < n)
-    return cfail(PG_E_BADARG, "pg_cosine_dense: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_cosine_dense: bad argument");
   if ((m + CS_T - 1) / CS_T > 65535 || cs_groups(n) > 0x7FFFFFFFll)
-    return cfail(PG_E_BADARG, "pg_cosine_dense: m too large for one launch");
+    return pg_fail(PG_E_BADARG, "pg_cosine_dense: m too large for one launch");
   const dim3 grid((unsigned)cs_groups(n), (unsigned)((m + CS_T - 1) / CS_T));
   pg_cos_dense_kernel<<<grid, dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
       similarity ? 1 : 0, out, ldo);
-  return claunched("pg_cos_dense_kernel");
+  return pg_launched("pg_cos_dense_kernel");
 }
 
 int pg_cosine_knn(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
                   const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
                   int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out)
-    return cfail(PG_E_BADARG, "pg_cosine_knn: bad argument");
-  if (k < 1 || first < 0 || first + k > 64) return cfail(PG_E_BADARG, "pg_cosine_knn: first + k must be at most 64");
-  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return cfail(PG_E_BADARG, "pg_cosine_knn: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_cosine_knn: bad argument");
+  if (k < 1 || first < 0 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_cosine_knn: first + k must be at most 64");
+  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return pg_fail(PG_E_BADARG, "pg_cosine_knn: too many vectors for one launch");
   pg_cos_knn_kernel<false><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
       similarity ? 1 : 0, k, first, idx_out, w_out, nullptr, nullptr, 0, k);
-  return claunched("pg_cos_knn_kernel");
+  return pg_launched("pg_cos_knn_kernel");
 }
 
 int pg_cosine_knn_round(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
@@ -401,14 +330,14 @@ int pg_cosine_knn_round(const void *x_packed, const float *x_norms, const float 
                         int32_t *idx_out, float *w_out, int64_t ldo, void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out ||
       !floor_idx || !floor_w || floor_ld < 0 || ldo < k)
-    return cfail(PG_E_BADARG, "pg_cosine_knn_round: bad argument");
-  if (k < 1 || k > 64) return cfail(PG_E_BADARG, "pg_cosine_knn_round: k must be 1..64");
+    return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: bad argument");
+  if (k < 1 || k > 64) return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: k must be 1..64");
   if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
-    return cfail(PG_E_BADARG, "pg_cosine_knn_round: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: too many vectors for one launch");
   pg_cos_knn_kernel<true><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
       similarity ? 1 : 0, k, 0, idx_out, w_out, floor_idx, floor_w, floor_ld, ldo);
-  return claunched("pg_cos_knn_kernel(round)");
+  return pg_launched("pg_cos_knn_kernel(round)");
 }
 
 int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
@@ -417,22 +346,18 @@ int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float 
                         void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !slot_idx ||
       !slot_w || !counts || cap < 1 || pg_cmp_bad(cmp))
-    return cfail(PG_E_BADARG, "pg_cosine_eps_slots: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_cosine_eps_slots: bad argument");
   if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
-    return cfail(PG_E_BADARG, "pg_cosine_eps_slots: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_cosine_eps_slots: too many vectors for one launch");
   pg_cos_eps_kernel<<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
       similarity ? 1 : 0, cmp, eps, nullptr, 0, cap, slot_idx, slot_w, counts, nullptr, nullptr, nullptr);
-  return claunched("pg_cos_eps_kernel(slots)");
+  return pg_launched("pg_cos_eps_kernel(slots)");
 }
 
 int pg_cosine_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const float *slot_w, const uint32_t *counts,
                           const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
-  if (!slot_idx || !slot_w || !counts || !indptr || !indices || !weights || m <= 0 || cap < 1)
-    return cfail(PG_E_BADARG, "pg_cosine_eps_compact: bad argument");
-  pg_cos_eps_compact_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
-      m, cap, slot_idx, slot_w, counts, (const long long *)indptr, indices, weights);
-  return claunched("pg_cos_eps_compact_kernel");
+  return pg_eps_compact_launch<float>("pg_cosine_eps_compact", m, cap, slot_idx, slot_w, counts, indptr, indices, weights, stream);
 }
 
 int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
@@ -441,14 +366,14 @@ int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const fl
                             const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
   if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !row_list ||
       n_list <= 0 || !indptr || !indices || !weights || pg_cmp_bad(cmp))
-    return cfail(PG_E_BADARG, "pg_cosine_eps_fill_rows: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_cosine_eps_fill_rows: bad argument");
   if (n > 0x7FFFFFFFll || cs_groups(n_list) > 0x7FFFFFFFll)
-    return cfail(PG_E_BADARG, "pg_cosine_eps_fill_rows: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_cosine_eps_fill_rows: too many vectors for one launch");
   pg_cos_eps_kernel<<<dim3((unsigned)cs_groups(n_list)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
       similarity ? 1 : 0, cmp, eps, (const long long *)row_list, n_list, 1, nullptr, nullptr, nullptr,
       (const long long *)indptr, indices, weights);
-  return claunched("pg_cos_eps_kernel(fill)");
+  return pg_launched("pg_cos_eps_kernel(fill)");
 }
 
 }  // extern "C"

@@ -21,14 +21,9 @@
 // Layout: embeddings are packed chunk-major like the token planes: chunk q (8 halfs, 16 bytes) of
 // vector n at byte (q * Npad + n) * 16, so 64 consecutive vectors load one chunk each as a coalesced
 // 1 KiB global_load_dwordx4.
-#include "pg_common.h"
-#include "../../include/prograph_hip.h"
-
-// cmp of the eps entries: one of the five codes, with or without PG_CMP_KEEP_ZERO
-static inline bool pg_cmp_bad(int cmp) { return (cmp & ~PG_CMP_KEEP_ZERO) < PG_CMP_LE || (cmp & ~PG_CMP_KEEP_ZERO) > PG_CMP_GT; }
+#include "pg_select.h"
 
 #include <hip/hip_fp16.h>
-#include <stdio.h>
 
 typedef _Float16 pg_h2 __attribute__((ext_vector_type(2)));
 
@@ -156,21 +151,7 @@ __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *_
     const u32 key = c < n ? mk_key(d[c], descending) : 0xFFFFFFFFu;
     bool cand = c < n && (key < tk || (key == tk && (u32)c < tc));
     if (FLOOR) cand = cand && knn_after(key, (u32)c, fk, fc);
-    u64 mask = __builtin_amdgcn_ballot_w64(cand);
-    while (mask) {
-      const int j = __builtin_ctzll(mask);
-      mask &= mask - 1;
-      const u32 xk = __builtin_amdgcn_readlane(key, j), xc = (u32)(c0 + j);
-      if (xk < tk || (xk == tk && xc < tc)) {
-        const bool keep = lk < xk || (lk == xk && lc <= xc);            // entries not after x stay
-        const u32 pk = wave_shr1(lk, 0u), pc = wave_shr1(lc, 0u);
-        const bool prev_after = pk > xk || (pk == xk && pc > xc);        // lane-1's entry also moves: take it, else x lands here
-        lk = keep ? lk : (prev_after ? pk : xk);
-        lc = keep ? lc : (prev_after ? pc : xc);
-        tk = __builtin_amdgcn_readlane(lk, last);
-        tc = __builtin_amdgcn_readlane(lc, last);
-      }
-    }
+    knn_insert(lk, lc, tk, tc, __builtin_amdgcn_ballot_w64(cand), key, 0, c0, last);
   }
   if (lane >= first && lane <= last) {
     const long long o = row * (FLOOR ? ldo : (long long)k) + (lane - first);
@@ -179,23 +160,7 @@ __global__ __launch_bounds__(256) void pg_f16_knn_kernel(const unsigned short *_
   }
 }
 
-// epsilon selection on a distance / similarity block: count, or fill at indptr
-//   distances:    comp(d, eps) & (d > 0)      (prograph.py:736)
-//   similarities: comp(eps, s) & (s < 1)      (:734), eps already 1/(1+eps) rounded to fp16
-//   cmp | PG_CMP_KEEP_ZERO: without the second test (queries: a vector equal to the query is a hit)
-__device__ __forceinline__ bool mk_match(float v, float eps, int cmp, int similarity) {
-  const float a = similarity ? eps : v, b = similarity ? v : eps;
-  bool ok;
-  switch (cmp & ~PG_CMP_KEEP_ZERO) {
-    case PG_CMP_LE: ok = a <= b; break;
-    case PG_CMP_LT: ok = a < b; break;
-    case PG_CMP_EQ: ok = a == b; break;
-    case PG_CMP_GE: ok = a >= b; break;
-    default: ok = a > b; break;
-  }
-  return ok && ((cmp & PG_CMP_KEEP_ZERO) || (similarity ? v < 1.0f : v > 0.0f));
-}
-
+// epsilon selection (pg_match) on a distance / similarity block: count, or fill at indptr
 __global__ __launch_bounds__(256) void pg_f16_eps_kernel(const __half *__restrict__ dist, long long m, long long n, long long ld,
                                                          int cmp, float eps, int similarity, u32 *__restrict__ counts,
                                                          const long long *__restrict__ indptr, int *__restrict__ indices,
@@ -209,7 +174,7 @@ __global__ __launch_bounds__(256) void pg_f16_eps_kernel(const __half *__restric
   for (long long c0 = 0; c0 < n; c0 += 64) {
     const long long c = c0 + lane;
     const __half v = c < n ? d[c] : __float2half(0.0f);
-    const bool hit = c < n && mk_match(__half2float(v), eps, cmp, similarity);
+    const bool hit = c < n && pg_match(__half2float(v), eps, cmp, similarity);
     const u64 mask = __builtin_amdgcn_ballot_w64(hit);
     if (indptr && hit) {
       const long long o = run + mask_rank(mask);
@@ -302,21 +267,7 @@ __global__ __launch_bounds__(256) void pg_mink_knn_kernel(const uint4 *__restric
         const u32 col = (u32)(t0 + cc);
         bool cand = cc < ncol && (key < tk[j] || (key == tk[j] && col < tc[j]));
         if (FLOOR) cand = cand && knn_after(key, col, fk[j], fc[j]);
-        u64 mask = __builtin_amdgcn_ballot_w64(cand);
-        while (mask) {
-          const int b = __builtin_ctzll(mask);
-          mask &= mask - 1;
-          const u32 xk = __builtin_amdgcn_readlane(key, b), xc = (u32)(t0 + s0 + b);
-          if (xk < tk[j] || (xk == tk[j] && xc < tc[j])) {
-            const bool keep = lk[j] < xk || (lk[j] == xk && lc[j] <= xc);     // entries not after x stay
-            const u32 pk = wave_shr1(lk[j], 0u), pc = wave_shr1(lc[j], 0u);
-            const bool prev_after = pk > xk || (pk == xk && pc > xc);          // lane-1's entry also moves, else x lands here
-            lk[j] = keep ? lk[j] : (prev_after ? pk : xk);
-            lc[j] = keep ? lc[j] : (prev_after ? pc : xc);
-            tk[j] = __builtin_amdgcn_readlane(lk[j], last);
-            tc[j] = __builtin_amdgcn_readlane(lc[j], last);
-          }
-        }
+        knn_insert(lk[j], lc[j], tk[j], tc[j], __builtin_amdgcn_ballot_w64(cand), key, 0, t0 + s0, last);
       }
     }
   }
@@ -366,7 +317,7 @@ __global__ __launch_bounds__(256) void pg_mink_eps_kernel(const uint4 *__restric
       for (int s0 = 0; s0 < ncol; s0 += 64) {
         const int cc = s0 + lane;
         const unsigned short v = cc < ncol ? tile[r][cc] : 0;
-        const bool hit = cc < ncol && mk_match(__half2float(__ushort_as_half(v)), eps, cmp, similarity);
+        const bool hit = cc < ncol && pg_match(__half2float(__ushort_as_half(v)), eps, cmp, similarity);
         const u64 mask = __builtin_amdgcn_ballot_w64(hit);
         if (hit) {
           const long long o = (long long)cnt[j] + mask_rank(mask);
@@ -389,102 +340,70 @@ __global__ __launch_bounds__(256) void pg_mink_eps_kernel(const uint4 *__restric
   }
 }
 
-// slots -> CSR for the rows that kept all their matches (count <= cap); one wave per row
-__global__ __launch_bounds__(256) void pg_mink_eps_compact_kernel(long long m, int cap, const int *__restrict__ slot_idx,
-                                                                  const unsigned short *__restrict__ slot_w,
-                                                                  const u32 *__restrict__ counts, const long long *__restrict__ indptr,
-                                                                  int *__restrict__ indices, unsigned short *__restrict__ weights) {
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= m) return;
-  const u32 cnt = counts[row];
-  if (cnt > (u32)cap) return;                                        // pg_minkowski_eps_fill_rows writes this row
-  const long long o = indptr[row], s = row * (long long)cap;
-  for (u32 i = lane; i < cnt; i += 64) {
-    indices[o + i] = slot_idx[s + i];
-    weights[o + i] = slot_w[s + i];
-  }
-}
-
-static int mfail(int code, const char *msg) {
-  pg_set_error(msg);
-  return code;
-}
-static int mlaunched(const char *where) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    char buf[200];
-    snprintf(buf, sizeof(buf), "%s: %s", where, hipGetErrorString(e));
-    pg_set_error(buf);
-    return (int)e;
-  }
-  return 0;
-}
-
 extern "C" {
 
 int pg_f16_nchunks(int d) { return d <= 0 ? 1 : (d + 7) / 8; }
 
 int pg_pack_f16(const void *src, int64_t n, int d, int64_t ld, const int64_t *rows, void *packed, int64_t npad, void *stream) {
-  if (!src || !packed || n < 0 || d <= 0 || ld < d) return mfail(PG_E_BADARG, "pg_pack_f16: bad argument");
-  if (npad < n || npad % 256) return mfail(PG_E_BADARG, "pg_pack_f16: npad must be pg_npad(n)");
+  if (!src || !packed || n < 0 || d <= 0 || ld < d) return pg_fail(PG_E_BADARG, "pg_pack_f16: bad argument");
+  if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_pack_f16: npad must be pg_npad(n)");
   pg_pack_f16_kernel<<<dim3((unsigned)(npad / 256)), dim3(256), 0, (hipStream_t)stream>>>(
       (const __half *)src, n, d, ld, (const long long *)rows, (uint4 *)packed, npad, pg_f16_nchunks(d));
-  return mlaunched("pg_pack_f16_kernel");
+  return pg_launched("pg_pack_f16_kernel");
 }
 
 int pg_minkowski_dense(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
                        int d, int similarity, void *out_f16, int64_t ldo, void *stream) {
   if (!x_packed || !y_packed || !out_f16 || n <= 0 || m <= 0 || d <= 0 || ldo < n)
-    return mfail(PG_E_BADARG, "pg_minkowski_dense: bad argument");
-  if (x_npad < n || x_npad % 256 || y_npad < m) return mfail(PG_E_BADARG, "pg_minkowski_dense: bad npad");
-  if ((m + MK_ROWS - 1) / MK_ROWS > 65535) return mfail(PG_E_BADARG, "pg_minkowski_dense: m too large for one launch");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_dense: bad argument");
+  if (x_npad < n || x_npad % 256 || y_npad < m) return pg_fail(PG_E_BADARG, "pg_minkowski_dense: bad npad");
+  if ((m + MK_ROWS - 1) / MK_ROWS > 65535) return pg_fail(PG_E_BADARG, "pg_minkowski_dense: m too large for one launch");
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)((m + MK_ROWS - 1) / MK_ROWS));
   pg_mink_dense_kernel<<<grid, dim3(256), 0, (hipStream_t)stream>>>((const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m,
                                                                     y_npad, pg_f16_nchunks(d), similarity ? 1 : 0,
                                                                     (__half *)out_f16, ldo);
-  return mlaunched("pg_mink_dense_kernel");
+  return pg_launched("pg_mink_dense_kernel");
 }
 
 int pg_f16_knn(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, int first, int descending, int32_t *idx_out,
                void *w_out_f16, void *stream) {
-  if (!dist_f16 || !idx_out || !w_out_f16 || m <= 0 || n <= 0 || ld < n) return mfail(PG_E_BADARG, "pg_f16_knn: bad argument");
-  if (k < 1 || first < 0 || first + k > 64) return mfail(PG_E_BADARG, "pg_f16_knn: first + k must be at most 64");
+  if (!dist_f16 || !idx_out || !w_out_f16 || m <= 0 || n <= 0 || ld < n) return pg_fail(PG_E_BADARG, "pg_f16_knn: bad argument");
+  if (k < 1 || first < 0 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_f16_knn: first + k must be at most 64");
   pg_f16_knn_kernel<false><<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const unsigned short *)dist_f16, m, n, ld, k, first, descending ? 1 : 0, idx_out, (unsigned short *)w_out_f16, nullptr,
       nullptr, 0, k);
-  return mlaunched("pg_f16_knn_kernel");
+  return pg_launched("pg_f16_knn_kernel");
 }
 
 int pg_f16_knn_round(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int k, int descending, const int32_t *floor_idx,
                      const void *floor_w_f16, int64_t floor_ld, int32_t *idx_out, void *w_out_f16, int64_t ldo, void *stream) {
   if (!dist_f16 || !idx_out || !w_out_f16 || !floor_idx || !floor_w_f16 || m <= 0 || n <= 0 || ld < n || floor_ld < 0 ||
       ldo < k)
-    return mfail(PG_E_BADARG, "pg_f16_knn_round: bad argument");
-  if (k < 1 || k > 64) return mfail(PG_E_BADARG, "pg_f16_knn_round: k must be 1..64");
+    return pg_fail(PG_E_BADARG, "pg_f16_knn_round: bad argument");
+  if (k < 1 || k > 64) return pg_fail(PG_E_BADARG, "pg_f16_knn_round: k must be 1..64");
   pg_f16_knn_kernel<true><<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const unsigned short *)dist_f16, m, n, ld, k, 0, descending ? 1 : 0, idx_out, (unsigned short *)w_out_f16, floor_idx,
       (const unsigned short *)floor_w_f16, floor_ld, ldo);
-  return mlaunched("pg_f16_knn_kernel(round)");
+  return pg_launched("pg_f16_knn_kernel(round)");
 }
 
 int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                      uint32_t *counts, void *stream) {
   if (!dist_f16 || !counts || m <= 0 || n <= 0 || ld < n || pg_cmp_bad(cmp))
-    return mfail(PG_E_BADARG, "pg_f16_eps_count: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_f16_eps_count: bad argument");
   pg_f16_eps_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const __half *)dist_f16, m, n, ld, cmp, eps_f16, similarity ? 1 : 0, counts, nullptr, nullptr, nullptr);
-  return mlaunched("pg_f16_eps_kernel(count)");
+  return pg_launched("pg_f16_eps_kernel(count)");
 }
 
 int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                     const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
   if (!dist_f16 || !indptr || !indices || !weights_f16 || m <= 0 || n <= 0 || ld < n || pg_cmp_bad(cmp))
-    return mfail(PG_E_BADARG, "pg_f16_eps_fill: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_f16_eps_fill: bad argument");
   pg_f16_eps_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
       (const __half *)dist_f16, m, n, ld, cmp, eps_f16, similarity ? 1 : 0, nullptr, (const long long *)indptr, indices,
       (__half *)weights_f16);
-  return mlaunched("pg_f16_eps_kernel(fill)");
+  return pg_launched("pg_f16_eps_kernel(fill)");
 }
 
 static int mk_operands_bad(const void *xp, int64_t n, int64_t x_npad, const void *yp, int64_t m, int64_t y_npad, int d) {
@@ -494,14 +413,14 @@ static int mk_operands_bad(const void *xp, int64_t n, int64_t x_npad, const void
 int pg_minkowski_knn(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad, int d,
                      int similarity, int k, int first, int32_t *idx_out, void *w_out_f16, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !idx_out || !w_out_f16)
-    return mfail(PG_E_BADARG, "pg_minkowski_knn: bad argument");
-  if (k < 1 || first < 0 || first + k > 64) return mfail(PG_E_BADARG, "pg_minkowski_knn: first + k must be at most 64");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_knn: bad argument");
+  if (k < 1 || first < 0 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_minkowski_knn: first + k must be at most 64");
   if (n > 0xFFFFFFFFll - 1 || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
-    return mfail(PG_E_BADARG, "pg_minkowski_knn: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_knn: too many vectors for one launch");
   pg_mink_knn_kernel<false><<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, k, first,
       idx_out, (unsigned short *)w_out_f16, nullptr, nullptr, 0, k);
-  return mlaunched("pg_mink_knn_kernel");
+  return pg_launched("pg_mink_knn_kernel");
 }
 
 int pg_minkowski_knn_round(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
@@ -509,14 +428,14 @@ int pg_minkowski_knn_round(const void *x_packed, int64_t n, int64_t x_npad, cons
                            int32_t *idx_out, void *w_out_f16, int64_t ldo, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !idx_out || !w_out_f16 || !floor_idx || !floor_w_f16 ||
       floor_ld < 0 || ldo < k)
-    return mfail(PG_E_BADARG, "pg_minkowski_knn_round: bad argument");
-  if (k < 1 || k > 64) return mfail(PG_E_BADARG, "pg_minkowski_knn_round: k must be 1..64");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_knn_round: bad argument");
+  if (k < 1 || k > 64) return pg_fail(PG_E_BADARG, "pg_minkowski_knn_round: k must be 1..64");
   if (n > 0xFFFFFFFFll - 1 || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
-    return mfail(PG_E_BADARG, "pg_minkowski_knn_round: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_knn_round: too many vectors for one launch");
   pg_mink_knn_kernel<true><<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, k, 0,
       idx_out, (unsigned short *)w_out_f16, floor_idx, (const unsigned short *)floor_w_f16, floor_ld, ldo);
-  return mlaunched("pg_mink_knn_kernel(round)");
+  return pg_launched("pg_mink_knn_kernel(round)");
 }
 
 int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
@@ -524,23 +443,19 @@ int pg_minkowski_eps_slots(const void *x_packed, int64_t n, int64_t x_npad, cons
                            uint32_t *counts, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !slot_idx || !slot_w_f16 || !counts || cap < 1 ||
       pg_cmp_bad(cmp))
-    return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_eps_slots: bad argument");
   if (n > 0x7FFFFFFFll || (m + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
-    return mfail(PG_E_BADARG, "pg_minkowski_eps_slots: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_eps_slots: too many vectors for one launch");
   pg_mink_eps_kernel<<<dim3((unsigned)((m + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, cmp, eps_f16,
       nullptr, 0, cap, slot_idx, (unsigned short *)slot_w_f16, counts, nullptr, nullptr, nullptr);
-  return mlaunched("pg_mink_eps_kernel(slots)");
+  return pg_launched("pg_mink_eps_kernel(slots)");
 }
 
 int pg_minkowski_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const void *slot_w_f16, const uint32_t *counts,
                              const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
-  if (!slot_idx || !slot_w_f16 || !counts || !indptr || !indices || !weights_f16 || m <= 0 || cap < 1)
-    return mfail(PG_E_BADARG, "pg_minkowski_eps_compact: bad argument");
-  pg_mink_eps_compact_kernel<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, (hipStream_t)stream>>>(
-      m, cap, slot_idx, (const unsigned short *)slot_w_f16, counts, (const long long *)indptr, indices,
-      (unsigned short *)weights_f16);
-  return mlaunched("pg_mink_eps_compact_kernel");
+  return pg_eps_compact_launch<unsigned short>("pg_minkowski_eps_compact", m, cap, slot_idx, slot_w_f16, counts, indptr, indices,
+                                               weights_f16, stream);
 }
 
 int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m, int64_t y_npad,
@@ -548,14 +463,14 @@ int pg_minkowski_eps_fill_rows(const void *x_packed, int64_t n, int64_t x_npad, 
                                const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream) {
   if (mk_operands_bad(x_packed, n, x_npad, y_packed, m, y_npad, d) || !row_list || n_list <= 0 || !indptr || !indices ||
       !weights_f16 || pg_cmp_bad(cmp))
-    return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: bad argument");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: bad argument");
   if (n > 0x7FFFFFFFll || (n_list + MK_ROWS - 1) / MK_ROWS > 0x7FFFFFFFll)
-    return mfail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: too many vectors for one launch");
+    return pg_fail(PG_E_BADARG, "pg_minkowski_eps_fill_rows: too many vectors for one launch");
   pg_mink_eps_kernel<<<dim3((unsigned)((n_list + MK_ROWS - 1) / MK_ROWS)), dim3(256), 0, (hipStream_t)stream>>>(
       (const uint4 *)x_packed, n, x_npad, (const uint4 *)y_packed, m, y_npad, pg_f16_nchunks(d), similarity ? 1 : 0, cmp, eps_f16,
       (const long long *)row_list, n_list, 1, nullptr, nullptr, nullptr, (const long long *)indptr, indices,
       (unsigned short *)weights_f16);
-  return mlaunched("pg_mink_eps_kernel(fill)");
+  return pg_launched("pg_mink_eps_kernel(fill)");
 }
 
 }  // extern "C"

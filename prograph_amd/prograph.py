@@ -577,15 +577,41 @@ class Prograph:
             qp = _native.pack(torch.from_numpy(np.ascontiguousarray(T.astype(np.uint8))), bits=bits, width=width)
         return n, bits, X, T, qp, dp
 
+    _BLOCK_ELEMS = 1 << 27        # elements of a staged distance block: <= 256 MB of fp16 at a time
+
+    def _block_rows(self, n, rows, floor):
+        """Rows per staged block of distances to n columns: `floor` is 64 for self graphs, 1 for queries."""
+        return max(floor, min(rows, self._BLOCK_ELEMS // n))
+
+    @staticmethod
+    def _select_blocks(blocks, knn=None, eps=None, wdtype=None):
+        """The selection over an iterator of fp16 distance blocks (row blocks of one matrix), one block alive at a time:
+        knn = (k, first, descending) -> (idx, w) of `f16_knn`, or eps = (cmp, thr, similarity, keep_zero) -> the CSR
+        (indptr, indices, w) of `f16_eps`, the blocks' results concatenated.  wdtype: what the fp16 weights are cast to."""
+        parts = []
+        for block in blocks:
+            if knn is not None:
+                part = _native.f16_knn(block, knn[0], first=knn[1], descending=knn[2])
+            else:
+                cmp, thr, similarity, keep_zero = eps                     # self graphs call f16_eps without keep_zero, as ever
+                part = _native.f16_eps(block, cmp, thr, similarity=similarity, **({"keep_zero": True} if keep_zero else {}))
+            del block
+            parts.append(part if wdtype is None else part[:-1] + (part[-1].to(wdtype),))
+        if knn is None:
+            return _native.cat_csr(parts)
+        return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+
+    @staticmethod
+    def _empty_knn(n, wdtype, dev, similarity, final=False):
+        """The kNN graph of k = 0 (after clamping to n - 1)."""
+        return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=dev), torch.zeros((n, 0), dtype=wdtype, device=dev), n,
+                        similarity=similarity, final=final)
+
     def _search_hamming_long(self, X, T, kk, bits, similarity):
         """Sequences beyond one record (up to 2048 positions): ranks 0..kk-1 of every fp16 block of
         `_hamming_long_blocks` (`pg_f16_knn`, first = 0; rounds beyond 64)."""
-        parts = []
-        for block in self._hamming_long_blocks(X, T, bits):
-            idx, wt = _native.f16_knn(block, kk, first=0, descending=False)
-            parts.append((idx, wt.to(torch.int16)))
-        return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), X.shape[0],
-                        similarity=similarity, first=0)
+        idx, wt = self._select_blocks(self._hamming_long_blocks(X, T, bits), knn=(kk, 0, False), wdtype=torch.int16)
+        return KNNGraph(idx, wt, X.shape[0], similarity=similarity, first=0)
 
     def _hamming_long_blocks(self, X, T, bits):
         """`_build_graph_long`'s staging for queries: the dense kernel over column segments of whole records into an
@@ -600,7 +626,7 @@ class Prograph:
         w = (_native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L) // 32 * 32
         segs = [(a, min(width, a + w)) for a in range(0, width, w)]
         xs = [_native.pack(Xd[:, a:b], bits=bits) for a, b in segs]
-        rows_per_block = max(64, min(q, (1 << 27) // n))                 # <= 256 MB of fp16 distances at a time
+        rows_per_block = self._block_rows(n, q, 64)
         for r0 in range(0, q, rows_per_block):
             block = None
             for (a, b), xp in zip(segs, xs):
@@ -622,10 +648,7 @@ class Prograph:
         if distance is minkowski:
             xp = _native.pack_f16(X)
             if Y.shape[0] < self._MINK_STAGED_ROWS:
-                rows = max(1, min(Y.shape[0], (1 << 27) // n))
-                parts = [_native.f16_knn(_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity),
-                                         kk, first=0, descending=similarity) for r0 in range(0, Y.shape[0], rows)]
-                idx, w = torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+                idx, w = self._select_blocks(self._mink_blocks(xp, Y, similarity), knn=(kk, 0, similarity))
             else:
                 idx, w = _native.minkowski_knn(xp, _native.pack_f16(Y), kk, first=0, similarity=similarity)
             return KNNGraph(idx, w, n, similarity=similarity, first=0)
@@ -634,6 +657,12 @@ class Prograph:
             return None
         idx, w = _native.cosine_knn(xc, yc, kk, first=0, similarity=similarity)
         return KNNGraph(idx, w, n, similarity=similarity, final=True, first=0)
+
+    def _mink_blocks(self, xp, Y, similarity):
+        """The staged Minkowski path of few queries: their dense fp16 blocks against the packed dataset."""
+        rows = self._block_rows(xp.n, Y.shape[0], 1)
+        return (_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity)
+                for r0 in range(0, Y.shape[0], rows))
 
     def _embedding_operands(self, Y, representation):
         """The fp16 device staging of dataset and queries (X, Y), the narrower one right-padded with zeros; None when the
@@ -680,32 +709,17 @@ class Prograph:
         if qo is None:
             return None
         n, q = xo.n, qo.n
-        rows = max(1, min(q, (1 << 27) // n))                            # <= 256 MB of fp16 distances at a time
+        rows = self._block_rows(n, q, 1)
         blocks = (_native.levenshtein_dense(xo, qo, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
         if k is not None:
-            parts = [_native.f16_knn(block, min(k, n), first=0, descending=False) for block in blocks]
-            return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]).to(torch.uint8), n,
-                            similarity=similarity, first=0)
+            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.uint8)
+            return KNNGraph(idx, w, n, similarity=similarity, first=0)
         cmp = _CMP_CODE[comp]
         thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
-        parts = []
-        for block in blocks:
-            ip, ix, w = _native.f16_eps(block, cmp, thr, similarity=False, keep_zero=True)
-            parts.append((ip, ix, w.to(torch.uint8)))
-        indptr, indices, wts = self._cat_csr(parts, _native.device())
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.uint8)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
-    @staticmethod
-    def _cat_csr(parts, dev):
-        if len(parts) == 1:
-            return parts[0]
-        base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
-        for indptr, _, _ in parts:
-            ptrs.append(indptr[1:] + base)
-            base += int(indptr[-1].item())
-        return torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts])
-
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
         """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
         the staged blocks and the fp16 selection with d = 0 kept (int16 weights, as `_build_graph_long` gives them).
@@ -721,11 +735,8 @@ class Prograph:
             indptr, indices, wts = _native.query_eps(qp, dp, cmp, eps)
         else:
             thr = self._integer_threshold(cmp, eps)
-            parts = []
-            for block in self._hamming_long_blocks(X, T, bits):
-                ip, ix, w = _native.f16_eps(block, cmp, thr, similarity=False, keep_zero=True)
-                parts.append((ip, ix, w.to(torch.int16)))
-            indptr, indices, wts = self._cat_csr(parts, _native.device())
+            indptr, indices, wts = self._select_blocks(self._hamming_long_blocks(X, T, bits), eps=(cmp, thr, False, True),
+                                                       wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _search_eps_embedding(self, Y, eps, comp, similarity, representation, distance):
@@ -742,10 +753,7 @@ class Prograph:
         if distance is minkowski:
             xp = _native.pack_f16(X)
             if Y.shape[0] < self._MINK_STAGED_ROWS:
-                rows = max(1, min(Y.shape[0], (1 << 27) // n))
-                parts = [_native.f16_eps(_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity),
-                                         cmp, eps, similarity=similarity, keep_zero=True) for r0 in range(0, Y.shape[0], rows)]
-                indptr, indices, wts = self._cat_csr(parts, X.device)
+                indptr, indices, wts = self._select_blocks(self._mink_blocks(xp, Y, similarity), eps=(cmp, eps, similarity, True))
             else:
                 indptr, indices, wts = _native.minkowski_eps(xp, _native.pack_f16(Y), cmp, eps, similarity=similarity,
                                                              keep_zero=True)
@@ -777,7 +785,7 @@ class Prograph:
             indptr = torch.zeros(d.shape[0] + 1, dtype=torch.int64, device=d.device)
             indptr[1:] = torch.cumsum(torch.bincount(loc[0], minlength=d.shape[0]), 0)
             parts.append((indptr, loc[1].to(torch.int32), d[loc]))
-        indptr, indices, wts = self._cat_csr(parts, parts[0][0].device)
+        indptr, indices, wts = _native.cat_csr(parts)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
 
     def _search_generic(self, strings, Y, k, similarity, representation, distance, output):
@@ -941,33 +949,23 @@ class Prograph:
         cmp = _CMP_CODE[comp]
         if eps:
             thr = self._integer_threshold(cmp, eps)
-        rows_per_block = max(64, min(n, (1 << 27) // n))                  # <= 256 MB of fp16 distances at a time
-        kk = min(k, n - 1) if k else 0
-        parts = []
-        for r0 in range(0, n, rows_per_block):
-            r1 = min(n, r0 + rows_per_block)
-            block = None
-            for (a, b), xp in zip(segs, xs):
-                block = _native.hamming_dense(xp, _native.pack(T[r0:r1, a:b], bits=bits), out_bytes=2, out=block)
-            if k:
-                if kk:
-                    idx, wt = _native.f16_knn(block, kk, first=1, descending=False)
-                    parts.append((idx, wt.to(torch.int16)))
-            else:
-                indptr, indices, wts = _native.f16_eps(block, cmp, thr, similarity=False)
-                parts.append((indptr, indices, wts.to(torch.int16)))
-            del block
+        rows_per_block = self._block_rows(n, n, 64)
+
+        def blocks():
+            for r0 in range(0, n, rows_per_block):
+                block = None
+                for (a, b), xp in zip(segs, xs):
+                    block = _native.hamming_dense(xp, _native.pack(T[r0:r0 + rows_per_block, a:b], bits=bits), out_bytes=2, out=block)
+                yield block
+
         if k:
+            kk = min(k, n - 1)
             if not kk:
-                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=dev), torch.zeros((n, 0), dtype=torch.int16, device=dev),
-                                n, similarity=similarity)
-            return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), n, similarity=similarity)
-        base, ptrs = 0, [torch.zeros(1, dtype=torch.int64, device=dev)]
-        for indptr, _, _ in parts:
-            ptrs.append(indptr[1:] + base)
-            base += int(indptr[-1].item())
-        return CSRGraph(torch.cat(ptrs), torch.cat([p_[1] for p_ in parts]), torch.cat([p_[2] for p_ in parts]), n,
-                        similarity=similarity)
+                return self._empty_knn(n, torch.int16, dev, similarity)
+            idx, wt = self._select_blocks(blocks(), knn=(kk, 1, False), wdtype=torch.int16)
+            return KNNGraph(idx, wt, n, similarity=similarity)
+        indptr, indices, wts = self._select_blocks(blocks(), eps=(cmp, thr, False, False), wdtype=torch.int16)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_minkowski(self, idxs, eps, k, similarity, representation, comp, cap=256):
         """
@@ -996,8 +994,7 @@ class Prograph:
         if k:
             kk = min(k, n - 1)
             if not kk:
-                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=X.device),
-                                torch.zeros((n, 0), dtype=torch.float16, device=X.device), n, similarity=similarity)
+                return self._empty_knn(n, torch.float16, X.device, similarity)
             idx, w = _native.minkowski_knn(xp, xp, kk, first=1, similarity=similarity)
             return KNNGraph(idx, w, n, similarity=similarity)
         indptr, indices, wts = _native.minkowski_eps(xp, xp, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
@@ -1031,8 +1028,7 @@ class Prograph:
         if k:
             kk = min(k, n - 1)
             if not kk:
-                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=X.device),
-                                torch.zeros((n, 0), dtype=torch.float32, device=X.device), n, similarity=similarity, final=True)
+                return self._empty_knn(n, torch.float32, X.device, similarity, final=True)
             idx, w = _native.cosine_knn(xc, xc, kk, first=1, similarity=similarity)
             return KNNGraph(idx, w, n, similarity=similarity, final=True)
         indptr, indices, wts = _native.cosine_eps(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
@@ -1065,12 +1061,11 @@ class Prograph:
             return None
         n, dev = op.n, op.tokens.device
         dense_only = os.environ.get("PG_LEV_ROUTE", "") == "dense"
-        block_rows = max(64, min(n, (1 << 27) // n))                     # <= 256 MB of fp16 distances at a time
+        block_rows = self._block_rows(n, n, 64)
         if k:
             kk = min(k, n - 1)
             if not kk:
-                return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=dev), torch.zeros((n, 0), dtype=torch.uint8, device=dev),
-                                n, similarity=similarity)
+                return self._empty_knn(n, torch.uint8, dev, similarity)
             if kk <= _native.MAX_K and n <= _native.MAX_N_KNN and not dense_only:
                 idx, dist = _native.levenshtein_knn(op.tokens, kk, band=self._LEV_FUSED_MAX)
                 todo = torch.nonzero(dist[:, kk - 1] > self._LEV_FUSED_MAX).reshape(-1)
@@ -1094,12 +1089,8 @@ class Prograph:
         if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr <= self._LEV_FUSED_MAX and not dense_only:
             indptr, indices, wts = _native.levenshtein_eps(op, cmp, thr, cap=max(int(cap), 64))
             return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-        parts = []
-        for r0 in range(0, n, block_rows):
-            ip, ix, w = _native.f16_eps(_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))), cmp, thr,
-                                        similarity=False)
-            parts.append((ip, ix, w.to(torch.uint8)))
-        indptr, indices, wts = self._cat_csr(parts, dev)
+        blocks = (_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.uint8)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
