@@ -376,6 +376,34 @@ int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_id
                     int32_t *indices, uint8_t *weights, void *stream);
 
 /*
+ * Substitution-matrix distance — BUILD DEFINED (the reference has Hamming only, which is the table 1 - I):
+ *     d(y, x) = sum_j C[y_j][x_j]     over zero-right-padded token rows, token 0 an ordinary index of C,
+ * C symmetric with at most 32 symbols and entries 0..255 (the caller validates the table; the kernels mask tokens
+ * to 0..31, so a bad operand gives wrong numbers, never an access out of bounds).
+ *   pg_sub_pack        (n, l) row-major uint8 tokens, leading dimension ld, -> the transposed dword order the
+ *                      dense kernel reads: dword g of sequence c (positions 4g..4g+3, low byte first) at byte
+ *                      (g * npad + c) * 4, npad = pg_npad(n); positions past l and sequences past n are 0.
+ *                      packed: ceil(l / 4) * npad * 4 bytes.  l <= 2048.  flags: uint32[1] the caller zeroes;
+ *                      set to 1 when some token is >= a (1 <= a <= 32).  Positions [p, l) of a packed matrix,
+ *                      p a multiple of 4, are the same buffer from byte (p / 4) * npad * 4 on.
+ *   pg_substitution_dense  out[r * ldo + c] = d(Y row r, X row c) for all m x n pairs; both operands packed at
+ *                      the same width l <= 2048 (PG_E_TOOLONG beyond).  cost_u8: the table as 32 x 32 bytes on
+ *                      the device, rows and columns from the alphabet size on zero.  out_elem_bytes 8 = int64,
+ *                      4 = int32, 2 = fp16 - the block format of pg_f16_knn / pg_f16_eps_*, exact while
+ *                      d <= 2048, which the caller guarantees (l * max C <= 2048); the kernel does not test it.
+ *                      accumulate != 0 adds to `out` instead of overwriting it, as in pg_hamming_dense: a
+ *                      distance is the sum over column segments.  Sums are kept in 16-bit lanes for at most 120
+ *                      positions (30 600 at cost 255) and widened when they are added into `out`, so any width
+ *                      is exact in the integer outputs.  A Y operand that starts at row r0 of a packed matrix is
+ *                      y_packed + 4 * r0 bytes with the matrix's npad.  Does not allocate; LDS only.
+ */
+int pg_sub_pack(const uint8_t *tokens, int64_t n, int l, int64_t ld, int a, void *packed, int64_t npad,
+                uint32_t *flags, void *stream);
+int pg_substitution_dense(const void *x_packed, int64_t n, int64_t x_npad, const void *y_packed, int64_t m,
+                          int64_t y_npad, int l, const uint8_t *cost_u8, void *out, int64_t ldo,
+                          int out_elem_bytes, int accumulate, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

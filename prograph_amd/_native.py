@@ -23,6 +23,7 @@ BITS_5, BITS_8 = 5, 8
 CMP_LE, CMP_LT, CMP_EQ, CMP_GE, CMP_GT = 0, 1, 2, 3, 4
 CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine eps entries: d = 0 (s = 1) is a hit
 MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 1023, 1 << 24, 8
+SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, symbols of the cost table
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -32,6 +33,7 @@ SYMBOLS = [
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
+    "pg_sub_pack", "pg_substitution_dense",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -125,6 +127,8 @@ def _load():
         lib.pg_lev_eps_pairs.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_lev_eps_count.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
         lib.pg_lev_eps_fill.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_sub_pack.argtypes = [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp]
+        lib.pg_substitution_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp]
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -741,6 +745,73 @@ def levenshtein_eps(op, cmp, thr, cap=512, keep_zero=False):
         _check(L.pg_lev_eps_fill(n, cap, code, thr, _ptr(slot_idx), _ptr(slot_w), _ptr(counts), _ptr(counts_lo), _ptr(indptr),
                                  _ptr(indices), _ptr(weights), _stream()), "pg_lev_eps_fill")
     return indptr, indices, weights
+
+
+class SubOperand:
+    """A token matrix staged for pg_substitution_dense (pg_sub_pack): `buf` int32 [ceil(l / 4) * npad], dword g of sequence
+    c at g * npad + c, and the validity word (non-zero: a token is outside the cost table)."""
+    __slots__ = ("buf", "n", "l", "npad", "flags")
+
+    def __init__(self, buf, n, l, flags):
+        self.buf, self.n, self.l, self.npad, self.flags = buf, int(n), int(l), npad(n), flags
+
+    def valid(self):
+        """One host sync: is every token an index of the table it was packed for?"""
+        return int(self.flags.item()) == 0
+
+
+def sub_cost(table):
+    """(A, A) integer cost table, A <= 32, entries 0..255 -> the 32 x 32 uint8 device table of pg_substitution_dense."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[0] != t.shape[1] or not 1 <= t.shape[0] <= SUB_MAX_A or t.min() < 0 or t.max() > 255:
+        raise ValueError("cost table: square, at most 32 symbols, entries 0..255")
+    full = np.zeros((SUB_MAX_A, SUB_MAX_A), dtype=np.uint8)
+    full[:t.shape[0], :t.shape[0]] = t
+    return torch.from_numpy(full).to(device())
+
+
+def sub_operand(tokens, a):
+    """(N, L <= 2048) uint8 tokens -> SubOperand for a table of `a` symbols.  No host sync: ask `valid()` before trusting a
+    result computed from it (the kernel masks tokens, so an invalid operand gives wrong numbers, nothing else)."""
+    dev = device()
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dtype != torch.uint8 or tokens.dim() != 2 or tokens.shape[0] == 0 or tokens.shape[1] == 0:
+        raise TypeError("sub_operand expects a non-empty 2-D uint8 token matrix")
+    if tokens.shape[1] > SUB_MAX_L:
+        raise ValueError(f"sub_operand: at most {SUB_MAX_L} tokens per sequence")
+    tokens = tokens.to(dev).contiguous()
+    n, l = tokens.shape
+    np_ = npad(n)
+    buf = torch.empty(((l + 3) // 4) * np_, dtype=torch.int32, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    _check(lib().pg_sub_pack(_ptr(tokens), n, l, tokens.stride(0), int(a), _ptr(buf), np_, _ptr(flags), _stream()), "pg_sub_pack")
+    return SubOperand(buf, n, l, flags)
+
+
+def substitution_dense(xo, yo, cost, out_bytes=8, rows=None, out=None, cols=None):
+    """(M, N) substitution distances of the rows of SubOperand `yo` (rows = (r0, r1): only those) against every row of
+    `xo` (pg_substitution_dense); `cost` from sub_cost.  int64 (out_bytes 8), int32 (4) or the fp16 block f16_knn /
+    f16_eps select from (2: exact while the distances stay within 2048).  With `out` given the distances are ADDED to
+    it; cols = (p0, p1), p0 a multiple of 4: only those positions (a distance is the sum over column segments)."""
+    if xo.l != yo.l:
+        raise ValueError("operands must be packed at the same width")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    p0, p1 = (0, xo.l) if cols is None else (int(cols[0]), int(cols[1]))
+    if not 0 <= p0 < p1 <= xo.l or p0 % 4:
+        raise ValueError("column segment outside the operand, or not from a multiple of 4 on")
+    accumulate = out is not None
+    if out is None:
+        out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    elif out.shape != (r1 - r0, xo.n) or out.stride(1) != 1:
+        raise ValueError("out must be a (rows, N) matrix with contiguous rows")
+    _check(lib().pg_substitution_dense(ctypes.c_void_p(xo.buf.data_ptr() + 4 * (p0 // 4) * xo.npad), xo.n, xo.npad,
+                                       ctypes.c_void_p(yo.buf.data_ptr() + 4 * ((p0 // 4) * yo.npad + r0)), r1 - r0,
+                                       yo.npad, p1 - p0, _ptr(cost), _ptr(out), out.stride(0), out.element_size(),
+                                       1 if accumulate else 0, _stream()), "pg_substitution_dense")
+    return out
 
 
 def csr_row_stats(indptr, indices, weights, f=None, want=("deg",), row0=0, ncols=None):

@@ -2,4 +2,5 @@ from .cosine import cosine
 from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn
 from .minkowski import minkowski
+from .substitution import substitution
 from .utils import clean_input

@@ -33,7 +33,7 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import cosine, hamming, levenshtein, minkowski
+from .distance import cosine, hamming, levenshtein, minkowski, substitution
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
@@ -469,8 +469,9 @@ class Prograph:
         or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
         Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
         dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; Levenshtein (queries of
-        any length up to 128, not only the dataset's) blocks of `pg_levenshtein_dense` plus the fp16 selection; any other
-        `distance` the generic loop.
+        any length up to 128, not only the dataset's) blocks of `pg_levenshtein_dense` plus the fp16 selection; a
+        `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; any other `distance` the generic
+        loop.
         """
         if eps is None:
             if not k:                                                      # build_graph's errors for k
@@ -509,6 +510,8 @@ class Prograph:
                 g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
             elif distance is levenshtein and comp in _CMP_CODE:
                 g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
+            elif isinstance(distance, substitution) and comp in _CMP_CODE:
+                g = self._search_substitution(strings, Y, None, eps, comp, similarity, representation, distance)
             if g is None:
                 g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
             return g if output == "csr" else g.to_tuples()
@@ -518,6 +521,8 @@ class Prograph:
             g = self._search_embedding(Y, k, similarity, representation, distance)
         elif distance is levenshtein and k <= _native.MAX_K_ROUNDS:
             g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
+        elif isinstance(distance, substitution) and k <= _native.MAX_K_ROUNDS:
+            g = self._search_substitution(strings, Y, k, None, None, similarity, representation, distance)
         if g is None:
             return self._search_generic(strings, Y, k, similarity, representation, distance, output)
         return g if output == "csr" else g.to_tuples()
@@ -719,6 +724,55 @@ class Prograph:
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.uint8)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
+    def _sub_tokens(self, mat, distance):
+        """The uint8 form of an integer token matrix whose tokens all index the table of `distance`, else None."""
+        mat = np.asarray(mat)
+        if mat.ndim != 2 or mat.shape[0] == 0 or mat.shape[1] == 0 or not np.issubdtype(mat.dtype, np.integer):
+            return None
+        if mat.min() < 0 or mat.max() >= distance.symbols:
+            return None
+        return mat.astype(np.uint8)
+
+    def _sub_native(self, width, distance):
+        """Does a width take the kernel route?  One call covers it, and every distance - at most width * max(C) - is an
+        integer that is exact in fp16."""
+        return width <= _native.SUB_MAX_L and width * distance.max_cost <= self._LONG_MAX_L
+
+    def _search_substitution(self, strings, Y, k, eps, comp, similarity, representation, distance):
+        """Queries under a `substitution` distance: Q x N blocks of `pg_substitution_dense` in fp16 and the fp16 selection
+        with rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width;
+        the narrower of queries and dataset is right-padded with zeros.  None (the generic loop with the operator) when
+        dataset or queries are not integer tokens of the table, or a distance could exceed 2048."""
+        try:
+            X = self._sub_tokens(self._dataset_matrix(representation), distance)
+        except (ValueError, TypeError):
+            return None
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        T = self._sub_tokens(T, distance) if X is not None else None
+        if T is None:
+            return None
+        width = max(X.shape[1], T.shape[1])
+        if not self._sub_native(width, distance):
+            return None
+        wide = [np.zeros((M.shape[0], width), dtype=np.uint8) for M in (X, T)]     # clean_input's zero right-padding
+        wide[0][:, :X.shape[1]], wide[1][:, :T.shape[1]] = X, T
+        xo, qo = (_native.sub_operand(torch.from_numpy(M), distance.symbols) for M in wide)
+        cost = distance.device_cost()
+        n, q = xo.n, qo.n
+        rows = self._block_rows(n, q, 1)
+        blocks = (_native.substitution_dense(xo, qo, cost, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+        if k is not None:
+            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.int16)
+            return KNNGraph(idx, w, n, similarity=similarity, first=0)
+        cmp = _CMP_CODE[comp]
+        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
         """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
@@ -864,6 +918,8 @@ class Prograph:
             g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
         if distance is levenshtein and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
+        if isinstance(distance, substitution) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+            g = self._build_graph_substitution(idxs, eps, k, similarity, representation, comp, distance)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:
@@ -1091,6 +1147,42 @@ class Prograph:
             return CSRGraph(indptr, indices, wts, n, similarity=similarity)
         blocks = (_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.uint8)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
+    def _build_graph_substitution(self, idxs, eps, k, similarity, representation, comp, distance):
+        """
+        `build_graph(distance=substitution(C))` on the HIP kernel: row blocks of `pg_substitution_dense` in fp16 and the
+        selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
+        thresholded CSR (`pg_f16_eps_*`), as `_build_graph_long` does for long Hamming sequences.  Taken when the
+        representation holds integer tokens of the table, at most 2048 positions, and width * max(C) <= 2048, so that
+        every distance is an integer fp16 holds exactly; else None (the generic loop with the operator).  Returns a
+        KNNGraph / CSRGraph with int16 weights; similarities as for Hamming: the same integer test on d, formed by the
+        container.
+        """
+        try:
+            mat = np.asarray(self._dataset_matrix(representation))
+            if idxs is not None:
+                mat = mat[np.asarray(idxs)]
+            T = self._sub_tokens(mat, distance)
+        except (ValueError, TypeError):
+            return None
+        if T is None or not self._sub_native(T.shape[1], distance):
+            return None
+        op = _native.sub_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+        cost = distance.device_cost()
+        n, dev = op.n, op.buf.device
+        block_rows = self._block_rows(n, n, 64)
+        blocks = (_native.substitution_dense(op, op, cost, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
+                  for r0 in range(0, n, block_rows))
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return self._empty_knn(n, torch.int16, dev, similarity)
+            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
+            return KNNGraph(idx, wt, n, similarity=similarity)
+        cmp = _CMP_CODE[comp]
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, self._integer_threshold(cmp, eps), False, False),
+                                                   wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
