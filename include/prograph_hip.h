@@ -404,6 +404,28 @@ int pg_substitution_dense(const void *x_packed, int64_t n, int64_t x_npad, const
                           int out_elem_bytes, int accumulate, void *stream);
 
 /*
+ * Gapped alignment distance - BUILD DEFINED (the reference has no such distance): global alignment (Needleman-Wunsch)
+ * under a symmetric cost table C (at most 32 symbols, entries 0..255) with a linear gap penalty,
+ *     H[0][j] = j * gap,  H[i][0] = i * gap,
+ *     H[i][j] = min(H[i-1][j-1] + C[x_i][y_j], H[i-1][j] + gap, H[i][j-1] + gap),     d(y, x) = H[len x][len y],
+ * a row's sequence being the row without its trailing zeros (an all-zero row is empty; an interior zero is symbol 0
+ * of C).  With C = 1 - I and gap 1 it is the Levenshtein distance.
+ *   pg_alignment_dense out[r * ldo + c] = d(Y row r, X row c) for all m x n pairs.  Both operands in the transposed
+ *                      dword order of pg_sub_pack, X packed at width xl, Y at width yl, each <= 128 (PG_E_TOOLONG
+ *                      beyond); the widths need not agree.  The lengths are found on the device, from the packed
+ *                      tokens; tokens are masked to 0..31 (the caller validates them: pg_sub_pack's flags word).
+ *                      cost_u8: the table as 32 x 32 bytes on the device (rows and columns from the alphabet size
+ *                      on zero); gap in 1..255.  out_elem_bytes 8 = int64 (a distance is at most 128 * 255 = 32 640),
+ *                      2 = fp16 - the block format of pg_f16_knn / pg_f16_eps_*, exact while d <= 2048, which the
+ *                      caller guarantees (max(xl, yl) * max(max C, gap) <= 2048); the kernel does not test it.
+ *                      A Y operand that starts at row r0 of a packed matrix is y_packed + 4 * r0 bytes with the
+ *                      matrix's npad.  Does not allocate; LDS only.
+ */
+int pg_alignment_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                       int64_t y_npad, int yl, const uint8_t *cost_u8, int gap, void *out, int64_t ldo,
+                       int out_elem_bytes, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

@@ -24,6 +24,7 @@ CMP_LE, CMP_LT, CMP_EQ, CMP_GE, CMP_GT = 0, 1, 2, 3, 4
 CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine eps entries: d = 0 (s = 1) is a hit
 MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 1023, 1 << 24, 8
 SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, symbols of the cost table
+ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -33,7 +34,7 @@ SYMBOLS = [
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
-    "pg_sub_pack", "pg_substitution_dense",
+    "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -129,6 +130,7 @@ def _load():
         lib.pg_lev_eps_fill.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_sub_pack.argtypes = [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp]
         lib.pg_substitution_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp]
+        lib.pg_alignment_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp]
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -811,6 +813,40 @@ def substitution_dense(xo, yo, cost, out_bytes=8, rows=None, out=None, cols=None
                                        ctypes.c_void_p(yo.buf.data_ptr() + 4 * ((p0 // 4) * yo.npad + r0)), r1 - r0,
                                        yo.npad, p1 - p0, _ptr(cost), _ptr(out), out.stride(0), out.element_size(),
                                        1 if accumulate else 0, _stream()), "pg_substitution_dense")
+    return out
+
+
+class AlnOperand(SubOperand):
+    """A token matrix staged for pg_alignment_dense: the transposed dwords and validity word of a SubOperand, at most
+    ALN_MAX_L positions.  The kernel finds the sequence lengths (last non-zero + 1) in these dwords itself."""
+    __slots__ = ()
+
+
+def aln_operand(tokens, a):
+    """(N, L <= 128) uint8 tokens -> AlnOperand for a table of `a` symbols (pg_sub_pack).  No host sync: ask `valid()`
+    before trusting a result computed from it (the kernel masks tokens, so an invalid operand gives wrong numbers, nothing
+    else)."""
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dim() == 2 and tokens.shape[1] > ALN_MAX_L:
+        raise ValueError(f"aln_operand: at most {ALN_MAX_L} tokens per sequence")
+    so = sub_operand(tokens, a)
+    return AlnOperand(so.buf, so.n, so.l, so.flags)
+
+
+def alignment_dense(xo, yo, cost, gap, out_bytes=8, rows=None):
+    """(M, N) gapped alignment distances of the rows of AlnOperand `yo` (rows = (r0, r1): only those) against every row
+    of `xo` (pg_alignment_dense); `cost` from sub_cost, `gap` 1..255; the operands' widths need not agree.  int64
+    (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2: exact while the distances stay within 2048)."""
+    if out_bytes not in (2, 8):
+        raise ValueError("alignment_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    _check(lib().pg_alignment_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
+                                    yo.npad, yo.l, _ptr(cost), int(gap), _ptr(out), out.stride(0), out_bytes, _stream()),
+           "pg_alignment_dense")
     return out
 
 

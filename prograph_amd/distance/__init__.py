@@ -1,3 +1,4 @@
+from .alignment import alignment
 from .cosine import cosine
 from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn

@@ -1,0 +1,144 @@
+"""
+Gapped alignment distance over tokenised, zero right-padded sequences - NOT in the reference (acmater/prograph ships
+only hamming / minkowski); defined by this build.
+
+    dist = alignment(C, gap)                  # C: (A, A) cost table indexed by token value, or a `substitution`
+    d = dist(X (N,D1), Y (M,D2))              # (M, N): global alignment of Y[m] with X[n]
+
+Global alignment (Needleman-Wunsch) with a linear gap penalty: d(x, y) is the minimum, over all alignments of the two
+sequences, of the sum of C[x_i, y_j] over the aligned pairs plus `gap` per symbol left unaligned,
+
+    H[0][j] = j * gap,   H[i][0] = i * gap,
+    H[i][j] = min(H[i-1][j-1] + C[x_i, y_j], H[i-1][j] + gap, H[i][j-1] + gap),       d = H[len x][len y].
+
+`dist` follows the operator protocol of `hamming`: row m is Y[m] against every row of X, `torch.int64`, on the device of
+X; `ValueError` on an empty operand; `similarity=True` returns 1/(1+d).
+
+    * a row's sequence is the row with its trailing zeros removed (an all-zero row is the empty sequence), as for
+      `levenshtein`, so the zero padding `clean_input` adds to the narrower operand changes nothing;
+    * an interior zero - a letter outside the alphabet - is an ordinary symbol: row and column 0 of C;
+    * the table takes the rules of `substitution` (square, 2..32 symbols, integers 0..255, symmetric, zero diagonal,
+      copied; `ValueError` otherwise) and is checked by that class; a `substitution` instance lends its table, so
+      `substitution.from_scores` and `substitution.for_alphabet` serve both distances;
+    * `gap` is an integer in 1..255 (`ValueError` for a bool, a fraction, 0 or more than 255);
+    * operands must hold integers in 0..A-1 (any dtype); anything else raises `ValueError`.
+
+`alignment(1 - I, 1)` is the Levenshtein distance; on operands of one length L without zeros and with
+2 * gap > L * max(C) no gap pays and the distance is `substitution(C)`.
+
+Device byte-token operands of at most 128 positions run on the HIP kernel (`pg_alignment_dense`,
+prograph_amd/csrc/pg_aln.hip).  Everything else is evaluated by the torch expression below on the device the operands
+live on, CPU included: the table row by row over the whole (M, N) batch, as in `levenshtein`, the dependency inside a
+row resolved by v[j] = j * gap + cummin(c[k] - k * gap).  It is the slow path; it is exact.
+
+`build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_alignment`, `_search_alignment`);
+two instances with equal table and gap behave identically.
+"""
+import numpy as np
+import torch
+
+from .. import _native
+from .hamming import _as_byte_tokens
+from .levenshtein import _lengths
+from .substitution import substitution
+from .utils import clean_input
+
+_DP_ELEMS = 1 << 24            # table entries (pairs x columns) alive per block of the torch expression
+
+
+def _gap(gap):
+    """An integer in 1..255 as int, or ValueError."""
+    if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)):
+        raise ValueError("the gap penalty must be an integer in 1..255")
+    if not np.isfinite(gap) or gap != int(gap) or not 1 <= int(gap) <= _native.ALN_MAX_GAP:
+        raise ValueError("the gap penalty must be an integer in 1..255")
+    return int(gap)
+
+
+class alignment:
+    """The distance of one cost table and gap penalty (see the module text)."""
+
+    def __init__(self, C, gap):
+        self._sub = C if isinstance(C, substitution) else substitution(C)      # its constructor validates and copies
+        self._gap = _gap(gap)
+
+    @property
+    def table(self):
+        """The (A, A) uint8 cost table (read-only)."""
+        return self._sub.table
+
+    @property
+    def gap(self):
+        return self._gap
+
+    @property
+    def symbols(self):
+        return self._sub.symbols
+
+    @property
+    def max_cost(self):
+        """The largest cost of one alignment column: max(max C, gap).  A distance is at most width * max_cost."""
+        return max(self._sub.max_cost, self._gap)
+
+    def __repr__(self):
+        return f"alignment(<{self.symbols} x {self.symbols} table, costs up to {self._sub.max_cost}>, gap={self._gap})"
+
+    def device_cost(self):
+        """The kernel's 32 x 32 uint8 table on the current HIP device."""
+        return self._sub.device_cost()
+
+    # ------------------------------------------------------------------ the operator
+    def _dp_block(self, Ct, x, lx, y, ly):
+        """(m, n) int64 distances of y rows (lengths ly) against x rows (lengths lx); x, y already cut to the longest
+        sequence among their rows."""
+        m, n, dx, gap = y.shape[0], x.shape[0], x.shape[1], self._gap
+        jg = torch.arange(dx + 1, device=x.device, dtype=torch.int32) * gap
+        v = jg.expand(m, n, dx + 1).contiguous()                             # row 0 of every table: H[0][j] = j * gap
+        at = lx.view(1, n, 1).expand(m, n, 1)
+        res = v.gather(2, at).squeeze(2)                                     # empty y: d = len(x) * gap
+        xl = x.long().view(1, n, dx)
+        for i in range(1, y.shape[1] + 1):
+            cost = Ct[y[:, i - 1].long().view(m, 1, 1), xl]                  # (m, n, dx): C[y_i, x_j]
+            c = torch.empty_like(v)
+            c[..., 0] = i * gap
+            c[..., 1:] = torch.minimum(v[..., 1:] + gap, v[..., :-1] + cost)  # gap in x | aligned pair
+            v = torch.cummin(c - jg, dim=2).values + jg                      # gaps in y: min over k <= j of c[k] + (j - k) gap
+            res = torch.where((ly == i).view(m, 1), v.gather(2, at).squeeze(2), res)
+        return res.to(torch.int64)
+
+    def _torch_expression(self, X, Y):
+        """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
+        Ct = self._sub._table_on(X.device).to(torch.int32)
+        lx, ly = _lengths(X), _lengths(Y)
+        X, Y = X[:, :int(lx.max())], Y[:, :int(ly.max())]
+        n, m = X.shape[0], Y.shape[0]
+        cols = max(1, min(n, _DP_ELEMS // (X.shape[1] + 1)))
+        rows = max(1, min(m, _DP_ELEMS // (cols * (X.shape[1] + 1))))
+        out = torch.empty((m, n), dtype=torch.int64, device=X.device)
+        for r0 in range(0, m, rows):
+            for c0 in range(0, n, cols):
+                out[r0:r0 + rows, c0:c0 + cols] = self._dp_block(Ct, X[c0:c0 + cols], lx[c0:c0 + cols], Y[r0:r0 + rows],
+                                                                 ly[r0:r0 + rows])
+        return out
+
+    def __call__(self, X, Y, similarity=False):
+        """(M, N) distances (or similarities 1/(1+d)) of the M rows of Y against the N rows of X, int64."""
+        X, Y = clean_input(X, Y)
+        Y = Y.to(X.device)
+        xb = _as_byte_tokens(X)
+        yb = xb if Y is X else _as_byte_tokens(Y)
+        if xb is None or yb is None:
+            raise ValueError("alignment: the tokens must be integers in 0..255")
+        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
+        if native:
+            xo = _native.aln_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
+            d = _native.alignment_dense(xo, yo, self.device_cost(), self._gap, out_bytes=8)
+            inside = int((xo.flags | yo.flags).item()) == 0                   # the pack's validity words: the one host sync
+        else:
+            inside = int(xb.max()) < self.symbols and int(yb.max()) < self.symbols
+        if not inside:
+            raise ValueError(f"alignment: a token is outside the cost table (0..{self.symbols - 1})")
+        if not native:
+            d = self._torch_expression(xb, yb)
+        return 1 / (1 + d) if similarity else d

@@ -33,7 +33,7 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import cosine, hamming, levenshtein, minkowski, substitution
+from .distance import alignment, cosine, hamming, levenshtein, minkowski, substitution
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
@@ -401,18 +401,18 @@ class Prograph:
             _, _, flags = _native.index_flags(planes, int(self.query(seq)), want=want,
                                               want_dist_out=False, want_hist=False)
             return _native.compact_flags(flags).cpu().numpy()
-        if distance is levenshtein and comp in _CMP_CODE:
-            return self.search(self._lev_query(seq), eps=eps, distance=levenshtein, comp=comp)[0][0]
+        if (distance is levenshtein or isinstance(distance, alignment)) and comp in _CMP_CODE:
+            return self.search(self._lev_query(seq), eps=eps, distance=distance, comp=comp)[0][0]
         d = distance(self.tokenized, self.tokenized[self.query(seq)].reshape(1, -1))
         return np.where(comp(d, eps))[1]
 
     def neighbourhood(self, seq, eps, distance=hamming):
         """All rows within `eps` of `seq`, the row itself included (reference :571-588).  A string that is not in the
         dataset is answered by `search(seq, eps=eps)`: the dataset rows within `eps` of it.  `distance=levenshtein`: the rows
-        within `eps` edits, for a string of any length up to 128."""
-        if distance is levenshtein:
+        within `eps` edits, for a string of any length up to 128; an `alignment` instance likewise."""
+        if distance is levenshtein or isinstance(distance, alignment):
             hit = np.zeros(len(self), dtype=bool)
-            hit[self.search(self._lev_query(seq), eps=eps, distance=levenshtein)[0][0]] = True
+            hit[self.search(self._lev_query(seq), eps=eps, distance=distance)[0][0]] = True
             return self[hit]
         if isinstance(seq, str) and seq not in self.seq_idxs:
             hit = np.zeros(len(self), dtype=bool)
@@ -470,7 +470,8 @@ class Prograph:
         Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
         dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; Levenshtein (queries of
         any length up to 128, not only the dataset's) blocks of `pg_levenshtein_dense` plus the fp16 selection; a
-        `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; any other `distance` the generic
+        `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; an `alignment` distance (queries
+        of any length up to 128) blocks of `pg_alignment_dense` plus the fp16 selection; any other `distance` the generic
         loop.
         """
         if eps is None:
@@ -512,6 +513,8 @@ class Prograph:
                 g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
             elif isinstance(distance, substitution) and comp in _CMP_CODE:
                 g = self._search_substitution(strings, Y, None, eps, comp, similarity, representation, distance)
+            elif isinstance(distance, alignment) and comp in _CMP_CODE:
+                g = self._search_alignment(strings, Y, None, eps, comp, similarity, representation, distance)
             if g is None:
                 g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
             return g if output == "csr" else g.to_tuples()
@@ -523,6 +526,8 @@ class Prograph:
             g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
         elif isinstance(distance, substitution) and k <= _native.MAX_K_ROUNDS:
             g = self._search_substitution(strings, Y, k, None, None, similarity, representation, distance)
+        elif isinstance(distance, alignment) and k <= _native.MAX_K_ROUNDS:
+            g = self._search_alignment(strings, Y, k, None, None, similarity, representation, distance)
         if g is None:
             return self._search_generic(strings, Y, k, similarity, representation, distance, output)
         return g if output == "csr" else g.to_tuples()
@@ -773,6 +778,42 @@ class Prograph:
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
+    def _aln_native(self, width, distance):
+        """Does a width take the alignment kernel route?  At most 128 positions, and every distance - at most
+        width * max(max C, gap): align the shorter sequence, gap the rest - is an integer that is exact in fp16."""
+        return width <= _native.ALN_MAX_L and width * distance.max_cost <= self._LONG_MAX_L
+
+    def _search_alignment(self, strings, Y, k, eps, comp, similarity, representation, distance):
+        """Queries under an `alignment` distance: Q x N blocks of `pg_alignment_dense` in fp16 and the fp16 selection with
+        rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width, any
+        length up to 128; dataset and queries keep their own widths.  None (the generic loop with the operator) when dataset
+        or queries are not integer tokens of the table, or a distance could exceed 2048."""
+        try:
+            X = self._sub_tokens(self._dataset_matrix(representation), distance)
+        except (ValueError, TypeError):
+            return None
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        T = self._sub_tokens(T, distance) if X is not None else None
+        if T is None or not self._aln_native(max(X.shape[1], T.shape[1]), distance):
+            return None
+        xo, qo = (_native.aln_operand(torch.from_numpy(np.ascontiguousarray(M)), distance.symbols) for M in (X, T))
+        cost = distance.device_cost()
+        n, q = xo.n, qo.n
+        rows = self._block_rows(n, q, 1)
+        blocks = (_native.alignment_dense(xo, qo, cost, distance.gap, out_bytes=2, rows=(r0, min(q, r0 + rows)))
+                  for r0 in range(0, q, rows))
+        if k is not None:
+            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.int16)
+            return KNNGraph(idx, w, n, similarity=similarity, first=0)
+        cmp = _CMP_CODE[comp]
+        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
         """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
@@ -920,6 +961,8 @@ class Prograph:
             g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
         if isinstance(distance, substitution) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_substitution(idxs, eps, k, similarity, representation, comp, distance)
+        if isinstance(distance, alignment) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+            g = self._build_graph_alignment(idxs, eps, k, similarity, representation, comp, distance)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:
@@ -1173,6 +1216,43 @@ class Prograph:
         n, dev = op.n, op.buf.device
         block_rows = self._block_rows(n, n, 64)
         blocks = (_native.substitution_dense(op, op, cost, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
+                  for r0 in range(0, n, block_rows))
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return self._empty_knn(n, torch.int16, dev, similarity)
+            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
+            return KNNGraph(idx, wt, n, similarity=similarity)
+        cmp = _CMP_CODE[comp]
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, self._integer_threshold(cmp, eps), False, False),
+                                                   wdtype=torch.int16)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
+    def _build_graph_alignment(self, idxs, eps, k, similarity, representation, comp, distance):
+        """
+        `build_graph(distance=alignment(C, gap))` on the HIP kernel: row blocks of `pg_alignment_dense` in fp16 and the
+        selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
+        thresholded CSR (`pg_f16_eps_*`), as `_build_graph_substitution` does.  Taken when the representation holds
+        integer tokens of the table, at most 128 positions, and width * max(max C, gap) <= 2048, so that every distance
+        is an integer fp16 holds exactly; else None (the generic loop with the operator).  Returns a KNNGraph / CSRGraph
+        with int16 weights; similarities as for Hamming: the same integer test on d, formed by the container.
+        """
+        if k is not None and k < 1:
+            raise ValueError("K must be at least 1.")
+        try:
+            mat = np.asarray(self._dataset_matrix(representation))
+            if idxs is not None:
+                mat = mat[np.asarray(idxs)]
+            T = self._sub_tokens(mat, distance)
+        except (ValueError, TypeError):
+            return None
+        if T is None or not self._aln_native(T.shape[1], distance):
+            return None
+        op = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+        cost = distance.device_cost()
+        n, dev = op.n, op.buf.device
+        block_rows = self._block_rows(n, n, 64)
+        blocks = (_native.alignment_dense(op, op, cost, distance.gap, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
                   for r0 in range(0, n, block_rows))
         if k:
             kk = min(k, n - 1)

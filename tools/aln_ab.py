@@ -1,0 +1,178 @@
+"""
+Timings behind DESIGN.md §4.15 (gapped alignment distance), on one GPU.  Every time is a whole call on a host clock,
+from the call to the end of a device synchronise, after a warm-up; arms alternate; inputs are seeded and random;
+medians with min / max.
+
+  dense   pg_alignment_dense, 8192 rows x N = 50 000, fp16 output, 21 symbols, at two shapes: rows of 125..128 tokens
+          (the shape pg_levenshtein_dense was measured at) and rows of exactly 64.  Time, pairs/s, cell updates/s
+          (pairs x len x x len y) and the share of the VALU issue rate: the unrolled body of one outer step is
+          VALU_PER_STEP[chunks] instructions in the ISA (523 for 8 chunks of 16 cells, 4.09 per cell), a wave runs one
+          outer step per position of its longest X row, and 256 CUs x 4 SIMDs x 2.4 GHz instructions/s is the rate.
+          Beside it, in the same run, as context: `pg_levenshtein_dense` (bit-parallel) and `pg_substitution_dense`
+          (no recurrence) at the same shapes, and the blocked torch expression of the operator on --torch-rows rows.
+  graph   build_graph(k = 16) at N = --n-graph with lengths 48..64: `_build_graph_alignment` against
+          `_build_graph_generic` with the operator (--generic-reps runs: it takes long); graphs compared.
+  pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
+
+Prints one JSON line; progress goes to stderr.
+
+    python tools/aln_ab.py [--reps 5] [--only dense,graph] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import pandas as pd
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from prograph_amd import Prograph, _native  # noqa: E402
+from prograph_amd.distance import alignment  # noqa: E402
+
+# VALU instructions of one outer step (one X symbol against 16 * chunks cells) in the gfx950 ISA of pg_aln_dense_kernel.
+# Counted by hand from the compiler's assembly (`--save-temps`; the table is in profiles/aln_dense.txt).  Nothing keeps it
+# in step with the kernel: after any change to csrc/pg_aln.hip, its build flags or the compiler, count again and update
+# both places, or `share_of_valu_issue` below is wrong without a sign of it.
+VALU_PER_STEP = {1: 69, 2: 134, 3: 199, 4: 264, 5: 329, 6: 394, 7: 459, 8: 523}
+ISSUE_RATE = 256 * 4 * 2.4e9
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def stats(v):
+    return {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v)), "runs": len(v)}
+
+
+def alternate(fns, reps, log, skip_after=None):
+    """Medians of alternating windows; an arm named in `skip_after` is timed only that many times (the slow ones)."""
+    skip_after = skip_after or {}
+    for f in fns.values():
+        f()                                                                    # warm-up (code objects loaded)
+    times, outs = {k: [] for k in fns}, {}
+    for r in range(reps):
+        for key, f in fns.items():
+            if r >= skip_after.get(key, reps):
+                continue
+            outs[key] = None
+            t, outs[key] = timed(f)
+            times[key].append(t)
+    res = {k: stats(v) for k, v in times.items()}
+    print(log, json.dumps(res), file=sys.stderr, flush=True)
+    return res, outs
+
+
+def random_table(rng, a, hi):
+    C = np.triu(rng.integers(1, hi + 1, (a, a)), 1)
+    return C + C.T
+
+
+def varlen(rng, n, lo, hi, a):
+    """(n, hi) uint8 rows of tokens 1..a-1 with lengths lo..hi, zero right-padded."""
+    tok = rng.integers(1, a, (n, hi), dtype=np.uint8)
+    lens = rng.integers(lo, hi + 1, n)
+    tok[np.arange(hi)[None, :] >= lens[:, None]] = 0
+    return tok, lens
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--torch-reps", type=int, default=2)
+    ap.add_argument("--generic-reps", type=int, default=1)
+    ap.add_argument("--n", type=int, default=50_000)
+    ap.add_argument("--rows", type=int, default=8192)
+    ap.add_argument("--torch-rows", type=int, default=256)
+    ap.add_argument("--n-graph", type=int, default=50_000)
+    ap.add_argument("--only", default="dense,graph")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = _native.device()
+    out = {"device": _native.device_info()["arch"], "reps": args.reps, "library": os.path.basename(_native.LIB_PATH)}
+    only = args.only.split(",")
+    rng = np.random.default_rng(1)
+    a = 21
+
+    if "dense" in only or "pmc" in only:
+        n, m, tr = args.n, args.rows, args.torch_rows
+        for name, lo, hi in (("l125_128", 125, 128), ("l64", 64, 64)):
+            C = random_table(rng, a, 2048 // hi)
+            dist = alignment(C, 2048 // hi)
+            host, lens = varlen(rng, n, lo, hi, a)
+            tok = torch.from_numpy(host).to(dev)
+            xo = _native.aln_operand(tok, a)
+            cost = dist.device_cost()
+            assert xo.valid()
+            aln = lambda: _native.alignment_dense(xo, xo, cost, dist.gap, out_bytes=2, rows=(0, m))     # noqa: E731
+            if "pmc" in only:
+                aln()
+                torch.cuda.synchronize()
+                print(json.dumps({"pmc": "one dense call", "n": n, "rows": m, "shape": name}))
+                return
+            lo_ = _native.lev_operand(tok)
+            so = _native.sub_operand(tok, a)
+            fns = {"alignment_dense_f16": aln,
+                   "levenshtein_dense_f16": lambda: _native.levenshtein_dense(lo_, lo_, out_bytes=2, rows=(0, m)),
+                   "substitution_dense_f16": lambda: _native.substitution_dense(so, so, cost, out_bytes=2, rows=(0, m)),
+                   "torch_expression": lambda: dist._torch_expression(tok, tok[:tr])}
+            res, outs = alternate(fns, args.reps, name, skip_after={"torch_expression": args.torch_reps})
+            same = bool(torch.equal(outs["alignment_dense_f16"][:tr].to(torch.int64), outs["torch_expression"]))
+            ms = res["alignment_dense_f16"]["median_ms"]
+            pairs = m * n / (ms * 1e-3)
+            cells = float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3)
+            # per wave: one outer step per position of its longest row, the body of the Y row's chunk count
+            wave_max = np.pad(lens, (0, -len(lens) % 64)).reshape(-1, 64).max(axis=1).astype(np.float64).sum()
+            body = np.array([VALU_PER_STEP[max(1, (int(l) + 15) // 16)] for l in lens[:m]], dtype=np.float64).sum()
+            valu = wave_max * body / (ms * 1e-3)
+            torch_pairs = tr * n / (res["torch_expression"]["median_ms"] * 1e-3)
+            res.update(n=n, rows=m, lengths=[lo, hi], symbols=a, gap=dist.gap, pairs_per_s=pairs, cell_updates_per_s=cells,
+                       valu_instructions_per_s=valu, share_of_valu_issue=valu / ISSUE_RATE, torch_rows=tr,
+                       torch_pairs_per_s=torch_pairs, speedup_over_torch_expression=pairs / torch_pairs,
+                       levenshtein_pairs_per_s=m * n / (res["levenshtein_dense_f16"]["median_ms"] * 1e-3),
+                       substitution_pairs_per_s=m * n / (res["substitution_dense_f16"]["median_ms"] * 1e-3),
+                       first_rows_equal_torch=same)
+            out["dense_" + name] = res
+            del outs, xo, lo_, so, tok, fns
+            torch.cuda.empty_cache()
+
+    if "graph" in only:
+        n = args.n_graph
+        C = random_table(rng, a, 12)
+        dist = alignment(C, 5)
+        tok, lens = varlen(rng, n, 48, 64, a)
+        tok[1::2, 3:] = tok[0::2, 3:][:len(tok[1::2])]                         # near pairs, so that ranks are not all ties of noise
+        tok = tok.astype(np.int64)
+        pg = Prograph.__new__(Prograph)                                        # the graph builder alone: no file
+        pg.tokenized = tok
+        pg.graph = pd.DataFrame({"Tokenized": list(tok)})
+        native = lambda: pg._build_graph_alignment(None, None, 16, False, "Tokenized", None, dist)     # noqa: E731
+        res, outs = alternate({"native_k16": native}, args.reps, "graph")
+        G = outs["native_k16"]
+        times = []
+        for _ in range(args.generic_reps):
+            t, tuples = timed(lambda: pg._build_graph_generic(None, 8, None, 16, False, "Tokenized", dist, None))
+            times.append(t)
+        res["generic_loop_operator_k16"] = stats(times)
+        gi = np.array([i for i, _ in tuples])
+        gw = np.array([w for _, w in tuples])
+        res.update(n=n, lengths=[48, 64], k=16, gap=5,
+                   identical=bool(np.array_equal(G.idx.cpu().numpy(), gi) and np.array_equal(G.dist.cpu().numpy(), gw)),
+                   speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
+        out["graph"] = res
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
