@@ -426,6 +426,24 @@ int pg_alignment_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, 
                        int out_elem_bytes, void *stream);
 
 /*
+ * The same distance with AFFINE gap penalties - BUILD DEFINED: a maximal run of g consecutive unaligned symbols of one
+ * sequence costs gap_open + g * gap; a run in x directly followed by a run in y is two runs.  With e = gap, o = gap_open:
+ *     H[0][0] = 0,  H[0][j] = o + j e,  H[i][0] = o + i e,
+ *     E[i][j] = min(E[i-1][j] + e, H[i-1][j] + o + e),   F[i][j] = min(F[i][j-1] + e, H[i][j-1] + o + e),
+ *     H[i][j] = min(H[i-1][j-1] + C[x_i][y_j], E[i][j], F[i][j]),                     d(y, x) = H[len x][len y]
+ * (E[0][j] and F[i][0] infinite).
+ *   pg_alignment_affine_dense  operands, cost table, lengths, output formats, row offsets and error codes as for
+ *                      pg_alignment_dense; gap in 1..255, gap_open in 0..255 (PG_E_BADARG otherwise).  With
+ *                      gap_open = 0 the result is pg_alignment_dense's.  A distance is at most
+ *                      128 * 255 + 255 = 32 895; the fp16 output is exact while d <= 2048, which the caller
+ *                      guarantees (max(xl, yl) * max(max C, gap) + gap_open <= 2048); the kernel does not test it.
+ *                      Does not allocate; LDS only.
+ */
+int pg_alignment_affine_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                              int64_t y_npad, int yl, const uint8_t *cost_u8, int gap, int gap_open, void *out,
+                              int64_t ldo, int out_elem_bytes, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

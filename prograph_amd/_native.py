@@ -25,6 +25,7 @@ CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine 
 MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 1023, 1 << 24, 8
 SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, symbols of the cost table
 ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
+ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-open penalty
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -34,7 +35,7 @@ SYMBOLS = [
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
-    "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense",
+    "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -131,6 +132,8 @@ def _load():
         lib.pg_sub_pack.argtypes = [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp]
         lib.pg_substitution_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp]
         lib.pg_alignment_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp]
+        lib.pg_alignment_affine_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32,
+                                                  _vp]
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -847,6 +850,22 @@ def alignment_dense(xo, yo, cost, gap, out_bytes=8, rows=None):
     _check(lib().pg_alignment_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
                                     yo.npad, yo.l, _ptr(cost), int(gap), _ptr(out), out.stride(0), out_bytes, _stream()),
            "pg_alignment_dense")
+    return out
+
+
+def alignment_affine_dense(xo, yo, cost, gap, gap_open, out_bytes=8, rows=None):
+    """`alignment_dense` with affine gap penalties (pg_alignment_affine_dense): a run of g unaligned symbols costs
+    gap_open + g * gap, `gap` 1..255, `gap_open` 0..255 (0: the distances of `alignment_dense`).  Same AlnOperands, row
+    range and outputs; fp16 is exact while width * max(max C, gap) + gap_open stays within 2048."""
+    if out_bytes not in (2, 8):
+        raise ValueError("alignment_affine_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    _check(lib().pg_alignment_affine_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
+                                           r1 - r0, yo.npad, yo.l, _ptr(cost), int(gap), int(gap_open), _ptr(out),
+                                           out.stride(0), out_bytes, _stream()), "pg_alignment_affine_dense")
     return out
 
 

@@ -3,6 +3,7 @@ Gapped alignment distance over tokenised, zero right-padded sequences - NOT in t
 only hamming / minkowski); defined by this build.
 
     dist = alignment(C, gap)                  # C: (A, A) cost table indexed by token value, or a `substitution`
+    dist = alignment(C, gap, gap_open=o)      # affine: a run of g unaligned symbols costs o + g * gap (see below)
     d = dist(X (N,D1), Y (M,D2))              # (M, N): global alignment of Y[m] with X[n]
 
 Global alignment (Needleman-Wunsch) with a linear gap penalty: d(x, y) is the minimum, over all alignments of the two
@@ -31,8 +32,22 @@ prograph_amd/csrc/pg_aln.hip).  Everything else is evaluated by the torch expres
 live on, CPU included: the table row by row over the whole (M, N) batch, as in `levenshtein`, the dependency inside a
 row resolved by v[j] = j * gap + cummin(c[k] - k * gap).  It is the slow path; it is exact.
 
+Affine gap penalties: `alignment(C, gap, gap_open=o)`, o an integer in 0..255, prices a maximal run of g consecutive
+unaligned symbols of one sequence at o + g * gap (a run in x directly followed by a run in y is two runs) - an indel of
+several residues is one event, as the open / extend pair that accompanies a score matrix has it.  With e = gap:
+
+    H[0][0] = 0,   H[0][j] = o + j e,   H[i][0] = o + i e,
+    E[i][j] = min(E[i-1][j] + e, H[i-1][j] + o + e),   F[i][j] = min(F[i][j-1] + e, H[i][j-1] + o + e),
+    H[i][j] = min(H[i-1][j-1] + C[x_i, y_j], E[i][j], F[i][j]),                       d = H[len x][len y],
+
+E[0][j] and F[i][0] infinite.  gap_open = 0 is the linear form above in every respect.  With gap_open > 0 the kernel is
+`pg_alignment_affine_dense` (prograph_amd/csrc/pg_aln_affine.hip) and the torch expression carries E between rows:
+A[j] = min(v_old[j-1] + cost, E[j]), F[j] = o + j e + cummin_{k<j}(A[k] - k e) - a cell that is itself in a gap never
+opens a cheaper one than extending does, so the cummin may run over A instead of H - and v[j] = min(A[j], F[j]).
+A distance is at most width * max(max C, gap) + gap_open: align the shorter sequence, gap the rest in one run.
+
 `build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_alignment`, `_search_alignment`);
-two instances with equal table and gap behave identically.
+two instances with equal table, gap and gap_open behave identically.
 """
 import numpy as np
 import torch
@@ -46,6 +61,15 @@ from .utils import clean_input
 _DP_ELEMS = 1 << 24            # table entries (pairs x columns) alive per block of the torch expression
 
 
+def _gap_open(gap_open):
+    """An integer in 0..255 as int, or ValueError."""
+    if isinstance(gap_open, (bool, np.bool_)) or not isinstance(gap_open, (int, float, np.integer, np.floating)):
+        raise ValueError("the gap-open penalty must be an integer in 0..255")
+    if not np.isfinite(gap_open) or gap_open != int(gap_open) or not 0 <= int(gap_open) <= _native.ALN_MAX_OPEN:
+        raise ValueError("the gap-open penalty must be an integer in 0..255")
+    return int(gap_open)
+
+
 def _gap(gap):
     """An integer in 1..255 as int, or ValueError."""
     if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)):
@@ -56,11 +80,12 @@ def _gap(gap):
 
 
 class alignment:
-    """The distance of one cost table and gap penalty (see the module text)."""
+    """The distance of one cost table and gap penalty, linear or affine (see the module text)."""
 
-    def __init__(self, C, gap):
+    def __init__(self, C, gap, gap_open=0):
         self._sub = C if isinstance(C, substitution) else substitution(C)      # its constructor validates and copies
         self._gap = _gap(gap)
+        self._open = _gap_open(gap_open)
 
     @property
     def table(self):
@@ -72,16 +97,23 @@ class alignment:
         return self._gap
 
     @property
+    def gap_open(self):
+        """The price of opening a run of unaligned symbols, on top of `gap` per symbol; 0 is the linear penalty."""
+        return self._open
+
+    @property
     def symbols(self):
         return self._sub.symbols
 
     @property
     def max_cost(self):
-        """The largest cost of one alignment column: max(max C, gap).  A distance is at most width * max_cost."""
+        """The largest cost of one alignment column: max(max C, gap).  A distance is at most width * max_cost +
+        gap_open."""
         return max(self._sub.max_cost, self._gap)
 
     def __repr__(self):
-        return f"alignment(<{self.symbols} x {self.symbols} table, costs up to {self._sub.max_cost}>, gap={self._gap})"
+        opening = f", gap_open={self._open}" if self._open else ""
+        return f"alignment(<{self.symbols} x {self.symbols} table, costs up to {self._sub.max_cost}>, gap={self._gap}{opening})"
 
     def device_cost(self):
         """The kernel's 32 x 32 uint8 table on the current HIP device."""
@@ -91,6 +123,8 @@ class alignment:
     def _dp_block(self, Ct, x, lx, y, ly):
         """(m, n) int64 distances of y rows (lengths ly) against x rows (lengths lx); x, y already cut to the longest
         sequence among their rows."""
+        if self._open:
+            return self._dp_block_affine(Ct, x, lx, y, ly)
         m, n, dx, gap = y.shape[0], x.shape[0], x.shape[1], self._gap
         jg = torch.arange(dx + 1, device=x.device, dtype=torch.int32) * gap
         v = jg.expand(m, n, dx + 1).contiguous()                             # row 0 of every table: H[0][j] = j * gap
@@ -106,14 +140,38 @@ class alignment:
             res = torch.where((ly == i).view(m, 1), v.gather(2, at).squeeze(2), res)
         return res.to(torch.int64)
 
+    def _dp_block_affine(self, Ct, x, lx, y, ly):
+        """`_dp_block` under affine penalties: E (a run ending in a gap against y_i) is carried from row to row, F (a run
+        along the row) is resolved inside the row by the cummin over A = min(diagonal, E)."""
+        m, n, dx, e, o = y.shape[0], x.shape[0], x.shape[1], self._gap, self._open
+        jg = torch.arange(dx + 1, device=x.device, dtype=torch.int32) * e
+        v = (jg + o).expand(m, n, dx + 1).contiguous()                       # row 0: H[0][j] = o + j e,
+        v[..., 0] = 0                                                        # H[0][0] = 0
+        E = v + o                                                            # stands for E[0][j] = inf: E + e = H + o + e
+        at = lx.view(1, n, 1).expand(m, n, 1)
+        res = v.gather(2, at).squeeze(2)                                     # empty y: one run of len(x), or nothing
+        xl = x.long().view(1, n, dx)
+        for i in range(1, y.shape[1] + 1):
+            cost = Ct[y[:, i - 1].long().view(m, 1, 1), xl]                  # (m, n, dx): C[y_i, x_j]
+            E = torch.minimum(E + e, v + (o + e))                            # extend the run | open one from the row above
+            A = torch.empty_like(v)
+            A[..., 0] = o + i * e                                            # H[i][0], which is E[i][0]
+            A[..., 1:] = torch.minimum(v[..., :-1] + cost, E[..., 1:])       # aligned pair | gap against y_i
+            F = torch.full_like(v, 1 << 30)                                  # F[i][0] = inf
+            F[..., 1:] = torch.cummin(A - jg, dim=2).values[..., :-1] + jg[1:] + o      # min over k < j of A[k] + o + (j - k) e
+            v = torch.minimum(A, F)
+            res = torch.where((ly == i).view(m, 1), v.gather(2, at).squeeze(2), res)
+        return res.to(torch.int64)
+
     def _torch_expression(self, X, Y):
         """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
         Ct = self._sub._table_on(X.device).to(torch.int32)
         lx, ly = _lengths(X), _lengths(Y)
         X, Y = X[:, :int(lx.max())], Y[:, :int(ly.max())]
         n, m = X.shape[0], Y.shape[0]
-        cols = max(1, min(n, _DP_ELEMS // (X.shape[1] + 1)))
-        rows = max(1, min(m, _DP_ELEMS // (cols * (X.shape[1] + 1))))
+        elems = _DP_ELEMS // 2 if self._open else _DP_ELEMS                  # the affine form keeps E beside every row
+        cols = max(1, min(n, elems // (X.shape[1] + 1)))
+        rows = max(1, min(m, elems // (cols * (X.shape[1] + 1))))
         out = torch.empty((m, n), dtype=torch.int64, device=X.device)
         for r0 in range(0, m, rows):
             for c0 in range(0, n, cols):
@@ -133,7 +191,10 @@ class alignment:
         if native:
             xo = _native.aln_operand(xb, self.symbols)
             yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
-            d = _native.alignment_dense(xo, yo, self.device_cost(), self._gap, out_bytes=8)
+            if self._open:
+                d = _native.alignment_affine_dense(xo, yo, self.device_cost(), self._gap, self._open, out_bytes=8)
+            else:
+                d = _native.alignment_dense(xo, yo, self.device_cost(), self._gap, out_bytes=8)
             inside = int((xo.flags | yo.flags).item()) == 0                   # the pack's validity words: the one host sync
         else:
             inside = int(xb.max()) < self.symbols and int(yb.max()) < self.symbols

@@ -780,11 +780,21 @@ class Prograph:
 
     def _aln_native(self, width, distance):
         """Does a width take the alignment kernel route?  At most 128 positions, and every distance - at most
-        width * max(max C, gap): align the shorter sequence, gap the rest - is an integer that is exact in fp16."""
-        return width <= _native.ALN_MAX_L and width * distance.max_cost <= self._LONG_MAX_L
+        width * max(max C, gap) + gap_open: align the shorter sequence, gap the rest in one run - is an integer that is
+        exact in fp16."""
+        return width <= _native.ALN_MAX_L and width * distance.max_cost + distance.gap_open <= self._LONG_MAX_L
+
+    @staticmethod
+    def _aln_dense(distance, xo, yo, cost, rows):
+        """One fp16 block of the alignment kernel the distance asks for: `pg_alignment_affine_dense` with a gap-open
+        penalty, `pg_alignment_dense` without."""
+        if distance.gap_open:
+            return _native.alignment_affine_dense(xo, yo, cost, distance.gap, distance.gap_open, out_bytes=2, rows=rows)
+        return _native.alignment_dense(xo, yo, cost, distance.gap, out_bytes=2, rows=rows)
 
     def _search_alignment(self, strings, Y, k, eps, comp, similarity, representation, distance):
-        """Queries under an `alignment` distance: Q x N blocks of `pg_alignment_dense` in fp16 and the fp16 selection with
+        """Queries under an `alignment` distance: Q x N blocks of `pg_alignment_dense` (`pg_alignment_affine_dense` when
+        the distance has a gap-open penalty) in fp16 and the fp16 selection with
         rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width, any
         length up to 128; dataset and queries keep their own widths.  None (the generic loop with the operator) when dataset
         or queries are not integer tokens of the table, or a distance could exceed 2048."""
@@ -804,8 +814,7 @@ class Prograph:
         cost = distance.device_cost()
         n, q = xo.n, qo.n
         rows = self._block_rows(n, q, 1)
-        blocks = (_native.alignment_dense(xo, qo, cost, distance.gap, out_bytes=2, rows=(r0, min(q, r0 + rows)))
-                  for r0 in range(0, q, rows))
+        blocks = (self._aln_dense(distance, xo, qo, cost, (r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
         if k is not None:
             idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.int16)
             return KNNGraph(idx, w, n, similarity=similarity, first=0)
@@ -1230,10 +1239,11 @@ class Prograph:
 
     def _build_graph_alignment(self, idxs, eps, k, similarity, representation, comp, distance):
         """
-        `build_graph(distance=alignment(C, gap))` on the HIP kernel: row blocks of `pg_alignment_dense` in fp16 and the
+        `build_graph(distance=alignment(C, gap[, gap_open]))` on the HIP kernel: row blocks of `pg_alignment_dense`
+        (`pg_alignment_affine_dense` when the distance has a gap-open penalty) in fp16 and the
         selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
         thresholded CSR (`pg_f16_eps_*`), as `_build_graph_substitution` does.  Taken when the representation holds
-        integer tokens of the table, at most 128 positions, and width * max(max C, gap) <= 2048, so that every distance
+        integer tokens of the table, at most 128 positions, and width * max(max C, gap) + gap_open <= 2048, so that every distance
         is an integer fp16 holds exactly; else None (the generic loop with the operator).  Returns a KNNGraph / CSRGraph
         with int16 weights; similarities as for Hamming: the same integer test on d, formed by the container.
         """
@@ -1252,8 +1262,7 @@ class Prograph:
         cost = distance.device_cost()
         n, dev = op.n, op.buf.device
         block_rows = self._block_rows(n, n, 64)
-        blocks = (_native.alignment_dense(op, op, cost, distance.gap, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
-                  for r0 in range(0, n, block_rows))
+        blocks = (self._aln_dense(distance, op, op, cost, (r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
         if k:
             kk = min(k, n - 1)
             if not kk:

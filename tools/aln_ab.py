@@ -1,5 +1,5 @@
 """
-Timings behind DESIGN.md §4.15 (gapped alignment distance), on one GPU.  Every time is a whole call on a host clock,
+Timings behind DESIGN.md §4.15 and §4.16 (gapped alignment distance, linear and affine gap penalties), on one GPU.  Every time is a whole call on a host clock,
 from the call to the end of a device synchronise, after a warm-up; arms alternate; inputs are seeded and random;
 medians with min / max.
 
@@ -12,11 +12,15 @@ medians with min / max.
           (no recurrence) at the same shapes, and the blocked torch expression of the operator on --torch-rows rows.
   graph   build_graph(k = 16) at N = --n-graph with lengths 48..64: `_build_graph_alignment` against
           `_build_graph_generic` with the operator (--generic-reps runs: it takes long); graphs compared.
+  affine  §4.16: `pg_alignment_affine_dense` (gap_open 11) beside `pg_alignment_dense` at the two dense shapes - time, the
+          ratio of the two in the same run, cell updates/s, share of the VALU issue rate from AFFINE_VALU_PER_STEP.
+  affine_graph  build_graph(k = 16) at N = --n-graph, lengths 48..64, with alignment(C, 5, gap_open=7): native against
+          the generic loop with the operator; graphs compared.
   pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
 
 Prints one JSON line; progress goes to stderr.
 
-    python tools/aln_ab.py [--reps 5] [--only dense,graph] [--out FILE]
+    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph] [--out FILE]
 """
 import argparse
 import json
@@ -37,6 +41,9 @@ from prograph_amd.distance import alignment  # noqa: E402
 # in step with the kernel: after any change to csrc/pg_aln.hip, its build flags or the compiler, count again and update
 # both places, or `share_of_valu_issue` below is wrong without a sign of it.
 VALU_PER_STEP = {1: 69, 2: 134, 3: 199, 4: 264, 5: 329, 6: 394, 7: 459, 8: 523}
+# The same for pg_aln_affine_dense_kernel (profiles/aln_affine_dense.txt; here every v_* of the loop is counted), kept by
+# hand in the same way.
+AFFINE_VALU_PER_STEP = {1: 131, 2: 260, 3: 389, 4: 518, 5: 647, 6: 775, 7: 905, 8: 1033}
 ISSUE_RATE = 256 * 4 * 2.4e9
 
 
@@ -92,7 +99,7 @@ def main():
     ap.add_argument("--rows", type=int, default=8192)
     ap.add_argument("--torch-rows", type=int, default=256)
     ap.add_argument("--n-graph", type=int, default=50_000)
-    ap.add_argument("--only", default="dense,graph")
+    ap.add_argument("--only", default="dense,graph,affine,affine_graph")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = _native.device()
@@ -167,6 +174,62 @@ def main():
                    identical=bool(np.array_equal(G.idx.cpu().numpy(), gi) and np.array_equal(G.dist.cpu().numpy(), gw)),
                    speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
         out["graph"] = res
+    if "affine" in only:
+        n, m = args.n, args.rows
+        rng = np.random.default_rng(2)
+        for name, lo, hi in (("l125_128", 125, 128), ("l64", 64, 64)):
+            top = (2048 - 11) // hi
+            C = random_table(rng, a, top)
+            dist = alignment(C, top, gap_open=11)
+            host, lens = varlen(rng, n, lo, hi, a)
+            tok = torch.from_numpy(host).to(dev)
+            xo = _native.aln_operand(tok, a)
+            cost = dist.device_cost()
+            assert xo.valid()
+            fns = {"alignment_affine_dense_f16": lambda: _native.alignment_affine_dense(xo, xo, cost, dist.gap, dist.gap_open,
+                                                                                        out_bytes=2, rows=(0, m)),
+                   "alignment_dense_f16": lambda: _native.alignment_dense(xo, xo, cost, dist.gap, out_bytes=2, rows=(0, m))}
+            res, outs = alternate(fns, args.reps, "affine " + name)
+            zero = _native.alignment_affine_dense(xo, xo, cost, dist.gap, 0, out_bytes=2, rows=(0, min(m, 256)))
+            same = bool(torch.equal(zero, outs["alignment_dense_f16"][:256]))
+            ms = res["alignment_affine_dense_f16"]["median_ms"]
+            cells = float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3)
+            wave_max = np.pad(lens, (0, -len(lens) % 64)).reshape(-1, 64).max(axis=1).astype(np.float64).sum()
+            body = np.array([AFFINE_VALU_PER_STEP[max(1, (int(l) + 15) // 16)] for l in lens[:m]], dtype=np.float64).sum()
+            valu = wave_max * body / (ms * 1e-3)
+            res.update(n=n, rows=m, lengths=[lo, hi], symbols=a, gap=dist.gap, gap_open=dist.gap_open,
+                       pairs_per_s=m * n / (ms * 1e-3), cell_updates_per_s=cells, valu_instructions_per_s=valu,
+                       share_of_valu_issue=valu / ISSUE_RATE,
+                       ratio_to_linear=ms / res["alignment_dense_f16"]["median_ms"], gap_open_zero_equals_linear=same)
+            out["affine_" + name] = res
+            del outs, xo, tok, fns, zero
+            torch.cuda.empty_cache()
+
+    if "affine_graph" in only:
+        n = args.n_graph
+        rng = np.random.default_rng(3)
+        C = random_table(rng, a, 12)
+        dist = alignment(C, 5, gap_open=7)
+        tok, lens = varlen(rng, n, 48, 64, a)
+        tok[1::2, 3:] = tok[0::2, 3:][:len(tok[1::2])]
+        tok = tok.astype(np.int64)
+        pg = Prograph.__new__(Prograph)
+        pg.tokenized = tok
+        pg.graph = pd.DataFrame({"Tokenized": list(tok)})
+        native = lambda: pg._build_graph_alignment(None, None, 16, False, "Tokenized", None, dist)     # noqa: E731
+        res, outs = alternate({"native_k16": native}, args.reps, "affine graph")
+        G = outs["native_k16"]
+        times = []
+        for _ in range(args.generic_reps):
+            t, tuples = timed(lambda: pg._build_graph_generic(None, 8, None, 16, False, "Tokenized", dist, None))
+            times.append(t)
+        res["generic_loop_operator_k16"] = stats(times)
+        gi = np.array([i for i, _ in tuples])
+        gw = np.array([w for _, w in tuples])
+        res.update(n=n, lengths=[48, 64], k=16, gap=5, gap_open=7,
+                   identical=bool(np.array_equal(G.idx.cpu().numpy(), gi) and np.array_equal(G.dist.cpu().numpy(), gw)),
+                   speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
+        out["affine_graph"] = res
     line = json.dumps(out)
     print(line)
     if args.out:
