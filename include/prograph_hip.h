@@ -444,6 +444,25 @@ int pg_alignment_affine_dense(const void *x_packed, int64_t n, int64_t x_npad, i
                               int64_t ldo, int out_elem_bytes, void *stream);
 
 /*
+ * LOCAL alignment score (Smith-Waterman, Gotoh's affine gaps) - BUILD DEFINED; a SIMILARITY: larger is nearer.  Under a
+ * symmetric score table S (at most 32 symbols, entries -128..127), e = gap, o = gap_open:
+ *     H[i][0] = H[0][j] = 0,  E[0][j] = F[i][0] = -inf,
+ *     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - o - e),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - o - e),
+ *     H[i][j] = max(0, H[i-1][j-1] + S[x_i][y_j], E[i][j], F[i][j]),          s(y, x) = max over all i, j of H[i][j]:
+ * the best score of any pair of substrings.  Sequences as for pg_alignment_dense (a row without its trailing zeros, an
+ * interior zero is symbol 0 of S); padding never scores, whatever S[a][0] is.
+ *   pg_alignment_local_dense  out[r * ldo + c] = s(Y row r, X row c).  Operands, lengths, output formats, row offsets,
+ *                      checks and error codes as for pg_alignment_affine_dense; gap in 1..255, gap_open in 0..255
+ *                      (0: linear gaps).  score_i8: the table as 32 x 32 signed bytes on the device (rows and columns
+ *                      from the alphabet size on zero).  A score is at most min(len x, len y) * max(S) <= 128 * 127 =
+ *                      16 256; the fp16 output is exact while s <= 2048, which the caller guarantees
+ *                      (max(xl, yl) * max(S) <= 2048); the kernel does not test it.  Does not allocate; LDS only.
+ */
+int pg_alignment_local_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                             int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out,
+                             int64_t ldo, int out_elem_bytes, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

@@ -26,6 +26,7 @@ MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 
 SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, symbols of the cost table
 ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
 ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-open penalty
+ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entries of a score table
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -36,6 +37,7 @@ SYMBOLS = [
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
+    "pg_alignment_local_dense",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -134,6 +136,7 @@ def _load():
         lib.pg_alignment_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp]
         lib.pg_alignment_affine_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32,
                                                   _vp]
+        lib.pg_alignment_local_dense.argtypes = lib.pg_alignment_affine_dense.argtypes
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -866,6 +869,34 @@ def alignment_affine_dense(xo, yo, cost, gap, gap_open, out_bytes=8, rows=None):
     _check(lib().pg_alignment_affine_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
                                            r1 - r0, yo.npad, yo.l, _ptr(cost), int(gap), int(gap_open), _ptr(out),
                                            out.stride(0), out_bytes, _stream()), "pg_alignment_affine_dense")
+    return out
+
+
+def aln_local_score(table):
+    """(A, A) integer score table, A <= 32, entries -128..127 -> the 32 x 32 int8 device table of pg_alignment_local_dense."""
+    t = np.asarray(table)
+    if (t.ndim != 2 or t.shape[0] != t.shape[1] or not 1 <= t.shape[0] <= SUB_MAX_A or t.min() < ALN_LOCAL_MIN
+            or t.max() > ALN_LOCAL_MAX):
+        raise ValueError("score table: square, at most 32 symbols, entries -128..127")
+    full = np.zeros((SUB_MAX_A, SUB_MAX_A), dtype=np.int8)
+    full[:t.shape[0], :t.shape[0]] = t
+    return torch.from_numpy(full).to(device())
+
+
+def alignment_local_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
+    """(M, N) local alignment SCORES (larger is nearer) of the rows of AlnOperand `yo` (rows = (r0, r1): only those)
+    against every row of `xo` (pg_alignment_local_dense); `score` from aln_local_score, `gap` 1..255, `gap_open` 0..255;
+    the operands' widths need not agree.  int64 (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2: exact
+    while width * max(S) stays within 2048)."""
+    if out_bytes not in (2, 8):
+        raise ValueError("alignment_local_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    _check(lib().pg_alignment_local_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
+                                          r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), _ptr(out),
+                                          out.stride(0), out_bytes, _stream()), "pg_alignment_local_dense")
     return out
 
 

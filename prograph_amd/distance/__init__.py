@@ -2,6 +2,7 @@ from .alignment import alignment
 from .cosine import cosine
 from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn
+from .local_alignment import local_alignment
 from .minkowski import minkowski
 from .substitution import substitution
 from .utils import clean_input

@@ -1,0 +1,177 @@
+"""
+Local alignment score (Smith-Waterman) over tokenised, zero right-padded sequences - NOT in the reference
+(acmater/prograph ships only hamming / minkowski); defined by this build.
+
+    score = local_alignment(S, gap)               # S: (A, A) SCORE table indexed by token value: larger is nearer
+    score = local_alignment(S, gap, gap_open=o)   # affine: a run of g unaligned symbols costs o + g * gap
+    s = score(X (N,D1), Y (M,D2))                 # (M, N): the best local alignment of Y[m] with X[n]
+
+`alignment` is global: every symbol of both sequences is aligned or paid for.  This is its local counterpart: s(x, y) is
+the best score, over all pairs of a substring of x and a substring of y and all alignments of the two, of the sum of
+S[x_i, y_j] over the aligned pairs minus o + g * gap per maximal run of g unaligned symbols - what answers "do the two
+share a domain, whatever surrounds it".  Gotoh's form, maximising, with a zero floor (e = gap):
+
+    H[i][0] = H[0][j] = 0,   E[0][j] = F[i][0] = -inf,
+    E[i][j] = max(E[i-1][j] - e, H[i-1][j] - o - e),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - o - e),
+    H[i][j] = max(0, H[i-1][j-1] + S[x_i, y_j], E[i][j], F[i][j]),          s = max over all i, j of H[i][j].
+
+s is symmetric, at least 0 (the empty alignment) and at most min(len x, len y) * max(S); gap_open = 0 is the linear gap
+penalty.  It is a SIMILARITY, not a distance: there is no triangle inequality, s(x, x) depends on x, and larger is
+nearer.  The operator owns that: `score(X, Y)` and `score(X, Y, similarity=True)` return the scores, `similarity=False`
+raises `ValueError`; `build_graph` and `search` rank largest first whatever their `similarity` argument says.
+
+    * a row's sequence is the row with its trailing zeros removed (an all-zero row is the empty sequence, which scores 0
+      against everything), as for `alignment`; padding never scores, whatever S[a][0] is;
+    * an interior zero - a letter outside the alphabet - is an ordinary symbol: row and column 0 of S;
+    * the table: 2-D and square with 2..32 symbols, integers in -128..127, symmetric, at least one entry of 1 or more
+      (else every score is 0); `ValueError` otherwise.  No rule for the diagonal.  It is copied;
+    * `gap` is an integer in 1..255, `gap_open` one in 0..255, validated as `alignment` validates them;
+    * operands must hold integers in 0..A-1 (any dtype); anything else raises `ValueError`; so does an empty operand.
+
+Device byte-token operands of at most 128 positions run on the HIP kernel (`pg_alignment_local_dense`,
+prograph_amd/csrc/pg_aln_local.hip).  Everything else is evaluated by the torch expression below on the device the
+operands live on, CPU included: the table row by row over the whole (M, N) batch in `alignment._dp_block_affine`'s style,
+E carried between rows, A[j] = max(0, v_old[j-1] + S, E[j]), F[j] = cummax_{k<j}(A[k] + k e) - j e - o - a cell that sits
+in a gap never opens a better gap than extending does, so the cummax may run over A -, v = max(A, F), and the running
+maximum over the cells with j <= len x and i <= len y.  It is the slow path; it is exact.
+
+`build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_local`, `_search_local`); two
+instances with equal table, gap and gap_open behave identically.
+"""
+import numpy as np
+import torch
+
+from .. import _native
+from .alignment import _gap, _gap_open
+from .hamming import _as_byte_tokens
+from .levenshtein import _lengths
+from .substitution import _integer_table
+from .utils import clean_input
+
+_DP_ELEMS = 1 << 23            # table entries (pairs x columns) alive per block of the torch expression (E beside every row)
+
+
+class local_alignment:
+    """The score of one score table and gap penalty, linear or affine (see the module text)."""
+
+    def __init__(self, S, gap, gap_open=0):
+        S = _integer_table(S, "the score table")
+        if not 2 <= S.shape[0] <= _native.SUB_MAX_A:
+            raise ValueError(f"the score table must have 2..{_native.SUB_MAX_A} symbols")
+        if S.min() < _native.ALN_LOCAL_MIN or S.max() > _native.ALN_LOCAL_MAX:
+            raise ValueError("the scores must be in -128..127")
+        if not np.array_equal(S, S.T):
+            raise ValueError("the score table must be symmetric")
+        if S.max() < 1:
+            raise ValueError("the score table must have an entry of at least 1 (else every score is 0)")
+        self._table = S.astype(np.int8)              # a copy of the caller's data
+        self._table.setflags(write=False)
+        self._gap = _gap(gap)
+        self._open = _gap_open(gap_open)
+        self._on = {}                                # device -> (A, A) int32 table of the torch expression
+        self._score = None                           # the 32 x 32 int8 table of the kernel, on its device
+
+    @property
+    def table(self):
+        """The (A, A) int8 score table (read-only)."""
+        return self._table
+
+    @property
+    def gap(self):
+        return self._gap
+
+    @property
+    def gap_open(self):
+        """The price of opening a run of unaligned symbols, on top of `gap` per symbol; 0 is the linear penalty."""
+        return self._open
+
+    @property
+    def symbols(self):
+        return self._table.shape[0]
+
+    @property
+    def max_score(self):
+        """The largest entry of the table.  A score is at most width * max_score."""
+        return int(self._table.max())
+
+    def __repr__(self):
+        opening = f", gap_open={self._open}" if self._open else ""
+        return (f"local_alignment(<{self.symbols} x {self.symbols} table, scores {int(self._table.min())}..{self.max_score}>, "
+                f"gap={self._gap}{opening})")
+
+    def device_score(self):
+        """The kernel's 32 x 32 int8 table on the current HIP device."""
+        dev = _native.device()
+        if self._score is None or self._score.device != dev:
+            self._score = _native.aln_local_score(self._table)
+        return self._score
+
+    # ------------------------------------------------------------------ the operator
+    def _table_on(self, dev):
+        key = str(dev)
+        if key not in self._on:
+            self._on[key] = torch.from_numpy(self._table.astype(np.int32)).to(dev)
+        return self._on[key]
+
+    def _dp_block(self, St, x, lx, y, ly):
+        """(m, n) int64 scores of y rows (lengths ly) against x rows (lengths lx); x, y already cut to the longest
+        sequence among their rows.  Row i of every table at once; F is resolved inside the row by the cummax over A."""
+        m, n, dx, e, o = y.shape[0], x.shape[0], x.shape[1], self._gap, self._open
+        jg = torch.arange(dx + 1, device=x.device, dtype=torch.int32) * e
+        v = torch.zeros((m, n, dx + 1), dtype=torch.int32, device=x.device)    # row 0: H[0][j] = 0
+        E = torch.full_like(v, -(1 << 28))                                     # E[0][j] = -inf
+        inside = (torch.arange(dx + 1, device=x.device).view(1, 1, -1) <= lx.view(1, n, 1))      # j <= len x
+        best = torch.zeros((m, n), dtype=torch.int32, device=x.device)
+        xl = x.long().view(1, n, dx)
+        for i in range(1, y.shape[1] + 1):
+            score = St[y[:, i - 1].long().view(m, 1, 1), xl]                   # (m, n, dx): S[y_i, x_j]
+            E = torch.maximum(E - e, v - (o + e))                              # extend the run | open one from the row above
+            A = torch.zeros_like(v)                                            # H[i][0] = 0
+            A[..., 1:] = torch.maximum(v[..., :-1] + score, E[..., 1:]).clamp_(min=0)      # floor | aligned pair | gap against y_i
+            F = torch.full_like(v, -(1 << 28))                                 # F[i][0] = -inf
+            F[..., 1:] = torch.cummax(A + jg, dim=2).values[..., :-1] - jg[1:] - o         # max over k < j of A[k] - o - (j - k) e
+            v = torch.maximum(A, F)
+            live = inside & (ly >= i).view(m, 1, 1)                            # padding of either sequence never scores
+            best = torch.maximum(best, torch.where(live, v, torch.zeros_like(v)).amax(dim=2))
+        return best.to(torch.int64)
+
+    def _torch_expression(self, X, Y):
+        """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
+        St = self._table_on(X.device)
+        lx, ly = _lengths(X), _lengths(Y)
+        X, Y = X[:, :int(lx.max())], Y[:, :int(ly.max())]
+        n, m = X.shape[0], Y.shape[0]
+        cols = max(1, min(n, _DP_ELEMS // (X.shape[1] + 1)))
+        rows = max(1, min(m, _DP_ELEMS // (cols * (X.shape[1] + 1))))
+        out = torch.empty((m, n), dtype=torch.int64, device=X.device)
+        for r0 in range(0, m, rows):
+            for c0 in range(0, n, cols):
+                out[r0:r0 + rows, c0:c0 + cols] = self._dp_block(St, X[c0:c0 + cols], lx[c0:c0 + cols], Y[r0:r0 + rows],
+                                                                 ly[r0:r0 + rows])
+        return out
+
+    def __call__(self, X, Y, similarity=True):
+        """(M, N) int64 scores of the M rows of Y against the N rows of X.  A score is a similarity: `similarity=False`
+        raises."""
+        if not similarity:
+            raise ValueError("local_alignment: a local alignment score is a similarity (larger is nearer), not a distance; "
+                             "there is no similarity=False form")
+        X, Y = clean_input(X, Y)
+        Y = Y.to(X.device)
+        xb = _as_byte_tokens(X)
+        yb = xb if Y is X else _as_byte_tokens(Y)
+        if xb is None or yb is None:
+            raise ValueError("local_alignment: the tokens must be integers in 0..255")
+        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
+        if native:
+            xo = _native.aln_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
+            s = _native.alignment_local_dense(xo, yo, self.device_score(), self._gap, self._open, out_bytes=8)
+            inside = int((xo.flags | yo.flags).item()) == 0                   # the packs' validity words: the one host sync
+        else:
+            inside = int(xb.max()) < self.symbols and int(yb.max()) < self.symbols
+        if not inside:
+            raise ValueError(f"local_alignment: a token is outside the score table (0..{self.symbols - 1})")
+        if not native:
+            s = self._torch_expression(xb, yb)
+        return s

@@ -33,13 +33,16 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import alignment, cosine, hamming, levenshtein, minkowski, substitution
+from .distance import alignment, cosine, hamming, levenshtein, local_alignment, minkowski, substitution
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
 
 _CMP_CODE = {operator.le: _native.CMP_LE, operator.lt: _native.CMP_LT, operator.eq: _native.CMP_EQ,
              operator.ge: _native.CMP_GE, operator.gt: _native.CMP_GT}
+# comp(t, s) as a test on s: what the fp16 eps kernels, which compare (value, threshold), are given for a score
+_CMP_MIRROR = {_native.CMP_LE: _native.CMP_GE, _native.CMP_LT: _native.CMP_GT, _native.CMP_EQ: _native.CMP_EQ,
+               _native.CMP_GE: _native.CMP_LE, _native.CMP_GT: _native.CMP_LT}
 _DEFAULT_SCALER = object()      # "use sklearn's MinMaxScaler" without importing sklearn at module import
 
 
@@ -473,6 +476,9 @@ class Prograph:
         `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; an `alignment` distance (queries
         of any length up to 128) blocks of `pg_alignment_dense` plus the fp16 selection; any other `distance` the generic
         loop.
+        A `local_alignment` instance is a score, not a distance: `similarity` is not consulted, `k` gives the LARGEST scores
+        first (ties to the lower dataset index), `eps` the rows with `s > 0 and comp(eps, s)` - the default comp reads
+        `s >= eps` - and the weights are the scores (blocks of `pg_alignment_local_dense` plus the fp16 selection).
         """
         if eps is None:
             if not k:                                                      # build_graph's errors for k
@@ -515,6 +521,8 @@ class Prograph:
                 g = self._search_substitution(strings, Y, None, eps, comp, similarity, representation, distance)
             elif isinstance(distance, alignment) and comp in _CMP_CODE:
                 g = self._search_alignment(strings, Y, None, eps, comp, similarity, representation, distance)
+            elif isinstance(distance, local_alignment):
+                g = self._search_local(strings, Y, None, eps, comp, representation, distance)
             if g is None:
                 g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
             return g if output == "csr" else g.to_tuples()
@@ -528,6 +536,8 @@ class Prograph:
             g = self._search_substitution(strings, Y, k, None, None, similarity, representation, distance)
         elif isinstance(distance, alignment) and k <= _native.MAX_K_ROUNDS:
             g = self._search_alignment(strings, Y, k, None, None, similarity, representation, distance)
+        elif isinstance(distance, local_alignment):
+            g = self._search_local(strings, Y, k, None, None, representation, distance)
         if g is None:
             return self._search_generic(strings, Y, k, similarity, representation, distance, output)
         return g if output == "csr" else g.to_tuples()
@@ -823,6 +833,121 @@ class Prograph:
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
+    # ---- local alignment scores: a similarity - largest first, whatever `similarity` says
+    def _local_native(self, width, distance):
+        """Does a width take the local alignment kernel's fp16 route?  At most 128 positions, and every score - at most
+        width * max(S) - is an integer that is exact in fp16."""
+        return width <= _native.ALN_MAX_L and width * distance.max_score <= self._LONG_MAX_L
+
+    def _local_tokens(self, mat, distance):
+        """`_sub_tokens`, with the operator's error instead of None: no generic loop ranks scores the right way round."""
+        T = self._sub_tokens(mat, distance)
+        if T is None:
+            raise ValueError(f"local_alignment: the tokens must be integers of the score table (0..{distance.symbols - 1})")
+        return T
+
+    def _local_select(self, distance, X, T, rows, k, first, eps, comp, diagonal):
+        """The selection of `local_alignment` scores of the rows of T (all of X when T is None: a self graph) against X, in
+        row blocks of `rows`: ranks first..first+k-1 of the stable descending (score, column) order -> (idx, scores), or
+        the CSR (indptr, indices, scores) of {(r, c): s > 0, comp(eps, s)} with ascending columns, without the entries
+        c == r when `diagonal` is False.  Within `_local_native` and the device's selection limits: fp16 blocks of
+        `pg_alignment_local_dense`, `_select_blocks` (descending; the comparator mirrored: the kernels test
+        (value, threshold)), int16 scores.  Outside: the same selection in torch over the operator's int64 blocks."""
+        Y = X if T is None else T
+        n, q = X.shape[0], Y.shape[0]
+        native = self._local_native(max(X.shape[1], Y.shape[1]), distance)
+        native = native and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)
+        if native:
+            xo = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+            yo = xo if T is None else _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+            score = distance.device_score()
+            blocks = (_native.alignment_local_dense(xo, yo, score, distance.gap, distance.gap_open, out_bytes=2,
+                                                    rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+            if k is not None:
+                return self._select_blocks(blocks, knn=(k, first, True), wdtype=torch.int16)
+            cmp = _CMP_MIRROR[_CMP_CODE[comp]]
+            thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
+            csr = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.int16)
+            return csr if diagonal else self._drop_diagonal(*csr)
+        dev = _native.device()
+        Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y, device=dev)
+        parts = []
+        for r0 in range(0, q, rows):
+            s = distance(Xd, Yd[r0:r0 + rows])
+            if k is not None:
+                o = torch.sort(s, dim=1, descending=True, stable=True)
+                parts.append((o[1][:, first:first + k].to(torch.int32), o[0][:, first:first + k]))
+                continue
+            keep = (s > 0) & comp(eps, s)
+            if not diagonal:
+                keep[torch.arange(s.shape[0], device=dev), torch.arange(r0, r0 + s.shape[0], device=dev)] = False
+            loc = torch.where(keep)
+            indptr = torch.zeros(s.shape[0] + 1, dtype=torch.int64, device=dev)
+            indptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
+            parts.append((indptr, loc[1].to(torch.int32), s[loc]))
+        if k is not None:
+            return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+        return _native.cat_csr(parts)
+
+    @staticmethod
+    def _drop_diagonal(indptr, indices, wts):
+        """A square CSR without its entries (r, r), on the device."""
+        n = indptr.numel() - 1
+        rows = torch.repeat_interleave(torch.arange(n, device=indptr.device), indptr[1:] - indptr[:-1])
+        keep = indices != rows
+        out = torch.zeros_like(indptr)
+        out[1:] = torch.cumsum(torch.bincount(rows[keep], minlength=n), 0)
+        return out, indices[keep], wts[keep]
+
+    def _search_local(self, strings, Y, k, eps, comp, representation, distance):
+        """Queries under a `local_alignment` score: `k` -> ranks 0..min(k, N)-1 of the stable descending (score, dataset
+        row) order; `eps` -> per query the dataset rows with s > 0 and comp(eps, s), ascending.  Strings are tokenised with
+        the dataset's letter table at their own width; dataset and queries keep their own widths, as in
+        `_search_alignment`.  `similarity` is not consulted.  The weights are the scores."""
+        X = self._local_tokens(self._dataset_matrix(representation), distance)
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        T = self._local_tokens(T, distance)
+        n = X.shape[0]
+        rows = self._block_rows(n, T.shape[0], 1)
+        if k is not None:
+            idx, w = self._local_select(distance, X, T, rows, min(k, n), 0, None, None, True)
+            return KNNGraph(idx, w, n, similarity=False, first=0)
+        indptr, indices, wts = self._local_select(distance, X, T, rows, None, 0, eps, comp, True)
+        return CSRGraph(indptr, indices, wts, n, similarity=False)
+
+    def _build_graph_local(self, idxs, eps, k, representation, comp, distance):
+        """
+        `build_graph(distance=local_alignment(S, gap[, gap_open]))`.  A local alignment score is a similarity, so the
+        graph ranks largest first and `similarity` is not consulted; the weights are the raw scores (the containers are
+        built with similarity=False, so nothing turns them into 1/(1+w)).
+        k: ranks 1..k of the stable descending (score, column) order; rank 0 is dropped, as the reference drops it for
+        every distance (:761-763) - it is the row itself unless a row of lower index contains it.  eps: the reference's
+        similarity form (:734) - the edges {(r, c): c != r, s > 0, comp(eps, s)}, so the default comp reads s >= eps -
+        with ascending columns.  Row blocks of `_block_rows(n, n, 64)` of `pg_alignment_local_dense` in fp16 and
+        `_select_blocks` while width <= 128 and width * max(S) <= 2048 (int16 scores); beyond, the same selection in
+        torch over the operator's blocks (`_local_select`).  Returns a KNNGraph / CSRGraph.
+        """
+        if k is not None and k < 1:
+            raise ValueError("K must be at least 1.")
+        mat = np.asarray(self._dataset_matrix(representation))
+        if idxs is not None:
+            mat = mat[np.asarray(idxs)]
+        T = self._local_tokens(mat, distance)
+        n = T.shape[0]
+        rows = self._block_rows(n, n, 64)
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return self._empty_knn(n, torch.int16, _native.device(), False)
+            idx, wt = self._local_select(distance, T, None, rows, kk, 1, None, None, True)
+            return KNNGraph(idx, wt, n, similarity=False)
+        indptr, indices, wts = self._local_select(distance, T, None, rows, None, 0, eps, comp, False)
+        return CSRGraph(indptr, indices, wts, n, similarity=False)
+
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
         """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
@@ -946,6 +1071,8 @@ class Prograph:
         (rows with more matches are recomputed exactly, so it only affects speed).  `store="Name"`
         also assigns the result to `self.graph["Name"]` and keeps the device CSR, so that `degree`,
         `dirichlet`, `local_variance`, `adjacency` on that name run from the CSR on the GPU.
+        `distance=local_alignment(...)` is a score, not a distance: `similarity` is not consulted, `k` keeps the largest
+        scores, `eps` the pairs with `s > 0 and comp(eps, s)`, and the weights are the scores (`_build_graph_local`).
         """
         if operator.xor(bool(eps), bool(k)) is False:
             raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
@@ -972,6 +1099,8 @@ class Prograph:
             g = self._build_graph_substitution(idxs, eps, k, similarity, representation, comp, distance)
         if isinstance(distance, alignment) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_alignment(idxs, eps, k, similarity, representation, comp, distance)
+        if isinstance(distance, local_alignment):
+            g = self._build_graph_local(idxs, eps, k, representation, comp, distance)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None
         if native:

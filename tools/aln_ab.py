@@ -1,5 +1,6 @@
 """
-Timings behind DESIGN.md §4.15 and §4.16 (gapped alignment distance, linear and affine gap penalties), on one GPU.  Every time is a whole call on a host clock,
+Timings behind DESIGN.md §4.15, §4.16 and §4.17 (gapped alignment distance, linear and affine gap penalties; local alignment
+scores), on one GPU.  Every time is a whole call on a host clock,
 from the call to the end of a device synchronise, after a warm-up; arms alternate; inputs are seeded and random;
 medians with min / max.
 
@@ -16,11 +17,15 @@ medians with min / max.
           ratio of the two in the same run, cell updates/s, share of the VALU issue rate from AFFINE_VALU_PER_STEP.
   affine_graph  build_graph(k = 16) at N = --n-graph, lengths 48..64, with alignment(C, 5, gap_open=7): native against
           the generic loop with the operator; graphs compared.
+  local   §4.17: `pg_alignment_local_dense` (a score table of -4..16 / -4..32, gap 1, gap_open 11) beside
+          `pg_alignment_affine_dense` at the two dense shapes - time, the ratio of the two in the same run, cell updates/s,
+          share of the VALU issue rate from LOCAL_VALU_PER_STEP; the first rows compared with the operator's torch
+          expression.
   pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
 
 Prints one JSON line; progress goes to stderr.
 
-    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph] [--out FILE]
+    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local] [--out FILE]
 """
 import argparse
 import json
@@ -34,7 +39,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from prograph_amd import Prograph, _native  # noqa: E402
-from prograph_amd.distance import alignment  # noqa: E402
+from prograph_amd.distance import alignment, local_alignment  # noqa: E402
 
 # VALU instructions of one outer step (one X symbol against 16 * chunks cells) in the gfx950 ISA of pg_aln_dense_kernel.
 # Counted by hand from the compiler's assembly (`--save-temps`; the table is in profiles/aln_dense.txt).  Nothing keeps it
@@ -44,6 +49,8 @@ VALU_PER_STEP = {1: 69, 2: 134, 3: 199, 4: 264, 5: 329, 6: 394, 7: 459, 8: 523}
 # The same for pg_aln_affine_dense_kernel (profiles/aln_affine_dense.txt; here every v_* of the loop is counted), kept by
 # hand in the same way.
 AFFINE_VALU_PER_STEP = {1: 131, 2: 260, 3: 389, 4: 518, 5: 647, 6: 775, 7: 905, 8: 1033}
+# The same for pg_aln_local_dense_kernel (profiles/aln_local_dense.txt), kept by hand in the same way.
+LOCAL_VALU_PER_STEP = {1: 152, 2: 305, 3: 458, 4: 611, 5: 764, 6: 917, 7: 1070, 8: 1222}
 ISSUE_RATE = 256 * 4 * 2.4e9
 
 
@@ -230,6 +237,42 @@ def main():
                    identical=bool(np.array_equal(G.idx.cpu().numpy(), gi) and np.array_equal(G.dist.cpu().numpy(), gw)),
                    speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
         out["affine_graph"] = res
+    if "local" in only:
+        n, m, tr = args.n, args.rows, args.torch_rows
+        rng = np.random.default_rng(4)
+        for name, lo, hi in (("l125_128", 125, 128), ("l64", 64, 64)):
+            top = 2048 // hi                                                   # width * max(S) = 2048: the fp16 bound
+            S = np.triu(rng.integers(-4, 1, (a, a)), 1)
+            S = S + S.T + np.diag(rng.integers(top // 2, top + 1, a))
+            S[1, 1] = top
+            score = local_alignment(S, 1, gap_open=11)
+            C = random_table(rng, a, (2048 - 11) // hi)
+            dist = alignment(C, 1, gap_open=11)
+            host, lens = varlen(rng, n, lo, hi, a)
+            tok = torch.from_numpy(host).to(dev)
+            xo = _native.aln_operand(tok, a)
+            table, cost = score.device_score(), dist.device_cost()
+            assert xo.valid()
+            fns = {"alignment_local_dense_f16": lambda: _native.alignment_local_dense(xo, xo, table, score.gap, score.gap_open,
+                                                                                      out_bytes=2, rows=(0, m)),
+                   "alignment_affine_dense_f16": lambda: _native.alignment_affine_dense(xo, xo, cost, dist.gap, dist.gap_open,
+                                                                                        out_bytes=2, rows=(0, m))}
+            res, outs = alternate(fns, args.reps, "local " + name)
+            same = bool(torch.equal(outs["alignment_local_dense_f16"][:tr].to(torch.int64), score._torch_expression(tok, tok[:tr])))
+            ms = res["alignment_local_dense_f16"]["median_ms"]
+            cells = float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3)
+            wave_max = np.pad(lens, (0, -len(lens) % 64)).reshape(-1, 64).max(axis=1).astype(np.float64).sum()
+            body = np.array([LOCAL_VALU_PER_STEP[max(1, (int(l) + 15) // 16)] for l in lens[:m]], dtype=np.float64).sum()
+            valu = wave_max * body / (ms * 1e-3)
+            res.update(n=n, rows=m, lengths=[lo, hi], symbols=a, gap=score.gap, gap_open=score.gap_open, max_score=score.max_score,
+                       pairs_per_s=m * n / (ms * 1e-3), cell_updates_per_s=cells, valu_instructions_per_s=valu,
+                       share_of_valu_issue=valu / ISSUE_RATE,
+                       ratio_to_affine=ms / res["alignment_affine_dense_f16"]["median_ms"],
+                       expected_ratio_from_instruction_counts=LOCAL_VALU_PER_STEP[8] / AFFINE_VALU_PER_STEP[8],
+                       torch_rows=tr, first_rows_equal_torch=same)
+            out["local_" + name] = res
+            del outs, xo, tok, fns
+            torch.cuda.empty_cache()
     line = json.dumps(out)
     print(line)
     if args.out:
