@@ -463,6 +463,36 @@ int pg_alignment_local_dense(const void *x_packed, int64_t n, int64_t x_npad, in
                              int64_t ldo, int out_elem_bytes, void *stream);
 
 /*
+ * The two alignment recurrences above for sequences BEYOND 128 positions - BUILD DEFINED (pg_aln_long.hip): the Y side
+ * is cut into strips of 128 positions, the strips' boundary columns pass through a caller-owned workspace.  Either
+ * operand may have up to PG_ALN_LONG_MAX_L positions (PG_E_TOOLONG beyond); operands in the transposed dword order of
+ * pg_sub_pack at their own widths, lengths found on the device, tokens masked to 0..31, as for pg_alignment_dense.
+ *   pg_alignment_long_workspace  bytes of workspace for X operands of width xl: *one_workgroup_bytes = 256 * xl_padded * 4
+ *                      (xl_padded = xl rounded up to 4), the least a call takes; *full_bytes = that times the workgroups
+ *                      a whole device keeps in flight (compute units x resident workgroups).  Either pointer may be
+ *                      NULL.  More workspace than full_bytes buys nothing.
+ *   pg_alignment_long_dense  pg_alignment_affine_dense's arguments, results and error codes (gap_open = 0: the linear
+ *                      penalty, exactly) with out_elem_bytes 4 = int32 (the block format of pg_i32_knn / pg_i32_eps_*)
+ *                      or 8 = int64.  Launches at most workspace_bytes / one_workgroup_bytes workgroups, each looping
+ *                      over its share of the (256 columns, 8 rows) tiles; a workspace smaller than one workgroup's
+ *                      share is PG_E_BADARG.  The workspace may be handed to later work on the same stream.  Cells are
+ *                      16 bits wide: the caller guarantees
+ *                          max(xl, yl) * max(max C, gap) + 2 * gap_open + 2 * gap <= 65 535;
+ *                      the kernel does not test it.
+ *   pg_alignment_local_long_dense  the same for pg_alignment_local_dense's scores (score_i8 as there); the caller
+ *                      guarantees min(xl, yl) * max(S) + 255 <= 65 535.
+ */
+#define PG_ALN_LONG_MAX_L 2048
+int pg_alignment_long_workspace(int xl, int64_t *one_workgroup_bytes, int64_t *full_bytes);
+int pg_alignment_long_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                            int64_t y_npad, int yl, const uint8_t *cost_u8, int gap, int gap_open, void *out,
+                            int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes, void *stream);
+int pg_alignment_local_long_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                                  int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out,
+                                  int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes,
+                                  void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],
@@ -522,6 +552,28 @@ int pg_f16_eps_count(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int
                      uint32_t *counts, void *stream);
 int pg_f16_eps_fill(const void *dist_f16, int64_t m, int64_t n, int64_t ld, int cmp, float eps_f16, int similarity,
                     const int64_t *indptr, int32_t *indices, void *weights_f16, void *stream);
+
+/*
+ * The same selection on (m, n) blocks of non-negative int32 values (leading dimension ld elements) - what
+ * pg_alignment_long_dense writes with out_elem_bytes 4 (pg_select_i32.hip).  The stable (value, column) order of the fp16
+ * entries, descending != 0: largest value first; int32 weights.
+ *   pg_i32_knn           ranks first..first+k-1 of every row, first + k <= 64; a rank that does not exist: index -1,
+ *                        weight 0
+ *   pg_i32_knn_round     the floor scheme of pg_f16_knn_round: the next k (1..64) ranks strictly after each row's
+ *                        floor - the previous round's last index and weight, read with row stride floor_ld - written
+ *                        with row stride ldo
+ *   pg_i32_eps_count/_fill  comp(v, thr) & (v > 0), cmp one of PG_CMP_*, thr an integer; cmp | PG_CMP_KEEP_ZERO:
+ *                        comp(v, thr) & (v >= 0); count -> pg_exclusive_scan -> fill (columns ascending)
+ */
+int pg_i32_knn(const int32_t *vals, int64_t m, int64_t n, int64_t ld, int k, int first, int descending, int32_t *idx_out,
+               int32_t *w_out, void *stream);
+int pg_i32_knn_round(const int32_t *vals, int64_t m, int64_t n, int64_t ld, int k, int descending,
+                     const int32_t *floor_idx, const int32_t *floor_w, int64_t floor_ld, int32_t *idx_out, int32_t *w_out,
+                     int64_t ldo, void *stream);
+int pg_i32_eps_count(const int32_t *vals, int64_t m, int64_t n, int64_t ld, int cmp, int64_t thr, uint32_t *counts,
+                     void *stream);
+int pg_i32_eps_fill(const int32_t *vals, int64_t m, int64_t n, int64_t ld, int cmp, int64_t thr, const int64_t *indptr,
+                    int32_t *indices, int32_t *weights, void *stream);
 
 /*
  * Fused Minkowski graphs: the distances of pg_minkowski_dense (same per-pair arithmetic, bit for bit) selected

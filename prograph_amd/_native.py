@@ -27,6 +27,8 @@ SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, s
 ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
 ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-open penalty
 ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entries of a score table
+ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / pg_alignment_local_long_dense: positions per operand
+ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -37,7 +39,8 @@ SYMBOLS = [
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
-    "pg_alignment_local_dense",
+    "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
+    "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
@@ -137,6 +140,14 @@ def _load():
         lib.pg_alignment_affine_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32,
                                                   _vp]
         lib.pg_alignment_local_dense.argtypes = lib.pg_alignment_affine_dense.argtypes
+        lib.pg_alignment_long_workspace.argtypes = [_i32, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]
+        lib.pg_alignment_long_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32,
+                                                _vp, _i64, _vp]
+        lib.pg_alignment_local_long_dense.argtypes = lib.pg_alignment_long_dense.argtypes
+        lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
+        lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
+        lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
+        lib.pg_i32_eps_fill.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]
         lib.pg_f16_nchunks.argtypes = [_i32]
         lib.pg_pack_f16.argtypes = [_vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         lib.pg_minkowski_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]
@@ -898,6 +909,116 @@ def alignment_local_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
                                           r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), _ptr(out),
                                           out.stride(0), out_bytes, _stream()), "pg_alignment_local_dense")
     return out
+
+
+def aln_long_ready():
+    """Can the kernels beyond 128 positions run (`alignment_long_dense`, `i32_knn`, ...)?  True only with a HIP device;
+    the routes of prograph.py and the operators ask before they leave the 128-position kernels / the torch expression."""
+    try:
+        return device().type == "cuda"
+    except NativeUnavailable:
+        return False
+
+
+def aln_long_fits(width, max_cost, gap, gap_open):
+    """Do `alignment` distances of operands up to `width` positions fit the 16-bit cells of pg_alignment_long_dense?  A
+    cell is at most width * max_cost + gap_open (max_cost = max(max C, gap)), E and F one gap_open + gap above it, and
+    the sums formed before a min add gap once more."""
+    return width <= ALN_LONG_MAX_L and width * max_cost + 2 * gap_open + 2 * gap <= ALN_LONG_CELL_MAX
+
+
+def aln_local_long_fits(width_x, width_y, max_score):
+    """The same for `local_alignment` scores: a cell is at most min(width) * max(S), the diagonal term adds a profile
+    byte (at most 255) before the bias comes off."""
+    return max(width_x, width_y) <= ALN_LONG_MAX_L and min(width_x, width_y) * max_score + 255 <= ALN_LONG_CELL_MAX
+
+
+def aln_long_operand(tokens, a):
+    """(N, L <= 2048) uint8 tokens -> AlnOperand for a table of `a` symbols, for the kernels beyond 128 positions
+    (pg_sub_pack at the operand's own width).  No host sync, as `aln_operand`."""
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dim() == 2 and tokens.shape[1] > ALN_LONG_MAX_L:
+        raise ValueError(f"aln_long_operand: at most {ALN_LONG_MAX_L} tokens per sequence")
+    so = sub_operand(tokens, a)
+    return AlnOperand(so.buf, so.n, so.l, so.flags)
+
+
+def aln_long_workspace(xo, nrows):
+    """The boundary-column workspace of one call (pg_alignment_long_workspace): a share per workgroup in flight on the
+    whole device, or per (256 columns, 8 rows) tile of the call when those are fewer."""
+    one, full = _i64(0), _i64(0)
+    _check(lib().pg_alignment_long_workspace(xo.l, ctypes.byref(one), ctypes.byref(full)), "pg_alignment_long_workspace")
+    tiles = ((xo.n + 255) // 256) * ((int(nrows) + 7) // 8)
+    return torch.empty(min(full.value, tiles * one.value), dtype=torch.uint8, device=xo.buf.device)
+
+
+def _aln_long(entry, name, xo, yo, table, gap, gap_open, out_bytes, rows):
+    if out_bytes not in (4, 8):
+        raise ValueError(f"{name}: out_bytes 8 (int64) or 4 (int32)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    ws = aln_long_workspace(xo, r1 - r0)
+    _check(getattr(lib(), entry)(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
+                                 yo.npad, yo.l, _ptr(table), int(gap), int(gap_open), _ptr(out), out.stride(0), out_bytes,
+                                 _ptr(ws), ws.numel(), _stream()), entry)
+    return out
+
+
+def alignment_long_dense(xo, yo, cost, gap, gap_open, out_bytes=8, rows=None):
+    """`alignment_affine_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_long_dense; gap_open = 0: the
+    linear penalty): int64 (out_bytes 8) or the int32 block i32_knn / i32_eps select from (4).  Exact while
+    `aln_long_fits(max(xo.l, yo.l), ...)` holds, which the caller checks.  Allocates the call's workspace."""
+    return _aln_long("pg_alignment_long_dense", "alignment_long_dense", xo, yo, cost, gap, gap_open, out_bytes, rows)
+
+
+def alignment_local_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
+    """`alignment_local_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_local_long_dense), outputs as
+    `alignment_long_dense`.  Exact while `aln_local_long_fits(xo.l, yo.l, max(S))` holds, which the caller checks."""
+    return _aln_long("pg_alignment_local_long_dense", "alignment_local_long_dense", xo, yo, score, gap, gap_open, out_bytes, rows)
+
+
+def i32_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):
+    """One round of pg_i32_knn_round: the next k <= 64 ranks of every row of an int32 block after its floor (views as for
+    f16_knn_round)."""
+    m, n = block.shape
+    _check(lib().pg_i32_knn_round(_ptr(block), m, n, block.stride(0), int(k), 1 if descending else 0, _ptr(floor_idx),
+                                  _ptr(floor_w), floor_idx.stride(0), _ptr(idx_out), _ptr(w_out), idx_out.stride(0),
+                                  _stream()), "pg_i32_knn_round")
+
+
+def i32_knn(block, k, first=1, descending=False):
+    """Ranks first..first+k-1 of every row of a block of non-negative int32 values in the stable (value, column) order
+    (descending: largest first) -> (idx int32, w int32).  first + k > 64 (k <= MAX_K_ROUNDS): in rounds of 64 ranks over
+    the same block (knn_rounds)."""
+    if first + k > 64:
+        return knn_rounds(block.shape[0], int(k), int(first), torch.int32, block.device,
+                          lambda kk: i32_knn(block, kk, first, descending),
+                          lambda kk, fi, fw, oi, ow: i32_knn_round(block, kk, fi, fw, oi, ow, descending))
+    m, n = block.shape
+    idx = torch.empty((m, k), dtype=torch.int32, device=block.device)
+    w = torch.empty((m, k), dtype=torch.int32, device=block.device)
+    _check(lib().pg_i32_knn(_ptr(block), m, n, block.stride(0), int(k), int(first), 1 if descending else 0, _ptr(idx), _ptr(w),
+                            _stream()), "pg_i32_knn")
+    return idx, w
+
+
+def i32_eps(block, cmp, thr, keep_zero=False):
+    """CSR of the entries of an int32 block with comp(v, thr) & (v > 0), thr an integer; keep_zero: v = 0 is a hit too
+    (rows of queries).  Returns (indptr int64 [m+1], indices int32 ascending within a row, weights int32)."""
+    L = lib()
+    m, n = block.shape
+    thr = min(max(int(thr), -1), 1 << 31)                                     # the same test on every value in 0..2^31-1
+    cmp = int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0)
+    counts = torch.empty(m, dtype=torch.int32, device=block.device)
+    _check(L.pg_i32_eps_count(_ptr(block), m, n, block.stride(0), cmp, thr, _ptr(counts), _stream()), "pg_i32_eps_count")
+    indptr, indices, weights = _csr_alloc(counts, torch.int32)
+    if indices.numel():
+        _check(L.pg_i32_eps_fill(_ptr(block), m, n, block.stride(0), cmp, thr, _ptr(indptr), _ptr(indices), _ptr(weights),
+                                 _stream()), "pg_i32_eps_fill")
+    return indptr, indices, weights
 
 
 def csr_row_stats(indptr, indices, weights, f=None, want=("deg",), row0=0, ncols=None):

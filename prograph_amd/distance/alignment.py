@@ -28,7 +28,9 @@ X; `ValueError` on an empty operand; `similarity=True` returns 1/(1+d).
 2 * gap > L * max(C) no gap pays and the distance is `substitution(C)`.
 
 Device byte-token operands of at most 128 positions run on the HIP kernel (`pg_alignment_dense`,
-prograph_amd/csrc/pg_aln.hip).  Everything else is evaluated by the torch expression below on the device the operands
+prograph_amd/csrc/pg_aln.hip); those of 129..2048 positions on the strip-mined kernel (`pg_alignment_long_dense`,
+prograph_amd/csrc/pg_aln_long.hip, linear and affine alike) while width * max(max C, gap) + 2 gap_open + 2 gap <= 65 535,
+the bound of its 16-bit cells.  Everything else is evaluated by the torch expression below on the device the operands
 live on, CPU included: the table row by row over the whole (M, N) batch, as in `levenshtein`, the dependency inside a
 row resolved by v[j] = j * gap + cummin(c[k] - k * gap).  It is the slow path; it is exact.
 
@@ -188,7 +190,15 @@ class alignment:
         if xb is None or yb is None:
             raise ValueError("alignment: the tokens must be integers in 0..255")
         native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
-        if native:
+        long = (not native and xb.is_cuda and _native.aln_long_ready()
+                and _native.aln_long_fits(xb.shape[1], self.max_cost, self._gap, self._open))
+        if long:                                                              # 129..2048 positions inside the 16-bit cells
+            xo = _native.aln_long_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_long_operand(yb, self.symbols)
+            d = _native.alignment_long_dense(xo, yo, self.device_cost(), self._gap, self._open, out_bytes=8)
+            native = True
+            inside = int((xo.flags | yo.flags).item()) == 0
+        elif native:
             xo = _native.aln_operand(xb, self.symbols)
             yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
             if self._open:

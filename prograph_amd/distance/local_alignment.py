@@ -29,7 +29,9 @@ raises `ValueError`; `build_graph` and `search` rank largest first whatever thei
     * operands must hold integers in 0..A-1 (any dtype); anything else raises `ValueError`; so does an empty operand.
 
 Device byte-token operands of at most 128 positions run on the HIP kernel (`pg_alignment_local_dense`,
-prograph_amd/csrc/pg_aln_local.hip).  Everything else is evaluated by the torch expression below on the device the
+prograph_amd/csrc/pg_aln_local.hip); those of 129..2048 positions on the strip-mined kernel
+(`pg_alignment_local_long_dense`, prograph_amd/csrc/pg_aln_long.hip) while width * max(S) + 255 <= 65 535, the bound of its
+16-bit cells.  Everything else is evaluated by the torch expression below on the device the
 operands live on, CPU included: the table row by row over the whole (M, N) batch in `alignment._dp_block_affine`'s style,
 E carried between rows, A[j] = max(0, v_old[j-1] + S, E[j]), F[j] = cummax_{k<j}(A[k] + k e) - j e - o - a cell that sits
 in a gap never opens a better gap than extending does, so the cummax may run over A -, v = max(A, F), and the running
@@ -163,7 +165,15 @@ class local_alignment:
         if xb is None or yb is None:
             raise ValueError("local_alignment: the tokens must be integers in 0..255")
         native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
-        if native:
+        long = (not native and xb.is_cuda and _native.aln_long_ready()
+                and _native.aln_local_long_fits(xb.shape[1], yb.shape[1], self.max_score))
+        if long:                                                              # 129..2048 positions inside the 16-bit cells
+            xo = _native.aln_long_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_long_operand(yb, self.symbols)
+            s = _native.alignment_local_long_dense(xo, yo, self.device_score(), self._gap, self._open, out_bytes=8)
+            native = True
+            inside = int((xo.flags | yo.flags).item()) == 0
+        elif native:
             xo = _native.aln_operand(xb, self.symbols)
             yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
             s = _native.alignment_local_dense(xo, yo, self.device_score(), self._gap, self._open, out_bytes=8)

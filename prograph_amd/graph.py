@@ -18,8 +18,9 @@ from . import _native
 
 
 class CSRGraph:
-    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|float32|float16 [nnz].
-    final=True: the weights are final values (not Hamming distances) whatever their dtype."""
+    """epsilon-neighbourhood graph: indptr int64 [n+1], indices int32 [nnz], weights uint8|int16|int32|float32|float16 [nnz].
+    final=True: the weights are final values (not Hamming distances) whatever their dtype.  Integer weights reach the
+    analytics as float32, which is exact up to 2^24 (the int32 weights of alignments beyond 128 positions stay below 2^16)."""
 
     def __init__(self, indptr, indices, weights, ncols, similarity=False, row0=0, final=False):
         self.indptr, self.indices, self.weights = indptr, indices, weights
@@ -69,7 +70,7 @@ class CSRGraph:
         if self.similarity:
             return (1 / (1 + self.weights.to(torch.int64))).to(torch.float32)
         if self.weights.dtype not in (torch.uint8, torch.float32):
-            return self.weights.to(torch.float32)          # int16 distances of sequences beyond one record: exact
+            return self.weights.to(torch.float32)          # int16 / int32 distances of long sequences: exact up to 2^24
         return self.weights
 
     def row_stats(self, f=None, boolean_weights=False, want=("deg",)):
@@ -132,7 +133,7 @@ class CSRGraph:
 
 
 class KNNGraph:
-    """k nearest neighbours: idx int32 (n,k), dist uint8|int16 (n,k) or fp16 Minkowski values; canonical (distance, index)
+    """k nearest neighbours: idx int32 (n,k), dist uint8|int16|int32 (n,k) or fp16 Minkowski values; canonical (distance, index)
     order (descending values for Minkowski similarities).  final=True: the values are final (cosine fp32) whatever
     their dtype.  first: the rank of column 0 - 1 for self-graphs (rank 0 dropped, ranks beyond N-1 do not exist), 0 for
     query results (`Prograph.search`: rank 0 kept, min(k, N) ranks)."""

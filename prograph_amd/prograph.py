@@ -599,9 +599,10 @@ class Prograph:
 
     _BLOCK_ELEMS = 1 << 27        # elements of a staged distance block: <= 256 MB of fp16 at a time
 
-    def _block_rows(self, n, rows, floor):
-        """Rows per staged block of distances to n columns: `floor` is 64 for self graphs, 1 for queries."""
-        return max(floor, min(rows, self._BLOCK_ELEMS // n))
+    def _block_rows(self, n, rows, floor, elem_bytes=2):
+        """Rows per staged block of distances to n columns: `floor` is 64 for self graphs, 1 for queries.  Blocks of
+        4-byte elements (the int32 blocks of the alignment kernels beyond 128 positions) hold half as many."""
+        return max(floor, min(rows, self._BLOCK_ELEMS * 2 // elem_bytes // n))
 
     @staticmethod
     def _select_blocks(blocks, knn=None, eps=None, wdtype=None):
@@ -617,6 +618,21 @@ class Prograph:
                 part = _native.f16_eps(block, cmp, thr, similarity=similarity, **({"keep_zero": True} if keep_zero else {}))
             del block
             parts.append(part if wdtype is None else part[:-1] + (part[-1].to(wdtype),))
+        if knn is None:
+            return _native.cat_csr(parts)
+        return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+
+    @staticmethod
+    def _select_blocks_i32(blocks, knn=None, eps=None):
+        """`_select_blocks` over int32 blocks (`pg_alignment_long_dense`): knn = (k, first, descending) -> (idx, w) of
+        `i32_knn`, or eps = (cmp, integer thr, keep_zero) -> the CSR of `i32_eps`; int32 weights as they come."""
+        parts = []
+        for block in blocks:
+            if knn is not None:
+                parts.append(_native.i32_knn(block, knn[0], first=knn[1], descending=knn[2]))
+            else:
+                parts.append(_native.i32_eps(block, eps[0], eps[1], keep_zero=eps[2]))
+            del block
         if knn is None:
             return _native.cat_csr(parts)
         return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
@@ -795,6 +811,19 @@ class Prograph:
         return width <= _native.ALN_MAX_L and width * distance.max_cost + distance.gap_open <= self._LONG_MAX_L
 
     @staticmethod
+    def _aln_long(width, distance):
+        """Does a width beyond `_aln_native` take the strip-mined kernel (`pg_alignment_long_dense`, int32 blocks)?  With
+        a device, 129..2048 positions, and inside the kernel's 16-bit cells: width * max(max C, gap) + 2 gap_open +
+        2 gap <= 65 535 (`_native.aln_long_fits`).  Narrower operands beyond the fp16 bound keep the generic loop."""
+        return (width > _native.ALN_MAX_L and _native.aln_long_ready()
+                and _native.aln_long_fits(width, distance.max_cost, distance.gap, distance.gap_open))
+
+    @staticmethod
+    def _long_threshold(cmp, eps):
+        """`_integer_threshold` for int32 values: the same comparison with an integer threshold, clamped to -1..2^31."""
+        return int(Prograph._integer_threshold(cmp, min(max(float(eps), -1.0), float(1 << 31)), top=1 << 31))
+
+    @staticmethod
     def _aln_dense(distance, xo, yo, cost, rows):
         """One fp16 block of the alignment kernel the distance asks for: `pg_alignment_affine_dense` with a gap-open
         penalty, `pg_alignment_dense` without."""
@@ -807,7 +836,9 @@ class Prograph:
         the distance has a gap-open penalty) in fp16 and the fp16 selection with
         rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width, any
         length up to 128; dataset and queries keep their own widths.  None (the generic loop with the operator) when dataset
-        or queries are not integer tokens of the table, or a distance could exceed 2048."""
+        or queries are not integer tokens of the table, or a distance could exceed 2048 - unless the wider of the two has
+        129..2048 positions and `_aln_long` holds: then int32 blocks of `pg_alignment_long_dense` and the int32 selection
+        (`_select_blocks_i32`), int32 weights, everything else the same."""
         try:
             X = self._sub_tokens(self._dataset_matrix(representation), distance)
         except (ValueError, TypeError):
@@ -818,8 +849,24 @@ class Prograph:
         else:
             T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
         T = self._sub_tokens(T, distance) if X is not None else None
-        if T is None or not self._aln_native(max(X.shape[1], T.shape[1]), distance):
+        if T is None:
             return None
+        if not self._aln_native(max(X.shape[1], T.shape[1]), distance):
+            if not self._aln_long(max(X.shape[1], T.shape[1]), distance):
+                return None
+            # beyond 128 positions: int32 blocks of the strip-mined kernel and the int32 selection (int32 weights)
+            xo, qo = (_native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(M)), distance.symbols) for M in (X, T))
+            cost = distance.device_cost()
+            n, q = xo.n, qo.n
+            rows = self._block_rows(n, q, 1, elem_bytes=4)
+            blocks = (_native.alignment_long_dense(xo, qo, cost, distance.gap, distance.gap_open, out_bytes=4,
+                                                   rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+            if k is not None:
+                idx, w = self._select_blocks_i32(blocks, knn=(min(k, n), 0, False))
+                return KNNGraph(idx, w, n, similarity=similarity, first=0)
+            cmp = _CMP_CODE[comp]
+            indptr, indices, wts = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, eps), True))
+            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
         xo, qo = (_native.aln_operand(torch.from_numpy(np.ascontiguousarray(M)), distance.symbols) for M in (X, T))
         cost = distance.device_cost()
         n, q = xo.n, qo.n
@@ -852,7 +899,9 @@ class Prograph:
         the CSR (indptr, indices, scores) of {(r, c): s > 0, comp(eps, s)} with ascending columns, without the entries
         c == r when `diagonal` is False.  Within `_local_native` and the device's selection limits: fp16 blocks of
         `pg_alignment_local_dense`, `_select_blocks` (descending; the comparator mirrored: the kernels test
-        (value, threshold)), int16 scores.  Outside: the same selection in torch over the operator's int64 blocks."""
+        (value, threshold)), int16 scores.  Beyond 128 and up to 2048 positions, inside `_native.aln_local_long_fits`: int32
+        blocks of `pg_alignment_local_long_dense` and `_select_blocks_i32` in the same way, int32 scores.  Outside both:
+        the same selection in torch over the operator's int64 blocks."""
         Y = X if T is None else T
         n, q = X.shape[0], Y.shape[0]
         native = self._local_native(max(X.shape[1], Y.shape[1]), distance)
@@ -868,6 +917,22 @@ class Prograph:
             cmp = _CMP_MIRROR[_CMP_CODE[comp]]
             thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
             csr = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.int16)
+            return csr if diagonal else self._drop_diagonal(*csr)
+        if (max(X.shape[1], Y.shape[1]) > _native.ALN_MAX_L and _native.aln_long_ready()
+                and _native.aln_local_long_fits(X.shape[1], Y.shape[1], distance.max_score)
+                and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)):
+            # beyond 128 positions: int32 blocks of the strip-mined kernel (`pg_alignment_local_long_dense`) and the int32
+            # selection, descending and with the mirrored comparator as above; int32 scores
+            xo = _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+            yo = xo if T is None else _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+            score = distance.device_score()
+            rows = self._block_rows(n, q, 64 if T is None else 1, elem_bytes=4)
+            blocks = (_native.alignment_local_long_dense(xo, yo, score, distance.gap, distance.gap_open, out_bytes=4,
+                                                         rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+            if k is not None:
+                return self._select_blocks_i32(blocks, knn=(k, first, True))
+            cmp = _CMP_MIRROR[_CMP_CODE[comp]]
+            csr = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, eps), False))
             return csr if diagonal else self._drop_diagonal(*csr)
         dev = _native.device()
         Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y, device=dev)
@@ -1143,13 +1208,14 @@ class Prograph:
     _LONG_MAX_L = 2048                               # integers up to here are exact in fp16
 
     @staticmethod
-    def _integer_threshold(cmp, eps):
+    def _integer_threshold(cmp, eps, top=4096):
         """comp(d, eps) on integer distances d in 0..2048 as the same comparison with an integer threshold, which is
-        exact in fp16 whatever eps is (-1: an `==` that nothing satisfies)."""
+        exact in fp16 whatever eps is (-1: an `==` that nothing satisfies).  `top`: the clamp, beyond every value the
+        block can hold (2^31 for the int32 blocks of the alignment kernels beyond 128 positions)."""
         e = float(eps)
         lo, hi = int(np.floor(e)), int(np.ceil(e))
         thr = {_native.CMP_LE: lo, _native.CMP_LT: hi, _native.CMP_GE: hi, _native.CMP_GT: lo}.get(cmp, lo if lo == hi else -1)
-        return float(min(max(thr, -1), 4096))
+        return float(min(max(thr, -1), top))
 
     def _build_graph_long(self, idxs, eps, k, similarity, representation, comp):
         """
@@ -1373,8 +1439,11 @@ class Prograph:
         selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
         thresholded CSR (`pg_f16_eps_*`), as `_build_graph_substitution` does.  Taken when the representation holds
         integer tokens of the table, at most 128 positions, and width * max(max C, gap) + gap_open <= 2048, so that every distance
-        is an integer fp16 holds exactly; else None (the generic loop with the operator).  Returns a KNNGraph / CSRGraph
-        with int16 weights; similarities as for Hamming: the same integer test on d, formed by the container.
+        is an integer fp16 holds exactly.  Beyond 128 and up to 2048 positions, inside the bound of `_aln_long`: row blocks of
+        `pg_alignment_long_dense` in int32 and `_select_blocks_i32` (`pg_i32_knn`, `pg_i32_eps_*`), int32 weights - exact
+        as float32 for the analytics up to 2^24, and the route's distances stay below 2^16.  Else None (the generic loop
+        with the operator).  Returns a KNNGraph / CSRGraph with int16 (int32) weights; similarities as for Hamming: the
+        same integer test on d, formed by the container.
         """
         if k is not None and k < 1:
             raise ValueError("K must be at least 1.")
@@ -1385,8 +1454,27 @@ class Prograph:
             T = self._sub_tokens(mat, distance)
         except (ValueError, TypeError):
             return None
-        if T is None or not self._aln_native(T.shape[1], distance):
+        if T is None:
             return None
+        if not self._aln_native(T.shape[1], distance):
+            if not self._aln_long(T.shape[1], distance):
+                return None
+            # beyond 128 positions: int32 blocks of the strip-mined kernel and the int32 selection (int32 weights)
+            op = _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+            cost = distance.device_cost()
+            n, dev = op.n, op.buf.device
+            block_rows = self._block_rows(n, n, 64, elem_bytes=4)
+            blocks = (_native.alignment_long_dense(op, op, cost, distance.gap, distance.gap_open, out_bytes=4,
+                                                   rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
+            if k:
+                kk = min(k, n - 1)
+                if not kk:
+                    return self._empty_knn(n, torch.int32, dev, similarity)
+                idx, wt = self._select_blocks_i32(blocks, knn=(kk, 1, False))
+                return KNNGraph(idx, wt, n, similarity=similarity)
+            cmp = _CMP_CODE[comp]
+            indptr, indices, wts = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, eps), False))
+            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
         op = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
         cost = distance.device_cost()
         n, dev = op.n, op.buf.device

@@ -21,11 +21,15 @@ medians with min / max.
           `pg_alignment_affine_dense` at the two dense shapes - time, the ratio of the two in the same run, cell updates/s,
           share of the VALU issue rate from LOCAL_VALU_PER_STEP; the first rows compared with the operator's torch
           expression.
+  long    §4.18: `pg_alignment_long_dense` (gap 1, gap_open 11) at 4096 x 20 000 int32 on rows of 300..400 tokens, beside
+          the operator's blocked torch expression on --torch-rows of the rows; the first rows compared.
+  long_graph  build_graph(k = 16) at N = 20 000, lengths 200..400: the long route against the generic loop with the
+          operator (`aln_long_ready` False); graphs compared.  Both write profiles/aln_long_ab.txt unless --out is given.
   pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
 
 Prints one JSON line; progress goes to stderr.
 
-    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local] [--out FILE]
+    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local,long,long_graph] [--out FILE]
 """
 import argparse
 import json
@@ -273,8 +277,64 @@ def main():
             out["local_" + name] = res
             del outs, xo, tok, fns
             torch.cuda.empty_cache()
+    if "long" in only:
+        # pg_alignment_long_dense at 4096 x 20 000 int32 on rows of 300..400 tokens, beside the blocked torch expression on
+        # 256 of the rows
+        n, m, tr = 20_000, 4096, args.torch_rows
+        rng = np.random.default_rng(5)
+        C = random_table(rng, a, 12)
+        dist = alignment(C, 1, gap_open=11)
+        host, lens = varlen(rng, n, 300, 400, a)
+        tok = torch.from_numpy(host).to(dev)
+        xo = _native.aln_long_operand(tok, a)
+        cost = dist.device_cost()
+        assert xo.valid() and _native.aln_long_fits(400, dist.max_cost, dist.gap, dist.gap_open)
+        fns = {"alignment_long_dense_i32": lambda: _native.alignment_long_dense(xo, xo, cost, dist.gap, dist.gap_open, out_bytes=4,
+                                                                                rows=(0, m)),
+               "torch_expression_256_rows": lambda: dist._torch_expression(tok, tok[:tr])}
+        res, outs = alternate(fns, args.reps, "long", skip_after={"torch_expression_256_rows": args.torch_reps})
+        ms = res["alignment_long_dense_i32"]["median_ms"]
+        res.update(n=n, rows=m, lengths=[300, 400], symbols=a, gap=dist.gap, gap_open=dist.gap_open, torch_rows=tr,
+                   pairs_per_s=m * n / (ms * 1e-3),
+                   cell_updates_per_s=float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3),
+                   first_rows_equal_torch=bool(torch.equal(outs["alignment_long_dense_i32"][:tr].to(torch.int64),
+                                                           outs["torch_expression_256_rows"])),
+                   speedup_per_row=(res["torch_expression_256_rows"]["median_ms"] / tr) / (ms / m))
+        out["long"] = res
+        del outs, xo, tok, fns
+        torch.cuda.empty_cache()
+    if "long_graph" in only:
+        # build_graph(k=16) at N = 20 000 with lengths 200..400: the long route, and the generic loop with the operator's
+        # torch expression (aln_long_ready False)
+        import pandas as pd
+        import tempfile
+        from prograph_amd import Prograph, synth
+        rng = np.random.default_rng(6)
+        host, _ = varlen(rng, 20_000, 200, 400, a)
+        with tempfile.TemporaryDirectory() as tmp:
+            f = os.path.join(tmp, "long.csv")
+            pd.DataFrame({"Sequence": synth.tokens_to_strings(host), "Fitness": rng.uniform(0, 1, len(host))}).to_csv(f)
+            P = Prograph(file=f)
+        dist = alignment(random_table(rng, a, 12), 1, gap_open=11)
+        ready = _native.aln_long_ready
+
+        def generic():
+            _native.aln_long_ready = lambda: False
+            try:
+                return P.build_graph(k=16, distance=dist, output="csr")
+            finally:
+                _native.aln_long_ready = ready
+        res, outs = alternate({"native_k16": lambda: P.build_graph(k=16, distance=dist, output="csr"), "generic_loop_operator_k16": generic},
+                              args.reps, "long_graph", skip_after={"generic_loop_operator_k16": args.generic_reps})
+        G, H = outs["native_k16"], outs["generic_loop_operator_k16"]
+        res.update(n=20_000, lengths=[200, 400], k=16, gap=1, gap_open=11,
+                   identical=bool(torch.equal(G.idx, H.idx) and torch.equal(G.dist.to(torch.int64), H.dist.to(torch.int64))),
+                   speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
+        out["long_graph"] = res
     line = json.dumps(out)
     print(line)
+    if args.out is None and ("long" in only or "long_graph" in only):
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "aln_long_ab.txt")
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
