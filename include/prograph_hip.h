@@ -493,6 +493,32 @@ int pg_alignment_local_long_dense(const void *x_packed, int64_t n, int64_t x_npa
                                   void *stream);
 
 /*
+ * SEMI-GLOBAL ("overlap", end-gap-free) alignment score, Gotoh's affine gaps - BUILD DEFINED (pg_aln_semiglobal.hip); a
+ * SIMILARITY: larger is nearer.  Both sequences are aligned end to end, the unaligned ends of either cost nothing.
+ * Under a symmetric score table S (at most 32 symbols, entries -128..127), e = gap, o = gap_open:
+ *     H[i][0] = H[0][j] = 0,  E[0][j] = F[i][0] = -inf,
+ *     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - o - e),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - o - e),
+ *     H[i][j] = max(H[i-1][j-1] + S[x_i][y_j], E[i][j], F[i][j])                               (no zero floor),
+ *     s(y, x) = max(max over i of H[i][len y], max over j of H[len x][j])                      (>= 0: H[0][len y] = 0).
+ * Sequences as for pg_alignment_dense; padding never scores, whatever S[a][0] is.
+ *   pg_alignment_semiglobal_dense  out[r * ldo + c] = s(Y row r, X row c).  Arguments, lengths, output formats (int64 /
+ *                      fp16), row offsets, checks and error codes of pg_alignment_local_dense; at most 128 positions.
+ *                      The fp16 output is exact while max(xl, yl) * max(S) <= 2048, which the caller guarantees.  Does
+ *                      not allocate; LDS only.
+ *   pg_alignment_semiglobal_long_dense  the same up to PG_ALN_LONG_MAX_L positions: the arguments, workspace
+ *                      (pg_alignment_long_workspace), outputs (int32 / int64) and error codes of
+ *                      pg_alignment_local_long_dense.  Cells are 16 bits wide and hold score + min(xl, yl) * max(S):
+ *                      the caller guarantees 2 * min(xl, yl) * max(S) + 255 <= 65 535; the kernel does not test it.
+ */
+int pg_alignment_semiglobal_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                                  int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out,
+                                  int64_t ldo, int out_elem_bytes, void *stream);
+int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                                       int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out,
+                                       int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes,
+                                       void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

@@ -27,8 +27,8 @@ SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, s
 ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
 ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-open penalty
 ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entries of a score table
-ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / pg_alignment_local_long_dense: positions per operand
-ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits)
+ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / ..._local_long_dense / ..._semiglobal_long_dense: positions per operand
+ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits / aln_semiglobal_long_fits)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -40,6 +40,7 @@ SYMBOLS = [
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
     "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
+    "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
@@ -144,6 +145,8 @@ def _load():
         lib.pg_alignment_long_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32,
                                                 _vp, _i64, _vp]
         lib.pg_alignment_local_long_dense.argtypes = lib.pg_alignment_long_dense.argtypes
+        lib.pg_alignment_semiglobal_dense.argtypes = lib.pg_alignment_affine_dense.argtypes
+        lib.pg_alignment_semiglobal_long_dense.argtypes = lib.pg_alignment_long_dense.argtypes
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
@@ -911,6 +914,22 @@ def alignment_local_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
     return out
 
 
+def alignment_semiglobal_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
+    """(M, N) semi-global alignment SCORES (both sequences end to end, free end gaps; larger is nearer) of the rows of
+    AlnOperand `yo` (rows = (r0, r1): only those) against every row of `xo` (pg_alignment_semiglobal_dense); arguments and
+    outputs as `alignment_local_dense`, `score` from aln_local_score."""
+    if out_bytes not in (2, 8):
+        raise ValueError("alignment_semiglobal_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    _check(lib().pg_alignment_semiglobal_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
+                                               r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), _ptr(out),
+                                               out.stride(0), out_bytes, _stream()), "pg_alignment_semiglobal_dense")
+    return out
+
+
 def aln_long_ready():
     """Can the kernels beyond 128 positions run (`alignment_long_dense`, `i32_knn`, ...)?  True only with a HIP device;
     the routes of prograph.py and the operators ask before they leave the 128-position kernels / the torch expression."""
@@ -931,6 +950,13 @@ def aln_local_long_fits(width_x, width_y, max_score):
     """The same for `local_alignment` scores: a cell is at most min(width) * max(S), the diagonal term adds a profile
     byte (at most 255) before the bias comes off."""
     return max(width_x, width_y) <= ALN_LONG_MAX_L and min(width_x, width_y) * max_score + 255 <= ALN_LONG_CELL_MAX
+
+
+def aln_semiglobal_long_fits(width_x, width_y, max_score):
+    """The same for `semiglobal_alignment` scores: a cell holds score + Z, Z = min(width) * max(S), a score is at most Z,
+    and the diagonal term adds a profile byte (at most 255) before the bias comes off."""
+    return (max(width_x, width_y) <= ALN_LONG_MAX_L
+            and 2 * min(width_x, width_y) * max(int(max_score), 0) + 255 <= ALN_LONG_CELL_MAX)
 
 
 def aln_long_operand(tokens, a):
@@ -978,6 +1004,14 @@ def alignment_local_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=N
     """`alignment_local_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_local_long_dense), outputs as
     `alignment_long_dense`.  Exact while `aln_local_long_fits(xo.l, yo.l, max(S))` holds, which the caller checks."""
     return _aln_long("pg_alignment_local_long_dense", "alignment_local_long_dense", xo, yo, score, gap, gap_open, out_bytes, rows)
+
+
+def alignment_semiglobal_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
+    """`alignment_semiglobal_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_semiglobal_long_dense),
+    outputs as `alignment_long_dense`.  Exact while `aln_semiglobal_long_fits(xo.l, yo.l, max(S))` holds, which the caller
+    checks."""
+    return _aln_long("pg_alignment_semiglobal_long_dense", "alignment_semiglobal_long_dense", xo, yo, score, gap, gap_open,
+                     out_bytes, rows)
 
 
 def i32_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):

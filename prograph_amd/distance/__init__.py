@@ -4,5 +4,6 @@ from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn
 from .local_alignment import local_alignment
 from .minkowski import minkowski
+from .semiglobal_alignment import semiglobal_alignment
 from .substitution import substitution
 from .utils import clean_input

@@ -39,6 +39,9 @@ maximum over the cells with j <= len x and i <= len y.  It is the slow path; it 
 
 `build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_local`, `_search_local`); two
 instances with equal table, gap and gap_open behave identically.
+
+`_score_operator` below is everything but the recurrence: the table's rules, the routes and the blocking of the torch
+expression.  `semiglobal_alignment` (semiglobal_alignment.py) is its other subclass.
 """
 import numpy as np
 import torch
@@ -53,8 +56,12 @@ from .utils import clean_input
 _DP_ELEMS = 1 << 23            # table entries (pairs x columns) alive per block of the torch expression (E beside every row)
 
 
-class local_alignment:
-    """The score of one score table and gap penalty, linear or affine (see the module text)."""
+class _score_operator:
+    """A similarity under one score table and gap penalty, linear or affine.  A subclass names its `_native` entries
+    (looked up at every call) and the bound of the long kernel's cells, and gives `_dp_block`, the torch expression of its
+    recurrence over one (m, n) batch."""
+    _DENSE = _LONG_DENSE = _LONG_FITS = None
+    _WHAT = None                                     # "a ... score", for the similarity=False error
 
     def __init__(self, S, gap, gap_open=0):
         S = _integer_table(S, "the score table")
@@ -98,7 +105,7 @@ class local_alignment:
 
     def __repr__(self):
         opening = f", gap_open={self._open}" if self._open else ""
-        return (f"local_alignment(<{self.symbols} x {self.symbols} table, scores {int(self._table.min())}..{self.max_score}>, "
+        return (f"{type(self).__name__}(<{self.symbols} x {self.symbols} table, scores {int(self._table.min())}..{self.max_score}>, "
                 f"gap={self._gap}{opening})")
 
     def device_score(self):
@@ -114,6 +121,74 @@ class local_alignment:
         if key not in self._on:
             self._on[key] = torch.from_numpy(self._table.astype(np.int32)).to(dev)
         return self._on[key]
+
+    def _native_dense(self, xo, yo, out_bytes, rows=None):
+        """The kernel up to 128 positions on two AlnOperands."""
+        return getattr(_native, self._DENSE)(xo, yo, self.device_score(), self._gap, self._open, out_bytes=out_bytes, rows=rows)
+
+    def _native_long_dense(self, xo, yo, out_bytes, rows=None):
+        """The strip-mined kernel up to 2048 positions; exact inside `_long_fits`."""
+        return getattr(_native, self._LONG_DENSE)(xo, yo, self.device_score(), self._gap, self._open, out_bytes=out_bytes,
+                                                   rows=rows)
+
+    def _long_fits(self, width_x, width_y):
+        return getattr(_native, self._LONG_FITS)(width_x, width_y, self.max_score)
+
+    def _torch_expression(self, X, Y):
+        """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
+        St = self._table_on(X.device)
+        lx, ly = _lengths(X), _lengths(Y)
+        X, Y = X[:, :int(lx.max())], Y[:, :int(ly.max())]
+        n, m = X.shape[0], Y.shape[0]
+        cols = max(1, min(n, _DP_ELEMS // (X.shape[1] + 1)))
+        rows = max(1, min(m, _DP_ELEMS // (cols * (X.shape[1] + 1))))
+        out = torch.empty((m, n), dtype=torch.int64, device=X.device)
+        for r0 in range(0, m, rows):
+            for c0 in range(0, n, cols):
+                out[r0:r0 + rows, c0:c0 + cols] = self._dp_block(St, X[c0:c0 + cols], lx[c0:c0 + cols], Y[r0:r0 + rows],
+                                                                 ly[r0:r0 + rows])
+        return out
+
+    def __call__(self, X, Y, similarity=True):
+        """(M, N) int64 scores of the M rows of Y against the N rows of X.  A score is a similarity: `similarity=False`
+        raises."""
+        name = type(self).__name__
+        if not similarity:
+            raise ValueError(f"{name}: {self._WHAT} is a similarity (larger is nearer), not a distance; "
+                             "there is no similarity=False form")
+        X, Y = clean_input(X, Y)
+        Y = Y.to(X.device)
+        xb = _as_byte_tokens(X)
+        yb = xb if Y is X else _as_byte_tokens(Y)
+        if xb is None or yb is None:
+            raise ValueError(f"{name}: the tokens must be integers in 0..255")
+        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
+        long = (not native and xb.is_cuda and _native.aln_long_ready()
+                and self._long_fits(xb.shape[1], yb.shape[1]))
+        if long:                                                              # 129..2048 positions inside the 16-bit cells
+            xo = _native.aln_long_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_long_operand(yb, self.symbols)
+            s = self._native_long_dense(xo, yo, 8)
+            native = True
+            inside = int((xo.flags | yo.flags).item()) == 0
+        elif native:
+            xo = _native.aln_operand(xb, self.symbols)
+            yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
+            s = self._native_dense(xo, yo, 8)
+            inside = int((xo.flags | yo.flags).item()) == 0                   # the packs' validity words: the one host sync
+        else:
+            inside = int(xb.max()) < self.symbols and int(yb.max()) < self.symbols
+        if not inside:
+            raise ValueError(f"{name}: a token is outside the score table (0..{self.symbols - 1})")
+        if not native:
+            s = self._torch_expression(xb, yb)
+        return s
+
+
+class local_alignment(_score_operator):
+    """The score of one score table and gap penalty, linear or affine (see the module text)."""
+    _DENSE, _LONG_DENSE, _LONG_FITS = "alignment_local_dense", "alignment_local_long_dense", "aln_local_long_fits"
+    _WHAT = "a local alignment score"
 
     def _dp_block(self, St, x, lx, y, ly):
         """(m, n) int64 scores of y rows (lengths ly) against x rows (lengths lx); x, y already cut to the longest
@@ -136,52 +211,3 @@ class local_alignment:
             live = inside & (ly >= i).view(m, 1, 1)                            # padding of either sequence never scores
             best = torch.maximum(best, torch.where(live, v, torch.zeros_like(v)).amax(dim=2))
         return best.to(torch.int64)
-
-    def _torch_expression(self, X, Y):
-        """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
-        St = self._table_on(X.device)
-        lx, ly = _lengths(X), _lengths(Y)
-        X, Y = X[:, :int(lx.max())], Y[:, :int(ly.max())]
-        n, m = X.shape[0], Y.shape[0]
-        cols = max(1, min(n, _DP_ELEMS // (X.shape[1] + 1)))
-        rows = max(1, min(m, _DP_ELEMS // (cols * (X.shape[1] + 1))))
-        out = torch.empty((m, n), dtype=torch.int64, device=X.device)
-        for r0 in range(0, m, rows):
-            for c0 in range(0, n, cols):
-                out[r0:r0 + rows, c0:c0 + cols] = self._dp_block(St, X[c0:c0 + cols], lx[c0:c0 + cols], Y[r0:r0 + rows],
-                                                                 ly[r0:r0 + rows])
-        return out
-
-    def __call__(self, X, Y, similarity=True):
-        """(M, N) int64 scores of the M rows of Y against the N rows of X.  A score is a similarity: `similarity=False`
-        raises."""
-        if not similarity:
-            raise ValueError("local_alignment: a local alignment score is a similarity (larger is nearer), not a distance; "
-                             "there is no similarity=False form")
-        X, Y = clean_input(X, Y)
-        Y = Y.to(X.device)
-        xb = _as_byte_tokens(X)
-        yb = xb if Y is X else _as_byte_tokens(Y)
-        if xb is None or yb is None:
-            raise ValueError("local_alignment: the tokens must be integers in 0..255")
-        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
-        long = (not native and xb.is_cuda and _native.aln_long_ready()
-                and _native.aln_local_long_fits(xb.shape[1], yb.shape[1], self.max_score))
-        if long:                                                              # 129..2048 positions inside the 16-bit cells
-            xo = _native.aln_long_operand(xb, self.symbols)
-            yo = xo if yb is xb else _native.aln_long_operand(yb, self.symbols)
-            s = _native.alignment_local_long_dense(xo, yo, self.device_score(), self._gap, self._open, out_bytes=8)
-            native = True
-            inside = int((xo.flags | yo.flags).item()) == 0
-        elif native:
-            xo = _native.aln_operand(xb, self.symbols)
-            yo = xo if yb is xb else _native.aln_operand(yb, self.symbols)
-            s = _native.alignment_local_dense(xo, yo, self.device_score(), self._gap, self._open, out_bytes=8)
-            inside = int((xo.flags | yo.flags).item()) == 0                   # the packs' validity words: the one host sync
-        else:
-            inside = int(xb.max()) < self.symbols and int(yb.max()) < self.symbols
-        if not inside:
-            raise ValueError(f"local_alignment: a token is outside the score table (0..{self.symbols - 1})")
-        if not native:
-            s = self._torch_expression(xb, yb)
-        return s

@@ -33,7 +33,9 @@ import pandas as pd
 import torch
 
 from . import _native
-from .distance import alignment, cosine, hamming, levenshtein, local_alignment, minkowski, substitution
+from .distance import alignment, cosine, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment, substitution
+
+_SCORES = (local_alignment, semiglobal_alignment)      # similarities: ranked largest first (`_local_select`)
 from .graph import CSRGraph, KNNGraph
 from .protein import Protein
 from .utils import Dataset, flatten
@@ -478,7 +480,8 @@ class Prograph:
         loop.
         A `local_alignment` instance is a score, not a distance: `similarity` is not consulted, `k` gives the LARGEST scores
         first (ties to the lower dataset index), `eps` the rows with `s > 0 and comp(eps, s)` - the default comp reads
-        `s >= eps` - and the weights are the scores (blocks of `pg_alignment_local_dense` plus the fp16 selection).
+        `s >= eps` - and the weights are the scores (blocks of `pg_alignment_local_dense` plus the fp16 selection).  A
+        `semiglobal_alignment` instance behaves in the same way on its own kernels (`pg_alignment_semiglobal_dense`).
         """
         if eps is None:
             if not k:                                                      # build_graph's errors for k
@@ -521,7 +524,7 @@ class Prograph:
                 g = self._search_substitution(strings, Y, None, eps, comp, similarity, representation, distance)
             elif isinstance(distance, alignment) and comp in _CMP_CODE:
                 g = self._search_alignment(strings, Y, None, eps, comp, similarity, representation, distance)
-            elif isinstance(distance, local_alignment):
+            elif isinstance(distance, _SCORES):
                 g = self._search_local(strings, Y, None, eps, comp, representation, distance)
             if g is None:
                 g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
@@ -536,7 +539,7 @@ class Prograph:
             g = self._search_substitution(strings, Y, k, None, None, similarity, representation, distance)
         elif isinstance(distance, alignment) and k <= _native.MAX_K_ROUNDS:
             g = self._search_alignment(strings, Y, k, None, None, similarity, representation, distance)
-        elif isinstance(distance, local_alignment):
+        elif isinstance(distance, _SCORES):
             g = self._search_local(strings, Y, k, None, None, representation, distance)
         if g is None:
             return self._search_generic(strings, Y, k, similarity, representation, distance, output)
@@ -880,7 +883,8 @@ class Prograph:
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
-    # ---- local alignment scores: a similarity - largest first, whatever `similarity` says
+    # ---- local and semi-global alignment scores (`_SCORES`): similarities - largest first, whatever `similarity` says; the
+    # two share every route below and differ in the kernels their instances name (`_native_dense`, `_native_long_dense`)
     def _local_native(self, width, distance):
         """Does a width take the local alignment kernel's fp16 route?  At most 128 positions, and every score - at most
         width * max(S) - is an integer that is exact in fp16."""
@@ -890,18 +894,21 @@ class Prograph:
         """`_sub_tokens`, with the operator's error instead of None: no generic loop ranks scores the right way round."""
         T = self._sub_tokens(mat, distance)
         if T is None:
-            raise ValueError(f"local_alignment: the tokens must be integers of the score table (0..{distance.symbols - 1})")
+            raise ValueError(f"{type(distance).__name__}: the tokens must be integers of the score table "
+                             f"(0..{distance.symbols - 1})")
         return T
 
     def _local_select(self, distance, X, T, rows, k, first, eps, comp, diagonal):
-        """The selection of `local_alignment` scores of the rows of T (all of X when T is None: a self graph) against X, in
+        """The selection of `local_alignment` / `semiglobal_alignment` scores of the rows of T (all of X when T is None: a self graph) against X, in
         row blocks of `rows`: ranks first..first+k-1 of the stable descending (score, column) order -> (idx, scores), or
         the CSR (indptr, indices, scores) of {(r, c): s > 0, comp(eps, s)} with ascending columns, without the entries
         c == r when `diagonal` is False.  Within `_local_native` and the device's selection limits: fp16 blocks of
         `pg_alignment_local_dense`, `_select_blocks` (descending; the comparator mirrored: the kernels test
         (value, threshold)), int16 scores.  Beyond 128 and up to 2048 positions, inside `_native.aln_local_long_fits`: int32
         blocks of `pg_alignment_local_long_dense` and `_select_blocks_i32` in the same way, int32 scores.  Outside both:
-        the same selection in torch over the operator's int64 blocks."""
+        the same selection in torch over the operator's int64 blocks.  A `semiglobal_alignment` instance takes the same
+        routes on `pg_alignment_semiglobal_dense` / `pg_alignment_semiglobal_long_dense` inside
+        `_native.aln_semiglobal_long_fits`: the instance names its kernels and its bound."""
         Y = X if T is None else T
         n, q = X.shape[0], Y.shape[0]
         native = self._local_native(max(X.shape[1], Y.shape[1]), distance)
@@ -909,9 +916,7 @@ class Prograph:
         if native:
             xo = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
             yo = xo if T is None else _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-            score = distance.device_score()
-            blocks = (_native.alignment_local_dense(xo, yo, score, distance.gap, distance.gap_open, out_bytes=2,
-                                                    rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+            blocks = (distance._native_dense(xo, yo, 2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
             if k is not None:
                 return self._select_blocks(blocks, knn=(k, first, True), wdtype=torch.int16)
             cmp = _CMP_MIRROR[_CMP_CODE[comp]]
@@ -919,16 +924,14 @@ class Prograph:
             csr = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.int16)
             return csr if diagonal else self._drop_diagonal(*csr)
         if (max(X.shape[1], Y.shape[1]) > _native.ALN_MAX_L and _native.aln_long_ready()
-                and _native.aln_local_long_fits(X.shape[1], Y.shape[1], distance.max_score)
+                and distance._long_fits(X.shape[1], Y.shape[1])
                 and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)):
             # beyond 128 positions: int32 blocks of the strip-mined kernel (`pg_alignment_local_long_dense`) and the int32
             # selection, descending and with the mirrored comparator as above; int32 scores
             xo = _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
             yo = xo if T is None else _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-            score = distance.device_score()
             rows = self._block_rows(n, q, 64 if T is None else 1, elem_bytes=4)
-            blocks = (_native.alignment_local_long_dense(xo, yo, score, distance.gap, distance.gap_open, out_bytes=4,
-                                                         rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+            blocks = (distance._native_long_dense(xo, yo, 4, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
             if k is not None:
                 return self._select_blocks_i32(blocks, knn=(k, first, True))
             cmp = _CMP_MIRROR[_CMP_CODE[comp]]
@@ -965,7 +968,7 @@ class Prograph:
         return out, indices[keep], wts[keep]
 
     def _search_local(self, strings, Y, k, eps, comp, representation, distance):
-        """Queries under a `local_alignment` score: `k` -> ranks 0..min(k, N)-1 of the stable descending (score, dataset
+        """Queries under a `local_alignment` or `semiglobal_alignment` score: `k` -> ranks 0..min(k, N)-1 of the stable descending (score, dataset
         row) order; `eps` -> per query the dataset rows with s > 0 and comp(eps, s), ascending.  Strings are tokenised with
         the dataset's letter table at their own width; dataset and queries keep their own widths, as in
         `_search_alignment`.  `similarity` is not consulted.  The weights are the scores."""
@@ -986,7 +989,7 @@ class Prograph:
 
     def _build_graph_local(self, idxs, eps, k, representation, comp, distance):
         """
-        `build_graph(distance=local_alignment(S, gap[, gap_open]))`.  A local alignment score is a similarity, so the
+        `build_graph(distance=local_alignment(S, gap[, gap_open]))` or `semiglobal_alignment(...)`.  Such a score is a similarity, so the
         graph ranks largest first and `similarity` is not consulted; the weights are the raw scores (the containers are
         built with similarity=False, so nothing turns them into 1/(1+w)).
         k: ranks 1..k of the stable descending (score, column) order; rank 0 is dropped, as the reference drops it for
@@ -1136,7 +1139,7 @@ class Prograph:
         (rows with more matches are recomputed exactly, so it only affects speed).  `store="Name"`
         also assigns the result to `self.graph["Name"]` and keeps the device CSR, so that `degree`,
         `dirichlet`, `local_variance`, `adjacency` on that name run from the CSR on the GPU.
-        `distance=local_alignment(...)` is a score, not a distance: `similarity` is not consulted, `k` keeps the largest
+        `distance=local_alignment(...)` or `semiglobal_alignment(...)` is a score, not a distance: `similarity` is not consulted, `k` keeps the largest
         scores, `eps` the pairs with `s > 0 and comp(eps, s)`, and the weights are the scores (`_build_graph_local`).
         """
         if operator.xor(bool(eps), bool(k)) is False:
@@ -1164,7 +1167,7 @@ class Prograph:
             g = self._build_graph_substitution(idxs, eps, k, similarity, representation, comp, distance)
         if isinstance(distance, alignment) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_alignment(idxs, eps, k, similarity, representation, comp, distance)
-        if isinstance(distance, local_alignment):
+        if isinstance(distance, _SCORES):
             g = self._build_graph_local(idxs, eps, k, representation, comp, distance)
         native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
         planes = None

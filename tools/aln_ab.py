@@ -1,6 +1,6 @@
 """
-Timings behind DESIGN.md §4.15, §4.16 and §4.17 (gapped alignment distance, linear and affine gap penalties; local alignment
-scores), on one GPU.  Every time is a whole call on a host clock,
+Timings behind DESIGN.md §4.15 .. §4.19 (gapped alignment distance, linear and affine gap penalties; local and semi-global
+alignment scores), on one GPU.  Every time is a whole call on a host clock,
 from the call to the end of a device synchronise, after a warm-up; arms alternate; inputs are seeded and random;
 medians with min / max.
 
@@ -25,11 +25,18 @@ medians with min / max.
           the operator's blocked torch expression on --torch-rows of the rows; the first rows compared.
   long_graph  build_graph(k = 16) at N = 20 000, lengths 200..400: the long route against the generic loop with the
           operator (`aln_long_ready` False); graphs compared.  Both write profiles/aln_long_ab.txt unless --out is given.
+  semiglobal  §4.19: `pg_alignment_semiglobal_dense` beside `pg_alignment_local_dense` under the same score table (as
+          `local`: -4..16 / -4..32, gap 1, gap_open 11) at the two dense shapes - time, the ratio of the two in the same
+          run, the ratio SEMIGLOBAL_VALU_PER_STEP / LOCAL_VALU_PER_STEP it should sit near; the first rows compared with
+          the operator's torch expression.
+  semiglobal_long  `pg_alignment_semiglobal_long_dense` beside `pg_alignment_local_long_dense` at `long`'s shape (4096 x
+          20 000 int32, rows of 300..400 tokens); the first rows compared with the operator's torch expression.  Both write
+          profiles/aln_semiglobal_ab.txt unless --out is given.
   pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
 
 Prints one JSON line; progress goes to stderr.
 
-    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local,long,long_graph] [--out FILE]
+    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local,long,long_graph,semiglobal,semiglobal_long] [--out FILE]
 """
 import argparse
 import json
@@ -43,7 +50,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from prograph_amd import Prograph, _native  # noqa: E402
-from prograph_amd.distance import alignment, local_alignment  # noqa: E402
+from prograph_amd.distance import alignment, local_alignment, semiglobal_alignment  # noqa: E402
 
 # VALU instructions of one outer step (one X symbol against 16 * chunks cells) in the gfx950 ISA of pg_aln_dense_kernel.
 # Counted by hand from the compiler's assembly (`--save-temps`; the table is in profiles/aln_dense.txt).  Nothing keeps it
@@ -55,6 +62,8 @@ VALU_PER_STEP = {1: 69, 2: 134, 3: 199, 4: 264, 5: 329, 6: 394, 7: 459, 8: 523}
 AFFINE_VALU_PER_STEP = {1: 131, 2: 260, 3: 389, 4: 518, 5: 647, 6: 775, 7: 905, 8: 1033}
 # The same for pg_aln_local_dense_kernel (profiles/aln_local_dense.txt), kept by hand in the same way.
 LOCAL_VALU_PER_STEP = {1: 152, 2: 305, 3: 458, 4: 611, 5: 764, 6: 917, 7: 1070, 8: 1222}
+# The same for pg_aln_semiglobal_dense_kernel (profiles/aln_semiglobal_dense.txt), kept by hand in the same way.
+SEMIGLOBAL_VALU_PER_STEP = {1: 179, 2: 324, 3: 470, 4: 616, 5: 762, 6: 908, 7: 1054, 8: 1198}
 ISSUE_RATE = 256 * 4 * 2.4e9
 
 
@@ -331,8 +340,70 @@ def main():
                    identical=bool(torch.equal(G.idx, H.idx) and torch.equal(G.dist.to(torch.int64), H.dist.to(torch.int64))),
                    speedup=res["generic_loop_operator_k16"]["median_ms"] / res["native_k16"]["median_ms"])
         out["long_graph"] = res
+    if "semiglobal" in only:
+        n, m, tr = args.n, args.rows, args.torch_rows
+        rng = np.random.default_rng(7)
+        for name, lo, hi in (("l125_128", 125, 128), ("l64", 64, 64)):
+            top = 2048 // hi                                                   # width * max(S) = 2048: the fp16 bound
+            S = np.triu(rng.integers(-4, 1, (a, a)), 1)
+            S = S + S.T + np.diag(rng.integers(top // 2, top + 1, a))
+            S[1, 1] = top
+            score, local = semiglobal_alignment(S, 1, gap_open=11), local_alignment(S, 1, gap_open=11)
+            host, lens = varlen(rng, n, lo, hi, a)
+            tok = torch.from_numpy(host).to(dev)
+            xo = _native.aln_operand(tok, a)
+            table = score.device_score()
+            assert xo.valid()
+            fns = {"alignment_semiglobal_dense_f16": lambda: score._native_dense(xo, xo, 2, rows=(0, m)),
+                   "alignment_local_dense_f16": lambda: _native.alignment_local_dense(xo, xo, table, local.gap, local.gap_open,
+                                                                                      out_bytes=2, rows=(0, m))}
+            res, outs = alternate(fns, args.reps, "semiglobal " + name)
+            same = bool(torch.equal(outs["alignment_semiglobal_dense_f16"][:tr].to(torch.int64), score._torch_expression(tok, tok[:tr])))
+            ms = res["alignment_semiglobal_dense_f16"]["median_ms"]
+            cells = float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3)
+            wave_max = np.pad(lens, (0, -len(lens) % 64)).reshape(-1, 64).max(axis=1).astype(np.float64).sum()
+            chunks = [max(1, (int(l) + 15) // 16) for l in lens[:m]]
+            body = np.array([SEMIGLOBAL_VALU_PER_STEP[c] for c in chunks], dtype=np.float64).sum()
+            valu = wave_max * body / (ms * 1e-3)
+            res.update(n=n, rows=m, lengths=[lo, hi], symbols=a, gap=score.gap, gap_open=score.gap_open, max_score=score.max_score,
+                       pairs_per_s=m * n / (ms * 1e-3), cell_updates_per_s=cells, valu_instructions_per_s=valu,
+                       share_of_valu_issue=valu / ISSUE_RATE,
+                       ratio_to_local=ms / res["alignment_local_dense_f16"]["median_ms"],
+                       expected_ratio_from_instruction_counts=body / np.array([LOCAL_VALU_PER_STEP[c] for c in chunks],
+                                                                              dtype=np.float64).sum(),
+                       torch_rows=tr, first_rows_equal_torch=same)
+            out["semiglobal_" + name] = res
+            del outs, xo, tok, fns
+            torch.cuda.empty_cache()
+    if "semiglobal_long" in only:
+        n, m, tr = 20_000, 4096, args.torch_rows
+        rng = np.random.default_rng(8)
+        S = np.triu(rng.integers(-4, 1, (a, a)), 1)
+        S = S + S.T + np.diag(rng.integers(4, 12, a))
+        score, local = semiglobal_alignment(S, 1, gap_open=11), local_alignment(S, 1, gap_open=11)
+        host, lens = varlen(rng, n, 300, 400, a)
+        tok = torch.from_numpy(host).to(dev)
+        xo = _native.aln_long_operand(tok, a)
+        table = score.device_score()
+        assert xo.valid() and score._long_fits(400, 400) and local._long_fits(400, 400)
+        fns = {"alignment_semiglobal_long_dense_i32": lambda: score._native_long_dense(xo, xo, 4, rows=(0, m)),
+               "alignment_local_long_dense_i32": lambda: _native.alignment_local_long_dense(xo, xo, table, local.gap, local.gap_open,
+                                                                                            out_bytes=4, rows=(0, m))}
+        res, outs = alternate(fns, args.reps, "semiglobal_long")
+        ms = res["alignment_semiglobal_long_dense_i32"]["median_ms"]
+        res.update(n=n, rows=m, lengths=[300, 400], symbols=a, gap=score.gap, gap_open=score.gap_open, max_score=score.max_score,
+                   torch_rows=tr, pairs_per_s=m * n / (ms * 1e-3),
+                   cell_updates_per_s=float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3),
+                   ratio_to_local=ms / res["alignment_local_long_dense_i32"]["median_ms"],
+                   first_rows_equal_torch=bool(torch.equal(outs["alignment_semiglobal_long_dense_i32"][:tr].to(torch.int64),
+                                                           score._torch_expression(tok, tok[:tr]))))
+        out["semiglobal_long"] = res
+        del outs, xo, tok, fns
+        torch.cuda.empty_cache()
     line = json.dumps(out)
     print(line)
+    if args.out is None and ("semiglobal" in only or "semiglobal_long" in only):
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "aln_semiglobal_ab.txt")
     if args.out is None and ("long" in only or "long_graph" in only):
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "aln_long_ab.txt")
     if args.out:
