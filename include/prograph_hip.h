@@ -519,6 +519,39 @@ int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t 
                                        void *stream);
 
 /*
+ * Alignment TRACEBACK - BUILD DEFINED (pg_aln_trace.hip, pg_aln_trace.h): the canonical alignment of a list of pairs under
+ * the tables H, E, F of pg_alignment_affine_dense (mode PG_ALN_TRACE_GLOBAL, table = cost_u8, gap_open = 0: the linear
+ * form), pg_alignment_local_dense (PG_ALN_TRACE_LOCAL, table = score_i8) or pg_alignment_semiglobal_dense
+ * (PG_ALN_TRACE_SEMIGLOBAL, score_i8); i runs over x, j over y, E leaves x_i unaligned, F leaves y_j unaligned.
+ *   End cell: global (len x, len y); local the maximal H, ties to the smallest i, then the smallest j, a maximum of 0 the
+ *   empty alignment at (0, 0); semi-global the best of H[i][len y] and H[len x][j], the same ties.
+ *   Walk back from it in state H.  In H at (i, j): local stops where H[i][j] = 0, semi-global where i = 0 or j = 0, global
+ *   at (0, 0) after leaving the j (i = 0) or i (j = 0) remaining symbols unaligned; otherwise a pair if
+ *   H[i][j] = H[i-1][j-1] + T[x_i][y_j], else state E if H[i][j] = E[i][j], else state F, at the same cell.  In E: x_i
+ *   unaligned, to (i-1, j), in state H if E[i][j] is the open term from H[i-1][j] (open wins a tie), else still in E.  F
+ *   mirrors E along j.
+ *   pg_alignment_trace_workspace  *bytes_per_wave = 64 * xl * ceil(yl / 8) * 4: the direction bits of 64 pairs.
+ *   pg_alignment_trace  operands as for pg_alignment_dense (pg_sub_pack's order, widths xl, yl <= 128, PG_E_TOOLONG
+ *                      beyond; x_npad >= n, y_npad >= m); xi, yi: int32[npairs] row numbers into the two operands, repeats
+ *                      allowed; gap in 1..255, gap_open in 0..255.  head: int32 (npairs, 8) = score (the operator's value),
+ *                      x_begin, x_end, y_begin, y_end (half-open ranges of the positions the alignment covers), n_ops,
+ *                      identities (pairs with x_i = y_j), status.  ops: uint8 (npairs, ldo), ldo >= xl + yl: the columns
+ *                      in forward order, 1 = pair, 2 = x symbol unaligned, 3 = y symbol unaligned, 0 from n_ops on (every
+ *                      byte of a row is written: no zeroed buffer is needed).  A pair whose index lies outside its operand
+ *                      touches no operand memory and gets status 1, n_ops -1, zeros elsewhere.  workspace: at least one
+ *                      wave's share (PG_E_BADARG below it); the call launches min(ceil(npairs / 64), workspace_bytes /
+ *                      share) waves, which stride over the list.  Every argument check returns before any launch.
+ */
+#define PG_ALN_TRACE_GLOBAL 0
+#define PG_ALN_TRACE_LOCAL 1
+#define PG_ALN_TRACE_SEMIGLOBAL 2
+int pg_alignment_trace_workspace(int xl, int yl, int64_t *bytes_per_wave);
+int pg_alignment_trace(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                       int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap,
+                       int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

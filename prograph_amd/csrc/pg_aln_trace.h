@@ -1,0 +1,152 @@
+// The canonical alignment of one pair: one row of the three integer tables with its direction bits, and
+// the walk back over those bits.  Plain integer code for host and device alike: pg_aln_trace.hip calls it with one pair
+// per lane (strides of 64), tests/capi_trace/trace_check.cpp compiles it for the CPU (strides of 1).
+//
+// One recurrence serves the three modes.  i runs over x, j over y, e = gap, oe = gap_open + gap, T = the score table, or
+// MINUS the cost table for the global distance, which turns its minimum into a maximum and leaves every equality test -
+// the whole of the tie rule - as it is:
+//     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - oe),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - oe),
+//     H[i][j] = max(H[i-1][j-1] + T[x_i][y_j], E[i][j], F[i][j])      (local: 0 where that is not positive),
+// borders H[i][0] = H[0][j] = 0 (global: H[0][0] = 0, else -(gap_open + k e)), E[0][j] = F[i][0] = PG_TR_NEG.  Cells are
+// int32: |H| <= 128 * 255 + 255, and PG_TR_NEG sinks by at most 128 * 255 more, so nothing overflows or meets a true value.
+//
+// Direction nibble of cell (i, j), i, j >= 1: bits 0-1 where H comes from (0 local stop, 1 diagonal, 2 E, 3 F; the
+// diagonal wins a tie, then E), bit 2 "E[i][j] opened from H[i-1][j]", bit 3 "F[i][j] opened from H[i][j-1]" (open wins
+// a tie).  Eight cells to a dword: cell j of row i in bits 4 * ((j-1) & 7) of dir[((i-1) * nd + ((j-1) >> 3)) * ds].
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define PG_TR_FN __host__ __device__ __forceinline__
+#else
+#define PG_TR_FN static inline
+#endif
+
+#define PG_TR_GLOBAL 0
+#define PG_TR_LOCAL 1
+#define PG_TR_SEMIGLOBAL 2
+#define PG_TR_MAX_L 128
+#define PG_TR_NEG (-(1 << 28))
+
+// token at position p (from 0) of a sequence in pg_sub_pack's dword order: dword g at tok[g * stride], masked to 0..31
+PG_TR_FN int pg_tr_token(const uint32_t *tok, long long stride, int p) {
+  return (int)((tok[(long long)(p >> 2) * stride] >> (8 * (p & 3))) & 31u);
+}
+
+// last non-zero byte + 1 over the ng dwords of a sequence
+PG_TR_FN int pg_tr_length(const uint32_t *tok, long long stride, int ng) {
+  int len = 0;
+  for (int g = 0; g < ng; ++g) {
+    const uint32_t w = tok[(long long)g * stride];
+    if (w) len = 4 * g + (w >> 24 ? 4 : w >> 16 ? 3 : w >> 8 ? 2 : 1);
+  }
+  return len;
+}
+
+// the running end cell (local: the maximal H; semi-global: the best of the last row and column), ties to the smallest i,
+// then the smallest j: candidates arrive in that order and only a larger value replaces
+struct pg_tr_end {
+  int best, i, j;
+};
+
+// row 0 of H and E, and the end cell before any row
+PG_TR_FN void pg_tr_row0(int mode, int lx, int ly, int e, int oe, int *colH, int *colE, int cs, pg_tr_end *end) {
+  for (int j = 0; j <= ly; ++j) {
+    colH[j * cs] = (mode == PG_TR_GLOBAL && j) ? -(oe - e) - j * e : 0;
+    colE[j * cs] = PG_TR_NEG;
+  }
+  end->best = 0;
+  end->i = mode == PG_TR_GLOBAL ? lx : 0;
+  end->j = mode == PG_TR_GLOBAL ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;     // semi-global: H[0][len y], or row 0 = row len x
+}
+
+// row i (1..lx) of one pair: colH / colE hold row i - 1 on entry and row i on return (cell j at [j * cs]); trow = T[x_i]
+// (32 ints), ytok / ys the y sequence as pg_tr_token reads it; the row's direction dwords go to dir[w * ds], w < ceil(ly / 8)
+PG_TR_FN void pg_tr_row(int mode, int i, int lx, int ly, int e, int oe, const int *trow, const uint32_t *ytok, long long ys,
+                        int *colH, int *colE, int cs, uint32_t *dir, int ds, pg_tr_end *end) {
+  int left = mode == PG_TR_GLOBAL ? -(oe - e) - i * e : 0;                 // H[i][0]
+  int diag = colH[0], F = PG_TR_NEG;
+  colH[0] = left;
+  uint32_t bits = 0;
+  for (int j = 1; j <= ly; ++j) {
+    const int hup = colH[j * cs], eup = colE[j * cs];
+    const int eopen = hup - oe, eext = eup - e, fopen = left - oe, fext = F - e;
+    const int E = eopen >= eext ? eopen : eext;
+    F = fopen >= fext ? fopen : fext;
+    const int D = diag + trow[pg_tr_token(ytok, ys, j - 1)];
+    int H = D >= E ? D : E;
+    if (F > H) H = F;
+    uint32_t nib = (H == D ? 1u : H == E ? 2u : 3u) | (eopen >= eext ? 4u : 0u) | (fopen >= fext ? 8u : 0u);
+    if (mode == PG_TR_LOCAL && H <= 0) {
+      H = 0;
+      nib &= ~3u;
+    }
+    if ((mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly))) && H > end->best) {
+      end->best = H;
+      end->i = i;
+      end->j = j;
+    }
+    diag = hup;
+    colH[j * cs] = H;
+    colE[j * cs] = E;
+    left = H;
+    bits |= nib << (4 * ((j - 1) & 7));
+    if ((j & 7) == 0 || j == ly) {
+      dir[((j - 1) >> 3) * ds] = bits;
+      bits = 0;
+    }
+  }
+}
+
+// The walk back from the end cell over the direction dwords (dir, nd dwords per row, stride ds), starting in state H.
+// Writes the codes (1 pair, 2 x symbol unaligned, 3 y symbol unaligned) in forward order to ops[0 .. n_ops), zeroes
+// ops[n_ops .. ldo), and fills head[1..6] = x_begin, x_end, y_begin, y_end, n_ops, identities.  ldo >= lx + ly.  Every
+// step moves towards (0, 0) and no cell outside 1..lx x 1..ly is read, whatever the dwords hold.
+PG_TR_FN void pg_tr_walk(int mode, int lx, int ly, int bi, int bj, const uint32_t *xtok, long long xs, const uint32_t *ytok,
+                         long long ys, const uint32_t *dir, int nd, int ds, unsigned char *ops, long long ldo, int32_t *head) {
+  int i = bi, j = bj, n = 0, ident = 0, state = 0;
+  const int room = (int)(ldo < 2 * PG_TR_MAX_L ? ldo : 2 * PG_TR_MAX_L);
+  while (n < room) {
+    if (state == 0 && (i == 0 || j == 0)) {
+      if (mode == PG_TR_GLOBAL) {                                           // the rest of the other sequence, unaligned
+        for (; i > 0 && n < room; --i) ops[n++] = 2;
+        for (; j > 0 && n < room; --j) ops[n++] = 3;
+      }
+      break;
+    }
+    if (i < 1 || j < 1 || i > lx || j > ly) break;                          // states E and F leave through H: not reached
+    const uint32_t nib = (dir[((long long)(i - 1) * nd + ((j - 1) >> 3)) * ds] >> (4 * ((j - 1) & 7))) & 15u;
+    if (state == 0) {
+      const uint32_t src = nib & 3u;
+      if (src == 0) break;                                                  // local: H[i][j] == 0 (never set otherwise)
+      if (src == 1) {
+        ops[n++] = 1;
+        ident += pg_tr_token(xtok, xs, i - 1) == pg_tr_token(ytok, ys, j - 1);
+        --i;
+        --j;
+      } else {
+        state = (int)src - 1;                                               // 1: E, 2: F, the same cell
+      }
+    } else if (state == 1) {
+      ops[n++] = 2;
+      if (nib & 4u) state = 0;
+      --i;
+    } else {
+      ops[n++] = 3;
+      if (nib & 8u) state = 0;
+      --j;
+    }
+  }
+  for (int a = 0, b = n - 1; a < b; ++a, --b) {                             // written backwards: turn round
+    const unsigned char t = ops[a];
+    ops[a] = ops[b];
+    ops[b] = t;
+  }
+  for (long long k = n; k < ldo; ++k) ops[k] = 0;
+  head[1] = i;
+  head[2] = bi;
+  head[3] = j;
+  head[4] = bj;
+  head[5] = n;
+  head[6] = ident;
+}

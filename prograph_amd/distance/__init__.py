@@ -1,3 +1,4 @@
+from ..alignments import Alignments
 from .alignment import alignment
 from .cosine import cosine
 from .hamming import hamming

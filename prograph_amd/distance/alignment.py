@@ -50,11 +50,15 @@ A distance is at most width * max(max C, gap) + gap_open: align the shorter sequ
 
 `build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_alignment`, `_search_alignment`);
 two instances with equal table, gap and gap_open behave identically.
+
+`dist.align(X, Y)` returns the alignments themselves - row p of X with row p of Y - and `Prograph.align` those of a graph's
+edges: see prograph_amd/alignments.py.
 """
 import numpy as np
 import torch
 
 from .. import _native
+from .. import alignments as _alignments
 from .hamming import _as_byte_tokens
 from .levenshtein import _lengths
 from .substitution import substitution
@@ -213,3 +217,10 @@ class alignment:
         if not native:
             d = self._torch_expression(xb, yb)
         return 1 / (1 + d) if similarity else d
+
+    def align(self, X, Y):
+        """The canonical optimal alignment of row p of X with row p of Y (P rows each, P may be 1) as an `Alignments`
+        container on X's device: which symbols pair, which stay unaligned, and the identities (prograph_amd/alignments.py
+        defines it).  `score` is this operator's distance.  Device byte tokens of at most 128 positions run on the HIP
+        kernel `pg_alignment_trace`; everything else on the exact, slow host expression."""
+        return _alignments.align(self, X, Y)

@@ -19,6 +19,9 @@ dependency inside a row resolved by v[j] = j + cummin(c[k] - k).  It is the slow
 
 `levenshtein_knn` is the banded (capped) kNN of BASELINE.json configs[4]: d = min(edit distance, band+1), canonical
 (d, index) order, rank 0 dropped.
+
+There is no `align` here: the edit script of a pair is `alignment(1 - I, 1).align(X, Y)`, I the identity over the alphabet
+(prograph_amd/alignments.py).
 """
 import torch
 

@@ -40,6 +40,9 @@ maximum over the cells with j <= len x and i <= len y.  It is the slow path; it 
 `build_graph` and `search` recognise instances by type (prograph.py: `_build_graph_local`, `_search_local`); two
 instances with equal table, gap and gap_open behave identically.
 
+`score.align(X, Y)` returns the alignments themselves - row p of X with row p of Y - and `Prograph.align` those of a graph's
+edges: see prograph_amd/alignments.py.
+
 `_score_operator` below is everything but the recurrence: the table's rules, the routes and the blocking of the torch
 expression.  `semiglobal_alignment` (semiglobal_alignment.py) is its other subclass.
 """
@@ -47,6 +50,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .. import alignments as _alignments
 from .alignment import _gap, _gap_open
 from .hamming import _as_byte_tokens
 from .levenshtein import _lengths
@@ -183,6 +187,14 @@ class _score_operator:
         if not native:
             s = self._torch_expression(xb, yb)
         return s
+
+    def align(self, X, Y):
+        """The canonical optimal alignment of row p of X with row p of Y (P rows each, P may be 1) as an `Alignments`
+        container on X's device: which symbols pair, which stay unaligned, where the alignment sits in either sequence,
+        and the identities (prograph_amd/alignments.py defines it).  `score` is this operator's score.  Device byte tokens
+        of at most 128 positions run on the HIP kernel `pg_alignment_trace`; everything else on the exact, slow host
+        expression."""
+        return _alignments.align(self, X, Y)
 
 
 class local_alignment(_score_operator):

@@ -32,6 +32,8 @@ which hold the score plus min(widths) * max(S).  Everything else is evaluated by
 the operands live on, CPU included: the table row by row over the whole (M, N) batch in `local_alignment._dp_block`'s
 style without the clamp, F by the cummax over A, and the result picked from column len x of every row i <= len y and from
 row len y (the batch tables run over the rows of Y, so X lies along a row).  It is the slow path; it is exact.
+
+`score.align(X, Y)`, inherited, returns the alignments themselves: see prograph_amd/alignments.py.
 """
 import torch
 

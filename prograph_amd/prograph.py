@@ -33,6 +33,7 @@ import pandas as pd
 import torch
 
 from . import _native
+from . import alignments as _alignments
 from .distance import alignment, cosine, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment, substitution
 
 _SCORES = (local_alignment, semiglobal_alignment)      # similarities: ranked largest first (`_local_select`)
@@ -1015,6 +1016,81 @@ class Prograph:
             return KNNGraph(idx, wt, n, similarity=False)
         indptr, indices, wts = self._local_select(distance, T, None, rows, None, 0, eps, comp, False)
         return CSRGraph(indptr, indices, wts, n, similarity=False)
+
+    # ---- alignment tracebacks (prograph_amd/alignments.py)
+    def _edge_lists(self, graph):
+        """(rows, columns) int64 numpy of the edges of a CSRGraph, a KNNGraph, a stored graph's name or a list of
+        (indices, weights) tuples, in the graph's order, `row0` added to the rows; kNN slots without a neighbour (-1) are
+        no edges."""
+        if isinstance(graph, str):
+            g = self._device_graph_any(graph)
+            if g is None:
+                indptr, indices, _ = self._column_csr(graph)
+                return np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr)), np.asarray(indices, dtype=np.int64)
+            graph = g
+        if isinstance(graph, KNNGraph):
+            graph = graph.as_csr()
+        if isinstance(graph, CSRGraph):
+            indptr, c = graph.indptr.cpu().numpy(), graph.indices.cpu().numpy().astype(np.int64)
+            r = np.repeat(np.arange(graph.nrows, dtype=np.int64) + graph.row0, np.diff(indptr))
+            return r[c >= 0], c[c >= 0]
+        if isinstance(graph, (list, tuple)) and all(isinstance(e, tuple) and len(e) == 2 for e in graph):
+            counts = np.fromiter((len(e[0]) for e in graph), dtype=np.int64, count=len(graph))
+            c = np.concatenate([np.asarray(e[0], dtype=np.int64) for e in graph]) if counts.sum() else np.zeros(0, dtype=np.int64)
+            return np.repeat(np.arange(len(graph), dtype=np.int64), counts), c
+        raise TypeError("align: graph must be a CSRGraph, a KNNGraph, the name of a stored graph or a list of (indices, weights) tuples")
+
+    def align(self, graph=None, rows=None, cols=None, queries=None, idxs=None, distance=None, representation="Tokenized",
+              workspace_bytes=256 << 20):
+        """
+        The canonical optimal alignments (`Alignments`, prograph_amd/alignments.py) of dataset pairs under
+        `distance`, which must be an `alignment`, `local_alignment` or `semiglobal_alignment` instance (`TypeError`
+        otherwise): which residues pair, where a fragment sits in its parent, how many columns are identical.
+        `graph`: a `CSRGraph`, a `KNNGraph`, a stored graph's name or the tuple list `build_graph` returns - one alignment
+        per edge in the graph's order, x the edge's row (`row0` honoured) and y its column; with `idxs`, the row selection
+        the graph was built over, both go through it.  `rows=` / `cols=`: explicit dataset pairs instead of a graph.
+        `queries=` (what `search` was given): the graph is a `search` result, x is the query and y the dataset row.
+        At most 128 positions run on the HIP kernel (`pg_alignment_trace`: one host sync for the index check, launches
+        split so that their direction bits fit `workspace_bytes`); beyond that the exact, slow host expression.
+        """
+        mode = _alignments._mode_of(distance)                               # TypeError for anything else
+        X = self._local_tokens(self._dataset_matrix(representation), distance)
+        if graph is not None:
+            if rows is not None or cols is not None:
+                raise ValueError("align: a graph or rows= / cols=, not both")
+            r, c = self._edge_lists(graph)
+        elif rows is not None and cols is not None:
+            r, c = np.asarray(rows, dtype=np.int64).reshape(-1), np.asarray(cols, dtype=np.int64).reshape(-1)
+            if len(r) != len(c):
+                raise ValueError("align: rows= and cols= must have one length")
+        else:
+            raise ValueError("align: give a graph, or rows= and cols=")
+        if idxs is not None:
+            idxs = np.arange(len(self))[idxs] if isinstance(idxs, slice) else np.asarray(idxs)
+            idxs = np.nonzero(idxs)[0] if idxs.dtype == bool else idxs.astype(np.int64)
+            c = idxs[c]
+            if queries is None:
+                r = idxs[r]
+        if queries is None:
+            Q = X
+        else:
+            if isinstance(queries, str) or (isinstance(queries, (list, tuple)) and len(queries)
+                                            and all(isinstance(q, str) for q in queries)):
+                raw, table = self._byte_view([queries] if isinstance(queries, str) else list(queries))
+                Q = table[raw]
+            else:
+                Q = queries.cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
+                Q = Q.reshape(1, -1) if Q.ndim == 1 else Q
+            Q = self._local_tokens(Q, distance)
+        if len(r) and (r.min() < 0 or r.max() >= Q.shape[0] or c.min() < 0 or c.max() >= X.shape[0]):
+            raise IndexError("align: an edge names a row outside the data")
+        letters = "?" + "".join(self.amino_acids) if all(len(a) == 1 for a in self.amino_acids) else None
+        dev = _native.device() if _native.aln_long_ready() else torch.device("cpu")
+        Xt = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
+        Qt = Xt if Q is X else torch.from_numpy(np.ascontiguousarray(Q)).to(dev)
+        native = _native.aln_long_ready() and max(X.shape[1], Q.shape[1]) <= _native.ALN_MAX_L
+        return _alignments.trace(distance, Qt, Xt, torch.from_numpy(r), torch.from_numpy(c), workspace_bytes=workspace_bytes,
+                                 letters=letters, native=native)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
