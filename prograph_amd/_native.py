@@ -311,7 +311,7 @@ def pack(tokens, rows=None, bits=None, width=None, check=True):
         wide[:, :l] = tokens
         tokens = wide
     buf = torch.empty(planes_bytes(n, lw, bits), dtype=torch.uint8, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)      # (pg_pack_planes zeroes it on the stream)
     _check(L.pg_pack_planes(_ptr(tokens), tokens.element_size(), n, lw, tokens.stride(0), _ptr(ridx), int(bits),
                             _ptr(buf), np_, _ptr(flags), _stream()), "pg_pack_planes")
     planes = Planes(buf, n, lw, bits, flags)
@@ -341,7 +341,7 @@ def pack_bytes(raw, lut, bits=BITS_5, want_tokens=True, check=True):
     lut_t = torch.as_tensor(np.asarray(lut, dtype=np.uint8).reshape(256)).to(dev)
     np_ = npad(n)
     buf = torch.empty(planes_bytes(n, width, bits), dtype=torch.uint8, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)      # (pg_pack_bytes zeroes it on the stream)
     tokens = torch.empty((n, width), dtype=torch.uint8, device=dev) if want_tokens else None
     _check(L.pg_pack_bytes(_ptr(raw), n, width, raw.stride(0), None, _ptr(lut_t), int(bits), _ptr(buf), np_, _ptr(tokens),
                            _ptr(flags), _stream()), "pg_pack_bytes")

@@ -88,70 +88,125 @@ int64_t pg_workspace_bytes(int64_t nrows) { return ws_evict_offset(nrows) + 4 * 
 }  // extern "C"
 
 // =======================================================================================
-// pack: row-major tokens -> bit-sliced records in chunk-major order (one thread per sequence)
+// pack: row-major tokens -> bit-sliced records in chunk-major order
 // =======================================================================================
+// A workgroup packs PG_PACK_SEQS consecutive sequences.  Work item (sequence, group): one lane gathers the 32 tokens of a
+// group as 32 bytes - 16-byte loads where the base, the row stride and the group allow, position by position otherwise -
+// and bit-slices them with four 8 x 8 bit transposes (word-level: no shift-and-or per bit and plane).  Items are
+// sequence-major, so the lanes of a wave read a contiguous stretch of a dense token matrix.  The plane words meet in
+// LDS in record order; one lane per (chunk, sequence) then stores a whole uint4 - a wave writes 1 KiB of a chunk array
+// - and the signature and fold sections are made from the LDS copy.
 // lut / tokOut (pg_pack_bytes): src holds the fixed-width BYTES of the sequences; token = lut[byte]
 // (the reference's letter table, prograph/prograph.py:127,454-474: unknown bytes and padding -> 0), written row-major
 // to tokOut as well when that is not NULL.
+#define PG_PACK_SEQS 64
+#define PG_PACK_LD 68        // LDS words per sequence: up to 8 groups x 8 planes, padded (16-byte aligned rows)
+
+// 8 x 8 bit transpose: byte i bit p of x -> byte p bit i (Hacker's Delight 7-3, three swap stages)
+__host__ __device__ __forceinline__ unsigned long long pg_transpose8(unsigned long long x) {
+  unsigned long long t;
+  t = (x ^ (x >> 7)) & 0x00AA00AA00AA00AAull;  x = x ^ t ^ (t << 7);
+  t = (x ^ (x >> 14)) & 0x0000CCCC0000CCCCull; x = x ^ t ^ (t << 14);
+  t = (x ^ (x >> 28)) & 0x00000000F0F0F0F0ull; x = x ^ t ^ (t << 28);
+  return x;
+}
+
 template <typename T, int B>
 __global__ __launch_bounds__(256) void pg_pack_kernel(const T *__restrict__ src, long long n, int l, long long ld,
                                                       const long long *__restrict__ rows, u32 *__restrict__ planes,
                                                       long long npad, int ng, int nq, u32 *flags,
                                                       const unsigned char *__restrict__ lut = nullptr,
                                                       unsigned char *__restrict__ tokOut = nullptr) {
-  const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (s >= npad) return;
-  const T *row = nullptr;
-  if (s < n) row = src + (rows ? rows[s] : s) * ld;
-  u32 bad = 0, fold[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sigw[2] = {0, 0};
-  for (int g = 0; g < ng; ++g) {
-    u32 pl[B];
+  constexpr int E = (int)sizeof(T), PER = 16 / E;           // tokens per 16-byte load
+  __shared__ __attribute__((aligned(16))) u32 words[PG_PACK_SEQS * PG_PACK_LD];
+  const long long s0 = (long long)blockIdx.x * PG_PACK_SEQS;   // (npad is a multiple of 256: whole workgroups)
+  const int tid = threadIdx.x;
+  // 16-byte loads: every row and every group of 32 tokens starts on a 16-byte boundary
+  const bool vec = !lut && ((unsigned long long)src & 15ull) == 0 && ((ld * E) & 15ll) == 0;
+  for (int item = tid; item < PG_PACK_SEQS * ng; item += 256) {
+    const int sl = item / ng, g = item - sl * ng;
+    const long long s = s0 + sl;
+    unsigned long long x[4] = {0, 0, 0, 0}, high = 0;     // the group's tokens, one byte each; OR of all bits of the elements
+    if (s < n) {
+      const T *row = src + (rows ? rows[s] : s) * ld;
+      if (vec && g * 32 + 32 <= l) {
+        const uint4 *r16 = reinterpret_cast<const uint4 *>(row + g * 32);
 #pragma unroll
-    for (int p = 0; p < B; ++p) pl[p] = 0;
-    if (row) {
-      for (int j = 0; j < 32; ++j) {
-        const int pos = g * 32 + j;
-        if (pos < l) {
-          long long v = (long long)row[pos];
-          if (lut) {
-            v = lut[(unsigned char)v];
-            if (tokOut) tokOut[s * (long long)l + pos] = (unsigned char)v;
+        for (int c = 0; c < 32 / PER; ++c) {
+          const uint4 v = r16[c];
+          T e[PER];
+          __builtin_memcpy(e, &v, 16);
+#pragma unroll
+          for (int i = 0; i < PER; ++i) {
+            const int j = c * PER + i;
+            const unsigned long long t = (unsigned long long)(long long)e[i];
+            high |= t;
+            x[j >> 3] |= (t & 0xFFull) << (8 * (j & 7));
           }
-          if (v < 0 || v >= (1ll << B)) bad = 1u;
+        }
+      } else {
 #pragma unroll
-          for (int p = 0; p < B; ++p) pl[p] |= (u32)((v >> p) & 1) << j;
+        for (int j = 0; j < 32; ++j) {
+          const int pos = g * 32 + j;
+          if (pos < l) {
+            long long v = (long long)row[pos];
+            if (lut) {
+              v = lut[(unsigned char)v];
+              if (tokOut) tokOut[s * (long long)l + pos] = (unsigned char)v;
+            }
+            high |= (unsigned long long)v;
+            x[j >> 3] |= ((unsigned long long)v & 0xFFull) << (8 * (j & 7));
+          }
         }
       }
     }
+    if (high >> B) atomicOr(flags, 1u);                   // a token outside the alphabet (negative ones: sign bits)
 #pragma unroll
-    for (int p = 0; p < B; ++p) fold[p] ^= pl[p];         // plane folds: XOR of each plane's group words
-    sigw[g & 1] ^= pl[0];                                 // plane 0, even / odd groups: the 64 bits behind the signature
+    for (int i = 0; i < 4; ++i) x[i] = pg_transpose8(x[i]);   // byte p of x[i]: bit p of tokens 8i .. 8i+7
 #pragma unroll
     for (int p = 0; p < B; ++p) {
-      const int w = p * ng + g;               // plane-major record order
-      planes[((long long)(w >> 2) * npad + s) * 4 + (w & 3)] = pl[p];
+      const u32 w = (u32)((x[0] >> (8 * p)) & 0xFFull) | (u32)((x[1] >> (8 * p)) & 0xFFull) << 8 |
+                    (u32)((x[2] >> (8 * p)) & 0xFFull) << 16 | (u32)((x[3] >> (8 * p)) & 0xFFull) << 24;
+      words[sl * PG_PACK_LD + p * ng + g] = w;             // plane-major record order
     }
   }
-  for (int w = ng * B; w < nq * 4; ++w) planes[((long long)(w >> 2) * npad + s) * 4 + (w & 3)] = 0;
-  // Signature section (after the nq chunk arrays, 32 * npad bytes): the column operands of the filter MFMAs
-  // (pg_mm.h), v_mfma_f32_32x32x64_f8f6f4 with FP4 elements: 1.0 (0x2) per set bit of the 54-bit signature,
-  // 1.0 in the ten bias slots k = 54..63 (0 for padding sequences: they never pass); per 32 sequences one
-  // 1 KiB block in fragment order: uint4 [tile][h * 32 + c] = elements k = 32h .. 32h+31 of sequence 32 * tile + c.
-  {
+  __syncthreads();
+  // chunk arrays: lane = sequence, a whole uint4 per store; words past ng * B are zero
+  const int nw = ng * B;
+  for (int item = tid; item < PG_PACK_SEQS * nq; item += 256) {
+    const int q = item / PG_PACK_SEQS, sl = item % PG_PACK_SEQS;
+    uint4 v = *reinterpret_cast<const uint4 *>(&words[sl * PG_PACK_LD + 4 * q]);
+    if (4 * q + 1 >= nw) v.y = 0;                          // (4 * q < nw always: nq = ceil(nw / 4))
+    if (4 * q + 2 >= nw) v.z = 0;
+    if (4 * q + 3 >= nw) v.w = 0;
+    reinterpret_cast<uint4 *>(planes)[(long long)q * npad + s0 + sl] = v;
+  }
+  const int sl = tid & 63;
+  const long long s = s0 + sl;
+  if (tid < 64) {
+    // Signature section (after the nq chunk arrays, 32 * npad bytes): the column operands of the filter MFMAs
+    // (pg_mm.h), v_mfma_f32_32x32x64_f8f6f4 with FP4 elements: 1.0 (0x2) per set bit of the 54-bit signature,
+    // 1.0 in the ten bias slots k = 54..63 (0 for padding sequences: they never pass); per 32 sequences one
+    // 1 KiB block in fragment order: uint4 [tile][h * 32 + c] = elements k = 32h .. 32h+31 of sequence 32 * tile + c.
+    u32 sigw[2] = {0, 0};                                   // plane 0, even / odd groups: the 64 bits behind the signature
+    for (int g = 0; g < ng; ++g) sigw[g & 1] ^= words[sl * PG_PACK_LD + g];
     const unsigned long long sig = pg_sig54(sigw[0], sigw[1]);
-    const u32 lo = (u32)sig, hi = (u32)(sig >> 32) | (row ? 0xFFC00000u : 0u);
+    const u32 lo = (u32)sig, hi = (u32)(sig >> 32) | (s < n ? 0xFFC00000u : 0u);
     uint4 *e = reinterpret_cast<uint4 *>(planes + (long long)nq * npad * 4) + (s >> 5) * 64 + (s & 31);
     e[0] = make_uint4(pg_nib8(lo) << 1, pg_nib8(lo >> 8) << 1, pg_nib8(lo >> 16) << 1, pg_nib8(lo >> 24) << 1);
     e[32] = make_uint4(pg_nib8(hi) << 1, pg_nib8(hi >> 8) << 1, pg_nib8(hi >> 16) << 1, pg_nib8(hi >> 24) << 1);
-  }
-  // Fold section (after the signatures, 32 * npad bytes): two uint4 arrays, planes 0..3 and 4..7 of every
-  // sequence's plane folds (unused planes 0): the operands of the dense form's folded-exact bound.
-  {
+  } else if (tid < 128) {
+    // Fold section (after the signatures, 32 * npad bytes): two uint4 arrays, planes 0..3 and 4..7 of every
+    // sequence's plane folds (XOR of each plane's group words; unused planes 0): the operands of the dense form's
+    // folded-exact bound.
+    u32 fold[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int p = 0; p < B; ++p)
+      for (int g = 0; g < ng; ++g) fold[p] ^= words[sl * PG_PACK_LD + p * ng + g];
     uint4 *f = reinterpret_cast<uint4 *>(planes + (long long)nq * npad * 4) + npad * 2;
     f[s] = make_uint4(fold[0], fold[1], fold[2], fold[3]);
     f[npad + s] = make_uint4(fold[4], fold[5], fold[6], fold[7]);
   }
-  if (bad) atomicOr(flags, bad);
 }
 
 // =======================================================================================
@@ -363,7 +418,8 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 // ---------------------------------------------------------------------------------------
 // Data probe + decision (no host round trip): pg_probe_kernel counts, for PG_PROBE_ROWS sample rows of the launch, the
 // columns nearer than the kNN cap and the columns inside the eps interval; pg_decide_kernel turns them into the gate
-// words the alternative kernels of the launch test at their start (NsqParams::gate):
+// words the alternative kernels of the launch test at their start (NsqParams::gate) - and zeroes the workspace's counter
+// block for the launch to come, which then needs no fill of its own (pass_counter):
 //   gate[0]  kNN engine: 0 = MFMA engine, 1 = VALU engine.  Unclustered data (fewer than half of the sample rows have
 //            k + 1 columns below the cap: the signature filter never gets a useful bound, every distance is needed)
 //            runs ~8 % faster on the VALU engine's direct form (profiles/r03_engine_landscape.txt: random N = 200k);
@@ -380,10 +436,11 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 // one workgroup: 16 threads per sample row (a quarter wave) sum the row's per-wave counts, the wave of a row then the
 // workgroup combine the verdicts
 __global__ __launch_bounds__(1024) void pg_decide_kernel(const u32 *counts, int nsample, int wavesPerRow, u32 need, long long ncols,
-                                                          int force, u32 *gate) {
+                                                          int force, u32 *gate, u32 *line, int lineWords) {
   __shared__ u32 sClustered[16];
   __shared__ unsigned long long sEps[16], sNear[16];
   const int tid = threadIdx.x, s = tid >> 4, sub = tid & 15;
+  if (tid < lineWords) line[tid] = 0u;                     // the counter block: nothing reads it before the launch behind this one
   u32 nearS = 0, epsS = 0;
   if (s < nsample)
     for (int w = sub; w < wavesPerRow; w += 16) {
@@ -469,7 +526,8 @@ static bool probe_enabled() {
   const char *e = getenv("PG_PROBE");
   return !(e && atoi(e) == 0) && !getenv("PG_ENGINE") && !getenv("PG_ENGINE_MIN_ROWS");
 }
-// zeroes and fills workspace[64, ...): returns the gate words through *gate
+// zeroes workspace[0, 576) (the counter block: pass_counter issues no fill behind a probe) and fills workspace[576, ...):
+// returns the gate words through *gate
 static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 span, u32 need, void *workspace, hipStream_t s,
                      const u32 **gate) {
   if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
@@ -486,7 +544,9 @@ static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 
   if (int rc = pg_launched(kProbe[pg_ngroups(l) - 1](bits, pp, s), "pg_probe_kernel")) return rc;
   const int force = getenv("PG_GATE_FORCE") ? atoi(getenv("PG_GATE_FORCE")) : -1;
   // (counts of a short sample: pg_decide_kernel reads counts[nsample + s] - same layout as the probe wrote)
-  pg_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates);   // (PG_PROBE_ROWS <= 64)
+  static_assert(PG_WS_GATES / 4 <= 1024, "pg_decide_kernel zeroes one word per thread");
+  pg_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates, (u32 *)workspace,
+                                                  PG_WS_GATES / 4);   // (PG_PROBE_ROWS <= 64)
   if (int rc = pg_launched("pg_decide_kernel")) return rc;
   *gate = gates;
   return 0;
@@ -589,7 +649,7 @@ int pg_pack_planes(const void *src, int elem_bytes, int64_t n, int l, int64_t ld
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s);
   if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
-  const dim3 grid((unsigned)((npad + 255) / 256)), block(256);
+  const dim3 grid((unsigned)(npad / PG_PACK_SEQS)), block(256);
   const long long *r = (const long long *)rows;
   u32 *pl = (u32 *)planes;
 #define PG_PACK(T)                                                                                          \
@@ -618,7 +678,7 @@ int pg_pack_bytes(const uint8_t *src, int64_t n, int width, int64_t ld, const in
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemsetAsync(flags, 0, sizeof(uint32_t), s);
   if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
-  const dim3 grid((unsigned)((npad + 255) / 256)), block(256);
+  const dim3 grid((unsigned)(npad / PG_PACK_SEQS)), block(256);
   if (bits == 5)
     pg_pack_kernel<unsigned char, 5><<<grid, block, 0, s>>>(src, n, width, ld, (const long long *)rows, (u32 *)planes, npad, ng, nq,
                                                             flags, lut256, tokens_out);
@@ -776,11 +836,14 @@ static void plan_mm(int64_t nrows, NsqParams *p, int *grid, int rb = PG_MM_RB, i
 // The pass counter of a launch lives in the caller's workspace (pg_workspace_bytes): zeroed on the launch's stream
 // right before the kernel.  Launch-private by contract, so concurrent launches - other streams, other devices,
 // any number of them - never share a word (the static ring of counters this replaces did after 256 launches).
-static int pass_counter(NsqParams *p, void *workspace, hipStream_t s) {
+// Behind a probe (`probed`: run_probe on this workspace, this stream, in this call) pg_decide_kernel has zeroed the block.
+static int pass_counter(NsqParams *p, void *workspace, hipStream_t s, bool probed = false) {
   if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
   unsigned *c = (unsigned *)workspace;
-  const hipError_t e = hipMemsetAsync(c, 0, PG_WS_GATES, s);   // (the counters and the row-block flags of a launch in column pieces)
-  if (e != hipSuccess) return pg_launched((int)e, "workspace: hipMemsetAsync");
+  if (!probed) {
+    const hipError_t e = hipMemsetAsync(c, 0, PG_WS_GATES, s);   // (the counters and the row-block flags of a launch in column pieces)
+    if (e != hipSuccess) return pg_launched((int)e, "workspace: hipMemsetAsync");
+  }
   p->mmPassCounter = c;
   return 0;
 }
@@ -851,7 +914,7 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
     // (records of up to three chunks - four waves per SIMD; longer ones, N = 100k L = 128: 0.75 against 0.67 with the old rule)
     const bool fine = pg_nchunks(l, bits) <= 3 && !(getenv("PG_MM_PLAN") && atoi(getenv("PG_MM_PLAN")) == 2);
     plan_mm(n, &p, &grid, PG_MM_RB, 4, false, fine ? (int)rs : 0);
-    if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
+    if (int rc = pass_counter(&p, workspace, (hipStream_t)stream, p.gate != nullptr)) return rc;
     return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps sym)");
   }
   if (!getenv("PG_ROWS_PER_WAVE") && !getenv("PG_WAVES_PER_CU")) {
@@ -1052,7 +1115,7 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
     if (p.gate) p.gateMask = alt32 ? (1u << 0) : ((1u << 0) | (1u << 2));
     plan_mm(mainRows, &p, &grid, rbm, occm, true);
     p.nrows = mainRows;
-    if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
+    if (int rc = pass_counter(&p, workspace, (hipStream_t)stream, p.gate != nullptr)) return rc;
     // rows that lose their optimistic cap are evicted from their passes and finished by pg_knn_rows_kernel behind the
     // launch (NsqParams::mmEvict; PG_MM_EVICT=0: the second phase inside the pass, as before)
     const bool evict = first == 1 && !floor_keys && !last_keys && p.knnGuess > 0 && evictOn;

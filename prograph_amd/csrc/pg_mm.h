@@ -1052,6 +1052,7 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
     const int sbeg = kSym ? (int)(pr0 / PG_MM_ST) : sb;    // EPS_SYM: from the super-tile that holds the pass's first row
     for (;;) {
       int S = sbeg;
+      [[maybe_unused]] int prioNext = sb;                   // R = 2: where the next step of the issue priority begins
       int dEnd = canFilter ? 0 : send;                      // a dense run is in progress up to here (no filter: throughout)
       for (;;) {
         if (S >= send || S >= nextCk) {                     // end of the sweep / a checkpoint: the queue is drained HERE
@@ -1069,13 +1070,24 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
         // a SIMD finish at 0.70 / 0.83 / 1.0 of the launch (profiles/r03_pass_timeline.txt) and its last third runs with
         // two, then one wave per SIMD.  cfg3 1.74 -> 1.65 ms, N = 270k 2.62 -> 2.42 (4 steps: 1.69; 64: 1.69); the 32-row
         // instances do not gain (N = 100k L = 128: 0.98 -> 0.99; N = 50k: 0.50 -> 0.52), nor do eps launches (3.02 / 3.00 ms): left alone.
+        // Step t begins at the first S with (S - sb) * 16 >= t * (se - sb).  The loop carries the next boundary, compares,
+        // and takes the quotient (S - sb) * 16 / (se - sb) only where S crosses one - 16 times per pass, against ~300
+        // calls of scan(): on every call it was 3.7 % of the kernel's vector issue.  Sweeps of fewer than 16 super-tiles:
+        // boundaries coincide, a crossing then skips steps as the quotient did.
+        // (se is not loop state either: it is `send` until the second phase shortens that, and se = nst there - column
+        // pieces, the passes with another se, have no checkpoints and so no second phase)
         if constexpr (R == 2) {
-          const int step = ((S - sb) * PG_MM_PRIO_STEPS) / (se - sb > 0 ? se - sb : 1);
-          const int pr = step & 3;
-          if (pr == 0) __builtin_amdgcn_s_setprio(3);
-          else if (pr == 1) __builtin_amdgcn_s_setprio(2);
-          else if (pr == 2) __builtin_amdgcn_s_setprio(1);
-          else __builtin_amdgcn_s_setprio(0);
+          if (S >= prioNext) {
+            const int e = resweep ? nst : send;
+            const int len = e - sb > 0 ? e - sb : 1;
+            const int step = ((S - sb) * PG_MM_PRIO_STEPS) / len;
+            prioNext = sb + ((step + 1) * len + PG_MM_PRIO_STEPS - 1) / PG_MM_PRIO_STEPS;   // > S: (step + 1) * len > (S - sb) * 16
+            const int pr = step & 3;
+            if (pr == 0) __builtin_amdgcn_s_setprio(3);
+            else if (pr == 1) __builtin_amdgcn_s_setprio(2);
+            else if (pr == 2) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+          }
         }
         const int Sin = S;
         PG_ST(18, 1);
