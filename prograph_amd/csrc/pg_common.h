@@ -270,11 +270,13 @@ __host__ __device__ __forceinline__ u32 pg_nib8(u32 x) {
 }
 // ten FP4 nibbles (40 bits, element k = 54 + i in nibble i) whose sum is the largest representable value
 // <= b, b clamped to [-60, 58]: q sixes, then the remainder (5 = 4 + 1); exact except b = -59 (-> -60) and 59
-__host__ __device__ __forceinline__ unsigned long long pg_bias_nibbles(int b) {
+#define PG_BIAS_MIN (-60)
+#define PG_BIAS_MAX 58
+__host__ __device__ __forceinline__ constexpr unsigned long long pg_bias_nibbles(int b) {
   const bool neg = b < 0;
   u32 v = (u32)(neg ? -b : b);
-  if (neg) v = v > 60u ? 60u : (v == 59u ? 60u : v);
-  else v = v > 58u ? 58u : v;
+  if (neg) v = v > (u32)-PG_BIAS_MIN ? (u32)-PG_BIAS_MIN : (v == 59u ? 60u : v);
+  else v = v > (u32)PG_BIAS_MAX ? (u32)PG_BIAS_MAX : v;
   const u32 q = (v * 43u) >> 8, r = v - 6u * q;            // v <= 60
   unsigned long long s = q ? (0x7777777777ull >> (4u * (10u - q))) : 0ull;
   s |= ((0x260605040200ull >> (8u * r)) & 0xFFull) << (4u * q);
@@ -282,6 +284,110 @@ __host__ __device__ __forceinline__ unsigned long long pg_bias_nibbles(int b) {
   if (neg && cnt) s |= 0x8888888888ull >> (4u * (10u - cnt));
   return s;
 }
+
+// ---- chained filter MFMAs (pg_mm.h, scan()) ------------------------------------------------------------------
+// A filter result D = (lb - pa) + bias is an integer in [PG_SIG_D_MIN, PG_SIG_D_MAX]: lb - pa lies in
+// [-PG_SIG_BITS, PG_SIG_BITS], the bias in [PG_BIAS_MIN, PG_BIAS_MAX].  Up to three column tiles share ONE
+// accumulator: the scaled form of the instruction multiplies tile t's products by 2^(8t - 22) (E8M0 block scale of the
+// row operand, byte t of PG_CHAIN_SCALE_A; the column operand's scale is 1) and the chain starts from 2.0:
+//     X = 2 + S * 2^-22,   S = D_0 + 256 * D_1 + 65536 * D_2,   |S| <= 127 * 65793 < 2^23.
+// Every partial sum is an integer multiple of 2^-22 below 4 in magnitude, so X is exact in f32 in any order.
+//   S >= 0: X in [2, 4), biased exponent 128 (bit 29 clear), mantissa = S: D_2 >= 0, and a negative D_0 or D_1 (>= -127)
+//           reads 256 + D_t - borrow >= 128 in its byte: bit 8t + 7 set.  No field negative: no borrow, every byte is
+//           D_t <= 127, bits 7 and 15 clear.
+//   S <  0: X in (0, 2), biased exponent <= 127: bit 29 set - and some D_t is negative (else S >= 0).
+// So "some D_t < 0"  <=>  (bits(X) & PG_CHAIN_FLAGS) != 0, with neither false negatives nor false positives; the flag
+// bits OR across registers like the sign bit did.  (A borrow may raise a higher field's flag: bits 7 / 15 / 29 say
+// that A tile of the chain holds a candidate, not which one.)
+#define PG_SIG_D_MIN (-PG_SIG_BITS + PG_BIAS_MIN)   // -114
+#define PG_SIG_D_MAX (PG_SIG_BITS + PG_BIAS_MAX)    //  112
+#define PG_CHAIN_BASE 2.0f
+#define PG_CHAIN_SCALE_A 0x7F797169u   // E8M0 bytes 105, 113, 121: 2^-22, 2^-14, 2^-6 (byte 3, 127 = 1: the plain form)
+#define PG_CHAIN_FLAGS 0x20008080u
+static_assert(PG_SIG_D_MIN >= -127 && PG_SIG_D_MAX <= 127, "a filter result must fit a byte field of the chained accumulator");
+static_assert(PG_SIG_BITS + PG_SIG_BIAS == 64, "signature + bias elements fill the K = 64 of the instruction");
+// the FP4 (E2M1) sum of ten bias nibbles, doubled (the element values are multiples of 0.5)
+__host__ __device__ constexpr int pg_bias_nibbles_sum2(unsigned long long s) {
+  constexpr int mag2[8] = {0, 1, 2, 3, 4, 6, 8, 12};
+  int t = 0;
+  for (int i = 0; i < PG_SIG_BIAS; ++i) {
+    const int nib = (int)((s >> (4 * i)) & 0xFull);
+    t += (nib & 8) ? -mag2[nib & 7] : mag2[nib & 7];
+  }
+  return t;
+}
+// every bias the encoder can produce lies in [PG_BIAS_MIN, PG_BIAS_MAX] and is never above the one asked for
+__host__ __device__ constexpr bool pg_bias_range_holds() {
+  for (int b = -300; b <= 300; ++b) {
+    const unsigned long long s = pg_bias_nibbles(b);
+    const int v2 = pg_bias_nibbles_sum2(s);
+    if ((s >> (4 * PG_SIG_BIAS)) != 0ull || v2 < 2 * PG_BIAS_MIN || v2 > 2 * PG_BIAS_MAX) return false;
+    if (b >= PG_BIAS_MIN && v2 > 2 * b) return false;    // (below PG_BIAS_MIN every pair passes either way)
+    if (b >= PG_BIAS_MIN && b < PG_BIAS_MAX && b != -59 && v2 != 2 * b) return false;
+  }
+  return true;
+}
+static_assert(pg_bias_range_holds(), "pg_bias_nibbles left the range the chained accumulator's byte fields are sized for");
+// the accumulator's value for three filter results (host checks; the device gets it from the matrix core)
+__host__ __device__ __forceinline__ float pg_chain_value(int d0, int d1, int d2) {
+  float x = PG_CHAIN_BASE;
+  x += (float)d0 * 0x1p-22f;
+  x += (float)d1 * 0x1p-14f;
+  x += (float)d2 * 0x1p-6f;
+  return x;
+}
+// != 0: some tile of the chain holds a result below zero
+__host__ __device__ __forceinline__ u32 pg_chain_flag(u32 xbits) { return xbits & PG_CHAIN_FLAGS; }
+
+// The chains as the hot loop issues them.  Inline assembly: the head's 2.0 must be the instruction's INLINE CONSTANT.
+// Through the builtin the compiler keeps the splat in 16 SGPRs and copies it to 16 VGPRs in every iteration (the
+// in-place chain overwrites them): 15 s_mov + 8 v_mov_b64 per super-tile, more than the chain saves.  What the compiler
+// therefore does not see, and the statements carry themselves:
+//   * a link reads the accumulator its predecessor writes - the SAME registers, which the matrix pipe forwards without
+//     wait states (the compiler's own code for the builtin issues such links back to back);
+//   * VALU code may read a result 12 wait states after the 8-pass MFMA that wrote it was issued (the compiler puts
+//     s_nop 10 behind MFMA + one more instruction): pg_chain_settle, or the nop at the end of a statement, 13 of them;
+//   * operands: the row operands and the scale register were written long before, column operands come from memory
+//     behind an s_waitcnt; results are early-clobber outputs, so no operand shares registers with them.
+// `sc`: a VGPR with PG_CHAIN_SCALE_A in every lane - byte SEL scales the row operand of link SEL, byte 3 (1) the column's.
+typedef int pg_v4i __attribute__((ext_vector_type(4)));
+typedef float pg_v16f __attribute__((ext_vector_type(16)));
+#define PG_CHAIN_MFMA "v_mfma_scale_f32_32x32x64_f8f6f4 "
+#define PG_CHAIN_SEL0 " op_sel:[0,1,0] op_sel_hi:[0,1,0] cbsz:4 blgp:4\n\t"
+#define PG_CHAIN_SEL1 " op_sel:[1,1,0] op_sel_hi:[0,1,0] cbsz:4 blgp:4\n\t"
+#define PG_CHAIN_SEL2 " op_sel:[0,1,0] op_sel_hi:[1,1,0] cbsz:4 blgp:4\n\t"
+#define PG_CHAIN_NOP "s_nop 12"
+// x = chain(a0 x b0, a0 x b1, a0 x b2), y = chain(a1 x b0, a1 x b1, a1 x b2); settled
+__device__ __forceinline__ void pg_chain_3x2(pg_v16f &x, pg_v16f &y, const pg_v4i &a0, const pg_v4i &a1, const pg_v4i &b0,
+                                             const pg_v4i &b1, const pg_v4i &b2, int sc) {
+  asm volatile(PG_CHAIN_MFMA "%0, %2, %4, 2.0, %7, %7" PG_CHAIN_SEL0
+               PG_CHAIN_MFMA "%0, %2, %5, %0, %7, %7" PG_CHAIN_SEL1
+               PG_CHAIN_MFMA "%0, %2, %6, %0, %7, %7" PG_CHAIN_SEL2
+               PG_CHAIN_MFMA "%1, %3, %4, 2.0, %7, %7" PG_CHAIN_SEL0
+               PG_CHAIN_MFMA "%1, %3, %5, %1, %7, %7" PG_CHAIN_SEL1
+               PG_CHAIN_MFMA "%1, %3, %6, %1, %7, %7" PG_CHAIN_SEL2
+               PG_CHAIN_NOP
+               : "=&v"(x), "=&v"(y) : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "v"(b2), "v"(sc));
+}
+// x = chain(a x b0, a x b1, a x b2), y = chain(a x b3); settled
+__device__ __forceinline__ void pg_chain_3p1(pg_v16f &x, pg_v16f &y, const pg_v4i &a, const pg_v4i &b0, const pg_v4i &b1,
+                                             const pg_v4i &b2, const pg_v4i &b3, int sc) {
+  asm volatile(PG_CHAIN_MFMA "%0, %2, %3, 2.0, %7, %7" PG_CHAIN_SEL0
+               PG_CHAIN_MFMA "%0, %2, %4, %0, %7, %7" PG_CHAIN_SEL1
+               PG_CHAIN_MFMA "%0, %2, %5, %0, %7, %7" PG_CHAIN_SEL2
+               PG_CHAIN_MFMA "%1, %2, %6, 2.0, %7, %7" PG_CHAIN_SEL0
+               PG_CHAIN_NOP
+               : "=&v"(x), "=&v"(y) : "v"(a), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(sc));
+}
+// x = chain(a0 x b0, a1 x b1), NOT settled: pg_chain_settle(x) comes before the first read.  `busy`: results of an
+// earlier chain that are read behind this one (the statement only holds that code in its place: under the MFMAs)
+__device__ __forceinline__ void pg_chain_2(pg_v16f &x, pg_v16f &busy, const pg_v4i &a0, const pg_v4i &b0, const pg_v4i &a1,
+                                           const pg_v4i &b1, int sc) {
+  asm volatile(PG_CHAIN_MFMA "%0, %2, %3, 2.0, %6, %6" PG_CHAIN_SEL0
+               PG_CHAIN_MFMA "%0, %4, %5, %0, %6, %6" PG_CHAIN_SEL1
+               : "=&v"(x), "+v"(busy) : "v"(a0), "v"(b0), "v"(a1), "v"(b1), "v"(sc));
+}
+__device__ __forceinline__ void pg_chain_settle(pg_v16f &x) { asm volatile(PG_CHAIN_NOP : "+v"(x)); }
 
 // Parameters of the all-pairs engine (one struct so the per-Q translation units share it)
 struct NsqParams {

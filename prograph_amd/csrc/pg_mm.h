@@ -19,9 +19,15 @@
 // nothing and make unrelated pairs invisible up to bounds of ~12 (one in 3e6 at 10; the 31-bit form let one
 // in 2e3 pass at 7): cfg3 3.73 -> 3.55 ms, a 125k x 1M slice 9.3 -> 6.1 ms, and the optimistic kNN cap could
 // go from 7 to 10.
-// One MFMA evaluates 32 rows x 32 columns; the 16 result registers are OR-ed (8 v_or3) and ONE sign test +
-// scalar branch per four of them decides whether the super-tile holds any candidate: ~0.56 VALU instructions
-// per 64 pairs instead of ~2.9 (pg_nsq.h), with the multiply-adds on a pipe the VALU does not compete for.
+// One MFMA evaluates 32 rows x 32 columns.  Up to THREE MFMAs of the hot loop - three column tiles - accumulate into ONE
+// set of 16 result registers (the scaled form of the instruction: tile t enters times 2^(8t - 22), the chain starts
+// from 2.0, so the three small integers sit in byte fields of the f32 mantissa and "some result is negative" is a test
+// of three flag bits: pg_common.h, "chained filter MFMAs"; tools/ubench/mfma_fp4_chain.hip checks exactness and the flag
+// identity on the hardware).  The 16 registers of a chain are OR-ed (7 v_bitop3 + 1 v_or) and ONE flag test + scalar
+// branch per super-tile decides whether it holds any candidate: ~0.24 VALU instructions per 64 pairs at two row blocks
+// (31 per 8192 pairs; one OR tree per MFMA cost 72) instead of ~2.9 (pg_nsq.h), with the multiply-adds on a pipe the
+// VALU does not compete for.  At a super-tile with candidates the chains' flagged links are evaluated again, unscaled
+// and from zero, for the sign of every result.
 // Measured on MI355X for the int8 form (tools/ubench/mfma_s1.hip, N = 200k full sweep): 1.45 ms against
 // 3.6 ms for xor + bcnt; insensitive to occupancy (2..8 waves per SIMD) and to how many row blocks share a
 // column fragment, i.e. not bound by the 1 KiB-per-MFMA fragment stream from L2.
@@ -44,7 +50,6 @@
 #pragma once
 #include "pg_common.h"
 
-typedef int pg_v4i __attribute__((ext_vector_type(4)));
 typedef int pg_v16i __attribute__((ext_vector_type(16)));
 
 #define PG_MM_RB 32          // rows per pass = M of the MFMA tile
@@ -68,7 +73,6 @@ static_assert(PG_QCAP >= 63 + 4 * 2 * PG_PUSH_MAX, "pg_nsq.h kNN queue: a group 
 static_assert(PG_QCAP_EPS >= 63 + 4 * 2 * 64, "pg_nsq.h eps queue: a group pushes up to 4 rows x 2 x 64 lanes");
 
 typedef int pg_v8i __attribute__((ext_vector_type(8)));
-typedef float pg_v16f __attribute__((ext_vector_type(16)));
 
 // D = A x B over K = 64 FP4 elements (only the first four registers of each operand are read); the result
 // comes back as its bit patterns: the filter looks at signs only, and sums of these small integers are exact
@@ -151,7 +155,8 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
   u32 *cq = &cqbuf[wv][0];
   const u32 bias = kEps ? opaque_vgpr(0u - p.lo) : 0u;     // eps: -lo rides in the popcount accumulator
   // eps entries carry the row in 5 bits above a 27-bit column; wider problems run the direct form
-  const bool canFilterK = p.filter != 0 && (!kEps || p.ncols < (1ll << 27));   // (per pass: canFilter below)
+  // (and the fragment offset of scan() + one super-tile stays below 2^32: at most 2^20 - 1 super-tiles)
+  const bool canFilterK = p.filter != 0 && (!kEps || p.ncols <= (1ll << 27) - PG_MM_ST);   // (per pass: canFilter below)
   const bool epsOrdered = kEps && (p.fillIndptr != nullptr || p.epsOrdered != 0);   // (see push_signs)
   constexpr int SH = kEps ? 27 : 24;
   // arguments that only cold code needs (staging a pass, storing results, the dense forms) are read from the
@@ -633,7 +638,7 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
                "global_load_dwordx4 %0, %5, %4 offset:0\n\t"                                     \
                "global_load_dwordx4 %1, %5, %4 offset:1024\n\t"                                  \
                PG_EXP_LD23                                                                       \
-               : c(x0), c(x1), c(x2), c(x3), "=&s"(ringBase) : "v"(voff), "s"(colsig) : "memory")
+               : c(x0), c(x1), c(x2), c(x3), "=&s"(ringBase) : "v"(voff), "s"(sigBase) : "memory")
     // THE HOT LOOP: super-tiles S, S+1, .. below `stop` in the MFMA form while none holds a candidate - per tile and
     // row block an MFMA on the ring, the OR of its result; one sign test per super-tile; the ring refilled with the
     // super-tile after next.  A tight loop of its own: nothing of the slow paths' state lives in registers across it, no
@@ -642,36 +647,62 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
     // 2: most lane slots of S hold a candidate - the signature is not selective here, the dense form takes over.
     auto scan = [&](int &S, int stop, int last) -> int {   // last = send - 1: nothing is fetched beyond it
       u32 voff = ulane * 16u + (u32)S * 4096u;
+      // nothing is fetched beyond super-tile `last`: the offset stops there (a vector minimum - `last` held as a scalar
+      // came back from its spill lane with a v_readlane in every iteration)
+      const u32 voffLast = opaque_vgpr((u32)last * 4096u) + ulane * 16u;
+      // the section's base: where SGPRs are scarcest - records of four chunks and more, and the short-list kNN instances
+      // for records of up to two - the kernel-wide value lives in a spill lane and came back with two v_readlane in
+      // front of every load statement; read again here (K(), above: one scalar load per stretch) it is a value of this
+      // stretch only, and stays in scalar registers across the loop.  (The other instances - the flagship's among them: its
+      // records have three chunks - keep it in SGPRs and are left alone.)
+      const pg_v4i *sigBase = colsig;
+      if constexpr (Q >= 4 || (Q <= 2 && kPar)) {
+        sigBase = reinterpret_cast<const pg_v4i *>(K().colSig);
+        asm volatile("" : "+s"(stop));                      // (likewise: the stretch's own copy of its end)
+      }
       // TWO rings: while one super-tile is evaluated the next one's fragments are already on their way - loads are
       // issued a whole iteration before they are needed; the loop is unrolled by two so the rings swap roles instead
       // of being copied.  vmcnt(4): the older ring has landed, the younger one (four loads) may still be out.
       pg_v4i r0, r1, r2, r3, q0, q1, q2, q3;
       unsigned long long ringBase;                          // (scratch SGPR pair of the load statement)
-      int av0 = 0, av1 = 0, av2 = 0, av3 = 0, av4 = 0, av5 = 0, av6 = 0, av7 = 0;   // OR of MFMA m = tile * R + block
+      // OR of the result registers of chain 0, 1, 2.  R = 2: chain 0 = row block 0 x tiles 0, 1, 2, chain 1 = row block 1 x
+      // tiles 0, 1, 2, chain 2 = tile 3 x row blocks 0, 1;  R = 1: chain 0 = tiles 0, 1, 2, chain 1 = tile 3
+      // kChain = false: the eps and symmetric eps instances (R = 1) keep ONE MFMA per result set and its own OR tree, av0..3
+      // = OR of tile 0..3 - measured with the chain of 3 + 1, cfg2 (symmetric eps, L = 32) lost 2.3 % (0.474 -> 0.485 ms):
+      // an eps sweep leaves the loop every few super-tiles, and what the chain saves inside it does not pay for the
+      // links evaluated again at each exit (profiles/r12_chain_scan.json)
+      constexpr bool kChain = !kEps;
+      int av0 = 0, av1 = 0, av2 = 0, av3 = 0;
+      const int csc = kChain ? (int)opaque_vgpr(PG_CHAIN_SCALE_A) : 0;   // the block scales of the chain's links
       bool found;
-      // two result sets in turn (the 128-VGPR budget), two MFMAs in the pipe before the first OR
+      // two result sets in turn (the 128-VGPR budget); a chain runs in place, its OR under the next chain's MFMAs
 #define PG_SB __builtin_amdgcn_sched_barrier(0)
+#define PG_OR16F(d) pg_or16(__builtin_bit_cast(pg_v16i, d))
 #define PG_RING_STEP(x0, x1, x2, x3)                                                               \
       {                                                                                            \
-        pg_v16i d0, d1;                                                                            \
-        if constexpr (R == 1) {                                                                    \
-          d0 = pg_mfma_fp4(A0, x0); d1 = pg_mfma_fp4(A0, x1); PG_SB;                               \
-          av0 = pg_or16(d0); PG_SB; d0 = pg_mfma_fp4(A0, x2);                                      \
-          av1 = pg_or16(d1); PG_SB; d1 = pg_mfma_fp4(A0, x3);                                      \
-          av2 = pg_or16(d0);                                                                       \
-          av3 = pg_or16(d1);                                                                       \
+        pg_v16f d0, d1;                                                                            \
+        if constexpr (!kChain) {                                                                   \
+          pg_v16i e0, e1;                                                                          \
+          e0 = pg_mfma_fp4(A0, x0); e1 = pg_mfma_fp4(A0, x1); PG_SB;                               \
+          av0 = pg_or16(e0); PG_SB; e0 = pg_mfma_fp4(A0, x2);                                      \
+          av1 = pg_or16(e1); PG_SB; e1 = pg_mfma_fp4(A0, x3);                                      \
+          av2 = pg_or16(e0);                                                                       \
+          av3 = pg_or16(e1);                                                                       \
           found = __builtin_amdgcn_ballot_w64((av0 | av1 | av2 | av3) < 0) != 0;                   \
+        } else if constexpr (R == 1) {                                                             \
+          pg_chain_3p1(d0, d1, A0, x0, x1, x2, x3, csc); PG_SB;                                    \
+          av0 = PG_OR16F(d0);                                                                      \
+          av1 = PG_OR16F(d1);                                                                      \
+          found = __builtin_amdgcn_ballot_w64(pg_chain_flag((u32)(av0 | av1)) != 0u) != 0;         \
         } else {                                                                                   \
-          d0 = pg_mfma_fp4(A0, x0); d1 = pg_mfma_fp4(A1, x0); PG_SB;                               \
-          av0 = pg_or16(d0); PG_SB; d0 = pg_mfma_fp4(A0, x1);                                      \
-          av1 = pg_or16(d1); PG_SB; d1 = pg_mfma_fp4(A1, x1);                                      \
-          av2 = pg_or16(d0); PG_SB; d0 = pg_mfma_fp4(A0, x2);                                      \
-          av3 = pg_or16(d1); PG_SB; d1 = pg_mfma_fp4(A1, x2);                                      \
-          av4 = pg_or16(d0); PG_SB; d0 = pg_mfma_fp4(A0, x3);                                      \
-          av5 = pg_or16(d1); PG_SB; d1 = pg_mfma_fp4(A1, x3);                                      \
-          av6 = pg_or16(d0);                                                                       \
-          av7 = pg_or16(d1);                                                                       \
-          found = __builtin_amdgcn_ballot_w64((av0 | av1 | av2 | av3 | av4 | av5 | av6 | av7) < 0) != 0; \
+          pg_v16f d2;                                                                              \
+          pg_chain_3x2(d0, d1, A0, A1, x0, x1, x2, csc); PG_SB;                                    \
+          av0 = PG_OR16F(d0); PG_SB;                                                               \
+          pg_chain_2(d2, d1, A0, x3, A1, x3, csc); PG_SB;                                          \
+          av1 = PG_OR16F(d1); PG_SB;                                                               \
+          pg_chain_settle(d2); PG_SB;                                                              \
+          av2 = PG_OR16F(d2);                                                                      \
+          found = __builtin_amdgcn_ballot_w64(pg_chain_flag((u32)pg_or3(av0, av1, av2)) != 0u) != 0; \
         }                                                                                          \
       }
       // (no branch around a load statement: where two paths with different statements meet, the compiler copies
@@ -680,13 +711,13 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
       PG_RING_LOAD("=&v", r0, r1, r2, r3, voff);
       bool inQ = false;                                     // the super-tile the loop stopped at sits in q0..3
       for (;;) {
-        voff += (S < last && !PG_EXP_SAMETILE) ? 4096u : 0u;
+        voff = PG_EXP_SAMETILE ? voff : (voff + 4096u < voffLast ? voff + 4096u : voffLast);
         PG_RING_LOAD("=&v", q0, q1, q2, q3, voff);
         asm volatile("s_waitcnt vmcnt(4)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) : : "memory");
         PG_RING_STEP(r0, r1, r2, r3);
         if (found || S + 1 >= stop) break;
         ++S;
-        voff += (S < last && !PG_EXP_SAMETILE) ? 4096u : 0u;
+        voff = PG_EXP_SAMETILE ? voff : (voff + 4096u < voffLast ? voff + 4096u : voffLast);
         PG_RING_LOAD("=&v", r0, r1, r2, r3, voff);
         asm volatile("s_waitcnt vmcnt(4)" : "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3) : : "memory");
         PG_RING_STEP(q0, q1, q2, q3);
@@ -698,36 +729,61 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
       asm volatile("s_waitcnt vmcnt(0)" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(q0), "+v"(q1), "+v"(q2), "+v"(q3) : : "memory");
       if (inQ) { r0 = q0; r1 = q1; r2 = q2; r3 = q3; }
 #undef PG_RING_STEP
+#undef PG_OR16F
 #undef PG_SB
       if (!found) {
         ++S;
         return 0;
       }
       PG_ST(1, 1);
-      // MFMAs with a candidate; the lane slots (column x 16-row half) that hold one
+      // The flagged chains' MFMAs again, from the ring, unscaled and from zero: the sign word of every MFMA (bit r =
+      // result register r holds a candidate).  From these: the MFMAs with a candidate, the lane slots (column x 16-row
+      // half) that hold one, and the tiles' sign words.  Which links of a chain are evaluated again: a negative field 0
+      // / 1 shows as bit 7 / 15 or - sum below zero - as bit 29; a negative field 2 always as bit 29.  (A superset: a
+      // borrow raises the flag of the field above, and bit 29 names all three.)
       int nslots = 0;
       u32 mask = 0;                                         // bit m = MFMA m (tile m / R, row block m % R)
-#define PG_FLAG(m, v) { const u64 mm = __builtin_amdgcn_ballot_w64((v) < 0); nslots += (int)__popcll(mm); mask |= mm ? (1u << (m)) : 0u; }
-      PG_FLAG(0, av0) PG_FLAG(1, av1) PG_FLAG(2, av2) PG_FLAG(3, av3)
-      if constexpr (R == 2) { PG_FLAG(4, av4) PG_FLAG(5, av5) PG_FLAG(6, av6) PG_FLAG(7, av7) }
-#undef PG_FLAG
+      auto flagged = [&](int av, u32 bits) -> bool { return __builtin_amdgcn_ballot_w64(((u32)av & bits) != 0u) != 0; };
+      auto mfma_signs = [&](int m, bool cand, const pg_v4i &a, const pg_v4i &x) -> u32 {
+        u32 sg = 0;
+        if (cand) {
+          sg = signs16(pg_mfma_fp4(a, x));
+          const u64 mm = __builtin_amdgcn_ballot_w64(sg != 0u);
+          nslots += (int)__popcll(mm);
+          mask |= mm ? (1u << m) : 0u;
+        }
+        return sg;
+      };
+      constexpr u32 F0 = 0x20000080u, F1 = 0x20008000u, F2 = 0x20000000u;
+      static_assert((F0 | F1 | F2) == PG_CHAIN_FLAGS, "the flags of the three fields");
+      u32 sw0, sw1, sw2, sw3;                               // (am[] / amMask change only with `return 1`)
+      if constexpr (!kChain) {                               // one MFMA per OR: the sign bit of av[t] names tile t exactly
+        static_assert(kChain || R == 1, "the single-MFMA step exists for one row block only");
+        sw0 = mfma_signs(0, flagged(av0, 0x80000000u), A0, r0);
+        sw1 = mfma_signs(1, flagged(av1, 0x80000000u), A0, r1);
+        sw2 = mfma_signs(2, flagged(av2, 0x80000000u), A0, r2);
+        sw3 = mfma_signs(3, flagged(av3, 0x80000000u), A0, r3);
+      } else if constexpr (R == 1) {
+        sw0 = mfma_signs(0, flagged(av0, F0), A0, r0);
+        sw1 = mfma_signs(1, flagged(av0, F1), A0, r1);
+        sw2 = mfma_signs(2, flagged(av0, F2), A0, r2);
+        sw3 = mfma_signs(3, flagged(av1, F0), A0, r3);
+      } else {
+        sw0 = mfma_signs(0, flagged(av0, F0), A0, r0);
+        sw0 |= mfma_signs(1, flagged(av1, F0), A1, r0) << 16;
+        sw1 = mfma_signs(2, flagged(av0, F1), A0, r1);
+        sw1 |= mfma_signs(3, flagged(av1, F1), A1, r1) << 16;
+        sw2 = mfma_signs(4, flagged(av0, F2), A0, r2);
+        sw2 |= mfma_signs(5, flagged(av1, F2), A1, r2) << 16;
+        sw3 = mfma_signs(6, flagged(av2, F0), A0, r3);
+        sw3 |= mfma_signs(7, flagged(av2, F1), A1, r3) << 16;
+      }
 #ifdef PG_MM_KNOBS
       if (nslots >= R * K().mmDenseL1) return 2;            // (tuning builds: PG_MM_L1 at run time)
 #else
       if (nslots >= R * PG_MM_DENSE_L1) return 2;
 #endif
-      // the flagged MFMAs again, from the ring: the sign word of every tile
-      auto tile_signs = [&](int t, const pg_v4i &x) -> u32 {
-        u32 a = 0;
-        if constexpr (R == 1) {
-          if ((mask >> t) & 1u) a = signs16(pg_mfma_fp4(A0, x));
-        } else {
-          if ((mask >> (2 * t + 1)) & 1u) a = signs16(pg_mfma_fp4(A1, x)) << 16;
-          if ((mask >> (2 * t)) & 1u) a |= signs16(pg_mfma_fp4(A0, x));
-        }
-        return a;
-      };
-      am0 = tile_signs(0, r0); am1 = tile_signs(1, r1); am2 = tile_signs(2, r2); am3 = tile_signs(3, r3);
+      am0 = sw0; am1 = sw1; am2 = sw2; am3 = sw3;
       if constexpr (R == 1) amMask = mask;
       else amMask = ((mask & 3u) ? 1u : 0u) | ((mask & 12u) ? 2u : 0u) | ((mask & 48u) ? 4u : 0u) | ((mask & 192u) ? 8u : 0u);
       return 1;
