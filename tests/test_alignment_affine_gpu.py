@@ -46,9 +46,11 @@ def dense(nat, C, gap, gap_open, X, Y, **kw):
 @pytest.mark.parametrize("a", [21, 32])
 def test_kernel_against_the_definition(nat, a, gap, gap_open):
     """Row r of either operand has length LENS[r % 8], so any window of 8 rows holds every length and every pair of
-    lengths meets: all eight instantiations of the row routine, every chunk edge.  The definition is evaluated once on
-    77 x 607 pairs and every (rows, columns) shape - partial row groups, partial column tiles, more than one tile - is a
-    window of it, from every offset 0..7."""
+    lengths meets: the empty row and instances 1, 2, 3 and 8 of the row routine (NC = ceil(len y / 16)), positions 1, 15
+    and 16 of a chunk.  Instances 4 to 7 and the other positions of the result select are run by
+    tests/test_alignment_lengths_gpu.py, on a row of every length 0..128.  The definition is evaluated once on 77 x 607
+    pairs and every (rows, columns) shape - partial row groups, partial column tiles, more than one tile - is a window
+    of it, from every offset 0..7."""
     rng = np.random.default_rng(1000 * a + 10 * gap + gap_open)
     C = table(rng, a, np.arange(256))
     C[1, a - 1] = C[a - 1, 1] = 255
