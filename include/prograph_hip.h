@@ -541,6 +541,11 @@ int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t 
  *                      touches no operand memory and gets status 1, n_ops -1, zeros elsewhere.  workspace: at least one
  *                      wave's share (PG_E_BADARG below it); the call launches min(ceil(npairs / 64), workspace_bytes /
  *                      share) waves, which stride over the list.  Every argument check returns before any launch.
+ *   pg_alignment_trace_long_workspace, pg_alignment_trace_long (pg_aln_trace_long.hip)  the same canonical alignment,
+ *                      arguments, outputs and checks for widths xl, yl of 1..2048 (PG_E_TOOLONG beyond; narrow operands
+ *                      are accepted), the row of the tables cut into strips of 128 columns.  Cells are int32, so every
+ *                      table and penalty of the three modes is exact: there is no "fits" condition.  *bytes_per_wave =
+ *                      64 * xl * ceil(yl / 8) * 4 (direction bits) + 64 * xl * 8 (one boundary column between strips).
  */
 #define PG_ALN_TRACE_GLOBAL 0
 #define PG_ALN_TRACE_LOCAL 1
@@ -550,6 +555,11 @@ int pg_alignment_trace(int mode, const void *x_packed, int64_t n, int64_t x_npad
                        int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap,
                        int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes,
                        void *stream);
+int pg_alignment_trace_long_workspace(int xl, int yl, int64_t *bytes_per_wave);
+int pg_alignment_trace_long(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                            int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table,
+                            int gap, int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace,
+                            int64_t workspace_bytes, void *stream);
 
 /*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the

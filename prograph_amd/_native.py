@@ -28,7 +28,8 @@ ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, t
 ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-open penalty
 ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entries of a score table
 ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / ..._local_long_dense / ..._semiglobal_long_dense: positions per operand
-ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_alignment_trace: the modes
+ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_alignment_trace / pg_alignment_trace_long: the modes
+ALN_TRACE_LONG_WORKSPACE = 2 << 30  # alignment_trace_long: the most workspace it takes unasked
 ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits / aln_semiglobal_long_fits)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
@@ -42,7 +43,7 @@ SYMBOLS = [
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
     "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
     "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
-    "pg_alignment_trace_workspace", "pg_alignment_trace",
+    "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
@@ -152,6 +153,8 @@ def _load():
         lib.pg_alignment_trace_workspace.argtypes = [_i32, _i32, ctypes.POINTER(_i64)]
         lib.pg_alignment_trace.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _i32,
                                            _vp, _vp, _i64, _vp, _i64, _vp]
+        lib.pg_alignment_trace_long_workspace.argtypes = lib.pg_alignment_trace_workspace.argtypes
+        lib.pg_alignment_trace_long.argtypes = lib.pg_alignment_trace.argtypes
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
@@ -1036,6 +1039,31 @@ def _trace_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops,
                                     ldo, _ptr(ws), ws.numel(), _stream()), "pg_alignment_trace")
 
 
+def _trace_list(name, wave_bytes, launch, xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes):
+    """`alignment_trace` / `alignment_trace_long`: the index check, the workspace, the split into launches."""
+    dev = xo.buf.device
+    xi = torch.as_tensor(xi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    yi = torch.as_tensor(yi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if xi.numel() != yi.numel() or xi.numel() == 0:
+        raise ValueError(f"{name}: xi and yi must be two non-empty lists of one length")
+    lo_hi = torch.stack([xi.min(), xi.max(), yi.min(), yi.max()]).tolist()                # the one host sync
+    if lo_hi[0] < 0 or lo_hi[1] >= xo.n or lo_hi[2] < 0 or lo_hi[3] >= yo.n:
+        raise IndexError(f"{name}: a pair's row number is outside its operand")
+    one = wave_bytes(xo.l, yo.l)
+    p, ldo = xi.numel(), xo.l + yo.l
+    if workspace_bytes is None:                                             # what the list needs; a share is 129 MiB at most
+        workspace_bytes = min(((p + 63) // 64) * one, ALN_TRACE_LONG_WORKSPACE)
+    if int(workspace_bytes) < one:
+        raise ValueError(f"{name}: workspace_bytes must hold one wave's share ({one} bytes)")
+    waves = min(int(workspace_bytes) // one, (p + 63) // 64)
+    ws = torch.empty(waves * one, dtype=torch.uint8, device=dev)
+    head = torch.empty((p, 8), dtype=torch.int32, device=dev)
+    ops = torch.empty((p, ldo), dtype=torch.uint8, device=dev)
+    for p0 in range(0, p, waves * 64):
+        launch(xo, yo, xi, yi, p0, min(p, p0 + waves * 64), mode, table, gap, gap_open, head, ops, ws)
+    return head, ops
+
+
 def alignment_trace(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes=256 << 20):
     """The canonical alignments (pg_alignment_trace) of the pairs (row xi[p] of AlnOperand `xo`, row yi[p]
     of `yo`), P >= 1 of them, repeats allowed: `mode` ALN_TRACE_GLOBAL (`table` from sub_cost), ALN_TRACE_LOCAL or
@@ -1044,25 +1072,44 @@ def alignment_trace(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes=
     unaligned, 0 from n_ops on) on the device.  The index ranges are checked on the host - ONE SYNC - and an index outside
     its operand raises IndexError.  The list is split into launches whose waves all fit `workspace_bytes` of direction
     bits (at least one wave's share, ValueError below it); the workspace is allocated here, once."""
-    dev = xo.buf.device
-    xi = torch.as_tensor(xi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    yi = torch.as_tensor(yi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    if xi.numel() != yi.numel() or xi.numel() == 0:
-        raise ValueError("alignment_trace: xi and yi must be two non-empty lists of one length")
-    lo_hi = torch.stack([xi.min(), xi.max(), yi.min(), yi.max()]).tolist()                # the one host sync
-    if lo_hi[0] < 0 or lo_hi[1] >= xo.n or lo_hi[2] < 0 or lo_hi[3] >= yo.n:
-        raise IndexError("alignment_trace: a pair's row number is outside its operand")
-    one = aln_trace_wave_bytes(xo.l, yo.l)
-    if int(workspace_bytes) < one:
-        raise ValueError(f"alignment_trace: workspace_bytes must hold one wave's share ({one} bytes)")
-    p, ldo = xi.numel(), xo.l + yo.l
-    waves = min(int(workspace_bytes) // one, (p + 63) // 64)
-    ws = torch.empty(waves * one, dtype=torch.uint8, device=dev)
-    head = torch.empty((p, 8), dtype=torch.int32, device=dev)
-    ops = torch.empty((p, ldo), dtype=torch.uint8, device=dev)
-    for p0 in range(0, p, waves * 64):
-        _trace_launch(xo, yo, xi, yi, p0, min(p, p0 + waves * 64), mode, table, gap, gap_open, head, ops, ws)
-    return head, ops
+    return _trace_list("alignment_trace", aln_trace_wave_bytes, _trace_launch, xo, yo, xi, yi, mode, table, gap,
+                       gap_open, workspace_bytes)
+
+
+def aln_trace_long_ready():
+    """Can `alignment_trace_long` run?  True only with a HIP device.  The routes of alignments.py and `Prograph.align` ask
+    this, not `aln_long_ready`, before they leave `host_trace` for operands beyond 128 positions."""
+    try:
+        return device().type == "cuda"
+    except NativeUnavailable:
+        return False
+
+
+def aln_trace_long_wave_bytes(xl, yl):
+    """One wave's share of pg_alignment_trace_long's workspace (pg_alignment_trace_long_workspace): the direction bits of
+    its 64 pairs and their boundary column between strips."""
+    one = _i64(0)
+    _check(lib().pg_alignment_trace_long_workspace(int(xl), int(yl), ctypes.byref(one)), "pg_alignment_trace_long_workspace")
+    return one.value
+
+
+def _trace_long_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws):
+    """One pg_alignment_trace_long call: pairs p0..p1-1 of the lists into rows p0..p1-1 of head and ops."""
+    ldo = ops.stride(0)
+    _check(lib().pg_alignment_trace_long(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
+                                         ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
+                                         p1 - p0, _ptr(table), int(gap), int(gap_open),
+                                         ctypes.c_void_p(head.data_ptr() + 32 * p0), ctypes.c_void_p(ops.data_ptr() + ldo * p0),
+                                         ldo, _ptr(ws), ws.numel(), _stream()), "pg_alignment_trace_long")
+
+
+def alignment_trace_long(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes=None):
+    """`alignment_trace` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_trace_long; `xo`,
+    `yo` from aln_long_operand): the same lists, index check (ONE SYNC), errors and (head, ops).  Cells are int32: every
+    table and penalty is exact, there is no "fits" condition.  `workspace_bytes` None: what the list needs, at most
+    ALN_TRACE_LONG_WORKSPACE (2 GiB: about 400 waves in flight at 400 positions) and at least one wave's share."""
+    return _trace_list("alignment_trace_long", aln_trace_long_wave_bytes, _trace_long_launch, xo, yo, xi, yi,
+                       mode, table, gap, gap_open, workspace_bytes)
 
 
 def i32_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):

@@ -26,10 +26,12 @@ n_ops) and `identities`, the pairs with x_i = y_j.  Sequences are the operators'
 interior zero is symbol 0, padding is never aligned.
 
 Routes (`trace`).  Device byte tokens of at most 128 positions: the HIP kernel `pg_alignment_trace`
-(prograph_amd/csrc/pg_aln_trace.hip).  Everything else - CPU tensors, widths up to 2048 and beyond - `host_trace` below:
-one pair at a time, the three tables row by row in numpy (F by the running maximum over A, as the operators' torch
-expressions have it), then the walk over the stored tables.  It is SLOW (milliseconds per pair at 128 positions, and the
-tables of one pair take 24 bytes per cell); it is exact.
+(prograph_amd/csrc/pg_aln_trace.hip).  Wider device tokens, up to 2048 positions: `pg_alignment_trace_long`
+(pg_aln_trace_long.hip), the same tables in strips of 128 columns, the same alignment field for field.
+Everything else - CPU tensors, widths beyond 2048, no device - `host_trace` below: one pair at a time, the three tables
+row by row in numpy (F by the running maximum over A, as the operators' torch expressions have it), then the walk over
+the stored tables.  It is SLOW (milliseconds per pair at 128 positions, and the tables of one pair take 24 bytes per
+cell); it is exact.
 """
 import numpy as np
 import torch
@@ -201,15 +203,17 @@ def _device_table(op, mode):
 
 
 def from_head(head, ops, **kept):
-    """Alignments from pg_alignment_trace's (P, 8) head and ops."""
+    """Alignments from the (P, 8) head and the ops of pg_alignment_trace / pg_alignment_trace_long."""
     h = head.to(torch.int64)
     return Alignments(*(h[:, c].contiguous() for c in range(7)), ops, **kept)
 
 
-def trace(op, X, Y, xi=None, yi=None, workspace_bytes=256 << 20, letters=None, native=None):
+def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native=None, native_long=None):
     """The alignments of the pairs (X[xi[p]], Y[yi[p]]) under operator `op`; X, Y uint8 token tensors on one device,
-    xi, yi integer lists (None: every row in order, X and Y of one height).  The kernel for device tokens of at most 128
-    positions (`native` overrides that choice), `host_trace` otherwise; the result lives on X's device."""
+    xi, yi integer lists (None: every row in order, X and Y of one height).  The 128-position kernel for device tokens of
+    at most 128 positions (`native` overrides that choice), the strip kernel for wider ones up to 2048 positions where
+    `_native.aln_trace_long_ready()` (`native_long` overrides that one), `host_trace` otherwise; the result lives on X's
+    device.  `workspace_bytes` None: 256 MiB for the first kernel, what the list needs up to 2 GiB for the second."""
     mode = _mode_of(op)
     name = type(op).__name__
     dev = X.device
@@ -227,11 +231,16 @@ def trace(op, X, Y, xi=None, yi=None, workspace_bytes=256 << 20, letters=None, n
                           X, Y, xi, yi, letters)
     if native is None:
         native = X.is_cuda and 1 <= width <= _native.ALN_MAX_L
-    if native:
-        xo = _native.aln_operand(X, op.symbols)
-        yo = xo if Y is X else _native.aln_operand(Y, op.symbols)
-        head, ops = _native.alignment_trace(xo, yo, xi, yi, mode, _device_table(op, mode), op.gap, op.gap_open,
-                                            workspace_bytes=workspace_bytes)
+    if native_long is None:
+        native_long = (not native and X.is_cuda and _native.ALN_MAX_L < width <= _native.ALN_LONG_MAX_L
+                       and _native.aln_trace_long_ready())
+    if native or native_long:
+        operand, tracer = ((_native.aln_operand, _native.alignment_trace) if native else
+                           (_native.aln_long_operand, _native.alignment_trace_long))
+        xo = operand(X, op.symbols)
+        yo = xo if Y is X else operand(Y, op.symbols)
+        head, ops = tracer(xo, yo, xi, yi, mode, _device_table(op, mode), op.gap, op.gap_open,
+                           workspace_bytes=256 << 20 if native and workspace_bytes is None else workspace_bytes)
         if int((xo.flags | yo.flags).item()):
             raise ValueError(f"{name}: a token is outside the table (0..{op.symbols - 1})")
         return from_head(head, ops, x=X, y=Y, xi=xi, yi=yi, letters=letters)

@@ -9,6 +9,10 @@
 //     H[i][j] = max(H[i-1][j-1] + T[x_i][y_j], E[i][j], F[i][j])      (local: 0 where that is not positive),
 // borders H[i][0] = H[0][j] = 0 (global: H[0][0] = 0, else -(gap_open + k e)), E[0][j] = F[i][0] = PG_TR_NEG.  Cells are
 // int32: |H| <= 128 * 255 + 255, and PG_TR_NEG sinks by at most 128 * 255 more, so nothing overflows or meets a true value.
+// The long trace (pg_aln_trace_long.hip, DESIGN.md §4.21: up to PG_TR_LONG_MAX_L positions, the row cut into strips of
+// PG_TR_STRIP columns) keeps int32 cells too: |H| <= 2048 * 255 + 255, PG_TR_NEG = -2^28 sinks by at most 2048 * 255 more,
+// so nothing overflows there either and no table or penalty is excluded - the long trace has no "fits" predicate, unlike
+// the 16-bit scoring kernels.
 //
 // Direction nibble of cell (i, j), i, j >= 1: bits 0-1 where H comes from (0 local stop, 1 diagonal, 2 E, 3 F; the
 // diagonal wins a tie, then E), bit 2 "E[i][j] opened from H[i-1][j]", bit 3 "F[i][j] opened from H[i][j-1]" (open wins
@@ -27,6 +31,8 @@
 #define PG_TR_SEMIGLOBAL 2
 #define PG_TR_MAX_L 128
 #define PG_TR_NEG (-(1 << 28))
+#define PG_TR_STRIP 128                 // columns of one strip of the long trace: a multiple of 8, no dword in two strips
+#define PG_TR_LONG_MAX_L 2048
 
 // token at position p (from 0) of a sequence in pg_sub_pack's dword order: dword g at tok[g * stride], masked to 0..31
 PG_TR_FN int pg_tr_token(const uint32_t *tok, long long stride, int p) {
@@ -98,14 +104,88 @@ PG_TR_FN void pg_tr_row(int mode, int i, int lx, int ly, int e, int oe, const in
   }
 }
 
+// ---- the strip forms (pg_aln_trace_long.hip): the same row, PG_TR_STRIP columns at a time, strip s over all rows before
+// strip s + 1.  The candidates of the end cell then arrive in (strip, i, j) order, so the rule states its ties itself.
+
+// H[k][0] = H[0][k]
+PG_TR_FN int pg_tr_border(int mode, int k, int e, int oe) { return (mode == PG_TR_GLOBAL && k) ? -(oe - e) - k * e : 0; }
+
+// the end cell before any row (pg_tr_row0's)
+PG_TR_FN void pg_tr_end0(int mode, int lx, int ly, pg_tr_end *end) {
+  end->best = 0;
+  end->i = mode == PG_TR_GLOBAL ? lx : 0;
+  end->j = mode == PG_TR_GLOBAL ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;
+}
+
+// A candidate (i, j) of value H, whatever was visited before: a larger value replaces, and so does an equal one of a
+// smaller i.  Among equal i the earlier strip has the smaller j and stays: local ties go to the smallest i, then the
+// smallest j; semi-global cells (i, len y), i < len x, come before the cells (len x, j), as in the canonical order; the
+// initial (0, 0) / (0, len y) is never displaced by an equal value.
+PG_TR_FN void pg_tr_end_take(pg_tr_end *end, int H, int i, int j) {
+  if (H > end->best || (H == end->best && i < end->i)) {
+    end->best = H;
+    end->i = i;
+    end->j = j;
+  }
+}
+
+// row 0 of the strip of columns j0 + 1 .. min(j0 + PG_TR_STRIP, ly): cell j at [(j - j0 - 1) * cs]
+PG_TR_FN void pg_tr_strip_row0(int mode, int j0, int ly, int e, int oe, int *colH, int *colE, int cs) {
+  const int j1 = ly < j0 + PG_TR_STRIP ? ly : j0 + PG_TR_STRIP;
+  for (int j = j0 + 1; j <= j1; ++j) {
+    colH[(j - j0 - 1) * cs] = pg_tr_border(mode, j, e, oe);
+    colE[(j - j0 - 1) * cs] = PG_TR_NEG;
+  }
+}
+
+// Row i (1..lx) of that strip: colH / colE hold the strip's cells of row i - 1 on entry and of row i on return; ytok / ys
+// the STRIP's y tokens (column j at position j - j0 - 1).  left = H[i][j0], F = F[i][j0], diag = H[i-1][j0] come in (strip 0:
+// pg_tr_border(i), PG_TR_NEG, pg_tr_border(i - 1)); *right_h, *right_f = H, F of the strip's last column go out.  dir is
+// the row's dwords as in pg_tr_row: the nibble of cell j in dword (j - 1) >> 3, bits 4 * ((j - 1) & 7).
+PG_TR_FN void pg_tr_row_strip(int mode, int i, int lx, int ly, int j0, int e, int oe, const int *trow, const uint32_t *ytok,
+                              long long ys, int *colH, int *colE, int cs, uint32_t *dir, int ds, pg_tr_end *end, int left, int F,
+                              int diag, int *right_h, int *right_f) {
+  const int j1 = ly < j0 + PG_TR_STRIP ? ly : j0 + PG_TR_STRIP;
+  uint32_t bits = 0;
+  for (int j = j0 + 1; j <= j1; ++j) {
+    const int c = (j - j0 - 1) * cs;
+    const int hup = colH[c], eup = colE[c];
+    const int eopen = hup - oe, eext = eup - e, fopen = left - oe, fext = F - e;
+    const int E = eopen >= eext ? eopen : eext;
+    F = fopen >= fext ? fopen : fext;
+    const int D = diag + trow[pg_tr_token(ytok, ys, j - j0 - 1)];
+    int H = D >= E ? D : E;
+    if (F > H) H = F;
+    uint32_t nib = (H == D ? 1u : H == E ? 2u : 3u) | (eopen >= eext ? 4u : 0u) | (fopen >= fext ? 8u : 0u);
+    if (mode == PG_TR_LOCAL && H <= 0) {
+      H = 0;
+      nib &= ~3u;
+    }
+    if (mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly))) pg_tr_end_take(end, H, i, j);
+    diag = hup;
+    colH[c] = H;
+    colE[c] = E;
+    left = H;
+    bits |= nib << (4 * ((j - 1) & 7));
+    if ((j & 7) == 0 || j == ly) {
+      dir[((j - 1) >> 3) * ds] = bits;
+      bits = 0;
+    }
+  }
+  *right_h = left;
+  *right_f = F;
+}
+
 // The walk back from the end cell over the direction dwords (dir, nd dwords per row, stride ds), starting in state H.
 // Writes the codes (1 pair, 2 x symbol unaligned, 3 y symbol unaligned) in forward order to ops[0 .. n_ops), zeroes
 // ops[n_ops .. ldo), and fills head[1..6] = x_begin, x_end, y_begin, y_end, n_ops, identities.  ldo >= lx + ly.  Every
-// step moves towards (0, 0) and no cell outside 1..lx x 1..ly is read, whatever the dwords hold.
-PG_TR_FN void pg_tr_walk(int mode, int lx, int ly, int bi, int bj, const uint32_t *xtok, long long xs, const uint32_t *ytok,
-                         long long ys, const uint32_t *dir, int nd, int ds, unsigned char *ops, long long ldo, int32_t *head) {
+// step moves towards (0, 0) and no cell outside 1..lx x 1..ly is read, whatever the dwords hold.  At most min(ldo, cap)
+// codes are written: cap = 2 * PG_TR_MAX_L for the 128-position kernel (pg_tr_walk), 2 * PG_TR_LONG_MAX_L for the long one.
+PG_TR_FN void pg_tr_walk_room(int mode, int lx, int ly, int bi, int bj, const uint32_t *xtok, long long xs, const uint32_t *ytok,
+                              long long ys, const uint32_t *dir, int nd, int ds, unsigned char *ops, long long ldo, int cap,
+                              int32_t *head) {
   int i = bi, j = bj, n = 0, ident = 0, state = 0;
-  const int room = (int)(ldo < 2 * PG_TR_MAX_L ? ldo : 2 * PG_TR_MAX_L);
+  const int room = (int)(ldo < cap ? ldo : cap);
   while (n < room) {
     if (state == 0 && (i == 0 || j == 0)) {
       if (mode == PG_TR_GLOBAL) {                                           // the rest of the other sequence, unaligned
@@ -149,4 +229,10 @@ PG_TR_FN void pg_tr_walk(int mode, int lx, int ly, int bi, int bj, const uint32_
   head[4] = bj;
   head[5] = n;
   head[6] = ident;
+}
+
+// the walk of the 128-position kernel: at most 2 * PG_TR_MAX_L codes
+PG_TR_FN void pg_tr_walk(int mode, int lx, int ly, int bi, int bj, const uint32_t *xtok, long long xs, const uint32_t *ytok,
+                         long long ys, const uint32_t *dir, int nd, int ds, unsigned char *ops, long long ldo, int32_t *head) {
+  pg_tr_walk_room(mode, lx, ly, bi, bj, xtok, xs, ytok, ys, dir, nd, ds, ops, ldo, 2 * PG_TR_MAX_L, head);
 }

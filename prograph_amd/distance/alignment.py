@@ -222,5 +222,6 @@ class alignment:
         """The canonical optimal alignment of row p of X with row p of Y (P rows each, P may be 1) as an `Alignments`
         container on X's device: which symbols pair, which stay unaligned, and the identities (prograph_amd/alignments.py
         defines it).  `score` is this operator's distance.  Device byte tokens of at most 128 positions run on the HIP
-        kernel `pg_alignment_trace`; everything else on the exact, slow host expression."""
+        kernel `pg_alignment_trace`, wider ones up to 2048 positions on `pg_alignment_trace_long`; everything else on the
+        exact, slow host expression."""
         return _alignments.align(self, X, Y)

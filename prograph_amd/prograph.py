@@ -1017,7 +1017,7 @@ class Prograph:
         indptr, indices, wts = self._local_select(distance, T, None, rows, None, 0, eps, comp, False)
         return CSRGraph(indptr, indices, wts, n, similarity=False)
 
-    # ---- alignment tracebacks (prograph_amd/alignments.py, DESIGN.md 4.20)
+    # ---- alignment tracebacks (prograph_amd/alignments.py, DESIGN.md 4.20, 4.21)
     def _edge_lists(self, graph):
         """(rows, columns) int64 numpy of the edges of a CSRGraph, a KNNGraph, a stored graph's name or a list of
         (indices, weights) tuples, in the graph's order, `row0` added to the rows; kNN slots without a neighbour (-1) are
@@ -1041,7 +1041,7 @@ class Prograph:
         raise TypeError("align: graph must be a CSRGraph, a KNNGraph, the name of a stored graph or a list of (indices, weights) tuples")
 
     def align(self, graph=None, rows=None, cols=None, queries=None, idxs=None, distance=None, representation="Tokenized",
-              workspace_bytes=256 << 20):
+              workspace_bytes=None):
         """
         The canonical optimal alignments (`Alignments`, prograph_amd/alignments.py) of dataset pairs under
         `distance`, which must be an `alignment`, `local_alignment` or `semiglobal_alignment` instance (`TypeError`
@@ -1050,8 +1050,10 @@ class Prograph:
         per edge in the graph's order, x the edge's row (`row0` honoured) and y its column; with `idxs`, the row selection
         the graph was built over, both go through it.  `rows=` / `cols=`: explicit dataset pairs instead of a graph.
         `queries=` (what `search` was given): the graph is a `search` result, x is the query and y the dataset row.
-        At most 128 positions run on the HIP kernel (`pg_alignment_trace`: one host sync for the index check, launches
-        split so that their direction bits fit `workspace_bytes`); beyond that the exact, slow host expression.
+        At most 128 positions run on the HIP kernel `pg_alignment_trace`, wider data and queries up to 2048 positions on
+        `pg_alignment_trace_long` (either: one host sync for the index check, launches split so that their waves' shares
+        fit `workspace_bytes`; None: 256 MiB for the first, what the edges need up to 2 GiB for the second); beyond 2048
+        positions, or without a device, the exact, slow host expression.
         """
         mode = _alignments._mode_of(distance)                               # TypeError for anything else
         X = self._local_tokens(self._dataset_matrix(representation), distance)
@@ -1088,9 +1090,11 @@ class Prograph:
         dev = _native.device() if _native.aln_long_ready() else torch.device("cpu")
         Xt = torch.from_numpy(np.ascontiguousarray(X)).to(dev)
         Qt = Xt if Q is X else torch.from_numpy(np.ascontiguousarray(Q)).to(dev)
-        native = _native.aln_long_ready() and max(X.shape[1], Q.shape[1]) <= _native.ALN_MAX_L
+        width = max(X.shape[1], Q.shape[1])
+        native = _native.aln_long_ready() and width <= _native.ALN_MAX_L
+        native_long = _native.aln_trace_long_ready() and _native.ALN_MAX_L < width <= _native.ALN_LONG_MAX_L
         return _alignments.trace(distance, Qt, Xt, torch.from_numpy(r), torch.from_numpy(c), workspace_bytes=workspace_bytes,
-                                 letters=letters, native=native)
+                                 letters=letters, native=native, native_long=native_long)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):

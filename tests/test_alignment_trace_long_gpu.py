@@ -1,0 +1,262 @@
+"""
+The strip traceback kernel (`pg_alignment_trace_long`, prograph_amd/csrc/pg_aln_trace_long.hip) on the GPU:
+every field of every pair against `definition` of tests/trace_testdata.py, exactly - lengths mixed within a wave around the
+strip boundaries 128 and 256, so that lanes differ in their number of strips - the cross-strip tie by hand, the full width
+against the host expression, the 128-position kernel bit for bit, and the scores of a graph's edges against its weights.
+One list of 80 pairs per (mode, gap, gap_open, widths) serves every list length: the reference is computed once.
+"""
+import functools
+
+import numpy as np
+import pandas as pd
+import pytest
+import torch
+
+from trace_testdata import FIELDS, GLOBAL, LOCAL, SEMIGLOBAL, definition, rescore
+from prograph_amd import _native, alignments, synth
+from prograph_amd.distance import alignment, local_alignment, semiglobal_alignment
+
+pytestmark = [pytest.mark.gpu, pytest.mark.one_engine]
+
+LENS = (0, 1, 127, 128, 129, 130, 135, 136, 137, 255, 256, 257, 300)      # around the strips and their 8-cell dwords
+A, ROWS, PAIRS = 6, 40, 80
+CLASSES = {GLOBAL: alignment, LOCAL: local_alignment, SEMIGLOBAL: semiglobal_alignment}
+
+
+def table(mode):
+    """Six symbols and small entries: ties abound."""
+    rng = np.random.default_rng(11 + mode)
+    if mode == GLOBAL:
+        T = rng.integers(1, 4, (A, A))
+        T = np.triu(T, 1) + np.triu(T, 1).T
+    else:
+        T = rng.integers(-3, 2, (A, A))
+        T = np.triu(T) + np.triu(T, 1).T
+        T[np.arange(A), np.arange(A)] = rng.integers(1, 5, A)
+        T[0, 1] = T[1, 0] = 2                                               # S[a][0] > 0: padding must not pair
+    return T
+
+
+def operand(rng, width):
+    """(ROWS, width) tokens: the lengths of LENS that fit and the width itself, mixed row by row (so within every wave:
+    short rows sit in wide operands, lanes differ in their strips), zeros inside."""
+    lens = sorted({l for l in LENS if l <= width} | {width})
+    M = np.zeros((ROWS, width), dtype=np.uint8)
+    for r in range(ROWS):
+        l = lens[r % len(lens)] if r < 2 * len(lens) else int(rng.choice(lens))
+        M[r, :l] = rng.integers(0, A, l)
+        if l:
+            M[r, l - 1] = rng.integers(1, A)
+    return M[rng.permutation(ROWS)]
+
+
+@functools.lru_cache(maxsize=None)
+def problem(mode, gap, gap_open, xw, yw):
+    """Two operands, a random pair list over their rows (80 pairs over 40 rows: rows and whole pairs repeat), and the
+    definition's answer for every pair."""
+    rng = np.random.default_rng(1000 * mode + 10 * gap + gap_open + xw)
+    X, Y = operand(rng, xw), operand(rng, yw)
+    xi, yi = rng.integers(0, ROWS, PAIRS), rng.integers(0, ROWS, PAIRS)
+    xi[1], yi[1] = xi[0], yi[0]                                             # the same pair twice, the same row in two pairs
+    xi[2] = xi[0]
+    T = table(mode)
+    want = [definition(mode, T, gap, gap_open, X[xi[p]], Y[yi[p]]) for p in range(PAIRS)]
+    return X, Y, xi, yi, T, want
+
+
+def device_table(mode, T):
+    return _native.sub_cost(T) if mode == GLOBAL else _native.aln_local_score(T)
+
+
+def operands(X, Y):
+    return _native.aln_long_operand(torch.from_numpy(X), A), _native.aln_long_operand(torch.from_numpy(Y), A)
+
+
+def check(head, ops, want, xw, yw):
+    head, ops = head.cpu().numpy(), ops.cpu().numpy()
+    assert head.shape == (len(want), 8) and ops.shape == (len(want), xw + yw) and ops.dtype == np.uint8
+    for p, w in enumerate(want):
+        assert head[p].tolist() == [w[f] for f in FIELDS] + [0], (p, head[p], w)
+        assert ops[p, :w["n_ops"]].tolist() == w["ops"] and not ops[p, w["n_ops"]:].any(), (p, ops[p], w["ops"])
+
+
+@pytest.mark.parametrize("pairs", [1, 64, 65, 80])
+@pytest.mark.parametrize("gap_open", [0, 11])
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+@pytest.mark.parametrize("xw,yw", [(129, 129), (300, 300), (300, 20), (20, 300)])
+def test_every_field_is_the_definition(xw, yw, mode, gap_open, pairs):
+    X, Y, xi, yi, T, want = problem(mode, 2, gap_open, xw, yw)
+    xo, yo = operands(X, Y)
+    head, ops = _native.alignment_trace_long(xo, yo, xi[:pairs], yi[:pairs], mode, device_table(mode, T), 2, gap_open)
+    assert xo.valid() and yo.valid()
+    check(head, ops, want[:pairs], xw, yw)
+
+
+@pytest.mark.parametrize("swap", [False, True])
+@pytest.mark.parametrize("gap_open", [0, 11])
+@pytest.mark.parametrize("mode", [LOCAL, SEMIGLOBAL])
+def test_the_cross_strip_tie(mode, gap_open, swap):
+    """M pairs with M at the cells up to (36, 8), N with N up to (8, 166), 16 either way (the filler 5 matches nothing, itself
+    included).  A strip sweep meets (36, 8) first, in strip 0; the canonical end cell is the one of the smaller i, in strip 1."""
+    S = np.full((A, A), -3)
+    S[np.arange(5), np.arange(5)] = 2
+    M, N = [1, 2] * 4, [3, 4] * 4
+    x, y = N + [5] * 20 + M, M + [5] * 150 + N
+    want = definition(mode, S, 1, gap_open, x, y)
+    assert [want[f] for f in FIELDS[:5]] == [16, 0, 8, 158, 166] and want["ops"] == [1] * 8
+    if swap:
+        x, y = y, x
+        want = definition(mode, S, 1, gap_open, x, y)
+        assert [want[f] for f in FIELDS[:5]] == [16, 0, 8, 28, 36]
+    xo, yo = operands(np.array([x], dtype=np.uint8), np.array([y], dtype=np.uint8))
+    head, ops = _native.alignment_trace_long(xo, yo, [0], [0], mode, device_table(mode, S), 1, gap_open)
+    check(head, ops, [want], len(x), len(y))
+
+
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+def test_the_largest_penalties(mode):
+    X, Y, xi, yi, T, want = problem(mode, 255, 255, 257, 257)
+    xo, yo = operands(X, Y)
+    head, ops = _native.alignment_trace_long(xo, yo, xi[:65], yi[:65], mode, device_table(mode, T), 255, 255)
+    check(head, ops, want[:65], 257, 257)
+
+
+@functools.lru_cache(maxsize=None)
+def full_width():
+    """Three rows of 2048, 2047 and 1920 tokens over a 2048-position operand, twice."""
+    rng = np.random.default_rng(77)
+    X, Y = np.zeros((3, 2048), dtype=np.uint8), np.zeros((3, 2048), dtype=np.uint8)
+    for r, l in enumerate((2048, 2047, 1920)):
+        X[r, :l], Y[r, :l] = rng.integers(1, A, l), rng.integers(1, A, l)
+        Y[r, :l:3] = X[r, :l:3]                                            # related sequences: long diagonals, real gaps
+    return X, Y
+
+
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+def test_the_full_width(mode):
+    """2048 x 2048: 16 strips of 2048 rows, one wave's share (129 MiB) the whole workspace.  `definition` would need
+    minutes here: the yardstick is the host expression, which tests/test_alignment_trace_cpu.py pins to it, and the ops
+    priced again from the table."""
+    X, Y = full_width()
+    T, gap, gap_open = table(mode), 2, 3
+    xi, yi = [0, 1, 2], [1, 2, 0]                                          # 2048 x 2047, 2047 x 1920, 1920 x 2048
+    xo, yo = operands(X, Y)
+    one = _native.aln_trace_long_wave_bytes(2048, 2048)
+    assert one == (128 << 20) + (1 << 20)
+    head, ops = _native.alignment_trace_long(xo, yo, xi, yi, mode, device_table(mode, T), gap, gap_open, workspace_bytes=one)
+    head, ops = head.cpu().numpy(), ops.cpu().numpy()
+    *fields, hops = alignments.host_trace(mode, T, gap, gap_open, X, Y, xi, yi)
+    assert np.array_equal(head[:, :7], np.stack(fields, 1)) and not head[:, 7].any() and np.array_equal(ops, hops)
+    for p in range(3):
+        value, i, j = rescore(mode, T, gap, gap_open, X[xi[p]], Y[yi[p]], head[p, 1], head[p, 3], ops[p, :head[p, 5]])
+        assert (value, i, j) == (head[p, 0], head[p, 2], head[p, 4]), p
+
+
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+def test_a_small_workspace_changes_nothing(mode):
+    """80 pairs are two waves: one wave's share of workspace makes two launches."""
+    X, Y, xi, yi, T, want = problem(mode, 2, 11, 300, 300)
+    xo, yo = operands(X, Y)
+    one = _native.aln_trace_long_wave_bytes(300, 300)
+    assert one == 64 * 300 * 38 * 4 + 64 * 300 * 8
+    whole = _native.alignment_trace_long(xo, yo, xi, yi, mode, device_table(mode, T), 2, 11)
+    check(*whole, want, 300, 300)
+    for ws in (one, 2 * one + 17):
+        part = _native.alignment_trace_long(xo, yo, xi, yi, mode, device_table(mode, T), 2, 11, workspace_bytes=ws)
+        assert torch.equal(part[0], whole[0]) and torch.equal(part[1], whole[1])
+    with pytest.raises(ValueError):
+        _native.alignment_trace_long(xo, yo, xi, yi, mode, device_table(mode, T), 2, 11, workspace_bytes=one - 1)
+    with pytest.raises(IndexError):
+        _native.alignment_trace_long(xo, yo, [0, ROWS], [0, 0], mode, device_table(mode, T), 2, 11)
+
+
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+def test_one_strip_is_the_short_kernel(mode):
+    """Widths (128, 128): the long entry accepts them, runs one strip, and equals `pg_alignment_trace` bit for bit."""
+    rng = np.random.default_rng(31 + mode)
+    X, Y = np.zeros((48, 128), dtype=np.uint8), np.zeros((48, 128), dtype=np.uint8)
+    for M in (X, Y):
+        for r in range(48):
+            l = int(rng.choice((0, 1, 7, 8, 9, 63, 64, 65, 127, 128)))
+            M[r, :l] = rng.integers(0, A, l)
+            if l:
+                M[r, l - 1] = rng.integers(1, A)
+    xi, yi = rng.integers(0, 48, 200), rng.integers(0, 48, 200)
+    T = device_table(mode, table(mode))
+    so, to = _native.aln_operand(torch.from_numpy(X), A), _native.aln_operand(torch.from_numpy(Y), A)
+    short = _native.alignment_trace(so, to, xi, yi, mode, T, 2, 11)
+    long = _native.alignment_trace_long(*operands(X, Y), xi, yi, mode, T, 2, 11)
+    assert torch.equal(short[0], long[0]) and torch.equal(short[1], long[1]) and int(short[0][:, 5].max()) > 100
+
+
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])
+def test_operator_align_on_device_tokens(mode):
+    """`op.align` on CUDA tokens 200 wide: the long route, CUDA fields equal to the definition."""
+    rng = np.random.default_rng(41 + mode)
+    X, Y = np.zeros((24, 200), dtype=np.uint8), np.zeros((24, 200), dtype=np.uint8)
+    for r in range(24):
+        lx, ly = (200, 200) if r == 0 else rng.integers(100, 201, 2)
+        X[r, :lx], Y[r, :ly] = rng.integers(1, A, lx), rng.integers(1, A, ly)
+    T = table(mode)
+    op = CLASSES[mode](T, 2, gap_open=11)
+    got = op.align(torch.from_numpy(X.astype(np.int64)).cuda(), torch.from_numpy(Y).cuda())
+    assert isinstance(got, alignments.Alignments) and len(got) == 24 and got.score.is_cuda and got.ops.is_cuda
+    assert got.ops.shape == (24, 400)
+    want = [definition(mode, T, 2, 11, X[p], Y[p]) for p in range(24)]
+    for f in FIELDS:
+        assert getattr(got, f).dtype == torch.int64
+        assert getattr(got, f).cpu().tolist() == [w[f] for w in want], f
+    ops = got.ops.cpu().numpy()
+    for p, w in enumerate(want):
+        assert ops[p, :w["n_ops"]].tolist() == w["ops"] and not ops[p, w["n_ops"]:].any(), p
+    full = op(torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda())
+    assert torch.equal(torch.diagonal(full), got.score)
+    with pytest.raises(ValueError, match="outside the table"):
+        op.align(torch.full((2, 150), A, dtype=torch.uint8).cuda(), torch.ones((2, 150), dtype=torch.uint8).cuda())
+
+
+@pytest.fixture(scope="module")
+def pg(tmp_path_factory):
+    from prograph_amd import Prograph
+    tok, lens = synth.clustered_varlen_tokens(120, Lmax=220, Lmin=100, seed=9, members=10)
+    tok = tok[:, :int(lens.max())]                                         # the dataset is as wide as its longest row
+    f =tmp_path_factory.mktemp("trace_long") / "trace_long.csv"
+    pd.DataFrame({"Sequence": synth.tokens_to_strings(tok),
+                  "Fitness": np.random.default_rng(0).uniform(0, 1, len(tok))}).to_csv(f)
+    P = Prograph(file=str(f))
+    assert np.array_equal(P.tokenized, tok) and tok.shape[1] > 128
+    return P, tok
+
+
+def _operators():
+    rng = np.random.default_rng(5)
+    S = rng.integers(-4, 2, (21, 21))
+    S = np.triu(S) + np.triu(S, 1).T
+    S[np.arange(21), np.arange(21)] = rng.integers(2, 6, 21)
+    C = rng.integers(1, 5, (21, 21))
+    C = np.triu(C, 1) + np.triu(C, 1).T
+    return ((alignment(C, 2, gap_open=3), GLOBAL, C, 2, 3), (local_alignment(S, 1, gap_open=4), LOCAL, S, 1, 4),
+            (semiglobal_alignment(S, 2), SEMIGLOBAL, S, 2, 0))
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_edge_scores_are_the_graph_weights(pg, which):
+    P, tok = pg
+    op, mode, T, gap, gap_open = _operators()[which]
+    G = P.build_graph(k=3, distance=op, output="csr")
+    got = P.align(G, distance=op)
+    assert len(got) == 360 and got.score.is_cuda and torch.equal(got.score, G.dist.reshape(-1).to(torch.int64))
+    idx = G.idx.cpu().numpy().reshape(-1)
+    for p in (0, 359):
+        w = definition(mode, T, gap, gap_open, tok[p // 3], tok[idx[p]])
+        assert [int(getattr(got, f)[p]) for f in FIELDS] == [w[f] for f in FIELDS]
+        assert got.ops[p, :w["n_ops"]].tolist() == w["ops"]
+    # a search result: x is the query, y the dataset row
+    Q = tok[[4, 77, 119]].copy()
+    Q[1, 3:6] = 0
+    R = P.search(Q, k=4, distance=op, output="csr")
+    got = P.align(R, queries=Q, distance=op)
+    assert len(got) == 12 and torch.equal(got.score, R.dist.reshape(-1).to(torch.int64))
+    ridx = R.idx.cpu().numpy().reshape(-1)
+    w = definition(mode, T, gap, gap_open, Q[1], tok[ridx[5]])
+    assert [int(getattr(got, f)[5]) for f in FIELDS] == [w[f] for f in FIELDS] and got.ops[5, :w["n_ops"]].tolist() == w["ops"]
