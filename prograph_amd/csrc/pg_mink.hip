@@ -18,6 +18,17 @@
 // This is why the ||x||^2 + ||y||^2 - 2 x.y form on the matrix cores is NOT used: it is ~10x cheaper at
 // large D but does not round like the reference.
 //
+// What pins the values beyond those three data sets is an INTERVAL MODEL (tests/minkowski_model.py,
+// tests/test_minkowski_values_gpu.py): difference and square are single correctly rounded fp16 operations, so the
+// exact sum S of the squares is an integer multiple of 2^-24; any sequence of fp32 additions of these D
+// non-negative terms lands within g*S of it, g = D*2^-24 / (1 - D*2^-24), and exactly on it when S = 0 or
+// S < 2^24 * (lowest set bit of the terms) - every partial sum of every order is then an fp32 value (integer
+// data, near-duplicates whose squares are fp16 subnormals, which the packed fp16 ops and the dot keep).  The two
+// ends round to the same or to adjacent fp16 values; each pair's result must be the finish of one of them, which
+// for most pairs is bit equality.  The accumulation ORDER is deliberately left free: the model holds for the
+// kernel's, for torch's and for the reference's alike, at every D (partial chunks, partial segments, both sides
+// of the staged switch) and scale (subnormal squares up to sums on the 65504 | inf boundary).
+//
 // Layout: embeddings are packed chunk-major like the token planes: chunk q (8 halfs, 16 bytes) of
 // vector n at byte (q * Npad + n) * 16, so 64 consecutive vectors load one chunk each as a coalesced
 // 1 KiB global_load_dwordx4.
