@@ -376,6 +376,32 @@ int pg_lev_eps_fill(int64_t n, int cap, int cmp, int thr, const int32_t *slot_id
                     int32_t *indices, uint8_t *weights, void *stream);
 
 /*
+ * Exact Levenshtein distance beyond 128 positions — the definition above, unchanged, for operands of 1..PG_LEV_LONG_MAX_L
+ * positions each (the two widths need not agree; PG_E_TOOLONG beyond): the block form of Myers' recurrence, one 128-bit
+ * pattern block after the other per 128 text positions (prograph_amd/csrc/pg_lev_long.hip, pg_lev_long.h).
+ *   pg_lev_long_pack   (n, l) row-major uint8 tokens, leading dimension ld, -> `planes`: ceil(l / 128) blocks x 5 bit
+ *                      planes x npad uint4 (80 * ceil(l / 128) * npad bytes, npad = pg_npad(n)), uint4 number
+ *                      (b * 5 + q) * npad + s = bit q of tokens 128 b .. 128 b + 127 of sequence s, so that block b of a
+ *                      long operand is a short operand; `lens` int32 [n]; *flags (one word, zeroed on the stream first)
+ *                      is set when a token is above 31 or a zero is not trailing padding.  No host sync.  The kernels
+ *                      mask symbols and clamp lengths to the width: an invalid operand gives wrong numbers, never an
+ *                      access out of bounds.
+ *   pg_levenshtein_long_dense  out[r * ldo + c] = d(Y row r, X row c) for all m x n pairs, X packed at width xl, Y at
+ *                      width yl; out_elem_bytes 8 = int64, 2 = fp16 (a distance is at most 2048, and fp16 holds every
+ *                      integer up to 2048: exact), the block format of pg_f16_knn / pg_f16_eps_*.  A Y operand that
+ *                      starts at row r0 of a packed matrix is y_planes + 16 * r0 bytes, y_lens + r0, with the matrix's
+ *                      npad.  No workspace, no allocation; the kernel is instantiated for 1, 2, 4, 8 and 16 pattern
+ *                      blocks and chosen by xl.
+ * NULL pointers, non-positive sizes and a bad out_elem_bytes are PG_E_BADARG, checked before any launch.
+ */
+#define PG_LEV_LONG_MAX_L 2048
+int pg_lev_long_pack(const uint8_t *tokens, int64_t n, int l, int64_t ld, void *planes, int64_t npad, int32_t *lens,
+                     uint32_t *flags, void *stream);
+int pg_levenshtein_long_dense(const void *x_planes, int64_t n, int64_t x_npad, const int32_t *x_lens, int xl,
+                              const void *y_planes, int64_t m, int64_t y_npad, const int32_t *y_lens, int yl, void *out,
+                              int out_elem_bytes, int64_t ldo, void *stream);
+
+/*
  * Substitution-matrix distance — BUILD DEFINED (the reference has Hamming only, which is the table 1 - I):
  *     d(y, x) = sum_j C[y_j][x_j]     over zero-right-padded token rows, token 0 an ordinary index of C,
  * C symmetric with at most 32 symbols and entries 0..255 (the caller validates the table; the kernels mask tokens

@@ -30,6 +30,7 @@ ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entr
 ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / ..._local_long_dense / ..._semiglobal_long_dense: positions per operand
 ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_alignment_trace / pg_alignment_trace_long: the modes
 ALN_TRACE_LONG_WORKSPACE = 2 << 30  # alignment_trace_long: the most workspace it takes unasked
+LEV_LONG_MAX_L = 2048             # pg_levenshtein_long_dense: positions per operand
 ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits / aln_semiglobal_long_fits)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
@@ -40,6 +41,7 @@ SYMBOLS = [
     "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
+    "pg_lev_long_pack", "pg_levenshtein_long_dense",
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
     "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
     "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
@@ -138,6 +140,8 @@ def _load():
         lib.pg_lev_eps_pairs.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_lev_eps_count.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]
         lib.pg_lev_eps_fill.argtypes = [_i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_lev_long_pack.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]
+        lib.pg_levenshtein_long_dense.argtypes = [_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _i64, _vp]
         lib.pg_sub_pack.argtypes = [_vp, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp]
         lib.pg_substitution_dense.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp]
         lib.pg_alignment_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _i32, _vp]
@@ -732,6 +736,75 @@ def levenshtein_dense(xo, yo, out_bytes=8, rows=None):
                                       ctypes.c_void_p(yo.planes.buf.data_ptr() + 16 * r0), r1 - r0, yo.planes.npad,
                                       ctypes.c_void_p(yo.lens.data_ptr() + 4 * r0), max(xo.l, yo.l), _ptr(out), out_bytes,
                                       out.stride(0), _stream()), "pg_levenshtein_dense")
+    return out
+
+
+class LevLongOperand:
+    """A token matrix staged for pg_levenshtein_long_dense (pg_lev_long_pack): `tokens` (n, l <= 2048) uint8 on the device,
+    `buf` = ceil(l / 128) blocks x 5 bit planes x npad uint4 (block b is a 128-position operand), `lens` int32 [n] and
+    the validity word."""
+    __slots__ = ("tokens", "buf", "lens", "flags", "n", "l", "npad")
+
+    def __init__(self, tokens, buf, lens, flags):
+        self.tokens, self.buf, self.lens, self.flags = tokens, buf, lens, flags
+        self.n, self.l = int(tokens.shape[0]), int(tokens.shape[1])
+        self.npad = npad(self.n)
+
+    def bad_word(self):
+        """Device int64 scalar, non-zero when a token is above 31 or a zero is not trailing padding."""
+        return self.flags[0].to(torch.int64)
+
+    def valid(self):
+        """One host sync: do the kernel's preconditions hold?"""
+        return int(self.bad_word().item()) == 0
+
+
+def lev_long_ready():
+    """Can the Levenshtein kernel beyond 128 positions run (`levenshtein_long_dense`)?  True only with a HIP device; the
+    routes of prograph.py and the operator ask before they leave the 128-position kernels / the torch expression."""
+    try:
+        return device().type == "cuda"
+    except NativeUnavailable:
+        return False
+
+
+def lev_long_operand(tokens):
+    """(N, L <= 2048) uint8 tokens -> LevLongOperand (pg_lev_long_pack).  No host sync: ask `valid()` before trusting a
+    result computed from it (the kernel masks symbols and clamps lengths, so an invalid operand gives wrong numbers,
+    never an out-of-bounds access)."""
+    L = lib()
+    dev = device()
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dtype != torch.uint8 or tokens.dim() != 2 or tokens.shape[0] == 0 or tokens.shape[1] == 0:
+        raise TypeError("lev_long_operand expects a non-empty 2-D uint8 token matrix")
+    if tokens.shape[1] > LEV_LONG_MAX_L:
+        raise ValueError(f"lev_long_operand: at most {LEV_LONG_MAX_L} tokens per sequence")
+    tokens = tokens.to(dev).contiguous()
+    n, l = tokens.shape
+    np_ = npad(n)
+    buf = torch.empty(((l + 127) // 128) * 5 * np_ * 16, dtype=torch.uint8, device=dev)
+    lens = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)       # (pg_lev_long_pack zeroes it on the stream)
+    _check(L.pg_lev_long_pack(_ptr(tokens), n, l, tokens.stride(0), _ptr(buf), np_, _ptr(lens), _ptr(flags), _stream()),
+           "pg_lev_long_pack")
+    return LevLongOperand(tokens, buf, lens, flags)
+
+
+def levenshtein_long_dense(xo, yo, out_bytes=8, rows=None):
+    """(M, N) exact edit distances of the rows of LevLongOperand `yo` (rows = (r0, r1): only those) against every row of
+    `xo` (pg_levenshtein_long_dense), each operand at its own width of up to 2048 positions: int64 (out_bytes 8) or the
+    fp16 block f16_knn / f16_eps select from (2; a distance is at most 2048: exact)."""
+    if out_bytes not in (2, 8):
+        raise ValueError("levenshtein_long_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.tokens.device)
+    _check(lib().pg_levenshtein_long_dense(_ptr(xo.buf), xo.n, xo.npad, _ptr(xo.lens), xo.l,
+                                           ctypes.c_void_p(yo.buf.data_ptr() + 16 * r0), r1 - r0, yo.npad,
+                                           ctypes.c_void_p(yo.lens.data_ptr() + 4 * r0), yo.l, _ptr(out), out_bytes,
+                                           out.stride(0), _stream()), "pg_levenshtein_long_dense")
     return out
 
 

@@ -12,9 +12,11 @@ Y[m] against every row of X, `torch.int64`, on the device of the inputs; `ValueE
       insertion and deletion cost 1; there is no band and no cap: d(empty, b) = len(b);
     * values must be integers in 0..255 (any dtype): anything else raises `ValueError`.
 
-Device operands with tokens up to 31, at most 128 positions and zeros only as trailing padding run on the HIP
-kernel (`pg_levenshtein_dense`, prograph_amd/csrc/pg_lev.hip).  Everything else is evaluated by the torch expression
-below, on the device the operands live on: the Wagner-Fischer table row by row over the whole (M, N) batch, the
+Device operands with tokens up to 31 and zeros only as trailing padding run on the HIP kernels: up to 128 positions
+`pg_levenshtein_dense` (prograph_amd/csrc/pg_lev.hip), from 129 to 2048 positions `pg_levenshtein_long_dense`
+(prograph_amd/csrc/pg_lev_long.hip).  Everything else - larger tokens, interior zeros, more than 2048 positions, CPU
+tensors - is evaluated by the torch expression below, on the device the operands live on: the Wagner-Fischer table row
+by row over the whole (M, N) batch, the
 dependency inside a row resolved by v[j] = j + cummin(c[k] - k).  It is the slow path; it is exact.
 
 `levenshtein_knn` is the banded (capped) kNN of BASELINE.json configs[4]: d = min(edit distance, band+1), canonical
@@ -74,6 +76,11 @@ def _torch_levenshtein(X, Y):
     return out
 
 
+def _on_device(T):
+    """Do the tokens live where the kernels run?  (One place to ask, which the host-logic tests patch.)"""
+    return T.is_cuda
+
+
 def levenshtein(X, Y, similarity=False):
     """(M, N) edit distances (or similarities 1/(1+d)) of the M rows of Y against the N rows of X, int64."""
     X, Y = clean_input(X, Y)
@@ -83,11 +90,16 @@ def levenshtein(X, Y, similarity=False):
     if xb is None or yb is None:
         raise ValueError("levenshtein: the symbols must be integers in 0..255")
     d = None
-    if xb.is_cuda and xb.shape[1] <= 128:
+    if _on_device(xb) and xb.shape[1] <= 128:
         xo = _native.lev_operand(xb)
         yo = xo if yb is xb else _native.lev_operand(yb)
         if xo.valid() and yo.valid():                                    # tokens <= 31, zeros trailing only
             d = _native.levenshtein_dense(xo, yo, out_bytes=8)
+    elif _on_device(xb) and xb.shape[1] <= _native.LEV_LONG_MAX_L and _native.lev_long_ready():
+        xo = _native.lev_long_operand(xb)
+        yo = xo if yb is xb else _native.lev_long_operand(yb)
+        if xo.valid() and yo.valid():
+            d = _native.levenshtein_long_dense(xo, yo, out_bytes=8)
     if d is None:
         d = _torch_levenshtein(xb, yb)
     return 1 / (1 + d) if similarity else d

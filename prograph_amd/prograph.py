@@ -415,7 +415,7 @@ class Prograph:
     def neighbourhood(self, seq, eps, distance=hamming):
         """All rows within `eps` of `seq`, the row itself included (reference :571-588).  A string that is not in the
         dataset is answered by `search(seq, eps=eps)`: the dataset rows within `eps` of it.  `distance=levenshtein`: the rows
-        within `eps` edits, for a string of any length up to 128; an `alignment` instance likewise."""
+        within `eps` edits, for a string of any length up to 2048; an `alignment` instance likewise."""
         if distance is levenshtein or isinstance(distance, alignment):
             hit = np.zeros(len(self), dtype=bool)
             hit[self.search(self._lev_query(seq), eps=eps, distance=distance)[0][0]] = True
@@ -475,7 +475,8 @@ class Prograph:
         or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
         Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
         dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; Levenshtein (queries of
-        any length up to 128, not only the dataset's) blocks of `pg_levenshtein_dense` plus the fp16 selection; a
+        any length up to 2048, not only the dataset's) blocks of `pg_levenshtein_dense`, or of `pg_levenshtein_long_dense`
+        when queries or dataset are wider than 128 positions, plus the fp16 selection; a
         `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; an `alignment` distance (queries
         of any length up to 128) blocks of `pg_alignment_dense` plus the fp16 selection; any other `distance` the generic
         loop.
@@ -732,12 +733,29 @@ class Prograph:
         op = _native.lev_operand(torch.from_numpy(np.ascontiguousarray(mat.astype(np.uint8))))
         return op if op.valid() else None
 
+    @staticmethod
+    def _lev_long_operand(mat):
+        """LevLongOperand of an integer token matrix the Levenshtein kernel beyond 128 positions takes (at most 2048
+        positions, tokens up to 31, zeros only as trailing padding; one host sync for the last two), else None."""
+        mat = np.asarray(mat)
+        if (mat.ndim != 2 or mat.shape[0] == 0 or not 1 <= mat.shape[1] <= _native.LEV_LONG_MAX_L
+                or not np.issubdtype(mat.dtype, np.integer)):
+            return None
+        if mat.min() < 0 or mat.max() > 31:
+            return None
+        op = _native.lev_long_operand(torch.from_numpy(np.ascontiguousarray(mat.astype(np.uint8))))
+        return op if op.valid() else None
+
     def _search_levenshtein(self, strings, Y, k, eps, comp, similarity, representation):
         """Edit-distance queries: Q x N blocks of `pg_levenshtein_dense` (fp16: distances are at most 128) and the fp16
-        selection with rank 0 / d = 0 kept.  Strings are tokenised with the dataset's letter table at their own width.
-        None (the generic loop with the operator) when dataset or queries are not what the kernel takes."""
+        selection with rank 0 / d = 0 kept, uint8 weights.  When the dataset or the queries are wider than 128 positions
+        (up to 2048 each, the two widths need not agree) both are staged as long operands and the blocks come from
+        `pg_levenshtein_long_dense` (fp16 holds every distance up to 2048), int16 weights.  Strings are tokenised with the
+        dataset's letter table at their own width.  None (the generic loop with the operator) when dataset or queries
+        are not what the kernels take."""
         try:
-            xo = self._lev_operand(self._dataset_matrix(representation))
+            X = self._dataset_matrix(representation)
+            xw = np.shape(X)[1] if np.ndim(X) == 2 else 0
         except (ValueError, TypeError):
             return None
         if strings is not None:
@@ -745,18 +763,27 @@ class Prograph:
             T = table[raw]
         else:
             T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-        qo = self._lev_operand(T) if xo is not None else None
+        long = max(xw, T.shape[1]) > _native.MAX_L
+        if long and not _native.lev_long_ready():
+            return None
+        stage, dense, wdtype = ((self._lev_long_operand, _native.levenshtein_long_dense, torch.int16) if long else
+                                (self._lev_operand, _native.levenshtein_dense, torch.uint8))
+        try:
+            xo = stage(X)
+        except (ValueError, TypeError):
+            return None
+        qo = stage(T) if xo is not None else None
         if qo is None:
             return None
         n, q = xo.n, qo.n
         rows = self._block_rows(n, q, 1)
-        blocks = (_native.levenshtein_dense(xo, qo, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
+        blocks = (dense(xo, qo, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
         if k is not None:
-            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.uint8)
+            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=wdtype)
             return KNNGraph(idx, w, n, similarity=similarity, first=0)
         cmp = _CMP_CODE[comp]
         thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.uint8)
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=wdtype)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _sub_tokens(self, mat, distance):
@@ -1424,8 +1451,9 @@ class Prograph:
 
     def _build_graph_levenshtein(self, idxs, eps, k, similarity, representation, comp, cap=256):
         """
-        `build_graph(distance=levenshtein)` on the HIP kernels, for token matrices they take (at most 128 positions,
-        tokens up to 31, zeros only as trailing padding; else None: the generic loop with the operator).
+        `build_graph(distance=levenshtein)` on the HIP kernels, for token matrices they take (tokens up to 31, zeros
+        only as trailing padding; else None: the generic loop with the operator).  Up to 128 positions the routes below;
+        129..2048 positions `_build_graph_levenshtein_long`; beyond 2048 None.
         eps, comp le / lt / eq with an integer threshold of 1..8: the fused graph (`_native.levenshtein_eps`: bag
         filter, every candidate pair's banded distance once, count / scan / fill).  Any other threshold or ordering:
         row blocks of `pg_levenshtein_dense` in fp16 and the thresholded CSR of `pg_f16_eps_*`.
@@ -1440,6 +1468,8 @@ class Prograph:
             mat = np.asarray(self._dataset_matrix(representation))
             if idxs is not None:
                 mat = mat[np.asarray(idxs)]
+            if mat.ndim == 2 and mat.shape[1] > _native.MAX_L:
+                return self._build_graph_levenshtein_long(mat, eps, k, similarity, comp)
             op = self._lev_operand(mat)
         except (ValueError, TypeError):
             return None
@@ -1477,6 +1507,39 @@ class Prograph:
             return CSRGraph(indptr, indices, wts, n, similarity=similarity)
         blocks = (_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
         indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.uint8)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+
+    def _build_graph_levenshtein_long(self, mat, eps, k, similarity, comp):
+        """
+        `build_graph(distance=levenshtein)` for token matrices of 129..2048 positions (tokens up to 31, zeros only as
+        trailing padding; else None: the generic loop with the operator): row blocks of `pg_levenshtein_long_dense` in
+        fp16 - a distance is at most 2048, which fp16 holds exactly - and the selection of `_select_blocks`: ranks 1..k
+        of the (d, column) order (`pg_f16_knn`, rounds beyond 63), or the thresholded CSR for every ordering
+        (`pg_f16_eps_*`).  Every pair goes through the full recurrence: no bag filter, no banded first pass and no fused
+        epsilon graph beyond 128 positions.  Returns a KNNGraph / CSRGraph with int16 weights; similarities as for
+        Hamming, formed by the container.
+        """
+        if not _native.lev_long_ready():
+            return None
+        op = self._lev_long_operand(mat)
+        if op is None:
+            return None
+        n, dev = op.n, op.tokens.device
+        block_rows = self._block_rows(n, n, 64)
+        blocks = (_native.levenshtein_long_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
+                  for r0 in range(0, n, block_rows))
+        if k:
+            kk = min(k, n - 1)
+            if not kk:
+                return self._empty_knn(n, torch.int16, dev, similarity)
+            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
+            return KNNGraph(idx, wt, n, similarity=similarity)
+        cmp = _CMP_CODE[comp]
+        thr = self._integer_threshold(cmp, eps)
+        if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr - (cmp == _native.CMP_LT) < 1:   # nothing in 1..thr
+            return CSRGraph(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                            torch.zeros(0, dtype=torch.int16, device=dev), n, similarity=similarity)
+        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.int16)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _build_graph_substitution(self, idxs, eps, k, similarity, representation, comp, distance):
