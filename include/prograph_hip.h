@@ -545,6 +545,34 @@ int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t 
                                        void *stream);
 
 /*
+ * FIT ("glocal") alignment score, Gotoh's affine gaps - BUILD DEFINED (pg_aln_fit.hip); a SIMILARITY: larger is nearer.
+ * ALL of y is aligned, within ANY substring of x: only the ends of x are free.  Under a symmetric score table S (at most
+ * 32 symbols, entries -128..127), e = gap, o = gap_open, i over x and j over y:
+ *     H[i][0] = 0,  H[0][j] = -(o + j e) (j >= 1),  E[0][j] = F[i][0] = -inf,
+ *     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - o - e),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - o - e),
+ *     H[i][j] = max(H[i-1][j-1] + S[x_i][y_j], E[i][j], F[i][j])                               (no zero floor),
+ *     s(y, x) = max over i = 0..len x of H[i][len y].
+ * NOT symmetric: the Y operand is the whole one.  -(o + e len y) <= s <= min(len x, len y) * max(0, max S): scores may be
+ * NEGATIVE.  Sequences as for pg_alignment_dense; padding never scores, whatever S[a][0] is.
+ *   pg_alignment_fit_dense  out[r * ldo + c] = s(Y row r, X row c) + bias.  Arguments, lengths, output formats (int64 /
+ *                      fp16), row offsets, checks and error codes of pg_alignment_semiglobal_dense, and `bias` >= 0
+ *                      (PG_E_BADARG below 0): a shift for callers whose next stage wants non-negative values; 0 gives
+ *                      the scores.  At most 128 positions.  Cells are 16 bits wide and hold score + Z, Z = o + yl * (e +
+ *                      max(0, max S)): the caller guarantees o + yl * (e + 2 max(0, max S)) + 255 <= 65 535 (128 positions
+ *                      at 255 / 255 / 127 do not fit); the kernel does not test it.  The fp16 output is exact while every
+ *                      out value is within 0..2048, which the caller guarantees.  Does not allocate; LDS only.
+ *   pg_alignment_fit_long_dense  the same up to PG_ALN_LONG_MAX_L positions: the arguments, workspace
+ *                      (pg_alignment_long_workspace), outputs (int32 / int64) and error codes of
+ *                      pg_alignment_semiglobal_long_dense, `bias` and the caller's guarantee as above.
+ */
+int pg_alignment_fit_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                           int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, int bias, void *out,
+                           int64_t ldo, int out_elem_bytes, void *stream);
+int pg_alignment_fit_long_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                                int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, int bias, void *out,
+                                int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * Alignment TRACEBACK - BUILD DEFINED (pg_aln_trace.hip, pg_aln_trace.h): the canonical alignment of a list of pairs under
  * the tables H, E, F of pg_alignment_affine_dense (mode PG_ALN_TRACE_GLOBAL, table = cost_u8, gap_open = 0: the linear
  * form), pg_alignment_local_dense (PG_ALN_TRACE_LOCAL, table = score_i8) or pg_alignment_semiglobal_dense
@@ -572,6 +600,12 @@ int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t 
  *                      are accepted), the row of the tables cut into strips of 128 columns.  Cells are int32, so every
  *                      table and penalty of the three modes is exact: there is no "fits" condition.  *bytes_per_wave =
  *                      64 * xl * ceil(yl / 8) * 4 (direction bits) + 64 * xl * 8 (one boundary column between strips).
+ *   pg_alignment_fit_trace, pg_alignment_fit_trace_long  the canonical alignment under pg_alignment_fit_dense's tables
+ *                      (table = score_i8; x has the free ends, y is whole): the arguments, workspaces, outputs and checks
+ *                      of the two entries above without `mode`, which go on rejecting every mode but 0, 1, 2.  End cell:
+ *                      the best H[i][len y], i = 0..len x, ties to the smallest i ((0, len y) before any row).  The walk
+ *                      stops in state H at j = 0; at i = 0 the j remaining symbols of y are left unaligned.  So y_begin = 0
+ *                      and y_end = len y always, and x_begin:x_end is where y sits in x.
  */
 #define PG_ALN_TRACE_GLOBAL 0
 #define PG_ALN_TRACE_LOCAL 1
@@ -586,6 +620,14 @@ int pg_alignment_trace_long(int mode, const void *x_packed, int64_t n, int64_t x
                             int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table,
                             int gap, int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace,
                             int64_t workspace_bytes, void *stream);
+int pg_alignment_fit_trace(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                           int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table,
+                           int gap, int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+int pg_alignment_fit_trace_long(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                                int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs,
+                                const void *table, int gap, int gap_open, int32_t *head, uint8_t *ops, int64_t ldo,
+                                void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the

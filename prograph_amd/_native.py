@@ -29,6 +29,7 @@ ALN_MAX_OPEN = 255                # pg_alignment_affine_dense: the largest gap-o
 ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entries of a score table
 ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / ..._local_long_dense / ..._semiglobal_long_dense: positions per operand
 ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_alignment_trace / pg_alignment_trace_long: the modes
+ALN_TRACE_FIT = 3                 # pg_aln_trace.h's PG_TR_FIT: pg_alignment_fit_trace / _long, which take no mode
 ALN_TRACE_LONG_WORKSPACE = 2 << 30  # alignment_trace_long: the most workspace it takes unasked
 LEV_LONG_MAX_L = 2048             # pg_levenshtein_long_dense: positions per operand
 ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits / aln_semiglobal_long_fits)
@@ -45,6 +46,7 @@ SYMBOLS = [
     "pg_sub_pack", "pg_substitution_dense", "pg_alignment_dense", "pg_alignment_affine_dense",
     "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
     "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
+    "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
@@ -154,11 +156,17 @@ def _load():
         lib.pg_alignment_local_long_dense.argtypes = lib.pg_alignment_long_dense.argtypes
         lib.pg_alignment_semiglobal_dense.argtypes = lib.pg_alignment_affine_dense.argtypes
         lib.pg_alignment_semiglobal_long_dense.argtypes = lib.pg_alignment_long_dense.argtypes
+        lib.pg_alignment_fit_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _i64,
+                                               _i32, _vp]
+        lib.pg_alignment_fit_long_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _vp,
+                                                    _i64, _i32, _vp, _i64, _vp]
         lib.pg_alignment_trace_workspace.argtypes = [_i32, _i32, ctypes.POINTER(_i64)]
         lib.pg_alignment_trace.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _i32,
                                            _vp, _vp, _i64, _vp, _i64, _vp]
         lib.pg_alignment_trace_long_workspace.argtypes = lib.pg_alignment_trace_workspace.argtypes
         lib.pg_alignment_trace_long.argtypes = lib.pg_alignment_trace.argtypes
+        lib.pg_alignment_fit_trace.argtypes = lib.pg_alignment_trace.argtypes[1:]
+        lib.pg_alignment_fit_trace_long.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
@@ -1040,6 +1048,52 @@ def aln_semiglobal_long_fits(width_x, width_y, max_score):
             and 2 * min(width_x, width_y) * max(int(max_score), 0) + 255 <= ALN_LONG_CELL_MAX)
 
 
+def aln_fit_fits(width_x, width_y, max_score, gap, gap_open):
+    """Do `fit_alignment` scores fit the 16-bit cells of pg_alignment_fit_dense AND pg_alignment_fit_long_dense?  A cell holds
+    score + Z, Z = gap_open + width_y * (gap + max(0, max S)) (the Y operand is the whole one), a score is at most
+    width_y * max(S), and the diagonal term adds a profile byte (at most 255) before the bias comes off.  Unlike the other
+    modes the short kernel needs it too: 128 positions at 255 / 255 / 127 give 65 662."""
+    top = max(int(max_score), 0)
+    return (max(width_x, width_y) <= ALN_LONG_MAX_L
+            and int(gap_open) + int(width_y) * (int(gap) + 2 * top) + 255 <= ALN_LONG_CELL_MAX)
+
+
+def alignment_fit_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None, bias=0):
+    """(M, N) fit alignment SCORES (all of the Y row within any substring of the X row; larger is nearer, NEGATIVE values
+    occur) of the rows of AlnOperand `yo` (rows = (r0, r1): only those) against every row of `xo`, plus `bias` >= 0
+    (pg_alignment_fit_dense); arguments and outputs as `alignment_semiglobal_dense`.  Exact while
+    `aln_fit_fits(xo.l, yo.l, max(S), gap, gap_open)` holds, and in fp16 while every score + bias lies in 0..2048; the
+    caller checks both."""
+    if out_bytes not in (2, 8):
+        raise ValueError("alignment_fit_dense: out_bytes 8 (int64) or 2 (fp16)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    _check(lib().pg_alignment_fit_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
+                                        r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), int(bias), _ptr(out),
+                                        out.stride(0), out_bytes, _stream()), "pg_alignment_fit_dense")
+    return out
+
+
+def alignment_fit_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None, bias=0):
+    """`alignment_fit_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_fit_long_dense): int64 (out_bytes
+    8) or the int32 block i32_knn / i32_eps select from (4).  Exact while `aln_fit_fits` holds, which the caller checks.
+    Allocates the call's workspace."""
+    if out_bytes not in (4, 8):
+        raise ValueError("alignment_fit_long_dense: out_bytes 8 (int64) or 4 (int32)")
+    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= yo.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    ws = aln_long_workspace(xo, r1 - r0)
+    _check(lib().pg_alignment_fit_long_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
+                                             r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), int(bias),
+                                             _ptr(out), out.stride(0), out_bytes, _ptr(ws), ws.numel(), _stream()),
+           "pg_alignment_fit_long_dense")
+    return out
+
+
 def aln_long_operand(tokens, a):
     """(N, L <= 2048) uint8 tokens -> AlnOperand for a table of `a` symbols, for the kernels beyond 128 positions
     (pg_sub_pack at the operand's own width).  No host sync, as `aln_operand`."""
@@ -1105,6 +1159,14 @@ def aln_trace_wave_bytes(xl, yl):
 def _trace_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws):
     """One pg_alignment_trace call: pairs p0..p1-1 of the lists into rows p0..p1-1 of head and ops."""
     ldo = ops.stride(0)
+    if int(mode) == ALN_TRACE_FIT:                                          # an entry of its own, without `mode`
+        _check(lib().pg_alignment_fit_trace(_ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
+                                            ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
+                                            p1 - p0, _ptr(table), int(gap), int(gap_open),
+                                            ctypes.c_void_p(head.data_ptr() + 32 * p0),
+                                            ctypes.c_void_p(ops.data_ptr() + ldo * p0), ldo, _ptr(ws), ws.numel(), _stream()),
+               "pg_alignment_fit_trace")
+        return
     _check(lib().pg_alignment_trace(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
                                     ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
                                     p1 - p0, _ptr(table), int(gap), int(gap_open),
@@ -1139,8 +1201,8 @@ def _trace_list(name, wave_bytes, launch, xo, yo, xi, yi, mode, table, gap, gap_
 
 def alignment_trace(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes=256 << 20):
     """The canonical alignments (pg_alignment_trace) of the pairs (row xi[p] of AlnOperand `xo`, row yi[p]
-    of `yo`), P >= 1 of them, repeats allowed: `mode` ALN_TRACE_GLOBAL (`table` from sub_cost), ALN_TRACE_LOCAL or
-    ALN_TRACE_SEMIGLOBAL (`table` from aln_local_score); `gap` 1..255, `gap_open` 0..255.  Returns (head int32 (P, 8): score,
+    of `yo`), P >= 1 of them, repeats allowed: `mode` ALN_TRACE_GLOBAL (`table` from sub_cost), ALN_TRACE_LOCAL,
+    ALN_TRACE_SEMIGLOBAL or ALN_TRACE_FIT (`table` from aln_local_score; FIT runs pg_alignment_fit_trace: y whole within x); `gap` 1..255, `gap_open` 0..255.  Returns (head int32 (P, 8): score,
     x_begin, x_end, y_begin, y_end, n_ops, identities, status; ops uint8 (P, xo.l + yo.l): 1 pair, 2 x unaligned, 3 y
     unaligned, 0 from n_ops on) on the device.  The index ranges are checked on the host - ONE SYNC - and an index outside
     its operand raises IndexError.  The list is split into launches whose waves all fit `workspace_bytes` of direction
@@ -1169,6 +1231,14 @@ def aln_trace_long_wave_bytes(xl, yl):
 def _trace_long_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws):
     """One pg_alignment_trace_long call: pairs p0..p1-1 of the lists into rows p0..p1-1 of head and ops."""
     ldo = ops.stride(0)
+    if int(mode) == ALN_TRACE_FIT:                                          # an entry of its own, without `mode`
+        _check(lib().pg_alignment_fit_trace_long(_ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
+                                                 ctypes.c_void_p(xi.data_ptr() + 4 * p0),
+                                                 ctypes.c_void_p(yi.data_ptr() + 4 * p0), p1 - p0, _ptr(table), int(gap),
+                                                 int(gap_open), ctypes.c_void_p(head.data_ptr() + 32 * p0),
+                                                 ctypes.c_void_p(ops.data_ptr() + ldo * p0), ldo, _ptr(ws), ws.numel(),
+                                                 _stream()), "pg_alignment_fit_trace_long")
+        return
     _check(lib().pg_alignment_trace_long(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
                                          ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
                                          p1 - p0, _ptr(table), int(gap), int(gap_open),

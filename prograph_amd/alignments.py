@@ -1,7 +1,7 @@
 """
-Alignment tracebacks: WHICH symbols the three alignment operators pair, not only what the pairing is worth.
+Alignment tracebacks: WHICH symbols the four alignment operators pair, not only what the pairing is worth.
 
-    A = alignment(C, 1, gap_open=3).align(X, Y)        # row p of X with row p of Y; also local_ / semiglobal_alignment
+    A = alignment(C, 1, gap_open=3).align(X, Y)        # row p of X with row p of Y; also local_ / semiglobal_ / fit_alignment
     A = pg.align(graph, distance=local_alignment(S, 1, 11))                        # one alignment per edge of a graph
     A.score, A.x_begin, A.x_end, A.y_begin, A.y_end, A.n_ops, A.identities, A.ops   # tensors, one row per pair
     A.identity(), A.cigar(p), A.gapped(p, letters), A.host(), len(A)
@@ -13,9 +13,12 @@ scores maximise).  Of all optimal alignments one is canonical:
 
   * end cell: global (len x, len y); local the cell of maximal H, ties to the smallest i, then the smallest j, and a
     maximum of 0 is the empty alignment (no ops, all four coordinates 0); semi-global the best of H[i][len y] and
-    H[len x][j], the same ties;
+    H[len x][j], the same ties; fit (`fit_alignment`: x has the free ends, y is whole) the best of H[i][len y],
+    i = 0..len x, ties to the smallest i;
   * walk back from it in state H.  In H at (i, j): local stops where H[i][j] = 0 (tested first), semi-global where i = 0 or
-    j = 0, global at (0, 0) - on i = 0 the j remaining symbols of y are left unaligned, on j = 0 the i of x.  Otherwise a
+    j = 0, global at (0, 0) - on i = 0 the j remaining symbols of y are left unaligned, on j = 0 the i of x; fit stops at
+    j = 0 and on i = 0 leaves the j remaining symbols of y unaligned, so y_begin = 0, y_end = len y always and
+    x_begin:x_end is where y sits.  Otherwise a
     pair if H[i][j] = H[i-1][j-1] + T[x_i][y_j], else state E if H[i][j] = E[i][j], else state F, at the same cell.  In E:
     x_i is unaligned; on to (i-1, j), in state H if E[i][j] equals the open term from H[i-1][j] (open wins a tie - with
     gap_open = 0 there always is one), else still in E.  F mirrors E along j.
@@ -39,6 +42,7 @@ import torch
 from . import _native
 
 GLOBAL, LOCAL, SEMIGLOBAL = _native.ALN_TRACE_GLOBAL, _native.ALN_TRACE_LOCAL, _native.ALN_TRACE_SEMIGLOBAL
+FIT = _native.ALN_TRACE_FIT
 _NEG = -(1 << 40)
 _DIGITS = "0123456789abcdefghijklmnopqrstuv"        # a token as one character when no letters are given
 _FIELDS = ("score", "x_begin", "x_end", "y_begin", "y_end", "n_ops", "identities")
@@ -115,6 +119,8 @@ def _host_pair(mode, T, e, o, x, y):
     if mode == GLOBAL:
         H[0, 1:] = -o - jg[1:]
         H[1:, 0] = -o - np.arange(1, lx + 1, dtype=np.int64) * e
+    if mode == FIT:
+        H[0, 1:] = -o - jg[1:]                                              # all of y is paid for; column 0 stays 0
     for i in range(1, lx + 1):
         E[i, 1:] = np.maximum(E[i - 1, 1:] - e, H[i - 1, 1:] - oe)
         A = np.empty(ly + 1, dtype=np.int64)
@@ -130,6 +136,8 @@ def _host_pair(mode, T, e, o, x, y):
         bi, bj = (int(v) for v in np.unravel_index(np.argmax(H), H.shape))  # the first maximum in row-major order
         if H[bi, bj] == 0:
             bi = bj = 0
+    elif mode == FIT:
+        bi, bj = int(np.argmax(H[:, ly])), ly                               # the first maximum: the smallest i
     else:
         col, row = H[:, ly], H[lx, :]
         top = max(int(col.max()), int(row.max()))
@@ -145,6 +153,9 @@ def _host_pair(mode, T, e, o, x, y):
                 if mode == GLOBAL:
                     ops += [3] * j if i == 0 else [2] * i
                     i = j = 0
+                if mode == FIT:                                             # the rest of y unaligned; x's prefix is free
+                    ops += [3] * j
+                    j = 0
                 break
             if H[i, j] == H[i - 1, j - 1] + T[x[i - 1], y[j - 1]]:
                 ops.append(1)
@@ -190,12 +201,12 @@ def host_trace(mode, table, gap, gap_open, X, Y, xi=None, yi=None):
 
 # ---------------------------------------------------------------------------------------------- routes
 def _mode_of(op):
-    from .distance import alignment, local_alignment, semiglobal_alignment
-    for cls, mode in ((alignment, GLOBAL), (local_alignment, LOCAL), (semiglobal_alignment, SEMIGLOBAL)):
+    from .distance import alignment, fit_alignment, local_alignment, semiglobal_alignment
+    for cls, mode in ((alignment, GLOBAL), (local_alignment, LOCAL), (semiglobal_alignment, SEMIGLOBAL), (fit_alignment, FIT)):
         if isinstance(op, cls):
             return mode
-    raise TypeError("align: distance must be an alignment, local_alignment or semiglobal_alignment instance, not "
-                    f"{op!r}")
+    raise TypeError("align: distance must be an alignment, local_alignment or semiglobal_alignment instance, or a "
+                    f"fit_alignment one, not {op!r}")
 
 
 def _device_table(op, mode):
@@ -254,7 +265,8 @@ def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native
 
 
 def align(op, X, Y):
-    """`op.align(X, Y)`: row p of X aligned with row p of Y (see the module text); the operators' input rules."""
+    """`op.align(X, Y)`: row p of X aligned with row p of Y (see the module text; `fit_alignment`: row p of Y, whole,
+    within row p of X); the operators' input rules."""
     from .distance.hamming import _as_byte_tokens
     from .distance.utils import clean_input
     name = type(op).__name__

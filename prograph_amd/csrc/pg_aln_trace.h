@@ -7,7 +7,8 @@
 // the whole of the tie rule - as it is:
 //     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - oe),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - oe),
 //     H[i][j] = max(H[i-1][j-1] + T[x_i][y_j], E[i][j], F[i][j])      (local: 0 where that is not positive),
-// borders H[i][0] = H[0][j] = 0 (global: H[0][0] = 0, else -(gap_open + k e)), E[0][j] = F[i][0] = PG_TR_NEG.  Cells are
+// borders H[i][0] = H[0][j] = 0 (global: H[0][0] = 0, else -(gap_open + k e); fit: H[0][j] as global, H[i][0] = 0),
+// E[0][j] = F[i][0] = PG_TR_NEG.  Cells are
 // int32: |H| <= 128 * 255 + 255, and PG_TR_NEG sinks by at most 128 * 255 more, so nothing overflows or meets a true value.
 // The long trace (pg_aln_trace_long.hip, DESIGN.md §4.21: up to PG_TR_LONG_MAX_L positions, the row cut into strips of
 // PG_TR_STRIP columns) keeps int32 cells too: |H| <= 2048 * 255 + 255, PG_TR_NEG = -2^28 sinks by at most 2048 * 255 more,
@@ -17,6 +18,10 @@
 // Direction nibble of cell (i, j), i, j >= 1: bits 0-1 where H comes from (0 local stop, 1 diagonal, 2 E, 3 F; the
 // diagonal wins a tie, then E), bit 2 "E[i][j] opened from H[i-1][j]", bit 3 "F[i][j] opened from H[i][j-1]" (open wins
 // a tie).  Eight cells to a dword: cell j of row i in bits 4 * ((j-1) & 7) of dir[((i-1) * nd + ((j-1) >> 3)) * ds].
+//
+// PG_TR_FIT (entered through pg_alignment_fit_trace / _long only): all of y inside any substring of x.
+// Row 0 is the global one, column 0 is 0; the end cell is the best H[i][len y], i = 0..len x, ties to the smallest i,
+// (0, len y) before any row; the walk stops in state H at j = 0 and leaves the j remaining symbols of y unaligned at i = 0.
 #pragma once
 #include <stdint.h>
 
@@ -29,6 +34,7 @@
 #define PG_TR_GLOBAL 0
 #define PG_TR_LOCAL 1
 #define PG_TR_SEMIGLOBAL 2
+#define PG_TR_FIT 3
 #define PG_TR_MAX_L 128
 #define PG_TR_NEG (-(1 << 28))
 #define PG_TR_STRIP 128                 // columns of one strip of the long trace: a multiple of 8, no dword in two strips
@@ -58,12 +64,12 @@ struct pg_tr_end {
 // row 0 of H and E, and the end cell before any row
 PG_TR_FN void pg_tr_row0(int mode, int lx, int ly, int e, int oe, int *colH, int *colE, int cs, pg_tr_end *end) {
   for (int j = 0; j <= ly; ++j) {
-    colH[j * cs] = (mode == PG_TR_GLOBAL && j) ? -(oe - e) - j * e : 0;
+    colH[j * cs] = ((mode == PG_TR_GLOBAL || mode == PG_TR_FIT) && j) ? -(oe - e) - j * e : 0;
     colE[j * cs] = PG_TR_NEG;
   }
-  end->best = 0;
+  end->best = (mode == PG_TR_FIT && ly) ? -(oe - e) - ly * e : 0;          // fit: H[0][len y]
   end->i = mode == PG_TR_GLOBAL ? lx : 0;
-  end->j = mode == PG_TR_GLOBAL ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;     // semi-global: H[0][len y], or row 0 = row len x
+  end->j = (mode == PG_TR_GLOBAL || mode == PG_TR_FIT) ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;     // semi-global: H[0][len y], or row 0 = row len x
 }
 
 // row i (1..lx) of one pair: colH / colE hold row i - 1 on entry and row i on return (cell j at [j * cs]); trow = T[x_i]
@@ -87,7 +93,7 @@ PG_TR_FN void pg_tr_row(int mode, int i, int lx, int ly, int e, int oe, const in
       H = 0;
       nib &= ~3u;
     }
-    if ((mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly))) && H > end->best) {
+    if ((mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly)) || (mode == PG_TR_FIT && j == ly)) && H > end->best) {
       end->best = H;
       end->i = i;
       end->j = j;
@@ -107,14 +113,26 @@ PG_TR_FN void pg_tr_row(int mode, int i, int lx, int ly, int e, int oe, const in
 // ---- the strip forms (pg_aln_trace_long.hip): the same row, PG_TR_STRIP columns at a time, strip s over all rows before
 // strip s + 1.  The candidates of the end cell then arrive in (strip, i, j) order, so the rule states its ties itself.
 
-// H[k][0] = H[0][k]
-PG_TR_FN int pg_tr_border(int mode, int k, int e, int oe) { return (mode == PG_TR_GLOBAL && k) ? -(oe - e) - k * e : 0; }
+// H[0][k]; H[k][0] too in every mode but fit (pg_tr_border_x)
+PG_TR_FN int pg_tr_border(int mode, int k, int e, int oe) {
+  return ((mode == PG_TR_GLOBAL || mode == PG_TR_FIT) && k) ? -(oe - e) - k * e : 0;
+}
 
-// the end cell before any row (pg_tr_row0's)
+// H[k][0]: fit leaves the prefix of x free
+PG_TR_FN int pg_tr_border_x(int mode, int k, int e, int oe) { return mode == PG_TR_FIT ? 0 : pg_tr_border(mode, k, e, oe); }
+
+// the end cell before any row (pg_tr_row0's); fit: pg_tr_end0_fit after it
 PG_TR_FN void pg_tr_end0(int mode, int lx, int ly, pg_tr_end *end) {
   end->best = 0;
   end->i = mode == PG_TR_GLOBAL ? lx : 0;
-  end->j = mode == PG_TR_GLOBAL ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;
+  end->j = (mode == PG_TR_GLOBAL || mode == PG_TR_FIT) ? ly : (mode == PG_TR_SEMIGLOBAL && lx) ? ly : 0;
+}
+
+// fit's end cell before any row: (0, len y) at H[0][len y]
+PG_TR_FN void pg_tr_end0_fit(int ly, int e, int oe, pg_tr_end *end) {
+  end->best = pg_tr_border(PG_TR_FIT, ly, e, oe);
+  end->i = 0;
+  end->j = ly;
 }
 
 // A candidate (i, j) of value H, whatever was visited before: a larger value replaces, and so does an equal one of a
@@ -161,7 +179,8 @@ PG_TR_FN void pg_tr_row_strip(int mode, int i, int lx, int ly, int j0, int e, in
       H = 0;
       nib &= ~3u;
     }
-    if (mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly))) pg_tr_end_take(end, H, i, j);
+    if (mode == PG_TR_LOCAL || (mode == PG_TR_SEMIGLOBAL && (i == lx || j == ly)) || (mode == PG_TR_FIT && j == ly))
+      pg_tr_end_take(end, H, i, j);
     diag = hup;
     colH[c] = H;
     colE[c] = E;
@@ -192,6 +211,8 @@ PG_TR_FN void pg_tr_walk_room(int mode, int lx, int ly, int bi, int bj, const ui
         for (; i > 0 && n < room; --i) ops[n++] = 2;
         for (; j > 0 && n < room; --j) ops[n++] = 3;
       }
+      if (mode == PG_TR_FIT)                                                // all of y: its rest unaligned; x's prefix is free
+        for (; j > 0 && n < room; --j) ops[n++] = 3;
       break;
     }
     if (i < 1 || j < 1 || i > lx || j > ly) break;                          // states E and F leave through H: not reached

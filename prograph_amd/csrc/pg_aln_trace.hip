@@ -60,6 +60,36 @@ __global__ __launch_bounds__(TR_WAVE) void pg_aln_trace_kernel(
   }
 }
 
+static int trace_fail(const char *who, int code, const char *what) {
+  char buf[200];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  return pg_fail(code, buf);
+}
+
+// the checks and the launch of both entries; `mode` is already checked
+static int trace_run(const char *who, int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed,
+    int64_t m, int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!x_packed || !y_packed || !xi || !yi || !table || !head || !ops || !workspace || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 ||
+      npairs <= 0)
+    return trace_fail(who, PG_E_BADARG, "bad argument");
+  if (xl > PG_TR_MAX_L || yl > PG_TR_MAX_L) return trace_fail(who, PG_E_TOOLONG, "at most 128 positions");
+  if (gap < 1 || gap > 255) return trace_fail(who, PG_E_BADARG, "gap must be in 1..255");
+  if (gap_open < 0 || gap_open > 255) return trace_fail(who, PG_E_BADARG, "gap_open must be in 0..255");
+  if (x_npad < n || y_npad < m) return trace_fail(who, PG_E_BADARG, "bad npad");
+  if (ldo < (int64_t)xl + yl) return trace_fail(who, PG_E_BADARG, "ldo must be at least xl + yl");
+  const long long one = (long long)TR_WAVE * xl * ((yl + 7) / 8) * 4;
+  if (workspace_bytes < one) return trace_fail(who, PG_E_BADARG, "the workspace is smaller than one wave's share");
+  const long long chunks = (npairs + TR_WAVE - 1) / TR_WAVE;
+  long long blocks = workspace_bytes / one;                                 // as many waves as the workspace holds
+  if (blocks > chunks) blocks = chunks;
+  if (blocks > 0x7fffffffll) blocks = 0x7fffffffll;
+  pg_aln_trace_kernel<<<dim3((unsigned)blocks), dim3(TR_WAVE), 0, (hipStream_t)stream>>>(
+      mode, (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+      gap_open + gap, head, ops, ldo, (u32 *)workspace, chunks);
+  return pg_launched(who);
+}
+
 extern "C" {
 
 int pg_alignment_trace_workspace(int xl, int yl, int64_t *bytes_per_wave) {
@@ -70,29 +100,20 @@ int pg_alignment_trace_workspace(int xl, int yl, int64_t *bytes_per_wave) {
 }
 
 int pg_alignment_trace(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
-                       int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap,
-                       int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes,
-                       void *stream) {
-  if (!x_packed || !y_packed || !xi || !yi || !table || !head || !ops || !workspace || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 ||
-      npairs <= 0)
-    return pg_fail(PG_E_BADARG, "pg_alignment_trace: bad argument");
+    int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
   if (mode != PG_ALN_TRACE_GLOBAL && mode != PG_ALN_TRACE_LOCAL && mode != PG_ALN_TRACE_SEMIGLOBAL)
-    return pg_fail(PG_E_BADARG, "pg_alignment_trace: mode must be 0 (global), 1 (local) or 2 (semi-global)");
-  if (xl > PG_TR_MAX_L || yl > PG_TR_MAX_L) return pg_fail(PG_E_TOOLONG, "pg_alignment_trace: at most 128 positions");
-  if (gap < 1 || gap > 255) return pg_fail(PG_E_BADARG, "pg_alignment_trace: gap must be in 1..255");
-  if (gap_open < 0 || gap_open > 255) return pg_fail(PG_E_BADARG, "pg_alignment_trace: gap_open must be in 0..255");
-  if (x_npad < n || y_npad < m) return pg_fail(PG_E_BADARG, "pg_alignment_trace: bad npad");
-  if (ldo < (int64_t)xl + yl) return pg_fail(PG_E_BADARG, "pg_alignment_trace: ldo must be at least xl + yl");
-  const long long one = (long long)TR_WAVE * xl * ((yl + 7) / 8) * 4;
-  if (workspace_bytes < one) return pg_fail(PG_E_BADARG, "pg_alignment_trace: the workspace is smaller than one wave's share");
-  const long long chunks = (npairs + TR_WAVE - 1) / TR_WAVE;
-  long long blocks = workspace_bytes / one;                                 // as many waves as the workspace holds
-  if (blocks > chunks) blocks = chunks;
-  if (blocks > 0x7fffffffll) blocks = 0x7fffffffll;
-  pg_aln_trace_kernel<<<dim3((unsigned)blocks), dim3(TR_WAVE), 0, (hipStream_t)stream>>>(
-      mode, (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
-      gap_open + gap, head, ops, ldo, (u32 *)workspace, chunks);
-  return pg_launched("pg_alignment_trace");
+    return trace_fail("pg_alignment_trace", PG_E_BADARG, "mode must be 0 (global), 1 (local) or 2 (semi-global)");
+  return trace_run("pg_alignment_trace", mode, x_packed, n, x_npad, xl, y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+                   gap_open, head, ops, ldo, workspace, workspace_bytes, stream);
+}
+
+// mode PG_TR_FIT: all of y within any substring of x (pg_aln_trace.h).  The entry above goes on rejecting mode 3.
+int pg_alignment_fit_trace(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+    int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
+  return trace_run("pg_alignment_fit_trace", PG_TR_FIT, x_packed, n, x_npad, xl, y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+                   gap_open, head, ops, ldo, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -53,6 +53,7 @@ __global__ __launch_bounds__(TR_WAVE) void pg_aln_trace_long_kernel(
     const int lx = min(pg_tr_length(xb, xnpad, xg), xl), ly = min(pg_tr_length(yb, ynpad, yg), yl);
     pg_tr_end end;
     pg_tr_end0(mode, lx, ly, &end);
+    if (mode == PG_TR_FIT) pg_tr_end0_fit(ly, e, oe, &end);
     int last = 0;                                                           // H[len x][len y] once the last strip is through
     for (int j0 = 0; j0 < ly; j0 += PG_TR_STRIP) {
       const int sg = min(PG_TR_STRIP / 4, yg - (j0 >> 2));
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(TR_WAVE) void pg_aln_trace_long_kernel(
       for (int i = 1; i <= lx; ++i) {
         if (((i - 1) & 3) == 0) xw = xb[(long long)((i - 1) >> 2) * xnpad];
         int *b = bnd + (long long)(i - 1) * 2 * TR_WAVE;
-        const int left = j0 ? b[0] : pg_tr_border(mode, i, e, oe), fin = j0 ? b[TR_WAVE] : PG_TR_NEG;
+        const int left = j0 ? b[0] : pg_tr_border_x(mode, i, e, oe), fin = j0 ? b[TR_WAVE] : PG_TR_NEG;
         int rh, rf;
         pg_tr_row_strip(mode, i, lx, ly, j0, e, oe, T + 32 * (int)((xw >> (8 * ((i - 1) & 3))) & 31u), ytok + lane, TR_WAVE,
                         colH + lane, colE + lane, TR_WAVE, dir + (long long)(i - 1) * nd * TR_WAVE, TR_WAVE, &end, left, fin, diag,
@@ -83,6 +84,36 @@ __global__ __launch_bounds__(TR_WAVE) void pg_aln_trace_long_kernel(
   }
 }
 
+static int trace_fail(const char *who, int code, const char *what) {
+  char buf[200];
+  snprintf(buf, sizeof(buf), "%s: %s", who, what);
+  return pg_fail(code, buf);
+}
+
+// the checks and the launch of both entries; `mode` is already checked
+static int trace_run(const char *who, int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed,
+    int64_t m, int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
+  if (!x_packed || !y_packed || !xi || !yi || !table || !head || !ops || !workspace || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 ||
+      npairs <= 0)
+    return trace_fail(who, PG_E_BADARG, "bad argument");
+  if (xl > PG_TR_LONG_MAX_L || yl > PG_TR_LONG_MAX_L) return trace_fail(who, PG_E_TOOLONG, "at most 2048 positions");
+  if (gap < 1 || gap > 255) return trace_fail(who, PG_E_BADARG, "gap must be in 1..255");
+  if (gap_open < 0 || gap_open > 255) return trace_fail(who, PG_E_BADARG, "gap_open must be in 0..255");
+  if (x_npad < n || y_npad < m) return trace_fail(who, PG_E_BADARG, "bad npad");
+  if (ldo < (int64_t)xl + yl) return trace_fail(who, PG_E_BADARG, "ldo must be at least xl + yl");
+  const long long one = trace_long_share(xl, yl);
+  if (workspace_bytes < one) return trace_fail(who, PG_E_BADARG, "the workspace is smaller than one wave's share");
+  const long long chunks = (npairs + TR_WAVE - 1) / TR_WAVE;
+  long long blocks = workspace_bytes / one;                                 // as many waves as the workspace holds
+  if (blocks > chunks) blocks = chunks;
+  if (blocks > 0x7fffffffll) blocks = 0x7fffffffll;
+  pg_aln_trace_long_kernel<<<dim3((unsigned)blocks), dim3(TR_WAVE), 0, (hipStream_t)stream>>>(
+      mode, (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+      gap_open + gap, head, ops, ldo, (u32 *)workspace, chunks);
+  return pg_launched(who);
+}
+
 extern "C" {
 
 int pg_alignment_trace_long_workspace(int xl, int yl, int64_t *bytes_per_wave) {
@@ -94,29 +125,20 @@ int pg_alignment_trace_long_workspace(int xl, int yl, int64_t *bytes_per_wave) {
 }
 
 int pg_alignment_trace_long(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
-                            int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table,
-                            int gap, int gap_open, int32_t *head, uint8_t *ops, int64_t ldo, void *workspace,
-                            int64_t workspace_bytes, void *stream) {
-  if (!x_packed || !y_packed || !xi || !yi || !table || !head || !ops || !workspace || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 ||
-      npairs <= 0)
-    return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: bad argument");
+    int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
   if (mode != PG_ALN_TRACE_GLOBAL && mode != PG_ALN_TRACE_LOCAL && mode != PG_ALN_TRACE_SEMIGLOBAL)
-    return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: mode must be 0 (global), 1 (local) or 2 (semi-global)");
-  if (xl > PG_TR_LONG_MAX_L || yl > PG_TR_LONG_MAX_L) return pg_fail(PG_E_TOOLONG, "pg_alignment_trace_long: at most 2048 positions");
-  if (gap < 1 || gap > 255) return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: gap must be in 1..255");
-  if (gap_open < 0 || gap_open > 255) return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: gap_open must be in 0..255");
-  if (x_npad < n || y_npad < m) return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: bad npad");
-  if (ldo < (int64_t)xl + yl) return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: ldo must be at least xl + yl");
-  const long long one = trace_long_share(xl, yl);
-  if (workspace_bytes < one) return pg_fail(PG_E_BADARG, "pg_alignment_trace_long: the workspace is smaller than one wave's share");
-  const long long chunks = (npairs + TR_WAVE - 1) / TR_WAVE;
-  long long blocks = workspace_bytes / one;                                 // as many waves as the workspace holds
-  if (blocks > chunks) blocks = chunks;
-  if (blocks > 0x7fffffffll) blocks = 0x7fffffffll;
-  pg_aln_trace_long_kernel<<<dim3((unsigned)blocks), dim3(TR_WAVE), 0, (hipStream_t)stream>>>(
-      mode, (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
-      gap_open + gap, head, ops, ldo, (u32 *)workspace, chunks);
-  return pg_launched("pg_alignment_trace_long");
+    return trace_fail("pg_alignment_trace_long", PG_E_BADARG, "mode must be 0 (global), 1 (local) or 2 (semi-global)");
+  return trace_run("pg_alignment_trace_long", mode, x_packed, n, x_npad, xl, y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+                   gap_open, head, ops, ldo, workspace, workspace_bytes, stream);
+}
+
+// mode PG_TR_FIT: all of y within any substring of x (pg_aln_trace.h).  The entry above goes on rejecting mode 3.
+int pg_alignment_fit_trace_long(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+    int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
+    int32_t *head, uint8_t *ops, int64_t ldo, void *workspace, int64_t workspace_bytes, void *stream) {
+  return trace_run("pg_alignment_fit_trace_long", PG_TR_FIT, x_packed, n, x_npad, xl, y_packed, m, y_npad, yl, xi, yi, npairs, table, gap,
+                   gap_open, head, ops, ldo, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

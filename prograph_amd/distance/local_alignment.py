@@ -44,7 +44,8 @@ instances with equal table, gap and gap_open behave identically.
 edges: see prograph_amd/alignments.py.
 
 `_score_operator` below is everything but the recurrence: the table's rules, the routes and the blocking of the torch
-expression.  `semiglobal_alignment` (semiglobal_alignment.py) is its other subclass.
+expression.  `semiglobal_alignment` (semiglobal_alignment.py) and `fit_alignment` (fit_alignment.py) are its other
+subclasses.
 """
 import numpy as np
 import torch
@@ -126,17 +127,39 @@ class _score_operator:
             self._on[key] = torch.from_numpy(self._table.astype(np.int32)).to(dev)
         return self._on[key]
 
-    def _native_dense(self, xo, yo, out_bytes, rows=None):
-        """The kernel up to 128 positions on two AlnOperands."""
+    def _native_dense(self, xo, yo, out_bytes, rows=None, bias=0):
+        """The kernel up to 128 positions on two AlnOperands.  `bias`: `_select_bias`'s shift, 0 for every score that
+        cannot be negative (only `fit_alignment`'s kernels take one)."""
+        assert not bias
         return getattr(_native, self._DENSE)(xo, yo, self.device_score(), self._gap, self._open, out_bytes=out_bytes, rows=rows)
 
-    def _native_long_dense(self, xo, yo, out_bytes, rows=None):
+    def _native_long_dense(self, xo, yo, out_bytes, rows=None, bias=0):
         """The strip-mined kernel up to 2048 positions; exact inside `_long_fits`."""
+        assert not bias
         return getattr(_native, self._LONG_DENSE)(xo, yo, self.device_score(), self._gap, self._open, out_bytes=out_bytes,
                                                    rows=rows)
 
     def _long_fits(self, width_x, width_y):
         return getattr(_native, self._LONG_FITS)(width_x, width_y, self.max_score)
+
+    def _short_fits(self, width_x, width_y):
+        """Is the kernel up to 128 positions exact at these widths?  Always, but for `fit_alignment`."""
+        return True
+
+    # what `Prograph._local_select` asks an instance (prograph.py): the shift that makes a block non-negative, and whether
+    # operands of these widths (x: the columns, y: the rows / queries) take the fp16 or the int32 selection
+    def _select_bias(self, width_y):
+        return 0
+
+    def _f16_route(self, width_x, width_y):
+        """At most 128 positions, and every score - at most width * max(S) - an integer that is exact in fp16."""
+        width = max(width_x, width_y)
+        return width <= _native.ALN_MAX_L and width * self.max_score <= 2048
+
+    def _i32_route(self, width_x, width_y):
+        """Beyond 128 positions, with a device, inside the strip-mined kernel's 16-bit cells."""
+        return (max(width_x, width_y) > _native.ALN_MAX_L and _native.aln_long_ready()
+                and self._long_fits(width_x, width_y))
 
     def _torch_expression(self, X, Y):
         """The definition as a torch expression: X (N, D), Y (M, D) uint8 on one device -> (M, N) int64."""
@@ -166,7 +189,7 @@ class _score_operator:
         yb = xb if Y is X else _as_byte_tokens(Y)
         if xb is None or yb is None:
             raise ValueError(f"{name}: the tokens must be integers in 0..255")
-        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L
+        native = xb.is_cuda and 1 <= xb.shape[1] <= _native.ALN_MAX_L and self._short_fits(xb.shape[1], yb.shape[1])
         long = (not native and xb.is_cuda and _native.aln_long_ready()
                 and self._long_fits(xb.shape[1], yb.shape[1]))
         if long:                                                              # 129..2048 positions inside the 16-bit cells

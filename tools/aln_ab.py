@@ -32,11 +32,16 @@ medians with min / max.
   semiglobal_long  `pg_alignment_semiglobal_long_dense` beside `pg_alignment_local_long_dense` at `long`'s shape (4096 x
           20 000 int32, rows of 300..400 tokens); the first rows compared with the operator's torch expression.  Both write
           profiles/aln_semiglobal_ab.txt unless --out is given.
+  fit     §4.23: `pg_alignment_fit_dense` beside the unchanged `pg_alignment_semiglobal_dense` under the same score table at
+          `semiglobal`'s two dense shapes - time and the ratio of the two in the same run (the loop body is the same; one fold
+          after the loop fewer: a ratio near 1); the first rows compared with the operator's torch expression.
+  fit_long  `pg_alignment_fit_long_dense` beside `pg_alignment_semiglobal_long_dense` at `long`'s shape.  Both write
+          profiles/aln_fit_ab.txt unless --out is given.
   pmc     one dense call and nothing else: the program of a counters-only `rocprofv3 --pmc` run.
 
 Prints one JSON line; progress goes to stderr.
 
-    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local,long,long_graph,semiglobal,semiglobal_long] [--out FILE]
+    python tools/aln_ab.py [--reps 5] [--only dense,graph,affine,affine_graph,local,long,long_graph,semiglobal,semiglobal_long,fit,fit_long] [--out FILE]
 """
 import argparse
 import json
@@ -50,7 +55,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from prograph_amd import Prograph, _native  # noqa: E402
-from prograph_amd.distance import alignment, local_alignment, semiglobal_alignment  # noqa: E402
+from prograph_amd.distance import alignment, fit_alignment, local_alignment, semiglobal_alignment  # noqa: E402
 
 # VALU instructions of one outer step (one X symbol against 16 * chunks cells) in the gfx950 ISA of pg_aln_dense_kernel.
 # Counted by hand from the compiler's assembly (`--save-temps`; the table is in profiles/aln_dense.txt).  Nothing keeps it
@@ -400,8 +405,60 @@ def main():
         out["semiglobal_long"] = res
         del outs, xo, tok, fns
         torch.cuda.empty_cache()
+    if "fit" in only:
+        n, m, tr = args.n, args.rows, args.torch_rows
+        rng = np.random.default_rng(7)
+        for name, lo, hi in (("l125_128", 125, 128), ("l64", 64, 64)):
+            top = (2048 - 11 - hi) // hi                                       # shifted scores stay fp16-exact: K + width * max(S) <= 2048
+            S = np.triu(rng.integers(-4, 1, (a, a)), 1)
+            S = S + S.T + np.diag(rng.integers(top // 2, top + 1, a))
+            S[1, 1] = top
+            score, semi = fit_alignment(S, 1, gap_open=11), semiglobal_alignment(S, 1, gap_open=11)
+            host, lens = varlen(rng, n, lo, hi, a)
+            tok = torch.from_numpy(host).to(dev)
+            xo = _native.aln_operand(tok, a)
+            K = score._select_bias(xo.l)
+            assert xo.valid() and score._f16_route(xo.l, xo.l)
+            fns = {"alignment_fit_dense_f16": lambda: score._native_dense(xo, xo, 2, rows=(0, m), bias=K),
+                   "alignment_semiglobal_dense_f16": lambda: semi._native_dense(xo, xo, 2, rows=(0, m))}
+            res, outs = alternate(fns, args.reps, "fit " + name)
+            same = bool(torch.equal(outs["alignment_fit_dense_f16"][:tr].to(torch.int64) - K, score._torch_expression(tok, tok[:tr])))
+            ms = res["alignment_fit_dense_f16"]["median_ms"]
+            res.update(n=n, rows=m, lengths=[lo, hi], symbols=a, gap=score.gap, gap_open=score.gap_open, max_score=score.max_score,
+                       bias=K, pairs_per_s=m * n / (ms * 1e-3),
+                       cell_updates_per_s=float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3),
+                       ratio_to_semiglobal=ms / res["alignment_semiglobal_dense_f16"]["median_ms"],
+                       torch_rows=tr, first_rows_equal_torch=same)
+            out["fit_" + name] = res
+            del outs, xo, tok, fns
+            torch.cuda.empty_cache()
+    if "fit_long" in only:
+        n, m, tr = 20_000, 4096, args.torch_rows
+        rng = np.random.default_rng(8)
+        S = np.triu(rng.integers(-4, 1, (a, a)), 1)
+        S = S + S.T + np.diag(rng.integers(4, 12, a))
+        score, semi = fit_alignment(S, 1, gap_open=11), semiglobal_alignment(S, 1, gap_open=11)
+        host, lens = varlen(rng, n, 300, 400, a)
+        tok = torch.from_numpy(host).to(dev)
+        xo = _native.aln_long_operand(tok, a)
+        assert xo.valid() and score._long_fits(400, 400) and semi._long_fits(400, 400)
+        fns = {"alignment_fit_long_dense_i32": lambda: score._native_long_dense(xo, xo, 4, rows=(0, m)),
+               "alignment_semiglobal_long_dense_i32": lambda: semi._native_long_dense(xo, xo, 4, rows=(0, m))}
+        res, outs = alternate(fns, args.reps, "fit_long")
+        ms = res["alignment_fit_long_dense_i32"]["median_ms"]
+        res.update(n=n, rows=m, lengths=[300, 400], symbols=a, gap=score.gap, gap_open=score.gap_open, max_score=score.max_score,
+                   torch_rows=tr, pairs_per_s=m * n / (ms * 1e-3),
+                   cell_updates_per_s=float(lens[:m].astype(np.float64).sum() * lens.astype(np.float64).sum()) / (ms * 1e-3),
+                   ratio_to_semiglobal=ms / res["alignment_semiglobal_long_dense_i32"]["median_ms"],
+                   first_rows_equal_torch=bool(torch.equal(outs["alignment_fit_long_dense_i32"][:tr].to(torch.int64),
+                                                           score._torch_expression(tok, tok[:tr]))))
+        out["fit_long"] = res
+        del outs, xo, tok, fns
+        torch.cuda.empty_cache()
     line = json.dumps(out)
     print(line)
+    if args.out is None and ("fit" in only or "fit_long" in only):
+        args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "aln_fit_ab.txt")
     if args.out is None and ("semiglobal" in only or "semiglobal_long" in only):
         args.out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "aln_semiglobal_ab.txt")
     if args.out is None and ("long" in only or "long_graph" in only):
