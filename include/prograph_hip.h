@@ -83,7 +83,7 @@ extern "C" {
 #define PG_CMP_EQ 2
 #define PG_CMP_GE 3
 #define PG_CMP_GT 4
-/* OR-ed into `cmp` of pg_f16_eps_*, pg_minkowski_eps_* and pg_cosine_eps_* (no other entry takes it): keep the pairs
+/* OR-ed into `cmp` of pg_f16_eps_*, pg_minkowski_eps_*, pg_cosine_eps_* and pg_euclidean_eps_* (no other entry takes it): keep the pairs
  * with d == 0 (similarities: s == 1) that those entries otherwise exclude - the rows of QUERIES, where a vector
  * equal to the query is a hit.  Without the flag the entries behave as before.                                   */
 #define PG_CMP_KEEP_ZERO 0x10
@@ -807,6 +807,40 @@ int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const fl
                             const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
                             int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
                             const int64_t *indptr, int32_t *indices, float *weights, void *stream);
+
+/*
+ * Euclidean graphs of fp16 embeddings on the matrix cores: `build_graph(representation="Embedded",
+ * distance=euclidean)` (prograph_amd/csrc/pg_cos.hip).  The same kernels as the cosine entries with
+ * another epilogue on the same three fp32 sums p, nx, ny:
+ *   d = 0 if p == nx == ny bitwise (identical vectors, two zero vectors);
+ *       else sqrt(max((nx + ny) - (p + p), 0)), every step rounded to fp32, the root correctly rounded;
+ *   similarity != 0: s = 1/(1+d).  A zero vector is an ordinary point: d(0, y) = sqrt(ny).
+ * Stated tolerance against the exact d^2 of the fp16 values:  |d^2 - exact| <= B(D)(nx + ny) + 2^-22 exact,
+ * B(D) = 2 D 2^-24 + 2^-21: the form cancels, so a non-identical pair closer than that may come out as 0.
+ * Each entry has the argument list, the checks and the output of its pg_cosine_* twin; the operands are pg_pack_f16
+ * buffers with their pg_cosine_prep norms (the rnorms arrays must be given and are not read; the caller checks the
+ * non-finite flag).  There is no pg_euclidean_eps_compact: pg_cosine_eps_compact moves slots whatever metric filled
+ * them, so the Euclidean CSR is pg_euclidean_eps_slots, pg_exclusive_scan, pg_cosine_eps_compact and
+ * pg_euclidean_eps_fill_rows.
+ */
+int pg_euclidean_dense(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                       const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                       int similarity, float *out, int64_t ldo, void *stream);
+int pg_euclidean_knn(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                     const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
+                     int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream);
+int pg_euclidean_knn_round(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                           const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
+                           int d, int similarity, int k, const int32_t *floor_idx, const float *floor_w, int64_t floor_ld,
+                           int32_t *idx_out, float *w_out, int64_t ldo, void *stream);
+int pg_euclidean_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                           const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
+                           int d, int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w,
+                           uint32_t *counts, void *stream);
+int pg_euclidean_eps_fill_rows(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
+                               const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
+                               int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
+                               const int64_t *indptr, int32_t *indices, float *weights, void *stream);
 
 /*
  * Multi-GPU: the path's ONE collective (e).  The N^2 pair space shards row-block

@@ -21,7 +21,7 @@ ABI_VERSION = 3
 
 BITS_5, BITS_8 = 5, 8
 CMP_LE, CMP_LT, CMP_EQ, CMP_GE, CMP_GT = 0, 1, 2, 3, 4
-CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine eps entries: d = 0 (s = 1) is a hit
+CMP_KEEP_ZERO = 0x10          # OR-ed into cmp of the fp16 / Minkowski / cosine / Euclidean eps entries: d = 0 (s = 1) is a hit
 MAX_L, MAX_L_5BIT, MAX_K, MAX_K_ROUNDS, MAX_N_KNN, LEV_MAX_BAND = 128, 255, 63, 1023, 1 << 24, 8
 SUB_MAX_L, SUB_MAX_A = 2048, 32   # pg_substitution_dense: positions per call, symbols of the cost table
 ALN_MAX_L, ALN_MAX_GAP = 128, 255 # pg_alignment_dense: positions per operand, the largest gap penalty (tables as above)
@@ -54,6 +54,7 @@ SYMBOLS = [
     "pg_f16_eps_fill", "pg_minkowski_knn", "pg_minkowski_knn_round", "pg_minkowski_eps_slots", "pg_minkowski_eps_compact",
     "pg_minkowski_eps_fill_rows", "pg_cosine_prep", "pg_cosine_dense", "pg_cosine_knn", "pg_cosine_knn_round",
     "pg_cosine_eps_slots", "pg_cosine_eps_compact", "pg_cosine_eps_fill_rows",
+    "pg_euclidean_dense", "pg_euclidean_knn", "pg_euclidean_knn_round", "pg_euclidean_eps_slots", "pg_euclidean_eps_fill_rows",
     "pg_query_workspace_bytes", "pg_query_knn_hamming",
     "pg_query_eps_segments", "pg_query_eps_count", "pg_query_eps_fill",
 ]
@@ -67,6 +68,7 @@ _lib = None
 _lock = threading.Lock()
 
 _i64, _i32, _vp, _dbl = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_double
+_COS_METRICS = ("cosine", "euclidean")      # the metrics of pg_cos.hip: pg_<metric>_dense / _knn / _knn_round / _eps_*
 
 
 def _load():
@@ -186,14 +188,15 @@ def _load():
         lib.pg_minkowski_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_minkowski_eps_fill_rows.argtypes = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _vp,
                                                    _i64, _vp, _vp, _vp, _vp]
-        _ops = [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32]     # x, y operands of pg_cosine_*
+        _ops = [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _i32]     # x, y operands of pg_cosine_* / pg_euclidean_*
         lib.pg_cosine_prep.argtypes = [_vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]
-        lib.pg_cosine_dense.argtypes = _ops + [_vp, _i64, _vp]
-        lib.pg_cosine_knn.argtypes = _ops + [_i32, _i32, _vp, _vp, _vp]
-        lib.pg_cosine_knn_round.argtypes = _ops + [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
-        lib.pg_cosine_eps_slots.argtypes = _ops + [_i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
         lib.pg_cosine_eps_compact.argtypes = [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
-        lib.pg_cosine_eps_fill_rows.argtypes = _ops + [_i32, ctypes.c_float, _vp, _i64, _vp, _vp, _vp, _vp]
+        for metric in _COS_METRICS:
+            getattr(lib, f"pg_{metric}_dense").argtypes = _ops + [_vp, _i64, _vp]
+            getattr(lib, f"pg_{metric}_knn").argtypes = _ops + [_i32, _i32, _vp, _vp, _vp]
+            getattr(lib, f"pg_{metric}_knn_round").argtypes = _ops + [_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
+            getattr(lib, f"pg_{metric}_eps_slots").argtypes = _ops + [_i32, ctypes.c_float, _i32, _vp, _vp, _vp, _vp]
+            getattr(lib, f"pg_{metric}_eps_fill_rows").argtypes = _ops + [_i32, ctypes.c_float, _vp, _i64, _vp, _vp, _vp, _vp]
         lib.pg_comm_unique_id.argtypes = [_vp]
         lib.pg_comm_init.argtypes = [ctypes.POINTER(_vp), _i32, _i32, _vp]
         lib.pg_comm_destroy.argtypes = [_vp]
@@ -1543,31 +1546,79 @@ def _cos_same_d(xc, yc):
         raise ValueError("operands must have the same dimension")
 
 
-def cosine_dense(xc, yc, similarity=False):
-    """(M, N) fp32 block: cosine distance (or 1/(1+d)) of every Y vector against every X vector (pg_cosine_dense).
-    Operands from cosine_prep; the caller checks their non-finite flags."""
+def _cos_dense(metric, xc, yc, similarity):
     _cos_same_d(xc, yc)
+    entry = f"pg_{metric}_dense"
+    fn = getattr(lib(), entry)
     dev = xc.packed.buf.device
     out = torch.empty((yc.n, xc.n), dtype=torch.float32, device=dev)
     for r0 in range(0, yc.n, 65535 * 32):                            # grid.y limit of one launch
         y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + 65535 * 32))
-        _check(lib().pg_cosine_dense(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, _ptr(out[r0:]),
-                                     out.stride(0), _stream()), "pg_cosine_dense")
+        _check(fn(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, _ptr(out[r0:]), out.stride(0), _stream()),
+               entry)
     return out
 
 
-_COS_ROWS = 1 << 20          # Y rows per launch of the fused cosine kernels
+_COS_ROWS = 1 << 20          # Y rows per launch of the fused cosine / Euclidean kernels
+
+
+def _cos_knn_round(metric, xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity, rows_per_block):
+    entry = f"pg_{metric}_knn_round"
+    fn = getattr(lib(), entry)
+    fld, ldo = floor_idx.stride(0), idx_out.stride(0)
+    for r0 in range(0, yc.n, rows_per_block):
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
+        _check(fn(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k), _ptr(floor_idx[r0:]),
+                  _ptr(floor_w[r0:]), fld, _ptr(idx_out[r0:]), _ptr(w_out[r0:]), ldo, _stream()), entry)
+
+
+def _cos_knn(metric, xc, yc, k, first, similarity, rows_per_block):
+    _cos_same_d(xc, yc)
+    if first + k > 64:
+        head, more = globals()[metric + "_knn"], globals()[metric + "_knn_round"]      # the public wrappers, as they are now
+        return knn_rounds(yc.n, int(k), int(first), torch.float32, xc.packed.buf.device,
+                          lambda kk: head(xc, yc, kk, first, similarity, rows_per_block),
+                          lambda kk, fi, fw, oi, ow: more(xc, yc, kk, fi, fw, oi, ow, similarity, rows_per_block))
+    entry = f"pg_{metric}_knn"
+    fn = getattr(lib(), entry)
+    dev = xc.packed.buf.device
+    idx = torch.empty((yc.n, int(k)), dtype=torch.int32, device=dev)
+    w = torch.empty((yc.n, int(k)), dtype=torch.float32, device=dev)
+    for r0 in range(0, yc.n, rows_per_block):
+        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
+        _check(fn(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k), int(first), _ptr(idx[r0:]),
+                  _ptr(w[r0:]), _stream()), entry)
+    return idx, w
+
+
+def _cos_eps(metric, xc, yc, cmp, eps, similarity, cap, keep_zero, rows_per_block):
+    _cos_same_d(xc, yc)
+    L = lib()
+    cap = max(1, int(cap))
+    sel = (1 if similarity else 0, int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0), float(np.float32(eps)))
+    slots, fill = f"pg_{metric}_eps_slots", f"pg_{metric}_eps_fill_rows"
+
+    def call(name, ops, *args):
+        _check(getattr(L, name)(*_cos_ops(xc, *ops, yc.packed.npad), *sel, *args, _stream()), name)
+
+    return _slots_eps(
+        yc.n, yc.rows,
+        lambda ops, si, sw, cnt: call(slots, ops, cap, _ptr(si), _ptr(sw), _ptr(cnt)),
+        lambda *a: _check(L.pg_cosine_eps_compact(*a), "pg_cosine_eps_compact"),     # metric-free
+        lambda ops, rows, n_over, ip, ix, w: call(fill, ops, _ptr(rows), n_over, _ptr(ip), _ptr(ix), _ptr(w)),
+        torch.float32, cap, rows_per_block, xc.packed.buf.device)
+
+
+def cosine_dense(xc, yc, similarity=False):
+    """(M, N) fp32 block: cosine distance (or 1/(1+d)) of every Y vector against every X vector (pg_cosine_dense).
+    Operands from cosine_prep; the caller checks their non-finite flags."""
+    return _cos_dense("cosine", xc, yc, similarity)
 
 
 def cosine_knn_round(xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity=False, rows_per_block=_COS_ROWS):
     """One round of pg_cosine_knn_round: the next k <= 64 ranks of every Y row after its floor, one fused sweep per
     block of Y rows (views as for f16_knn_round)."""
-    fld, ldo = floor_idx.stride(0), idx_out.stride(0)
-    for r0 in range(0, yc.n, rows_per_block):
-        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
-        _check(lib().pg_cosine_knn_round(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k),
-                                         _ptr(floor_idx[r0:]), _ptr(floor_w[r0:]), fld, _ptr(idx_out[r0:]), _ptr(w_out[r0:]),
-                                         ldo, _stream()), "pg_cosine_knn_round")
+    _cos_knn_round("cosine", xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity, rows_per_block)
 
 
 def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
@@ -1575,19 +1626,7 @@ def cosine_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
     for similarities, ties by column - in one fused sweep (pg_cosine_knn), Y rows in blocks.
     Returns (idx int32 (m, k), w fp32 (m, k)); missing ranks idx -1, weight 0.
     first + k > 64 (k <= MAX_K_ROUNDS): one more sweep per 64 ranks (knn_rounds), in the same row blocks."""
-    _cos_same_d(xc, yc)
-    if first + k > 64:
-        return knn_rounds(yc.n, int(k), int(first), torch.float32, xc.packed.buf.device,
-                          lambda kk: cosine_knn(xc, yc, kk, first, similarity, rows_per_block),
-                          lambda kk, fi, fw, oi, ow: cosine_knn_round(xc, yc, kk, fi, fw, oi, ow, similarity, rows_per_block))
-    dev = xc.packed.buf.device
-    idx = torch.empty((yc.n, int(k)), dtype=torch.int32, device=dev)
-    w = torch.empty((yc.n, int(k)), dtype=torch.float32, device=dev)
-    for r0 in range(0, yc.n, rows_per_block):
-        y, yn, yr, m = yc.rows(r0, min(yc.n, r0 + rows_per_block))
-        _check(lib().pg_cosine_knn(*_cos_ops(xc, y, yn, yr, m, yc.packed.npad), 1 if similarity else 0, int(k), int(first),
-                                   _ptr(idx[r0:]), _ptr(w[r0:]), _stream()), "pg_cosine_knn")
-    return idx, w
+    return _cos_knn("cosine", xc, yc, k, first, similarity, rows_per_block)
 
 
 def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False, rows_per_block=None):
@@ -1596,21 +1635,29 @@ def cosine_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False, row
     structure (_slots_eps): one sweep into per-row slots with exact counts, scan, compaction, and a second sweep over
     the rows with more than `cap` matches; one host sync per block of rows.  keep_zero: without the d > 0 (s < 1) test.
     Returns (indptr int64 [m+1], indices int32 [nnz], weights fp32 [nnz])."""
-    _cos_same_d(xc, yc)
-    L = lib()
-    cap = max(1, int(cap))
-    sel = (1 if similarity else 0, int(cmp) | (CMP_KEEP_ZERO if keep_zero else 0), float(np.float32(eps)))
+    return _cos_eps("cosine", xc, yc, cmp, eps, similarity, cap, keep_zero, rows_per_block)
 
-    def call(fn, name, ops, *args):
-        _check(fn(*_cos_ops(xc, *ops, yc.packed.npad), *sel, *args, _stream()), name)
 
-    return _slots_eps(
-        yc.n, yc.rows,
-        lambda ops, si, sw, cnt: call(L.pg_cosine_eps_slots, "pg_cosine_eps_slots", ops, cap, _ptr(si), _ptr(sw), _ptr(cnt)),
-        lambda *a: _check(L.pg_cosine_eps_compact(*a), "pg_cosine_eps_compact"),
-        lambda ops, rows, n_over, ip, ix, w: call(L.pg_cosine_eps_fill_rows, "pg_cosine_eps_fill_rows", ops, _ptr(rows), n_over,
-                                                  _ptr(ip), _ptr(ix), _ptr(w)),
-        torch.float32, cap, rows_per_block, xc.packed.buf.device)
+def euclidean_dense(xc, yc, similarity=False):
+    """cosine_dense with the Euclidean epilogue (pg_euclidean_dense): d = sqrt(max((nx + ny) - 2p, 0)) in fp32 steps, 0
+    for identical vectors.  Operands from cosine_prep (their reciprocal roots are not read)."""
+    return _cos_dense("euclidean", xc, yc, similarity)
+
+
+def euclidean_knn_round(xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity=False, rows_per_block=_COS_ROWS):
+    """cosine_knn_round over the Euclidean values (pg_euclidean_knn_round)."""
+    _cos_knn_round("euclidean", xc, yc, k, floor_idx, floor_w, idx_out, w_out, similarity, rows_per_block)
+
+
+def euclidean_knn(xc, yc, k, first=1, similarity=False, rows_per_block=_COS_ROWS):
+    """cosine_knn over euclidean_dense(xc, yc, similarity) (pg_euclidean_knn; first + k > 64 in rounds up to MAX_K_ROUNDS)."""
+    return _cos_knn("euclidean", xc, yc, k, first, similarity, rows_per_block)
+
+
+def euclidean_eps(xc, yc, cmp, eps, similarity=False, cap=256, keep_zero=False, rows_per_block=None):
+    """cosine_eps over euclidean_dense(xc, yc, similarity) (pg_euclidean_eps_slots / pg_euclidean_eps_fill_rows; the
+    compaction is the metric-free pg_cosine_eps_compact)."""
+    return _cos_eps("euclidean", xc, yc, cmp, eps, similarity, cap, keep_zero, rows_per_block)
 
 
 COMM_ID_BYTES = 128

@@ -20,6 +20,10 @@
 // The 32x32 result has the X column on the lane (l&31) and the Y rows in the 16 registers: register r of lane
 // half h is row (r&3) + 8(r>>2) + 4h.  The dense kernel writes it out; the fused kernels select from it in
 // registers.  Both call cs_tile and cs_finish, so the fused graphs are exactly the selection over the dense block.
+//
+// Euclidean distance, `distance=euclidean`, is a second epilogue on the same three sums: every kernel
+// below except the norm pass is a template over the epilogue and is instantiated for both metrics, and the pg_euclidean_*
+// entries share the pg_cosine_* entries' argument lists, checks and launch code.
 #include "pg_select.h"
 
 typedef _Float16 cs_h8 __attribute__((ext_vector_type(8)));
@@ -67,6 +71,32 @@ __device__ __forceinline__ float cs_finish(float p, float nx, float rx, float ny
   return similarity ? 1.0f / (1.0f + d) : d;
 }
 
+// Euclidean epilogue on the same three sums: d = sqrt(max((nx + ny) - (p + p), 0)), every step rounded
+// to fp32 and the root correctly rounded; identical vectors (p == nx == ny bitwise, two zero vectors included) are
+// exactly 0, and a zero vector is an ordinary point: d(0, y) = sqrt(ny).
+__device__ __forceinline__ float eu_finish(float p, float nx, float ny, int similarity) {
+  float d;
+  if (__float_as_uint(p) == __float_as_uint(nx) && __float_as_uint(p) == __float_as_uint(ny)) {
+    d = 0.0f;
+  } else {
+    d = sqrtf(fmaxf((nx + ny) - (p + p), 0.0f));
+  }
+  return similarity ? 1.0f / (1.0f + d) : d;
+}
+
+// The epilogue of a kernel instance: the dense, kNN and eps kernels below are templates over one of these and share
+// everything else.  The Euclidean instances never read the reciprocal roots.
+struct cs_cosine {
+  static __device__ __forceinline__ float finish(float p, float nx, float rx, float ny, float ry, int similarity) {
+    return cs_finish(p, nx, rx, ny, ry, similarity);
+  }
+};
+struct cs_euclid {
+  static __device__ __forceinline__ float finish(float p, float nx, float, float ny, float, int similarity) {
+    return eu_finish(p, nx, ny, similarity);
+  }
+};
+
 // sortable key of a non-negative fp32 value: ascending distance, or descending similarity (s > 0: never ~0u)
 __device__ __forceinline__ u32 cs_key(float v, int descending) {
   const u32 b = __float_as_uint(v);
@@ -112,7 +142,8 @@ __device__ __forceinline__ void cs_col_norms(const float *__restrict__ nx, const
   b = col < n ? rx[col] : 0.0f;
 }
 
-// (M, N) fp32 block: out[m * ldo + n] = cosine distance (or similarity) of Y[m] and X[n]; a wave per 32 x 32 tile
+// (M, N) fp32 block: out[m * ldo + n] = distance (or similarity) of Y[m] and X[n] by epilogue E; a wave per 32 x 32 tile
+template <class E>
 __global__ __launch_bounds__(256) void pg_cos_dense_kernel(const uint4 *__restrict__ xp, const float *__restrict__ nx,
                                                            const float *__restrict__ rx, long long n, long long xnpad,
                                                            const uint4 *__restrict__ yp, const float *__restrict__ ny,
@@ -129,7 +160,7 @@ __global__ __launch_bounds__(256) void pg_cos_dense_kernel(const uint4 *__restri
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const long long row = y0 + cs_row(r, h);
-    if (row < m && col < n) out[row * ldo + col] = cs_finish(acc[r], ncol, rcol, ny[row], ry[row], similarity);
+    if (row < m && col < n) out[row * ldo + col] = E::finish(acc[r], ncol, rcol, ny[row], ry[row], similarity);
   }
 }
 
@@ -151,7 +182,7 @@ __device__ __forceinline__ long long cs_wave_row(int i, long long m, const long 
 // FLOOR (pg_cosine_knn_round, first = 0): only pairs after each row's floor are candidates, rows written ldo elements
 // apart.  The floors sit lane-per-row in one VGPR pair (lane i and i + 32: row slot i, the cs_wave_row order) and are
 // read with readlane, instead of 32 more per-row values next to the lists.
-template <bool FLOOR>
+template <class E, bool FLOOR>
 __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict__ xp, const float *__restrict__ nx,
                                                          const float *__restrict__ rx, long long n, long long xnpad,
                                                          const uint4 *__restrict__ yp, const float *__restrict__ ny,
@@ -184,7 +215,7 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int i0 = cs_row(r, 0), i1 = cs_row(r, 1);
-      const u32 key = cs_key(cs_finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity), similarity);
+      const u32 key = cs_key(E::finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity), similarity);
       const u32 thk = h ? tk[i1] : tk[i0], thc = h ? tc[i1] : tc[i0];
       bool cand = cok && (key < thk || (key == thk && (u32)col < thc));
       if (FLOOR) {
@@ -213,6 +244,7 @@ __global__ __launch_bounds__(256) void pg_cos_knn_kernel(const uint4 *__restrict
 // first `cap` matches (ascending columns) into its slot.  Fill mode: the rows of row_list only, every match written
 // at indptr[row] (counts from a slot pass, so the segments fit).  A lane keeps the running count and output base of
 // the row of each of its registers.
+template <class E>
 __global__ __launch_bounds__(256) void pg_cos_eps_kernel(const uint4 *__restrict__ xp, const float *__restrict__ nx,
                                                          const float *__restrict__ rx, long long n, long long xnpad,
                                                          const uint4 *__restrict__ yp, const float *__restrict__ ny,
@@ -249,7 +281,7 @@ __global__ __launch_bounds__(256) void pg_cos_eps_kernel(const uint4 *__restrict
     cs_col_norms(nx, rx, col, n, ncol, rcol);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float v = cs_finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity);
+      const float v = E::finish(acc[r], ncol, rcol, nyv[r], ryv[r], similarity);
       const bool hit = cok && rok[r] && pg_match(v, eps, cmp, similarity);
       const u64 mask = __builtin_amdgcn_ballot_w64(hit);
       if (!mask) continue;                                           // wave-uniform
@@ -286,6 +318,89 @@ static int cs_operands_bad(const void *xp, const float *xn, const float *xr, int
 // workgroups of CS_WAVES waves, a wave per 32 rows
 static long long cs_groups(int64_t rows) { return (rows + CS_T * CS_WAVES - 1) / (CS_T * CS_WAVES); }
 
+// "<entry>: <what>" as the error message of an argument check
+static int cs_bad(const char *entry, const char *what) {
+  char buf[160];
+  snprintf(buf, sizeof(buf), "%s: %s", entry, what);
+  return pg_fail(PG_E_BADARG, buf);
+}
+
+// The bodies of the pg_cosine_* / pg_euclidean_* entries: the argument checks and the launch of epilogue E's instance.
+template <class E>
+static int cs_dense(const char *entry, const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n,
+                    int64_t x_npad, const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m,
+                    int64_t y_npad, int d, int similarity, float *out, int64_t ldo, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !out || ldo < n)
+    return cs_bad(entry, "bad argument");
+  if ((m + CS_T - 1) / CS_T > 65535 || cs_groups(n) > 0x7FFFFFFFll) return cs_bad(entry, "m too large for one launch");
+  const dim3 grid((unsigned)cs_groups(n), (unsigned)((m + CS_T - 1) / CS_T));
+  pg_cos_dense_kernel<E><<<grid, dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, out, ldo);
+  return pg_launched(entry);
+}
+
+template <class E>
+static int cs_knn(const char *entry, const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n,
+                  int64_t x_npad, const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
+                  int d, int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out)
+    return cs_bad(entry, "bad argument");
+  if (k < 1 || first < 0 || first + k > 64) return cs_bad(entry, "first + k must be at most 64");
+  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return cs_bad(entry, "too many vectors for one launch");
+  pg_cos_knn_kernel<E, false><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, k, first, idx_out, w_out, nullptr, nullptr, 0, k);
+  return pg_launched(entry);
+}
+
+template <class E>
+static int cs_knn_round(const char *entry, const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n,
+                        int64_t x_npad, const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m,
+                        int64_t y_npad, int d, int similarity, int k, const int32_t *floor_idx, const float *floor_w,
+                        int64_t floor_ld, int32_t *idx_out, float *w_out, int64_t ldo, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out ||
+      !floor_idx || !floor_w || floor_ld < 0 || ldo < k)
+    return cs_bad(entry, "bad argument");
+  if (k < 1 || k > 64) return cs_bad(entry, "k must be 1..64");
+  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return cs_bad(entry, "too many vectors for one launch");
+  pg_cos_knn_kernel<E, true><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, k, 0, idx_out, w_out, floor_idx, floor_w, floor_ld, ldo);
+  return pg_launched(entry);
+}
+
+template <class E>
+static int cs_eps_slots(const char *entry, const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n,
+                        int64_t x_npad, const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m,
+                        int64_t y_npad, int d, int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w,
+                        uint32_t *counts, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !slot_idx ||
+      !slot_w || !counts || cap < 1 || pg_cmp_bad(cmp))
+    return cs_bad(entry, "bad argument");
+  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return cs_bad(entry, "too many vectors for one launch");
+  pg_cos_eps_kernel<E><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, cmp, eps, nullptr, 0, cap, slot_idx, slot_w, counts, nullptr, nullptr, nullptr);
+  return pg_launched(entry);
+}
+
+template <class E>
+static int cs_eps_fill_rows(const char *entry, const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n,
+                            int64_t x_npad, const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m,
+                            int64_t y_npad, int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
+                            const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
+  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !row_list ||
+      n_list <= 0 || !indptr || !indices || !weights || pg_cmp_bad(cmp))
+    return cs_bad(entry, "bad argument");
+  if (n > 0x7FFFFFFFll || cs_groups(n_list) > 0x7FFFFFFFll) return cs_bad(entry, "too many vectors for one launch");
+  pg_cos_eps_kernel<E><<<dim3((unsigned)cs_groups(n_list)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
+      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
+      similarity ? 1 : 0, cmp, eps, (const long long *)row_list, n_list, 1, nullptr, nullptr, nullptr,
+      (const long long *)indptr, indices, weights);
+  return pg_launched(entry);
+}
+
 extern "C" {
 
 int pg_cosine_prep(const void *packed, int64_t n, int64_t npad, int d, float *norms, float *rnorms, uint32_t *flags,
@@ -297,83 +412,40 @@ int pg_cosine_prep(const void *packed, int64_t n, int64_t npad, int d, float *no
   return pg_launched("pg_cos_prep_kernel");
 }
 
-int pg_cosine_dense(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
-                    const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
-                    int similarity, float *out, int64_t ldo, void *stream) {
-  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !out || ldo < n)
-    return pg_fail(PG_E_BADARG, "pg_cosine_dense: bad argument");
-  if ((m + CS_T - 1) / CS_T > 65535 || cs_groups(n) > 0x7FFFFFFFll)
-    return pg_fail(PG_E_BADARG, "pg_cosine_dense: m too large for one launch");
-  const dim3 grid((unsigned)cs_groups(n), (unsigned)((m + CS_T - 1) / CS_T));
-  pg_cos_dense_kernel<<<grid, dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
-      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, out, ldo);
-  return pg_launched("pg_cos_dense_kernel");
-}
+// One argument list per entry, shared by the two metrics (include/prograph_hip.h).
+#define CS_ENTRIES(METRIC, E)                                                                                              \
+  int pg_##METRIC##_dense(CS_OPS, float *out, int64_t ldo, void *stream) {                                                 \
+    return cs_dense<E>("pg_" #METRIC "_dense", CS_OPA, out, ldo, stream);                                                  \
+  }                                                                                                                        \
+  int pg_##METRIC##_knn(CS_OPS, int k, int first, int32_t *idx_out, float *w_out, void *stream) {                          \
+    return cs_knn<E>("pg_" #METRIC "_knn", CS_OPA, k, first, idx_out, w_out, stream);                                      \
+  }                                                                                                                        \
+  int pg_##METRIC##_knn_round(CS_OPS, int k, const int32_t *floor_idx, const float *floor_w, int64_t floor_ld,             \
+                              int32_t *idx_out, float *w_out, int64_t ldo, void *stream) {                                 \
+    return cs_knn_round<E>("pg_" #METRIC "_knn_round", CS_OPA, k, floor_idx, floor_w, floor_ld, idx_out, w_out, ldo,       \
+                           stream);                                                                                        \
+  }                                                                                                                        \
+  int pg_##METRIC##_eps_slots(CS_OPS, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w, uint32_t *counts,     \
+                              void *stream) {                                                                              \
+    return cs_eps_slots<E>("pg_" #METRIC "_eps_slots", CS_OPA, cmp, eps, cap, slot_idx, slot_w, counts, stream);           \
+  }                                                                                                                        \
+  int pg_##METRIC##_eps_fill_rows(CS_OPS, int cmp, float eps, const int64_t *row_list, int64_t n_list,                     \
+                                  const int64_t *indptr, int32_t *indices, float *weights, void *stream) {                 \
+    return cs_eps_fill_rows<E>("pg_" #METRIC "_eps_fill_rows", CS_OPA, cmp, eps, row_list, n_list, indptr, indices,        \
+                               weights, stream);                                                                           \
+  }
+#define CS_OPS                                                                                                     \
+  const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad, const void *y_packed, \
+      const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d, int similarity
+#define CS_OPA x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d, similarity
 
-int pg_cosine_knn(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
-                  const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
-                  int similarity, int k, int first, int32_t *idx_out, float *w_out, void *stream) {
-  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out)
-    return pg_fail(PG_E_BADARG, "pg_cosine_knn: bad argument");
-  if (k < 1 || first < 0 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_cosine_knn: first + k must be at most 64");
-  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll) return pg_fail(PG_E_BADARG, "pg_cosine_knn: too many vectors for one launch");
-  pg_cos_knn_kernel<false><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
-      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, k, first, idx_out, w_out, nullptr, nullptr, 0, k);
-  return pg_launched("pg_cos_knn_kernel");
-}
+CS_ENTRIES(cosine, cs_cosine)
+CS_ENTRIES(euclidean, cs_euclid)       // the Euclidean instances ignore x_rnorms / y_rnorms (they must still be given)
 
-int pg_cosine_knn_round(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
-                        const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
-                        int similarity, int k, const int32_t *floor_idx, const float *floor_w, int64_t floor_ld,
-                        int32_t *idx_out, float *w_out, int64_t ldo, void *stream) {
-  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !idx_out || !w_out ||
-      !floor_idx || !floor_w || floor_ld < 0 || ldo < k)
-    return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: bad argument");
-  if (k < 1 || k > 64) return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: k must be 1..64");
-  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
-    return pg_fail(PG_E_BADARG, "pg_cosine_knn_round: too many vectors for one launch");
-  pg_cos_knn_kernel<true><<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
-      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, k, 0, idx_out, w_out, floor_idx, floor_w, floor_ld, ldo);
-  return pg_launched("pg_cos_knn_kernel(round)");
-}
-
-int pg_cosine_eps_slots(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
-                        const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad, int d,
-                        int similarity, int cmp, float eps, int cap, int32_t *slot_idx, float *slot_w, uint32_t *counts,
-                        void *stream) {
-  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !slot_idx ||
-      !slot_w || !counts || cap < 1 || pg_cmp_bad(cmp))
-    return pg_fail(PG_E_BADARG, "pg_cosine_eps_slots: bad argument");
-  if (n > 0x7FFFFFFFll || cs_groups(m) > 0x7FFFFFFFll)
-    return pg_fail(PG_E_BADARG, "pg_cosine_eps_slots: too many vectors for one launch");
-  pg_cos_eps_kernel<<<dim3((unsigned)cs_groups(m)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
-      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, cmp, eps, nullptr, 0, cap, slot_idx, slot_w, counts, nullptr, nullptr, nullptr);
-  return pg_launched("pg_cos_eps_kernel(slots)");
-}
-
+// metric-free: the Euclidean slots go through this entry too
 int pg_cosine_eps_compact(int64_t m, int cap, const int32_t *slot_idx, const float *slot_w, const uint32_t *counts,
                           const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
   return pg_eps_compact_launch<float>("pg_cosine_eps_compact", m, cap, slot_idx, slot_w, counts, indptr, indices, weights, stream);
-}
-
-int pg_cosine_eps_fill_rows(const void *x_packed, const float *x_norms, const float *x_rnorms, int64_t n, int64_t x_npad,
-                            const void *y_packed, const float *y_norms, const float *y_rnorms, int64_t m, int64_t y_npad,
-                            int d, int similarity, int cmp, float eps, const int64_t *row_list, int64_t n_list,
-                            const int64_t *indptr, int32_t *indices, float *weights, void *stream) {
-  if (cs_operands_bad(x_packed, x_norms, x_rnorms, n, x_npad, y_packed, y_norms, y_rnorms, m, y_npad, d) || !row_list ||
-      n_list <= 0 || !indptr || !indices || !weights || pg_cmp_bad(cmp))
-    return pg_fail(PG_E_BADARG, "pg_cosine_eps_fill_rows: bad argument");
-  if (n > 0x7FFFFFFFll || cs_groups(n_list) > 0x7FFFFFFFll)
-    return pg_fail(PG_E_BADARG, "pg_cosine_eps_fill_rows: too many vectors for one launch");
-  pg_cos_eps_kernel<<<dim3((unsigned)cs_groups(n_list)), dim3(64 * CS_WAVES), 0, (hipStream_t)stream>>>(
-      (const uint4 *)x_packed, x_norms, x_rnorms, n, x_npad, (const uint4 *)y_packed, y_norms, y_rnorms, m, y_npad, cs_nq(d),
-      similarity ? 1 : 0, cmp, eps, (const long long *)row_list, n_list, 1, nullptr, nullptr, nullptr,
-      (const long long *)indptr, indices, weights);
-  return pg_launched("pg_cos_eps_kernel(fill)");
 }
 
 }  // extern "C"

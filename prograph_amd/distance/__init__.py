@@ -1,6 +1,7 @@
 from ..alignments import Alignments
 from .alignment import alignment
 from .cosine import cosine
+from .euclidean import euclidean
 from .fit_alignment import fit_alignment
 from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn

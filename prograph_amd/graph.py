@@ -9,7 +9,7 @@ zero-copy views into two host arrays.
 
 Weights are Hamming distances (uint8 / int16 / float32; similarities are formed on the host) or fp16 Minkowski values
 (distances or similarities as the kernels computed them: those are final and pass through unchanged).  `final=True`
-marks weights of any dtype as final values in the same way - the fp32 cosine distances or similarities.
+marks weights of any dtype as final values in the same way - the fp32 cosine or Euclidean distances or similarities.
 """
 import numpy as np
 import torch
@@ -134,7 +134,7 @@ class CSRGraph:
 
 class KNNGraph:
     """k nearest neighbours: idx int32 (n,k), dist uint8|int16|int32 (n,k) or fp16 Minkowski values; canonical (distance, index)
-    order (descending values for Minkowski similarities).  final=True: the values are final (cosine fp32) whatever
+    order (descending values for Minkowski similarities).  final=True: the values are final (cosine / Euclidean fp32) whatever
     their dtype.  first: the rank of column 0 - 1 for self-graphs (rank 0 dropped, ranks beyond N-1 do not exist), 0 for
     query results (`Prograph.search`: rank 0 kept, min(k, N) ranks)."""
 

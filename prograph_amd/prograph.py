@@ -34,8 +34,10 @@ import torch
 
 from . import _native
 from . import alignments as _alignments
-from .distance import (alignment, cosine, fit_alignment, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment,
+from .distance import (alignment, cosine, euclidean, fit_alignment, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment,
                        substitution)
+
+_EMBED_F32 = {cosine: "cosine", euclidean: "euclidean"}      # fp32 embedding metrics of pg_cos.hip -> their _native prefix
 
 _SCORES = (local_alignment, semiglobal_alignment, fit_alignment)      # similarities: ranked largest first (`_local_select`)
 from .graph import CSRGraph, KNNGraph
@@ -475,7 +477,7 @@ class Prograph:
         queries and dataset is right-padded with zeros.  Returns a list of Q `(indices, weights)` tuples in rank order,
         or with `output="csr"` a device `KNNGraph` with Q rows whose columns are dataset rows.
         Hamming runs the fused query kernels (`pg_query_knn_hamming`, `pg_query_eps_*`), sequences beyond one record the
-        dense kernel plus the fp16 selection; Minkowski and cosine the fused embedding kernels; Levenshtein (queries of
+        dense kernel plus the fp16 selection; Minkowski, cosine and Euclidean the fused embedding kernels; Levenshtein (queries of
         any length up to 2048, not only the dataset's) blocks of `pg_levenshtein_dense`, or of `pg_levenshtein_long_dense`
         when queries or dataset are wider than 128 positions, plus the fp16 selection; a
         `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; an `alignment` distance (queries
@@ -522,7 +524,7 @@ class Prograph:
         if eps is not None:
             if distance is hamming and comp in _CMP_CODE:
                 g = self._search_eps_hamming(strings, Y, eps, comp, similarity, representation)
-            elif distance in (minkowski, cosine) and comp in _CMP_CODE and strings is None:
+            elif distance in (minkowski, cosine, euclidean) and comp in _CMP_CODE and strings is None:
                 g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
             elif distance is levenshtein and comp in _CMP_CODE:
                 g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
@@ -537,7 +539,7 @@ class Prograph:
             return g if output == "csr" else g.to_tuples()
         if distance is hamming and k <= _native.MAX_K_ROUNDS:
             g = self._search_hamming(strings, Y, k, similarity, representation)
-        elif distance in (minkowski, cosine) and k <= _native.MAX_K_ROUNDS and strings is None:
+        elif distance in (minkowski, cosine, euclidean) and k <= _native.MAX_K_ROUNDS and strings is None:
             g = self._search_embedding(Y, k, similarity, representation, distance)
         elif distance is levenshtein and k <= _native.MAX_K_ROUNDS:
             g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
@@ -681,10 +683,10 @@ class Prograph:
     _MINK_STAGED_ROWS = 4096      # fewer Minkowski queries: dense block + selection (the fused kernel: 16 queries per CU)
 
     def _search_embedding(self, Y, k, similarity, representation, distance):
-        """Minkowski / cosine queries on the fused kernels with first = 0 (fp16 staging of both operands, as
+        """Minkowski / cosine / Euclidean queries on the fused kernels with first = 0 (fp16 staging of both operands, as
         `build_graph` stages the column).  Few Minkowski queries take the staged dense + selection path instead, which
         gives the same values bit for bit.  None (the generic loop) when an operand is not a non-empty 2-D fp16 device
-        tensor, or for cosine when one holds an inf or nan."""
+        tensor, or for cosine and Euclidean when one holds an inf or nan."""
         ops = self._embedding_operands(Y, representation)
         if ops is None:
             return None
@@ -700,7 +702,8 @@ class Prograph:
         xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
         if xc.nonfinite() or yc.nonfinite():
             return None
-        idx, w = _native.cosine_knn(xc, yc, kk, first=0, similarity=similarity)
+        knn = getattr(_native, _EMBED_F32[distance] + "_knn")
+        idx, w = knn(xc, yc, kk, first=0, similarity=similarity)
         return KNNGraph(idx, w, n, similarity=similarity, final=True, first=0)
 
     def _mink_blocks(self, xp, Y, similarity):
@@ -1185,7 +1188,7 @@ class Prograph:
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _search_eps_embedding(self, Y, eps, comp, similarity, representation, distance):
-        """Minkowski / cosine queries on the fused eps kernels with d = 0 (s = 1) kept; fewer than `_MINK_STAGED_ROWS`
+        """Minkowski / cosine / Euclidean queries on the fused eps kernels with d = 0 (s = 1) kept; fewer than `_MINK_STAGED_ROWS`
         Minkowski queries take the dense block + fp16 selection, which gives the same CSR bit for bit.  None (the
         generic loop) as in `_search_embedding`."""
         ops = self._embedding_operands(Y, representation)
@@ -1206,7 +1209,8 @@ class Prograph:
         xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
         if xc.nonfinite() or yc.nonfinite():
             return None
-        indptr, indices, wts = _native.cosine_eps(xc, yc, cmp, eps, similarity=similarity, keep_zero=True)
+        sweep = getattr(_native, _EMBED_F32[distance] + "_eps")
+        indptr, indices, wts = sweep(xc, yc, cmp, eps, similarity=similarity, keep_zero=True)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
 
     def _search_eps_generic(self, strings, Y, eps, comp, similarity, representation, distance):
@@ -1313,6 +1317,8 @@ class Prograph:
             g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
         if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
+        if distance is euclidean and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+            g = self._build_graph_euclidean(idxs, eps, k, similarity, representation, comp, cap)
         if distance is levenshtein and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
         if isinstance(distance, substitution) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
@@ -1336,7 +1342,7 @@ class Prograph:
             return self._build_graph_generic(idxs, batch_size, eps, k, similarity, representation, distance, comp)
 
         if g is not None:
-            pass                                    # Minkowski / cosine embeddings, or sequences beyond one record: built above
+            pass                                    # Minkowski / cosine / Euclidean embeddings, or sequences beyond one record: built above
         elif eps:
             # similarity: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the mirrored integer test on d
             # (:720-721, :734); both sides are the same correctly rounded float32 quotient when d == eps
@@ -1468,6 +1474,18 @@ class Prograph:
         CSRGraph with final fp32 weights, or None (the generic path then) when the staged embedding is not a
         non-empty 2-D fp16 device tensor or holds an inf or nan.
         """
+        return self._build_graph_embed_f32("cosine", idxs, eps, k, similarity, representation, comp, cap)
+
+    def _build_graph_euclidean(self, idxs, eps, k, similarity, representation, comp, cap=256):
+        """
+        `build_graph(representation=<embedding>, distance=euclidean)`: `_build_graph_cosine` with the Euclidean
+        epilogue (`pg_euclidean_knn`, `pg_euclidean_knn_round`, `pg_euclidean_eps_*`) - the same
+        staging, norms and non-finite check, final fp32 weights, and None under the same conditions.
+        """
+        return self._build_graph_embed_f32("euclidean", idxs, eps, k, similarity, representation, comp, cap)
+
+    def _build_graph_embed_f32(self, metric, idxs, eps, k, similarity, representation, comp, cap):
+        """The body `_build_graph_cosine` and `_build_graph_euclidean` share; `metric` names the `_native` wrappers."""
         try:
             mat = np.vstack(self(representation))
             X = torch.as_tensor(mat, dtype=torch.float16, device=_native.device())
@@ -1487,9 +1505,9 @@ class Prograph:
             kk = min(k, n - 1)
             if not kk:
                 return self._empty_knn(n, torch.float32, X.device, similarity, final=True)
-            idx, w = _native.cosine_knn(xc, xc, kk, first=1, similarity=similarity)
+            idx, w = getattr(_native, metric + "_knn")(xc, xc, kk, first=1, similarity=similarity)
             return KNNGraph(idx, w, n, similarity=similarity, final=True)
-        indptr, indices, wts = _native.cosine_eps(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
+        indptr, indices, wts = getattr(_native, metric + "_eps")(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
 
     _LEV_FUSED_MAX = _native.LEV_MAX_BAND            # thresholds the fused epsilon graph (and the banded first kNN pass) cover
