@@ -630,6 +630,25 @@ int pg_alignment_fit_trace_long(const void *x_packed, int64_t n, int64_t x_npad,
                                 void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * Alignment STATISTICS - BUILD DEFINED (pg_aln_stats.hip, pg_aln_stats.h): the head of pg_alignment_trace without the
+ * alignment's columns - what a percent-identity cut needs.  The canonical alignment is the one defined above, unchanged;
+ * the forward recurrence hands every cell the counts of the predecessor the walk would choose, so no direction bits are
+ * stored and nothing is walked back.
+ *   pg_alignment_stats  mode 0, 1, 2 as above or 3 (fit: pg_alignment_fit_trace's alignment; table = score_i8, cost_u8
+ *                      for mode 0); operands, xi, yi, gap and gap_open as for pg_alignment_trace (widths xl, yl of 1..128,
+ *                      PG_E_TOOLONG beyond).  head: int32 (npairs, 8) = score, x_begin, x_end, y_begin, y_end, n_ops,
+ *                      identities, status - equal, field for field, to the head pg_alignment_trace / pg_alignment_fit_trace
+ *                      writes for the same pair.  There is no ops, no ldo and no workspace.  A pair whose index lies
+ *                      outside its operand touches no operand memory and gets status 1, n_ops -1, zeros elsewhere.  At
+ *                      most 1024 waves are launched; they stride over the list.  A bad mode, gap outside 1..255, gap_open
+ *                      outside 0..255, NULL pointers, non-positive sizes and npad < n are PG_E_BADARG; every argument check
+ *                      returns before any launch.
+ */
+int pg_alignment_stats(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                       int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap,
+                       int gap_open, int32_t *head, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

@@ -48,6 +48,7 @@ SYMBOLS = [
     "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
     "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
+    "pg_alignment_stats",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
@@ -169,6 +170,7 @@ def _load():
         lib.pg_alignment_trace_long.argtypes = lib.pg_alignment_trace.argtypes
         lib.pg_alignment_fit_trace.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_fit_trace_long.argtypes = lib.pg_alignment_trace.argtypes[1:]
+        lib.pg_alignment_stats.argtypes = lib.pg_alignment_trace.argtypes[:16] + [_vp]
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
@@ -1177,8 +1179,9 @@ def _trace_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops,
                                     ldo, _ptr(ws), ws.numel(), _stream()), "pg_alignment_trace")
 
 
-def _trace_list(name, wave_bytes, launch, xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes):
-    """`alignment_trace` / `alignment_trace_long`: the index check, the workspace, the split into launches."""
+def _pair_lists(name, xo, yo, xi, yi):
+    """The pair lists of `alignment_trace`, `alignment_trace_long` and `alignment_stats` as int32 device tensors, their
+    index ranges checked on the host: ONE SYNC, IndexError for a row number outside its operand."""
     dev = xo.buf.device
     xi = torch.as_tensor(xi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
     yi = torch.as_tensor(yi).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
@@ -1187,6 +1190,13 @@ def _trace_list(name, wave_bytes, launch, xo, yo, xi, yi, mode, table, gap, gap_
     lo_hi = torch.stack([xi.min(), xi.max(), yi.min(), yi.max()]).tolist()                # the one host sync
     if lo_hi[0] < 0 or lo_hi[1] >= xo.n or lo_hi[2] < 0 or lo_hi[3] >= yo.n:
         raise IndexError(f"{name}: a pair's row number is outside its operand")
+    return xi, yi
+
+
+def _trace_list(name, wave_bytes, launch, xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes):
+    """`alignment_trace` / `alignment_trace_long`: the index check, the workspace, the split into launches."""
+    dev = xo.buf.device
+    xi, yi = _pair_lists(name, xo, yo, xi, yi)
     one = wave_bytes(xo.l, yo.l)
     p, ldo = xi.numel(), xo.l + yo.l
     if workspace_bytes is None:                                             # what the list needs; a share is 129 MiB at most
@@ -1256,6 +1266,51 @@ def alignment_trace_long(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_b
     ALN_TRACE_LONG_WORKSPACE (2 GiB: about 400 waves in flight at 400 positions) and at least one wave's share."""
     return _trace_list("alignment_trace_long", aln_trace_long_wave_bytes, _trace_long_launch, xo, yo, xi, yi,
                        mode, table, gap, gap_open, workspace_bytes)
+
+
+ALN_STATS_OPS_BYTES = 256 << 20     # alignment_trace_long_heads: the most `ops` alive at a time
+
+
+def alignment_trace_long_heads(xo, yo, xi, yi, mode, table, gap, gap_open, ops_bytes=ALN_STATS_OPS_BYTES):
+    """The heads of `alignment_trace_long` without its `ops`, for lists whose ops would not fit: the pair list runs through
+    pg_alignment_trace_long in slices of `ops_bytes // (xo.l + yo.l)` pairs (at least one) that share ONE ops buffer of at
+    most `ops_bytes` and one workspace (a slice's need, at most ALN_TRACE_LONG_WORKSPACE), and only head (P, 8) is kept.
+    The same index check (ONE SYNC) and errors.  DESIGN.md §4.25: the route of `ops=False` beyond 128 positions."""
+    xi, yi = _pair_lists("alignment_trace_long_heads", xo, yo, xi, yi)
+    dev = xo.buf.device
+    one = aln_trace_long_wave_bytes(xo.l, yo.l)
+    p, ldo = xi.numel(), xo.l + yo.l
+    per = min(p, max(1, int(ops_bytes) // ldo))
+    waves = max(1, min(ALN_TRACE_LONG_WORKSPACE // one, (per + 63) // 64))
+    ws = torch.empty(waves * one, dtype=torch.uint8, device=dev)
+    head = torch.empty((p, 8), dtype=torch.int32, device=dev)
+    ops = torch.empty((per, ldo), dtype=torch.uint8, device=dev)
+    for s0 in range(0, p, per):
+        s1 = min(p, s0 + per)
+        for p0 in range(0, s1 - s0, waves * 64):
+            _trace_long_launch(xo, yo, xi[s0:s1], yi[s0:s1], p0, min(s1 - s0, p0 + waves * 64), mode, table, gap, gap_open,
+                               head[s0:s1], ops[:s1 - s0], ws)
+    return head
+
+
+def _stats_launch(xo, yo, xi, yi, mode, table, gap, gap_open, head):
+    """One pg_alignment_stats call: every pair of the lists into the rows of head."""
+    _check(lib().pg_alignment_stats(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l, _ptr(xi),
+                                    _ptr(yi), xi.numel(), _ptr(table), int(gap), int(gap_open), _ptr(head), _stream()),
+           "pg_alignment_stats")
+
+
+def alignment_stats(xo, yo, xi, yi, mode, table, gap, gap_open):
+    """The head of `alignment_trace` without the alignments' columns (pg_alignment_stats): int32 (P, 8) =
+    score, x_begin, x_end, y_begin, y_end, n_ops, identities, status of the canonical alignment of every pair, field for
+    field what `alignment_trace` returns, from a forward pass that carries the path's counts - no ops, no workspace, one
+    launch.  `mode` ALN_TRACE_GLOBAL (`table` from sub_cost), ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL or ALN_TRACE_FIT (`table`
+    from aln_local_score); operands from aln_operand (at most 128 positions); `gap` 1..255, `gap_open` 0..255.  The index
+    check is `alignment_trace`'s: ONE SYNC, IndexError for a row number outside its operand."""
+    xi, yi = _pair_lists("alignment_stats", xo, yo, xi, yi)
+    head = torch.empty((xi.numel(), 8), dtype=torch.int32, device=xo.buf.device)
+    _stats_launch(xo, yo, xi, yi, mode, table, gap, gap_open, head)
+    return head
 
 
 def i32_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):

@@ -35,6 +35,12 @@ Everything else - CPU tensors, widths beyond 2048, no device - `host_trace` belo
 row by row in numpy (F by the running maximum over A, as the operators' torch expressions have it), then the walk over
 the stored tables.  It is SLOW (milliseconds per pair at 128 positions, and the tables of one pair take 24 bytes per
 cell); it is exact.
+
+WITHOUT THE COLUMNS (`ops=False`).  A percent-identity cut wants `identities / n_ops` of every edge and
+throws the columns away.  `pg_alignment_stats` (pg_aln_stats.hip) gives the seven fields of the SAME canonical alignment
+from the forward pass alone: every cell carries the counts of the predecessor the walk would choose, so nothing is stored
+per cell and nothing is walked back - 32 bytes out per pair, no workspace.  `Prograph.build_graph(..., min_identity=)` and
+`Prograph.search(..., min_identity=)` filter a graph's edges by it.
 """
 import numpy as np
 import torch
@@ -50,7 +56,8 @@ _FIELDS = ("score", "x_begin", "x_end", "y_begin", "y_end", "n_ops", "identities
 
 class Alignments:
     """P canonical alignments.  Tensor fields on one device: score, x_begin, x_end, y_begin, y_end, n_ops, identities
-    (int64 (P,)) and ops (uint8 (P, W)).  `x`, `y` are the token matrices the pairs index through `xi`, `yi` (row p is
+    (int64 (P,)) and ops (uint8 (P, W); None when built with `ops=False`: `cigar` and `gapped` then raise ValueError, every
+    field, `identity()`, `host()` and `len` work).  `x`, `y` are the token matrices the pairs index through `xi`, `yi` (row p is
     x[xi[p]] against y[yi[p]]), kept for `gapped`."""
 
     def __init__(self, score, x_begin, x_end, y_begin, y_end, n_ops, identities, ops, x=None, y=None, xi=None, yi=None,
@@ -63,7 +70,8 @@ class Alignments:
         return int(self.score.shape[0])
 
     def __repr__(self):
-        return f"Alignments({len(self)} pairs, ops {tuple(self.ops.shape)}, {self.score.device})"
+        ops = "no ops" if self.ops is None else f"ops {tuple(self.ops.shape)}"
+        return f"Alignments({len(self)} pairs, {ops}, {self.score.device})"
 
     def identity(self):
         """identities / n_ops per pair as float64, 0 for an empty alignment."""
@@ -77,6 +85,8 @@ class Alignments:
                           self.letters)
 
     def _ops_of(self, p):
+        if self.ops is None:                                                # trace(..., ops=False): the statistics alone
+            raise ValueError("built without ops")
         return self.ops[p, :int(self.n_ops[p])].cpu().numpy()
 
     def cigar(self, p):
@@ -214,17 +224,22 @@ def _device_table(op, mode):
 
 
 def from_head(head, ops, **kept):
-    """Alignments from the (P, 8) head and the ops of pg_alignment_trace / pg_alignment_trace_long."""
+    """Alignments from the (P, 8) head and the ops of pg_alignment_trace / pg_alignment_trace_long (ops None: from the
+    head of pg_alignment_stats alone)."""
     h = head.to(torch.int64)
     return Alignments(*(h[:, c].contiguous() for c in range(7)), ops, **kept)
 
 
-def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native=None, native_long=None):
+def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native=None, native_long=None, ops=True):
     """The alignments of the pairs (X[xi[p]], Y[yi[p]]) under operator `op`; X, Y uint8 token tensors on one device,
     xi, yi integer lists (None: every row in order, X and Y of one height).  The 128-position kernel for device tokens of
     at most 128 positions (`native` overrides that choice), the strip kernel for wider ones up to 2048 positions where
     `_native.aln_trace_long_ready()` (`native_long` overrides that one), `host_trace` otherwise; the result lives on X's
-    device.  `workspace_bytes` None: 256 MiB for the first kernel, what the list needs up to 2 GiB for the second."""
+    device.  `workspace_bytes` None: 256 MiB for the first kernel, what the list needs up to 2 GiB for the second.
+    `ops=False`: the same fields without the columns (the container's `ops` is None) - at most 128 positions on
+    `pg_alignment_stats`, which has no workspace; 129..2048 positions on the strip kernel in slices of the pair list that
+    share one ops buffer of at most 256 MiB (`_native.alignment_trace_long_heads`); `host_trace` otherwise, its ops dropped.
+    `workspace_bytes` is not consulted then."""
     mode = _mode_of(op)
     name = type(op).__name__
     dev = X.device
@@ -238,8 +253,8 @@ def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native
         raise ValueError(f"{name}.align: as many rows as columns make the pairs")
     if xi.numel() == 0:
         z = torch.zeros(0, dtype=torch.int64, device=dev)
-        return Alignments(z, z, z, z, z, z, z, torch.zeros((0, X.shape[1] + Y.shape[1]), dtype=torch.uint8, device=dev),
-                          X, Y, xi, yi, letters)
+        none = torch.zeros((0, X.shape[1] + Y.shape[1]), dtype=torch.uint8, device=dev) if ops else None
+        return Alignments(z, z, z, z, z, z, z, none, X, Y, xi, yi, letters)
     if native is None:
         native = X.is_cuda and 1 <= width <= _native.ALN_MAX_L
     if native_long is None:
@@ -250,23 +265,28 @@ def trace(op, X, Y, xi=None, yi=None, workspace_bytes=None, letters=None, native
                            (_native.aln_long_operand, _native.alignment_trace_long))
         xo = operand(X, op.symbols)
         yo = xo if Y is X else operand(Y, op.symbols)
-        head, ops = tracer(xo, yo, xi, yi, mode, _device_table(op, mode), op.gap, op.gap_open,
-                           workspace_bytes=256 << 20 if native and workspace_bytes is None else workspace_bytes)
+        if ops:
+            head, cols = tracer(xo, yo, xi, yi, mode, _device_table(op, mode), op.gap, op.gap_open,
+                                workspace_bytes=256 << 20 if native and workspace_bytes is None else workspace_bytes)
+        else:
+            heads = _native.alignment_stats if native else _native.alignment_trace_long_heads
+            head, cols = heads(xo, yo, xi, yi, mode, _device_table(op, mode), op.gap, op.gap_open), None
         if int((xo.flags | yo.flags).item()):
             raise ValueError(f"{name}: a token is outside the table (0..{op.symbols - 1})")
-        return from_head(head, ops, x=X, y=Y, xi=xi, yi=yi, letters=letters)
+        return from_head(head, cols, x=X, y=Y, xi=xi, yi=yi, letters=letters)
     if int(X.max()) >= op.symbols or int(Y.max()) >= op.symbols:
         raise ValueError(f"{name}: a token is outside the table (0..{op.symbols - 1})")
     xh, yh = xi.cpu().numpy(), yi.cpu().numpy()
     if xh.min() < 0 or xh.max() >= X.shape[0] or yh.min() < 0 or yh.max() >= Y.shape[0]:
         raise IndexError(f"{name}.align: a pair's row number is outside its operand")
-    *fields, ops = host_trace(mode, op.table, op.gap, op.gap_open, X.cpu().numpy(), Y.cpu().numpy(), xh, yh)
-    return Alignments(*(torch.from_numpy(f).to(dev) for f in fields), torch.from_numpy(ops).to(dev), X, Y, xi, yi, letters)
+    *fields, cols = host_trace(mode, op.table, op.gap, op.gap_open, X.cpu().numpy(), Y.cpu().numpy(), xh, yh)
+    return Alignments(*(torch.from_numpy(f).to(dev) for f in fields), torch.from_numpy(cols).to(dev) if ops else None,
+                      X, Y, xi, yi, letters)
 
 
-def align(op, X, Y):
+def align(op, X, Y, ops=True):
     """`op.align(X, Y)`: row p of X aligned with row p of Y (see the module text; `fit_alignment`: row p of Y, whole,
-    within row p of X); the operators' input rules."""
+    within row p of X); the operators' input rules.  `ops=False`: `trace`'s."""
     from .distance.hamming import _as_byte_tokens
     from .distance.utils import clean_input
     name = type(op).__name__
@@ -276,4 +296,4 @@ def align(op, X, Y):
     yb = xb if Y is X else _as_byte_tokens(Y)
     if xb is None or yb is None:
         raise ValueError(f"{name}: the tokens must be integers in 0..255")
-    return trace(op, xb, yb)
+    return trace(op, xb, yb, ops=ops)

@@ -211,13 +211,15 @@ class _score_operator:
             s = self._torch_expression(xb, yb)
         return s
 
-    def align(self, X, Y):
+    def align(self, X, Y, ops=True):
         """The canonical optimal alignment of row p of X with row p of Y (P rows each, P may be 1) as an `Alignments`
         container on X's device: which symbols pair, which stay unaligned, where the alignment sits in either sequence,
         and the identities (prograph_amd/alignments.py defines it).  `score` is this operator's score.  Device byte tokens
         of at most 128 positions run on the HIP kernel `pg_alignment_trace`, wider ones up to 2048 positions on
-        `pg_alignment_trace_long`; everything else on the exact, slow host expression."""
-        return _alignments.align(self, X, Y)
+        `pg_alignment_trace_long`; everything else on the exact, slow host expression.  `ops=False`: the same fields
+        without the columns (`ops` is None; at most 128 positions on `pg_alignment_stats`, which stores and walks
+        nothing)."""
+        return _alignments.align(self, X, Y, ops=ops)
 
 
 class local_alignment(_score_operator):

@@ -458,7 +458,7 @@ class Prograph:
         return self[idx], np.min(distances)
 
     def search(self, queries, k=None, eps=None, distance=hamming, representation="Tokenized", similarity=False,
-               output="tuples", comp=operator.le):
+               output="tuples", comp=operator.le, min_identity=None, min_columns=0):
         """
         The k nearest dataset rows (`k`), or the dataset rows within a radius (`eps`), of sequences or embeddings that
         need not be in the dataset; exactly one of the two.
@@ -490,7 +490,15 @@ class Prograph:
         does a `fit_alignment` instance (`pg_alignment_fit_dense`), which is NOT symmetric: the QUERY is aligned whole within
         any stretch of a dataset row - a hit (q, c) reads "query q, whole, placed in row c" -, its scores may be negative
         (a `k` list ranks them), and `eps` keeps `s > 0`.
+        `min_identity=` (0..1) / `min_columns=`: as in `build_graph` - the hits are found as above, each is aligned with
+        its query (`align(..., queries=, ops=False)`), and those below the cut are dropped; the result is a `CSRGraph`
+        (`output="csr"`, also for `k`: a query may keep fewer than k hits) or the filtered tuple list.
         """
+        if self._identity_cut_asked("search", distance, min_identity, min_columns):
+            g = self.search(queries, k=k, eps=eps, distance=distance, representation=representation, similarity=similarity,
+                            output="csr", comp=comp)
+            g = self._identity_cut(g, distance, min_identity, min_columns, representation, queries=queries)
+            return g if output == "csr" else g.to_tuples()
         if eps is None:
             if not k:                                                      # build_graph's errors for k
                 raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
@@ -1105,7 +1113,7 @@ class Prograph:
         raise TypeError("align: graph must be a CSRGraph, a KNNGraph, the name of a stored graph or a list of (indices, weights) tuples")
 
     def align(self, graph=None, rows=None, cols=None, queries=None, idxs=None, distance=None, representation="Tokenized",
-              workspace_bytes=None):
+              workspace_bytes=None, ops=True):
         """
         The canonical optimal alignments (`Alignments`, prograph_amd/alignments.py) of dataset pairs under
         `distance`, which must be an `alignment`, `local_alignment`, `semiglobal_alignment` or `fit_alignment` instance (`TypeError`
@@ -1122,6 +1130,10 @@ class Prograph:
         the tracer's x is the sequence with the free ends, so there x is the edge's COLUMN and y its row or query:
         `tb.x_*` speak of the containing dataset sequence (`x_begin:x_end` is where the row sits in it), `tb.y_*` of the
         fitted one (`y_begin` = 0, `y_end` = its length), and `tb.score` equals the edge's weight.
+        `ops=False`: the same seven fields per edge without the columns (`tb.ops` is None, `cigar` / `gapped` raise) - what
+        an identity cut needs.  At most 128 positions that is `pg_alignment_stats`, a forward pass that stores and walks
+        nothing (32 bytes per edge, no workspace); 129..2048 positions the strip kernel in slices of the edge list with
+        one ops buffer of at most 256 MiB.
         """
         mode = _alignments._mode_of(distance)                               # TypeError for anything else
         X = self._local_tokens(self._dataset_matrix(representation), distance)
@@ -1163,9 +1175,48 @@ class Prograph:
         native_long = _native.aln_trace_long_ready() and _native.ALN_MAX_L < width <= _native.ALN_LONG_MAX_L
         if mode == _alignments.FIT:                                         # the tracer's x has the free ends: the column
             return _alignments.trace(distance, Xt, Qt, torch.from_numpy(c), torch.from_numpy(r), workspace_bytes=workspace_bytes,
-                                     letters=letters, native=native, native_long=native_long)
+                                     letters=letters, native=native, native_long=native_long, ops=ops)
         return _alignments.trace(distance, Qt, Xt, torch.from_numpy(r), torch.from_numpy(c), workspace_bytes=workspace_bytes,
-                                 letters=letters, native=native, native_long=native_long)
+                                 letters=letters, native=native, native_long=native_long, ops=ops)
+
+    # ---- percent-identity cuts of a graph's edges
+    @staticmethod
+    def _identity_cut_asked(who, distance, min_identity, min_columns):
+        """False for the defaults (nothing changes); else the checks of `min_identity=` / `min_columns=`."""
+        if min_identity is None and not min_columns:
+            return False
+        _alignments._mode_of(distance)                                      # TypeError for anything but the four operators
+        if min_identity is not None and not 0 <= float(min_identity) <= 1:
+            raise ValueError(f"{who}: min_identity must be in 0..1")
+        if int(min_columns) != min_columns or min_columns < 0:
+            raise ValueError(f"{who}: min_columns must be a non-negative integer")
+        return True
+
+    def _identity_cut(self, g, distance, min_identity, min_columns, representation, queries=None, idxs=None):
+        """The edges of `g` (a CSRGraph, a KNNGraph or a tuple list over `ncols` = the dataset or selection) whose canonical
+        alignment has at least `min_columns` columns and, with a threshold, `identities / max(n_ops, 1) >= min_identity`
+        in float64 on the alignments' device: a CSRGraph of the survivors in their order with their weights.  Every edge
+        is aligned with `ops=False`; `indptr` comes from the mask's cumulative sum, no row is visited by Python."""
+        if isinstance(g, KNNGraph):
+            g = g.as_csr()
+        elif not isinstance(g, CSRGraph):                                   # the generic loop's tuple list
+            counts = np.fromiter((len(e[0]) for e in g), dtype=np.int64, count=len(g))
+            cat = lambda k, dt: np.concatenate([np.asarray(e[k]) for e in g]) if counts.sum() else np.zeros(0, dtype=dt)
+            ncols = len(self) if idxs is None else len(idxs)
+            g = CSRGraph(torch.from_numpy(np.concatenate([[0], np.cumsum(counts)])), torch.from_numpy(cat(0, np.int64)).to(torch.int32),
+                         torch.from_numpy(cat(1, np.float32)), ncols, final=True)
+        tb = self.align(g, queries=queries, idxs=idxs, distance=distance, representation=representation, ops=False)
+        dev = g.indptr.device
+        n_ops = tb.n_ops.to(dev)
+        keep = n_ops >= int(min_columns)
+        if min_identity is not None:
+            keep &= tb.identities.to(dev).double() / n_ops.double().clamp(min=1) >= float(min_identity)
+        mask = g.indices >= 0                                               # kNN slots without a neighbour are no edges
+        mask[mask.clone()] = keep
+        before = torch.zeros(g.nnz + 1, dtype=torch.int64, device=dev)
+        before[1:] = torch.cumsum(mask, 0)
+        return CSRGraph(before[g.indptr], g.indices[mask], g.weights[mask], g.ncols, similarity=g.similarity, row0=g.row0,
+                        final=g.final)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
     def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
@@ -1281,7 +1332,7 @@ class Prograph:
     # ------------------------------------------------------------------ graph construction
     def build_graph(self, idxs=None, batch_size=8, eps=None, k=None, weighted=False, similarity=False,
                     representation="Tokenized", distance=hamming, comp=operator.le, output="tuples", cap=256,
-                    store=None, _keep=None):
+                    store=None, _keep=None, min_identity=None, min_columns=0):
         """
         epsilon-neighbourhood (`eps`) or kNN (`k`) graph over all pairwise distances
         (reference :656-765).  Returns the reference's list of N `(indices, weights)` tuples;
@@ -1297,7 +1348,22 @@ class Prograph:
         WHOLE within any stretch of column c, so row r lists the sequences that contain it best, (r, c) and (c, r) differ,
         and a `k` list may hold negative scores; rank 0 - the row itself or a row of lower index that contains it - is
         dropped as for every distance.
+        `min_identity=` (0..1) and `min_columns=` cut the graph by PERCENT IDENTITY; `distance` must then be one of the four
+        alignment operators (`TypeError`).  The graph is built exactly as without them; then every edge is aligned
+        (`align(..., ops=False)`: `pg_alignment_stats` at up to 128 positions) and kept iff its canonical alignment has
+        `n_ops >= min_columns` columns and `identities / max(n_ops, 1) >= min_identity` (None: the column cut alone; an
+        empty local alignment has identity 0).  Survivors keep their order and their weights; the result is a `CSRGraph`
+        (`output="csr"`, also for `k`: a row may keep fewer than k edges) or the filtered tuple list, and `store=` stores
+        the filtered graph.
         """
+        if self._identity_cut_asked("build_graph", distance, min_identity, min_columns):
+            g = self.build_graph(idxs=idxs, batch_size=batch_size, eps=eps, k=k, weighted=weighted, similarity=similarity,
+                                 representation=representation, distance=distance, comp=comp, output="csr", cap=cap)
+            if idxs is not None:                                            # the positions `align` maps edges through
+                idxs = np.arange(len(self))[idxs] if isinstance(idxs, slice) else np.asarray(idxs)
+                idxs = np.nonzero(idxs)[0] if idxs.dtype == bool else idxs
+            g = self._identity_cut(g, distance, min_identity, min_columns, representation, idxs=idxs)
+            return self._graph_result(g, idxs, store, _keep, output)
         if operator.xor(bool(eps), bool(k)) is False:
             raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
         if k is not None and not isinstance(k, int):
@@ -1351,6 +1417,11 @@ class Prograph:
         else:
             idx, dist = _native.knn_graph(planes, planes, k)
             g = KNNGraph(idx, dist, planes.n, similarity=similarity)
+        return self._graph_result(g, idxs, store, _keep, output)
+
+    def _graph_result(self, g, idxs, store, _keep, output):
+        """What `build_graph` hands back for the device graph `g`: stored under `store` / kept under `_keep` (whole-dataset
+        graphs only), as the container or as the tuple list."""
         tuples = None
         if store is not None and idxs is None:
             tuples = g.to_tuples()

@@ -1,0 +1,157 @@
+// Host-side check of the statistics kernel's routines (prograph_amd/csrc/pg_aln_stats.h: pg_st_row0, pg_st_row, pg_st_head)
+// against the traceback's own (pg_aln_trace.h: pg_tr_row0, pg_tr_row, pg_tr_walk): the seven fields of the canonical
+// alignment, counted forwards, must be the seven fields the walk back over the direction bits gives.  Exhaustive where
+// ties are the rule - every pair of sequences over 2 and 3 symbols at all lengths 0..6 under tables of -1..1 (costs 1..2),
+// four modes, gap_open 0 and 1 - then random pairs at the lengths around the dwords and at the ends of the range, with the
+// extreme tables among them.  In the random part every buffer is a fresh heap block of exactly the size the routines may
+// touch, so the address sanitizer sees a step outside.  Test infrastructure; no GPU.
+#include "pg_aln_stats.h"
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+static unsigned long long rng_state = 0x9E3779B97F4A7C15ull;
+static unsigned rnd() {
+  rng_state ^= rng_state << 13;
+  rng_state ^= rng_state >> 7;
+  rng_state ^= rng_state << 17;
+  return (unsigned)(rng_state >> 11);
+}
+
+static void pack(std::vector<uint32_t> &buf, long long stride, int c, const std::vector<int> &s) {
+  for (size_t p = 0; p < s.size(); ++p) buf[(p >> 2) * stride + c] |= (uint32_t)s[p] << (8 * (p & 3));
+}
+
+static int bad = 0;
+static long long pairs_done = 0, cells = 0;
+
+// a block of exactly n elements; `exact` (the random part) takes a fresh heap block, so that the sanitizer sees its end
+template <class V> static void block(V &v, size_t n, typename V::value_type fillv, bool exact) {
+  if (exact) V().swap(v);
+  v.assign(n, fillv);
+}
+
+// one pair, both ways; Tm is the table as the kernels hold it (negated costs for the distance)
+static void compare(int mode, const int *Tm, int e, int o, const std::vector<int> &x, const std::vector<int> &y, bool exact) {
+  const int lx = (int)x.size(), ly = (int)y.size(), oe = o + e;
+  const int xg = std::max((lx + 3) / 4, 1), yg = std::max((ly + 3) / 4, 1), nd = std::max((ly + 7) / 8, 1);
+  const long long xs = 3, ys = 5;                                           // columns 1 and 2 of small packed matrices
+  static std::vector<uint32_t> xbuf, ybuf, dir;
+  static std::vector<int> colH, colE;
+  static std::vector<unsigned char> ops;
+  static std::vector<pg_st_cell> col;
+  block(xbuf, xg * xs, 0u, exact);
+  block(ybuf, yg * ys, 0u, exact);
+  pack(xbuf, xs, 1, x);
+  pack(ybuf, ys, 2, y);
+  const uint32_t *xt = xbuf.data() + 1, *yt = ybuf.data() + 2;
+
+  int32_t want[8] = {0}, got[8] = {0};
+  {                                                                         // the traceback: rows, direction bits, the walk
+    block(colH, ly + 1, 0, exact);
+    block(colE, ly + 1, 0, exact);
+    block(dir, (size_t)std::max(lx, 1) * nd, 0xdeadbeefu, exact);
+    pg_tr_end end;
+    pg_tr_row0(mode, lx, ly, e, oe, colH.data(), colE.data(), 1, &end);
+    for (int i = 1; i <= lx; ++i)
+      pg_tr_row(mode, i, lx, ly, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
+                dir.data() + (size_t)(i - 1) * nd, 1, &end);
+    block(ops, lx + ly, (unsigned char)0xee, exact);
+    want[0] = mode == PG_TR_GLOBAL ? -colH[ly] : end.best;
+    pg_tr_walk(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), lx + ly, want);
+  }
+  {                                                                         // the statistics: rows with their count words
+    block(col, ly + 1, pg_st_cell(), exact);
+    pg_tr_end end;
+    uint32_t endw;
+    pg_st_row0(mode, lx, ly, e, oe, col.data(), 1, &end, &endw);
+    for (int i = 1; i <= lx; ++i) {
+      const int t = pg_tr_token(xt, xs, i - 1);
+      pg_st_row(mode, i, lx, ly, e, oe, Tm + 32 * t, t, yt, ys, col.data(), 1, &end, &endw);
+    }
+    pg_st_head(mode == PG_TR_GLOBAL ? -col[ly].h : end.best, &end, mode == PG_TR_GLOBAL ? col[ly].wh : endw, got);
+  }
+  ++pairs_done;
+  cells += (long long)lx * ly;
+  for (int k = 0; k < 7; ++k)
+    if (want[k] != got[k]) {
+      if (++bad <= 10)
+        printf("mode %d lx %d ly %d e %d o %d: stats %d %d %d %d %d %d %d, trace %d %d %d %d %d %d %d\n", mode, lx, ly, e, o, got[0],
+               got[1], got[2], got[3], got[4], got[5], got[6], want[0], want[1], want[2], want[3], want[4], want[5], want[6]);
+      return;
+    }
+}
+
+// every sequence over the symbols 1..a of lengths 0..top (a sequence ends in a non-zero symbol: 0 is left out)
+static std::vector<std::vector<int>> all_sequences(int a, int top) {
+  std::vector<std::vector<int>> out(1);
+  for (size_t done = 0, l = 1; (int)l <= top; ++l) {
+    const size_t end = out.size();
+    for (size_t k = done; k < end; ++k)
+      for (int s = 1; s <= a; ++s) {
+        std::vector<int> v = out[k];
+        v.push_back(s);
+        out.push_back(v);
+      }
+    done = end;
+  }
+  return out;
+}
+
+static void fill(int *Tm, int mode, int a, int kind) {
+  // kind 0: identity-like (score 1 / -1, cost 0 / 1); kind 1: one neutral and one dear pair (score 0, cost 2) among them
+  for (int k = 0; k < 32 * 32; ++k) Tm[k] = 0;
+  for (int p = 0; p <= a; ++p)
+    for (int q = 0; q <= a; ++q) {
+      int v;
+      if (mode == PG_TR_GLOBAL) v = p == q ? 0 : (kind && p + q == 3 ? 2 : 1);
+      else v = p == q ? (kind && p == 2 ? 0 : 1) : (kind && p + q == 3 ? 0 : -1);
+      Tm[p * 32 + q] = mode == PG_TR_GLOBAL ? -v : v;
+    }
+}
+
+int main() {
+  int Tm[32 * 32];
+  // ---- exhaustive: ties are the rule
+  for (int a = 2; a <= 3; ++a) {
+    const std::vector<std::vector<int>> seqs = all_sequences(a, 6);
+    for (int mode = 0; mode < 4; ++mode)
+      for (int kind = 0; kind < (a == 2 ? 2 : 1); ++kind) {
+        fill(Tm, mode, a, a == 2 ? kind : 1);
+        for (int o = 0; o <= 1; ++o)
+          for (int e = 1; e <= (a == 2 ? 2 : 1); ++e)
+            for (const auto &x : seqs)
+              for (const auto &y : seqs) compare(mode, Tm, e, o, x, y, false);
+      }
+  }
+  const long long exhaustive = pairs_done;
+  // ---- random pairs at the lengths around the dwords and the ends of the range; every fourth the extreme tables
+  const int lens[] = {0, 1, 15, 16, 17, 127, 128}, gaps[] = {1, 2, 255}, opens[] = {0, 1, 11, 255};
+  for (int it = 0; it < 2400 && bad < 10; ++it) {
+    const int mode = it % 4, A = 2 + rnd() % (it % 7 == 0 ? 30 : 3);
+    const bool extreme = it % 4 == (it / 4) % 4;
+    const int e = extreme ? 255 : gaps[rnd() % 3], o = extreme ? 255 : opens[rnd() % 4];
+    const int lx = lens[rnd() % 7], ly = lens[rnd() % 7];
+    for (int k = 0; k < 32 * 32; ++k) Tm[k] = 0;
+    for (int p = 0; p < A; ++p)
+      for (int q = p; q < A; ++q) {
+        int v;
+        if (mode == PG_TR_GLOBAL) v = p == q ? 0 : (extreme ? 255 : 1 + (int)(rnd() % 2));
+        else v = extreme ? (p == q ? 127 : -128) : (int)(rnd() % 3) - 1;
+        Tm[p * 32 + q] = Tm[q * 32 + p] = mode == PG_TR_GLOBAL ? -v : v;
+      }
+    std::vector<int> x(lx), y(ly);
+    for (int &v : x) v = rnd() % A;
+    for (int &v : y) v = rnd() % A;
+    if (it % 3 == 0)                                                        // related sequences: long diagonals, few gaps
+      for (int k = 0; k < std::min(lx, ly); ++k)
+        if (rnd() % 8) y[k] = x[k];
+    if (lx && !x[lx - 1]) x[lx - 1] = 1;
+    if (ly && !y[ly - 1]) y[ly - 1] = 1;
+    compare(mode, Tm, e, o, x, y, true);
+  }
+  if (bad) printf("STATS ROUTINES WRONG: %d\n", bad);
+  else printf("stats routines OK (%lld exhaustive pairs, %lld random, %lld cells)\n", exhaustive, pairs_done - exhaustive, cells);
+  return bad != 0;
+}
