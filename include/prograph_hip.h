@@ -649,6 +649,28 @@ int pg_alignment_stats(int mode, const void *x_packed, int64_t n, int64_t x_npad
                        int gap_open, int32_t *head, void *stream);
 
 /*
+ * k-mer SPECTRUM profiles - BUILD DEFINED (pg_spectrum.hip, pg_spectrum.h): the k-mer count vector of
+ * every row of a token matrix, as the fp16 matrix pg_pack_f16 -> pg_cosine_prep -> pg_cosine_* / pg_euclidean_* take.
+ * Tokens are 1..symbols; 0 is padding or an unknown letter and may stand anywhere.  Window i (0 <= i <= l - k) of a row
+ * counts iff none of its k tokens is 0; code = sum_j (t[i+j] - 1) * symbols^(k-1-j).
+ *   pg_spectrum_dims     the profile width D: symbols^k with dims == 0 (exact: bucket = code), dims itself otherwise
+ *                        (hashed: bucket = (((code + 1) * 2654435761) mod 2^32) >> (32 - log2 dims)).  PG_E_BADARG for k
+ *                        outside 1..6, symbols outside 2..255, symbols^k > 2^31, dims neither 0 nor a power of two in
+ *                        64..32768, and dims == 0 with symbols^k > 32768.
+ *   pg_spectrum_profile  tokens: (n, l) uint8, leading dimension ld, l <= 2048 (PG_E_TOOLONG beyond); rows: NULL, or n
+ *                        int64 row numbers of `tokens` (output row r is token row rows[r]; the caller answers for their
+ *                        range).  out_f16: fp16 row-major (n, D), leading dimension ldo >= D; exactly D elements of
+ *                        every row are written, zeros included - a count is at most 2048 and exact in fp16.  flags: one
+ *                        word, zeroed on the stream by this call and set when a token above `symbols` stands in the
+ *                        rows read; such a window is skipped and nothing outside the row's D counts is touched.  The
+ *                        arguments pg_spectrum_dims refuses, NULL tokens / out_f16 / flags, n <= 0, l <= 0, ld < l and
+ *                        ldo < D are PG_E_BADARG; every check returns before any launch.  No workspace.
+ */
+int pg_spectrum_dims(int k, int symbols, int dims);
+int pg_spectrum_profile(const uint8_t *tokens, int64_t n, int l, int64_t ld, const int64_t *rows, int k, int symbols, int dims,
+                        void *out_f16, int64_t ldo, int32_t *flags, void *stream);
+
+/*
  * pg_csr_row_stats — per-row reductions over a CSR graph for the analytics that consume the
  * `Neighbours` column (prograph/prograph.py:797-946: degree, laplacian, dirichlet, local_variance):
  *   deg[r] = sum_j w_rj,  sum_f[r] = sum_j f[col_j],  sum_wf[r] = sum_j w_rj * f[col_j],

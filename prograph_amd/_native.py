@@ -32,6 +32,7 @@ ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_align
 ALN_TRACE_FIT = 3                 # pg_aln_trace.h's PG_TR_FIT: pg_alignment_fit_trace / _long, which take no mode
 ALN_TRACE_LONG_WORKSPACE = 2 << 30  # alignment_trace_long: the most workspace it takes unasked
 LEV_LONG_MAX_L = 2048             # pg_levenshtein_long_dense: positions per operand
+SPECTRUM_MAX_L, SPECTRUM_MAX_K, SPECTRUM_MAX_D = 2048, 6, 32768   # pg_spectrum_profile: positions per row, window length, profile width
 ALN_LONG_CELL_MAX = 65535         # their cells are 16 bits wide (aln_long_fits / aln_local_long_fits / aln_semiglobal_long_fits)
 
 # every symbol include/prograph_hip.h declares (tests check the library exports them all)
@@ -49,6 +50,7 @@ SYMBOLS = [
     "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
     "pg_alignment_stats",
+    "pg_spectrum_dims", "pg_spectrum_profile",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
     "pg_f16_nchunks", "pg_pack_f16", "pg_minkowski_dense", "pg_f16_knn", "pg_f16_knn_round", "pg_f16_eps_count",
@@ -171,6 +173,8 @@ def _load():
         lib.pg_alignment_fit_trace.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_fit_trace_long.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_stats.argtypes = lib.pg_alignment_trace.argtypes[:16] + [_vp]
+        lib.pg_spectrum_dims.argtypes = [_i32, _i32, _i32]
+        lib.pg_spectrum_profile.argtypes = [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
         lib.pg_i32_knn_round.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]
         lib.pg_i32_eps_count.argtypes = [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp]
@@ -1311,6 +1315,42 @@ def alignment_stats(xo, yo, xi, yi, mode, table, gap, gap_open):
     head = torch.empty((xi.numel(), 8), dtype=torch.int32, device=xo.buf.device)
     _stats_launch(xo, yo, xi, yi, mode, table, gap, gap_open, head)
     return head
+
+
+def spectrum_profile(tokens, k, symbols, dims=None, rows=None):
+    """The k-mer count profiles of a (N, L <= 2048) uint8 token matrix (pg_spectrum_profile): tokens
+    1..symbols, 0 padding or unknown anywhere; `dims` None / 0 for the exact width symbols^k, else the hashed width.
+    `rows`: row numbers of `tokens` to profile, in that order (host values are checked here; a device tensor costs one
+    sync for the same check).  Returns ((len(rows) or N, D) fp16 device tensor, int32[1] flag tensor - non-zero when a
+    token above `symbols` was read); no host sync: read the flag before trusting the profiles."""
+    L = lib()
+    dev = device()
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.from_numpy(np.ascontiguousarray(np.asarray(tokens)))
+    if tokens.dtype != torch.uint8 or tokens.dim() != 2 or tokens.shape[0] == 0 or tokens.shape[1] == 0:
+        raise TypeError("spectrum_profile expects a non-empty 2-D uint8 token matrix")
+    if tokens.shape[1] > SPECTRUM_MAX_L:
+        raise ValueError(f"spectrum_profile: at most {SPECTRUM_MAX_L} tokens per sequence")
+    D = int(L.pg_spectrum_dims(int(k), int(symbols), int(dims or 0)))
+    if D < 0:
+        raise ValueError(L.pg_last_error().decode("utf-8", "replace"))
+    tokens = tokens.to(dev)
+    if tokens.stride(1) != 1 or tokens.stride(0) < tokens.shape[1]:
+        tokens = tokens.contiguous()
+    n = tokens.shape[0]
+    if rows is not None:
+        rows = torch.as_tensor(rows).reshape(-1).to(torch.int64)
+        if rows.numel() == 0:
+            raise ValueError("spectrum_profile: an empty row list")
+        if bool(((rows < 0) | (rows >= n)).any()):
+            raise ValueError("spectrum_profile: a row number outside the token matrix")
+        rows = rows.to(dev).contiguous()
+        n = rows.numel()
+    out = torch.empty((n, D), dtype=torch.float16, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)        # (pg_spectrum_profile zeroes it on the stream)
+    _check(L.pg_spectrum_profile(_ptr(tokens), n, tokens.shape[1], tokens.stride(0), _ptr(rows), int(k), int(symbols), int(dims or 0),
+                                 _ptr(out), out.stride(0), _ptr(flags), _stream()), "pg_spectrum_profile")
+    return out, flags
 
 
 def i32_knn_round(block, k, floor_idx, floor_w, idx_out, w_out, descending=False):

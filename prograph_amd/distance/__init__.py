@@ -8,5 +8,6 @@ from .levenshtein import levenshtein, levenshtein_knn
 from .local_alignment import local_alignment
 from .minkowski import minkowski
 from .semiglobal_alignment import semiglobal_alignment
+from .spectrum import spectrum
 from .substitution import substitution
 from .utils import clean_input

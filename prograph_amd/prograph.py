@@ -35,7 +35,7 @@ import torch
 from . import _native
 from . import alignments as _alignments
 from .distance import (alignment, cosine, euclidean, fit_alignment, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment,
-                       substitution)
+                       spectrum, substitution)
 
 _EMBED_F32 = {cosine: "cosine", euclidean: "euclidean"}      # fp32 embedding metrics of pg_cos.hip -> their _native prefix
 
@@ -481,8 +481,9 @@ class Prograph:
         any length up to 2048, not only the dataset's) blocks of `pg_levenshtein_dense`, or of `pg_levenshtein_long_dense`
         when queries or dataset are wider than 128 positions, plus the fp16 selection; a
         `substitution` distance blocks of `pg_substitution_dense` plus the fp16 selection; an `alignment` distance (queries
-        of any length up to 128) blocks of `pg_alignment_dense` plus the fp16 selection; any other `distance` the generic
-        loop.
+        of any length up to 128) blocks of `pg_alignment_dense` plus the fp16 selection; a `spectrum` distance (strings or
+        token arrays of any width up to 2048, wider or narrower than the dataset) `pg_spectrum_profile` on both sides
+        and then the fused cosine / Euclidean kernels; any other `distance` the generic loop.
         A `local_alignment` instance is a score, not a distance: `similarity` is not consulted, `k` gives the LARGEST scores
         first (ties to the lower dataset index), `eps` the rows with `s > 0 and comp(eps, s)` - the default comp reads
         `s >= eps` - and the weights are the scores (blocks of `pg_alignment_local_dense` plus the fp16 selection).  A
@@ -534,6 +535,8 @@ class Prograph:
                 g = self._search_eps_hamming(strings, Y, eps, comp, similarity, representation)
             elif distance in (minkowski, cosine, euclidean) and comp in _CMP_CODE and strings is None:
                 g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
+            elif isinstance(distance, spectrum) and comp in _CMP_CODE:
+                g = self._search_spectrum(strings, Y, None, eps, comp, similarity, representation, distance)
             elif distance is levenshtein and comp in _CMP_CODE:
                 g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
             elif isinstance(distance, substitution) and comp in _CMP_CODE:
@@ -549,6 +552,8 @@ class Prograph:
             g = self._search_hamming(strings, Y, k, similarity, representation)
         elif distance in (minkowski, cosine, euclidean) and k <= _native.MAX_K_ROUNDS and strings is None:
             g = self._search_embedding(Y, k, similarity, representation, distance)
+        elif isinstance(distance, spectrum) and k <= _native.MAX_K_ROUNDS:
+            g = self._search_spectrum(strings, Y, k, None, None, similarity, representation, distance)
         elif distance is levenshtein and k <= _native.MAX_K_ROUNDS:
             g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
         elif isinstance(distance, substitution) and k <= _native.MAX_K_ROUNDS:
@@ -698,7 +703,10 @@ class Prograph:
         ops = self._embedding_operands(Y, representation)
         if ops is None:
             return None
-        X, Y = ops
+        return self._search_embedding_staged(*ops, k, similarity, distance)
+
+    def _search_embedding_staged(self, X, Y, k, similarity, distance):
+        """`_search_embedding` from the staged operands on: X (N, D) and Y (Q, D) fp16 device tensors."""
         n, kk = X.shape[0], min(k, X.shape[0])
         if distance is minkowski:
             xp = _native.pack_f16(X)
@@ -1245,7 +1253,10 @@ class Prograph:
         ops = self._embedding_operands(Y, representation)
         if ops is None:
             return None
-        X, Y = ops
+        return self._search_eps_embedding_staged(*ops, eps, comp, similarity, distance)
+
+    def _search_eps_embedding_staged(self, X, Y, eps, comp, similarity, distance):
+        """`_search_eps_embedding` from the staged operands on: X (N, D) and Y (Q, D) fp16 device tensors."""
         n, cmp = X.shape[0], _CMP_CODE[comp]
         if similarity:
             eps = 1 / (1 + eps)                                          # :720-721
@@ -1348,6 +1359,10 @@ class Prograph:
         WHOLE within any stretch of column c, so row r lists the sequences that contain it best, (r, c) and (c, r) differ,
         and a `k` list may hold negative scores; rank 0 - the row itself or a row of lower index that contains it - is
         dropped as for every distance.
+        `distance=spectrum(...)` compares the sequences of the token column by their k-mer counts (`_build_graph_spectrum`):
+        profiles from `pg_spectrum_profile`, then the run of a stored embedding under the operator's metric - final fp32
+        weights, k up to 1023, `eps` under the five orderings; sequences with equal k-mer multisets are at distance 0 and
+        are dropped from `eps` graphs like duplicates.
         `min_identity=` (0..1) and `min_columns=` cut the graph by PERCENT IDENTITY; `distance` must then be one of the four
         alignment operators (`TypeError`).  The graph is built exactly as without them; then every edge is aligned
         (`align(..., ops=False)`: `pg_alignment_stats` at up to 128 positions) and kept iff its canonical alignment has
@@ -1385,6 +1400,8 @@ class Prograph:
             g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
         if distance is euclidean and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_euclidean(idxs, eps, k, similarity, representation, comp, cap)
+        if isinstance(distance, spectrum) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+            g = self._build_graph_spectrum(idxs, eps, k, similarity, representation, comp, cap, distance)
         if distance is levenshtein and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
             g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
         if isinstance(distance, substitution) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
@@ -1566,6 +1583,10 @@ class Prograph:
             return None
         if idxs is not None:
             X = X[torch.as_tensor(np.asarray(idxs), device=X.device)]
+        return self._build_graph_staged_f32(metric, X, eps, k, similarity, comp, cap)
+
+    def _build_graph_staged_f32(self, metric, X, eps, k, similarity, comp, cap):
+        """`_build_graph_embed_f32` from the staged vectors on: X a non-empty (n, D) fp16 device tensor."""
         n = X.shape[0]
         xc = _native.cosine_prep(X)
         if xc.nonfinite():
@@ -1580,6 +1601,66 @@ class Prograph:
             return KNNGraph(idx, w, n, similarity=similarity, final=True)
         indptr, indices, wts = getattr(_native, metric + "_eps")(xc, xc, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity, final=True)
+
+    def _spectrum_tokens(self, representation):
+        """The token column as `pg_spectrum_profile` takes it - a non-empty (N, L <= 2048) uint8 device tensor: the
+        constructor's device copy of the token matrix when there is one, else the column staged now.  None when the
+        column is not a matrix of integers in 0..255 of that width."""
+        tok = getattr(self, "_tok_u8_dev", None)
+        if representation == "Tokenized" and tok is not None:
+            return tok
+        try:
+            mat = np.asarray(self._dataset_matrix(representation))
+        except (ValueError, TypeError):
+            return None
+        if (mat.ndim != 2 or mat.shape[0] == 0 or not 1 <= mat.shape[1] <= _native.SPECTRUM_MAX_L
+                or not np.issubdtype(mat.dtype, np.integer) or mat.min() < 0 or mat.max() > 255):
+            return None
+        return torch.from_numpy(np.ascontiguousarray(mat.astype(np.uint8))).to(_native.device())
+
+    def _build_graph_spectrum(self, idxs, eps, k, similarity, representation, comp, cap, distance):
+        """
+        `build_graph(distance=spectrum(...))`: the token column staged as uint8 on the device, its k-mer
+        count profiles from `pg_spectrum_profile` (`idxs` as the kernel's gather list), the flag word read once, and from
+        the fp16 profiles on exactly the run of `_build_graph_embed_f32` for a stored embedding under the operator's
+        metric - a KNNGraph / CSRGraph with final fp32 weights.  None (the generic path, where the operator raises for bad
+        tokens) when the column is not byte tokens of at most 2048 positions or holds a token above `symbols`.
+        """
+        tok = self._spectrum_tokens(representation)
+        if tok is None or (idxs is not None and len(idxs) == 0):
+            return None
+        rows = None if idxs is None else np.asarray(idxs, dtype=np.int64)
+        if rows is not None:
+            rows = np.where(rows < 0, rows + tok.shape[0], rows)           # negative positions count from the end
+        prof, flags = _native.spectrum_profile(tok, distance.k, distance.symbols, distance.dims, rows=rows)
+        if int(flags.item()):
+            return None
+        return self._build_graph_staged_f32(distance.metric, prof, eps, k, similarity, comp, cap)
+
+    def _search_spectrum(self, strings, Y, k, eps, comp, similarity, representation, distance):
+        """Queries under a `spectrum` distance: dataset and queries through `pg_spectrum_profile`, each at its own width
+        (strings are tokenised with the dataset's letter table; the two widths need not agree, and no padding is needed:
+        a window holding a 0 does not count), the two flag words read once, then the cosine / Euclidean query paths from
+        the staged profiles on, rank 0 and d = 0 kept.  None (the generic loop with the operator, which raises for bad
+        tokens) when dataset or queries are not byte tokens of at most 2048 positions or hold a token above `symbols`."""
+        tok = self._spectrum_tokens(representation)
+        if tok is None:
+            return None
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            T = table[raw]
+        else:
+            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        if (T.ndim != 2 or T.shape[0] == 0 or not 1 <= T.shape[1] <= _native.SPECTRUM_MAX_L
+                or not np.issubdtype(T.dtype, np.integer) or T.min() < 0 or T.max() > 255):
+            return None
+        px, fx = _native.spectrum_profile(tok, distance.k, distance.symbols, distance.dims)
+        py, fy = _native.spectrum_profile(np.ascontiguousarray(T.astype(np.uint8)), distance.k, distance.symbols, distance.dims)
+        if int((fx | fy).item()):
+            return None
+        if k is not None:
+            return self._search_embedding_staged(px, py, k, similarity, distance.plain)
+        return self._search_eps_embedding_staged(px, py, eps, comp, similarity, distance.plain)
 
     _LEV_FUSED_MAX = _native.LEV_MAX_BAND            # thresholds the fused epsilon graph (and the banded first kNN pass) cover
 
