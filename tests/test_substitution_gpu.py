@@ -132,6 +132,106 @@ def test_kernel_accumulates_column_segments(nat):
     assert np.array_equal(one.cpu().numpy(), definition(C, X, Y))
 
 
+# ---------------------------------------------------------------- 1b. several tiles per workgroup, packed sums at their limit
+SUB_TILES = 8
+
+
+def tiles_of(m, n):
+    """The tiles of 512 columns one workgroup of `pg_sub_dense_kernel` sweeps per LDS image, as `pg_substitution_dense`
+    (prograph_amd/csrc/pg_sub.hip) chooses them: from SUB_TILES = 8, halved while (row blocks of 16) x (column groups of
+    `tiles` tiles) stays below 4096 workgroups.  Mirrored here so that a change of the rule makes the tests below say that
+    their shapes no longer reach the tile loop."""
+    row_blocks, ntiles = -(-m // 16), -(-n // 512)
+    tiles = SUB_TILES
+    while tiles > 1 and row_blocks * -(-ntiles // tiles) < 4096:
+        tiles >>= 1
+    return tiles
+
+
+def test_the_mirrored_tiles_rule_and_the_older_shapes():
+    assert tiles_of(70, 2100) == 1 and tiles_of(200, 1000) == 1          # every shape of the tests above: one tile
+    assert tiles_of(4096, 50_000) == 4 and tiles_of(65536, 50_000) == 8     # row blocks of a graph at N = 50 000
+
+
+#                 tiles  M      N     L    table entries  output types
+TILE_SHAPES = [(8, 32763, 5637, 5, 256, (2,)),       # groups of tiles 0-7 and 8-11 (breaks at the 12th); 5 columns in the last
+               (4, 16375, 6151, 33, 256, (4,)),      # the last workgroup holds a single tile of 7 columns
+               (2, 16375, 3172, 121, 17, (2, 4))]    # two LDS images: the tile loop runs again with add = true
+
+
+@pytest.mark.parametrize("tiles,M,N,L,values,outs", TILE_SHAPES, ids=lambda v: str(v) if isinstance(v, int) else None)
+def test_kernel_with_several_tiles_per_workgroup(nat, tiles, M, N, L, values, outs):
+    """Shapes at which a workgroup sweeps 8, 4 and 2 tiles with one image: the tile loop beyond its first turn, its
+    break past the last tile, the column base of the second group, the operand clamp of lanes beyond npad(N) and the
+    re-entry in a second pass.  The Y rows are a random gather of 48 distinct rows (every 16-row group mixes them), so
+    the definition is computed on 48 x N and gathered on the device."""
+    ntiles = -(-N // 512)
+    assert tiles_of(M, N) == tiles, "the tiles rule changed: this shape no longer runs the tile loop as stated"
+    assert -(-ntiles // tiles) * tiles > ntiles and M % 16                  # the last column group breaks early
+    assert L * (values - 1) <= 2048 or 2 not in outs                        # fp16 holds every distance exactly
+    rng = np.random.default_rng(M + N)
+    C = table(rng, 21, np.arange(values))
+    pool, X = rng.integers(0, 21, (48, L)), rng.integers(0, 21, (N, L))
+    pool[0] = 0                                                           # an all-zero row on either side
+    X[7] = X[N - 2] = 0
+    ids = rng.integers(0, 48, M)
+    ids[[5, M - 1]] = 0
+    assert min(len(set(g)) for g in ids[:M - M % 16].reshape(-1, 16)) > 4     # every 16-row group mixes pool rows
+    dev = nat.device()
+    xo = nat.sub_operand(torch.from_numpy(X.astype(np.uint8)), 21)
+    yo = nat.sub_operand(torch.from_numpy(pool[ids].astype(np.uint8)), 21)
+    assert xo.valid() and yo.valid()
+    cost = nat.sub_cost(C)
+    ref = torch.from_numpy(definition(C, X, pool)).to(dev)
+    ids_dev = torch.from_numpy(ids).to(dev)
+    for ob in outs:
+        got = nat.substitution_dense(xo, yo, cost, out_bytes=ob)
+        want = ref.to(got.dtype)[ids_dev]
+        same = got.shape == (M, N) and torch.equal(got, want)
+        assert same, (ob, "entries that differ:", int((got != want).sum()), "the first at", torch.nonzero(got != want)[:4].tolist())
+        del got, want
+    if len(outs) == 2:                                                    # a row range that starts inside a 16-row group
+        assert tiles_of(M - 5, N) == tiles
+        got = nat.substitution_dense(xo, yo, cost, rows=(5, M))
+        same = got.dtype == torch.int64 and torch.equal(got, ref[ids_dev[5:]])
+        assert same, "rows=(5, M)"
+
+
+def _lane_patterns():
+    """Groups of 16 Y rows over {0, 1}: 0101.., 1010.., 0011.., 0110.., and a single 1 at each of the 16 places."""
+    groups = [[0, 1] * 8, [1, 0] * 8, [0, 0, 1, 1] * 4, [0, 1, 1, 0] * 4] + [[int(i == j) for i in range(16)] for j in range(16)]
+    return np.array(groups).reshape(-1)
+
+
+@pytest.mark.parametrize("L", [PASS - 1, PASS, PASS + 1, 2048])
+def test_packed_sums_with_neighbouring_lanes_at_their_limits(nat, L):
+    """C[1][2] = 255 and C[1][3] = 0, X rows of 1s, Y rows of 2s (cost 255 at every position) or 3s (cost 0) arranged so
+    that the two byte lanes of a 16-bit half hold PASS * 255 and 0 in either order, next to equal lanes: the recovery
+    b0 = aw - (ao << 8) borrows, and a lane that leaks into its neighbour shows.  2048 positions: 18 passes, 522 240."""
+    C = np.zeros((21, 21), dtype=np.int64)
+    C[1, 2] = C[2, 1] = 255
+    rows = _lane_patterns()
+    X, Y = np.full((70, L), 1), np.where(rows[:, None] == 1, 2, 3) * np.ones((1, L), dtype=np.int64)
+    want = definition(C, X, Y)
+    assert want.max() == 255 * L and np.array_equal(want[:, 0], rows * 255 * L)
+    for ob, dtype in ((8, torch.int64), (4, torch.int32)):
+        got = dense(nat, C, X, Y, out_bytes=ob)
+        assert got.dtype == dtype and np.array_equal(got.cpu().numpy().astype(np.int64), want), (L, ob)
+
+
+def test_fp16_accumulation_over_eighteen_passes(nat):
+    """2048 positions under 1 - I: every pass adds into the fp16 output, the largest distance is exactly 2048."""
+    rng = np.random.default_rng(18)
+    C = 1 - np.eye(21, dtype=np.int64)
+    X, Y = rng.integers(0, 21, (300, 2048)), rng.integers(0, 21, (33, 2048))
+    X[17], Y[4] = 1, 2
+    X[40, 100:] = Y[9, 100:]                                              # a near pair: most passes add 0
+    want = definition(C, X, Y)
+    assert want.max() == 2048 and want[4, 17] == 2048 and want[9, 40] <= 100
+    got = dense(nat, C, X, Y, out_bytes=2)
+    assert got.dtype == torch.float16 and np.array_equal(got.cpu().numpy().astype(np.int64), want)
+
+
 def test_pack_flags_tokens_outside_the_table(nat):
     T = np.full((3, 9), 20, dtype=np.uint8)
     assert nat.sub_operand(torch.from_numpy(T), 21).valid()
