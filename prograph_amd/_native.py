@@ -952,36 +952,39 @@ def aln_operand(tokens, a):
     return AlnOperand(so.buf, so.n, so.l, so.flags)
 
 
-def alignment_dense(xo, yo, cost, gap, out_bytes=8, rows=None):
-    """(M, N) gapped alignment distances of the rows of AlnOperand `yo` (rows = (r0, r1): only those) against every row
-    of `xo` (pg_alignment_dense); `cost` from sub_cost, `gap` 1..255; the operands' widths need not agree.  int64
-    (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2: exact while the distances stay within 2048)."""
-    if out_bytes not in (2, 8):
-        raise ValueError("alignment_dense: out_bytes 8 (int64) or 2 (fp16)")
+def _aln_dense(entry, name, xo, yo, table, penalties, out_bytes, rows, long=False):
+    """One dense alignment entry: the rows (r0, r1) of `yo` against every row of `xo`; `penalties` are the entry's integers
+    between the table and `out` (gap[, gap_open[, bias]]).  `long`: int32 | int64 out and the call's workspace (the entries
+    beyond 128 positions), else fp16 | int64."""
+    small = 4 if long else 2
+    if out_bytes not in (small, 8):
+        raise ValueError(f"{name}: out_bytes 8 (int64) or {small} ({'int32' if long else 'fp16'})")
     r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
     if not 0 <= r0 < r1 <= yo.n:
         raise ValueError("row range outside the operand")
     out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    _check(lib().pg_alignment_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
-                                    yo.npad, yo.l, _ptr(cost), int(gap), _ptr(out), out.stride(0), out_bytes, _stream()),
-           "pg_alignment_dense")
+    tail = ()
+    if long:
+        ws = aln_long_workspace(xo, r1 - r0)
+        tail = (_ptr(ws), ws.numel())
+    _check(getattr(lib(), entry)(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
+                                 yo.npad, yo.l, _ptr(table), *(int(v) for v in penalties), _ptr(out), out.stride(0), out_bytes,
+                                 *tail, _stream()), entry)
     return out
+
+
+def alignment_dense(xo, yo, cost, gap, out_bytes=8, rows=None):
+    """(M, N) gapped alignment distances of the rows of AlnOperand `yo` (rows = (r0, r1): only those) against every row
+    of `xo` (pg_alignment_dense); `cost` from sub_cost, `gap` 1..255; the operands' widths need not agree.  int64
+    (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2: exact while the distances stay within 2048)."""
+    return _aln_dense("pg_alignment_dense", "alignment_dense", xo, yo, cost, (gap,), out_bytes, rows)
 
 
 def alignment_affine_dense(xo, yo, cost, gap, gap_open, out_bytes=8, rows=None):
     """`alignment_dense` with affine gap penalties (pg_alignment_affine_dense): a run of g unaligned symbols costs
     gap_open + g * gap, `gap` 1..255, `gap_open` 0..255 (0: the distances of `alignment_dense`).  Same AlnOperands, row
     range and outputs; fp16 is exact while width * max(max C, gap) + gap_open stays within 2048."""
-    if out_bytes not in (2, 8):
-        raise ValueError("alignment_affine_dense: out_bytes 8 (int64) or 2 (fp16)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    _check(lib().pg_alignment_affine_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
-                                           r1 - r0, yo.npad, yo.l, _ptr(cost), int(gap), int(gap_open), _ptr(out),
-                                           out.stride(0), out_bytes, _stream()), "pg_alignment_affine_dense")
-    return out
+    return _aln_dense("pg_alignment_affine_dense", "alignment_affine_dense", xo, yo, cost, (gap, gap_open), out_bytes, rows)
 
 
 def aln_local_score(table):
@@ -1000,32 +1003,14 @@ def alignment_local_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
     against every row of `xo` (pg_alignment_local_dense); `score` from aln_local_score, `gap` 1..255, `gap_open` 0..255;
     the operands' widths need not agree.  int64 (out_bytes 8) or the fp16 block f16_knn / f16_eps select from (2: exact
     while width * max(S) stays within 2048)."""
-    if out_bytes not in (2, 8):
-        raise ValueError("alignment_local_dense: out_bytes 8 (int64) or 2 (fp16)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    _check(lib().pg_alignment_local_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
-                                          r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), _ptr(out),
-                                          out.stride(0), out_bytes, _stream()), "pg_alignment_local_dense")
-    return out
+    return _aln_dense("pg_alignment_local_dense", "alignment_local_dense", xo, yo, score, (gap, gap_open), out_bytes, rows)
 
 
 def alignment_semiglobal_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
     """(M, N) semi-global alignment SCORES (both sequences end to end, free end gaps; larger is nearer) of the rows of
     AlnOperand `yo` (rows = (r0, r1): only those) against every row of `xo` (pg_alignment_semiglobal_dense); arguments and
     outputs as `alignment_local_dense`, `score` from aln_local_score."""
-    if out_bytes not in (2, 8):
-        raise ValueError("alignment_semiglobal_dense: out_bytes 8 (int64) or 2 (fp16)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    _check(lib().pg_alignment_semiglobal_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
-                                               r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), _ptr(out),
-                                               out.stride(0), out_bytes, _stream()), "pg_alignment_semiglobal_dense")
-    return out
+    return _aln_dense("pg_alignment_semiglobal_dense", "alignment_semiglobal_dense", xo, yo, score, (gap, gap_open), out_bytes, rows)
 
 
 def aln_long_ready():
@@ -1073,34 +1058,15 @@ def alignment_fit_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None, bi
     (pg_alignment_fit_dense); arguments and outputs as `alignment_semiglobal_dense`.  Exact while
     `aln_fit_fits(xo.l, yo.l, max(S), gap, gap_open)` holds, and in fp16 while every score + bias lies in 0..2048; the
     caller checks both."""
-    if out_bytes not in (2, 8):
-        raise ValueError("alignment_fit_dense: out_bytes 8 (int64) or 2 (fp16)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    _check(lib().pg_alignment_fit_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
-                                        r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), int(bias), _ptr(out),
-                                        out.stride(0), out_bytes, _stream()), "pg_alignment_fit_dense")
-    return out
+    return _aln_dense("pg_alignment_fit_dense", "alignment_fit_dense", xo, yo, score, (gap, gap_open, bias), out_bytes, rows)
 
 
 def alignment_fit_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None, bias=0):
     """`alignment_fit_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_fit_long_dense): int64 (out_bytes
     8) or the int32 block i32_knn / i32_eps select from (4).  Exact while `aln_fit_fits` holds, which the caller checks.
     Allocates the call's workspace."""
-    if out_bytes not in (4, 8):
-        raise ValueError("alignment_fit_long_dense: out_bytes 8 (int64) or 4 (int32)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    ws = aln_long_workspace(xo, r1 - r0)
-    _check(lib().pg_alignment_fit_long_dense(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0),
-                                             r1 - r0, yo.npad, yo.l, _ptr(score), int(gap), int(gap_open), int(bias),
-                                             _ptr(out), out.stride(0), out_bytes, _ptr(ws), ws.numel(), _stream()),
-           "pg_alignment_fit_long_dense")
-    return out
+    return _aln_dense("pg_alignment_fit_long_dense", "alignment_fit_long_dense", xo, yo, score, (gap, gap_open, bias), out_bytes,
+                      rows, long=True)
 
 
 def aln_long_operand(tokens, a):
@@ -1123,39 +1089,25 @@ def aln_long_workspace(xo, nrows):
     return torch.empty(min(full.value, tiles * one.value), dtype=torch.uint8, device=xo.buf.device)
 
 
-def _aln_long(entry, name, xo, yo, table, gap, gap_open, out_bytes, rows):
-    if out_bytes not in (4, 8):
-        raise ValueError(f"{name}: out_bytes 8 (int64) or 4 (int32)")
-    r0, r1 = (0, yo.n) if rows is None else (int(rows[0]), int(rows[1]))
-    if not 0 <= r0 < r1 <= yo.n:
-        raise ValueError("row range outside the operand")
-    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
-    ws = aln_long_workspace(xo, r1 - r0)
-    _check(getattr(lib(), entry)(_ptr(xo.buf), xo.n, xo.npad, xo.l, ctypes.c_void_p(yo.buf.data_ptr() + 4 * r0), r1 - r0,
-                                 yo.npad, yo.l, _ptr(table), int(gap), int(gap_open), _ptr(out), out.stride(0), out_bytes,
-                                 _ptr(ws), ws.numel(), _stream()), entry)
-    return out
-
-
 def alignment_long_dense(xo, yo, cost, gap, gap_open, out_bytes=8, rows=None):
     """`alignment_affine_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_long_dense; gap_open = 0: the
     linear penalty): int64 (out_bytes 8) or the int32 block i32_knn / i32_eps select from (4).  Exact while
     `aln_long_fits(max(xo.l, yo.l), ...)` holds, which the caller checks.  Allocates the call's workspace."""
-    return _aln_long("pg_alignment_long_dense", "alignment_long_dense", xo, yo, cost, gap, gap_open, out_bytes, rows)
+    return _aln_dense("pg_alignment_long_dense", "alignment_long_dense", xo, yo, cost, (gap, gap_open), out_bytes, rows, long=True)
 
 
 def alignment_local_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
     """`alignment_local_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_local_long_dense), outputs as
     `alignment_long_dense`.  Exact while `aln_local_long_fits(xo.l, yo.l, max(S))` holds, which the caller checks."""
-    return _aln_long("pg_alignment_local_long_dense", "alignment_local_long_dense", xo, yo, score, gap, gap_open, out_bytes, rows)
+    return _aln_dense("pg_alignment_local_long_dense", "alignment_local_long_dense", xo, yo, score, (gap, gap_open), out_bytes, rows, long=True)
 
 
 def alignment_semiglobal_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=None):
     """`alignment_semiglobal_dense` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_semiglobal_long_dense),
     outputs as `alignment_long_dense`.  Exact while `aln_semiglobal_long_fits(xo.l, yo.l, max(S))` holds, which the caller
     checks."""
-    return _aln_long("pg_alignment_semiglobal_long_dense", "alignment_semiglobal_long_dense", xo, yo, score, gap, gap_open,
-                     out_bytes, rows)
+    return _aln_dense("pg_alignment_semiglobal_long_dense", "alignment_semiglobal_long_dense", xo, yo, score, (gap, gap_open),
+                      out_bytes, rows, long=True)
 
 
 def aln_trace_wave_bytes(xl, yl):

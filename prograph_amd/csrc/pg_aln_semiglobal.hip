@@ -4,12 +4,9 @@
 //     E[i][j] = max(E[i-1][j] - e, H[i-1][j] - o - e),   F[i][j] = max(F[i][j-1] - e, H[i][j-1] - o - e),
 //     H[i][j] = max(H[i-1][j-1] + S[x_i][y_j], E[i][j], F[i][j])                                     (no zero floor),
 //     s(y, x) = max(max over i of H[i][len y], max over j of H[len x][j]).
-// BUILD DEFINED.  A similarity, >= 0 (H[0][len y] = 0).  Two kernels: pg_aln_semiglobal_dense_kernel, the shape of
-// pg_aln_local.hip up to 128 positions (one X sequence per lane, ALN_ROWS wave-uniform Y rows per workgroup, byte query
-// profiles in LDS at stride ALN_QSTRIDE, one 16-byte LDS read per 16 cells, P[j] = H | E << 16, a compile-time switch on
-// NC = ceil(ly / 16), the lengths found here, lanes past their own length masked out), and
-// pg_aln_semiglobal_long_dense_kernel, the strips, boundary column and profile slots of pg_aln_long.hip up to 2048.  The
-// staging code is those kernels', repeated here so that they stay as they are.
+// BUILD DEFINED.  A similarity, >= 0 (H[0][len y] = 0).  Two kernels, pg_aln_semiglobal_dense_kernel up to 128 positions and
+// pg_aln_semiglobal_long_dense_kernel up to 2048: the two frames of pg_aln_frame.h around the cell loop of pg_aln_score.h, with
+// row 0 = Z, the masked last column folded at every step and row len x folded after the loop.
 //
 // Arithmetic.  Cells go negative, the registers are unsigned: a cell holds H + Z, E + Z, F + Z with the wave-uniform
 // offset Z = min(xl, yl) * max(0, max S) of the operand WIDTHS, and every subtraction saturates as in pg_aln_local.hip
@@ -28,277 +25,42 @@
 // so a masked-out cell is 0 <= best.  An interior cell (j < len y, i < len x) is never folded.  (3) Padding: profile
 // bytes at j >= len y are 0 (a score of -bias <= 0), so a padded cell is at most a last-column cell of the same or an
 // earlier step - the fold after the loop may include them.
-#include "pg_common.h"
-#include "../../include/prograph_hip.h"
+#include "pg_aln_score.h"
 
-#define ALN_THREADS 256
-#define ALN_ROWS 8                 // Y rows per workgroup: 8 profiles = 36 KiB of LDS (long kernel: 8 strips of one row)
-#define ALN_MAX_L 128
-#define ALN_STRIP 128
-#define ALN_QSTRIDE 144
-#define ALN_QBYTES (32 * ALN_QSTRIDE)
-#define ALN_CSTRIDE 36             // bytes per row of the staged score table (as in pg_sub.hip)
-#define ALNG_MAX_L PG_ALN_LONG_MAX_L
-
-typedef unsigned short alns_u16x2 __attribute__((ext_vector_type(2)));
-
-// index of the last non-zero byte + 1 of dword g, 0 for an empty dword
-__device__ __forceinline__ int alns_len(u32 w, int g) { return w ? 4 * g + 4 - (__clz(w) >> 3) : 0; }
-
-// a - b, 0 where b > a
-__device__ __forceinline__ u32 alns_sat(u32 a, u32 b) { return __builtin_elementwise_sub_sat(a, b); }
-
-// the same on both 16-bit halves at once
-__device__ __forceinline__ u32 alns_sat2(u32 a, u32 b) {
-  return __builtin_bit_cast(u32, __builtin_elementwise_sub_sat(__builtin_bit_cast(alns_u16x2, a), __builtin_bit_cast(alns_u16x2, b)));
-}
-
-// One strip of 16 * NC cells of one Y row against the lane's X sequence: the whole row in the short kernel (j0 = 0, LAST),
-// strip j0 / 128 in the long one.  Q: the strip's profile; jl: the index of len y inside the LAST strip's last chunk
-// (1..16); wsb: the boundary column (read when j0 > 0, written unless LAST); best: the maximum so far (+ Z).
-template <int NC, bool LAST, bool LONG>
-__device__ __forceinline__ u32 alns_strip(const unsigned char *Q, const u32 *xb, u32 *wsb, int lane, long long xnpad, int lx, int lxmax,
-                                          int j0, int jl, u32 e, u32 oe, u32 bias, u32 Z, u32 best) {
-  const u32 K = oe | (e << 16);
-  u32 m[16];                                                              // scalar masks: all ones at len y
-#pragma unroll
-  for (int t = 0; t < 16; ++t) m[t] = (LAST && jl == t + 1) ? 0xffffffffu : 0u;
-  u32 P[16 * NC + 1];                                                     // P[j] = H[j0 + j] | E[j0 + j] << 16, + Z each; P[0]: H alone
-#pragma unroll
-  for (int j = 0; j <= 16 * NC; ++j) P[j] = Z;                            // row 0: H = 0, E = -inf
-  u32 xw = 0;
-  for (int i = 0; i < lxmax; ++i) {
-    if ((i & 3) == 0) xw = (xb + (long long)(i >> 2) * xnpad)[lane];          // wave-uniform branch and base, coalesced load
-    const u32 x = (xw >> (8 * (i & 3))) & 31u;
-    if (i < lx) {
-      const unsigned char *q = Q + x * ALN_QSTRIDE;
-      u32 left = Z, F = 0;                                                // H[i][0] = 0, F[i][0] = -inf
-      u32 *bd = LONG ? wsb + (long long)i * ALN_THREADS : nullptr;        // this step's line of the boundary column
-      if (LONG && j0) {                                                   // wave-uniform
-        const u32 v = bd[lane];
-        left = v & 0xffffu;
-        F = v >> 16;
-      }
-      u32 diag = P[0];
-      P[0] = left;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const uint4 v = *(const uint4 *)(q + 16 * c);
-        const u32 w[4] = {v.x, v.y, v.z, v.w};
-        // the diagonal terms first, from the old column: afterwards every cell is rewritten in place
-        u32 T[16];
-        T[0] = alns_sat((diag & 0xffffu) + (w[0] & 255u), bias);
-#pragma unroll
-        for (int t = 1; t < 16; ++t) T[t] = alns_sat((P[16 * c + t] & 0xffffu) + ((w[t >> 2] >> (8 * (t & 3))) & 255u), bias);
-        diag = P[16 * c + 16];
-#pragma unroll
-        for (int t = 0; t < 16; t += 2) {
-          u32 h[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const u32 s = alns_sat2(P[16 * c + t + u + 1], K);            // H -sat- (o + e) | (E -sat- e) << 16
-            const u32 E = max(s & 0xffffu, s >> 16);
-            F = max(alns_sat(F, e), alns_sat(left, oe));
-            left = max(T[t + u], max(E, F));
-            P[16 * c + t + u + 1] = left | (E << 16);
-            h[u] = left;
-          }
-          if (LAST && c == NC - 1) best = max(max(best, h[0] & m[t]), h[1] & m[t + 1]);      // H[i][len y] alone
-        }
-      }
-      if (LONG && !LAST) bd[lane] = left | (F << 16);                     // H[i + 1][j0 + 128] | F[i + 1][j0 + 128] << 16
-    }
+struct AlnSemiglobal : AlnModeBase {
+  static constexpr bool SCORE = true, TOP = true, ROWFOLD = true;
+  static constexpr int ROW0 = ALN_ROW0_Z, FOLD = ALN_FOLD_LASTCOL;
+  u32 e, oe, bias, Z;
+  // Z <= 128 * 127 in the short kernel; 2 Z + 255 <= 65 535 is the guarantee of the long entry's caller
+  __device__ __forceinline__ AlnSemiglobal(const AlnParams &p)
+      : e(p.gap), oe(p.open + p.gap), bias(p.bias), Z((u32)min(p.xl, p.yl) * p.top) {}
+  __device__ __forceinline__ u32 first(int, int) const { return Z; }        // H[0][len y] = 0
+  // rest = len y - j0 >= 1; its index inside the last chunk is rest - ((rest - 1) & ~15), 1..16
+  template <int NC>
+  __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const {
+    return aln_score_strip<AlnSemiglobal, NC, true, false>(q, x, nullptr, 0, ly - ((ly - 1) & ~15), e, oe, bias, Z, Z);
   }
-  // row len x of this strip (cells past len y: at most a folded last-column cell)
-#pragma unroll
-  for (int j = 1; j <= 16 * NC; j += 2) best = max(max(best, P[j] & 0xffffu), P[j + 1] & 0xffffu);
-  return best;
-}
-
-// the score table into LDS as bytes S + bias; returns bias = -min(0, min S) and *top = max(0, max S), both wave-uniform
-__device__ __forceinline__ u32 alns_table(const signed char *score, unsigned char *cs, int *smin, int *smax, int tid, u32 *top) {
-  if (tid == 0) {
-    *smin = 0;
-    *smax = 0;
+  template <int NC, bool LAST>
+  __device__ __forceinline__ u32 strip(const unsigned char *q, const AlnX &x, u32 *wsb, int j0, int rest, u32 best) const {
+    return aln_score_strip<AlnSemiglobal, NC, LAST, true>(q, x, wsb, j0, rest - ((rest - 1) & ~15), e, oe, bias, Z, best);
   }
-  int sc[4], lo = 0, hi = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    sc[k] = score[tid + k * ALN_THREADS];
-    lo = min(lo, sc[k]);
-    hi = max(hi, sc[k]);
-  }
-  __syncthreads();
-  if (lo < 0) atomicMin(smin, lo);
-  if (hi > 0) atomicMax(smax, hi);
-  __syncthreads();
-  const u32 bias = (u32)(-__builtin_amdgcn_readfirstlane(*smin));            // 0..128, in a scalar register
-  *top = (u32)__builtin_amdgcn_readfirstlane(*smax);                        // 0..127
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int i = tid + k * ALN_THREADS;
-    cs[(i >> 5) * ALN_CSTRIDE + (i & 31)] = (unsigned char)(sc[k] + (int)bias);
-  }
-  return bias;
-}
-
-// four profile bytes of symbol row `crow` against the tokens of dword w, positions past the sequence (keep < 4) zeroed
-__device__ __forceinline__ u32 alns_profile(const unsigned char *crow, u32 w, int keep) {
-  const u32 d = (u32)crow[w & 31u] | ((u32)crow[(w >> 8) & 31u] << 8) | ((u32)crow[(w >> 16) & 31u] << 16) |
-                ((u32)crow[(w >> 24) & 31u] << 24);
-  return d & (keep >= 4 ? 0xffffffffu : keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
-}
+  template <typename OUT>
+  __device__ __forceinline__ OUT value(u32 d) const { return (OUT)(d - Z); }
+};
 
 template <typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void pg_aln_semiglobal_dense_kernel(
     const u32 *__restrict__ xt, long long n, long long xnpad, int xl, const u32 *__restrict__ yt, long long m, long long ynpad,
-    int yl, const signed char *__restrict__ score, u32 gap, u32 open, OUT *__restrict__ out, long long ldo, long long colTiles) {
-  __shared__ __attribute__((aligned(16))) unsigned char Q[ALN_ROWS * ALN_QBYTES];
-  __shared__ u32 ytile[ALN_ROWS][ALN_MAX_L / 4];
-  __shared__ unsigned char cs[32 * ALN_CSTRIDE];
-  __shared__ int ylen[ALN_ROWS];
-  __shared__ int smin, smax;
-  const int tid = threadIdx.x;
-  const long long ct = (long long)blockIdx.x % colTiles, rg = (long long)blockIdx.x / colTiles;
-  const long long row0 = rg * ALN_ROWS;
-  const int xg = (xl + 3) >> 2, yg = (yl + 3) >> 2;                         // <= 32 dwords each (the host checks)
-
-  for (int i = tid; i < ALN_ROWS * (ALN_MAX_L / 4); i += ALN_THREADS) {
-    const int r = i >> 5, g = i & 31;
-    ytile[r][g] = (row0 + r < m && g < yg) ? yt[(long long)g * ynpad + row0 + r] : 0u;
-  }
-  u32 top;
-  const u32 bias = alns_table(score, cs, &smin, &smax, tid, &top);          // its barriers cover ytile
-  if (tid < ALN_ROWS) {
-    int len = 0;
-    for (int g = 0; g < ALN_MAX_L / 4; ++g) len = max(len, alns_len(ytile[tid][g], g));
-    ylen[tid] = len;
-  }
-  __syncthreads();
-  for (int i = tid; i < ALN_ROWS * 32 * 32; i += ALN_THREADS) {
-    const int g = i & 31, a = (i >> 5) & 31, r = i >> 10;
-    // S is symmetric: S[a][y] = S[y][a]; past len y: byte 0, a score of -bias
-    *(u32 *)(Q + r * ALN_QBYTES + a * ALN_QSTRIDE + 4 * g) = alns_profile(cs + a * ALN_CSTRIDE, ytile[r][g], ylen[r] - 4 * g);
-  }
-  __syncthreads();
-
-  // column ct * 256 + tid (< colTiles * 256 <= xnpad): a wave-uniform base and the lane, so that one VGPR addresses both
-  // the tokens and the output
-  const u32 *xb = xt + ct * ALN_THREADS;
-  const long long left_cols = n - ct * ALN_THREADS;                         // >= 1
-  int lx = 0;
-  for (int g = 0; g < xg; ++g) lx = max(lx, alns_len((xb + (long long)g * xnpad)[tid], g));
-  if (tid >= left_cols) lx = 0;
-  int lxmax = lx;
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) lxmax = max(lxmax, __shfl_xor(lxmax, s));
-  lxmax = __builtin_amdgcn_readfirstlane(lxmax);
-
-  const u32 oe = open + gap, Z = (u32)min(xl, yl) * top;                    // Z <= 128 * 127
-  for (int r = 0; r < ALN_ROWS; ++r) {
-    const long long row = row0 + r;
-    if (row >= m) break;
-    const int ly = __builtin_amdgcn_readfirstlane(ylen[r]);
-    const unsigned char *q = Q + r * ALN_QBYTES;
-    const int jl = ly - ((ly - 1) & ~15);                                   // 1..16 for ly >= 1
-    u32 d;
-#define ALNS_ROW(NC) alns_strip<NC, true, false>(q, xb, nullptr, tid, xnpad, lx, lxmax, 0, jl, gap, oe, bias, Z, Z)
-    switch ((ly + 15) >> 4) {
-      case 0: d = Z; break;                                                 // nothing to align with
-      case 1: d = ALNS_ROW(1); break;
-      case 2: d = ALNS_ROW(2); break;
-      case 3: d = ALNS_ROW(3); break;
-      case 4: d = ALNS_ROW(4); break;
-      case 5: d = ALNS_ROW(5); break;
-      case 6: d = ALNS_ROW(6); break;
-      case 7: d = ALNS_ROW(7); break;
-      default: d = ALNS_ROW(8); break;
-    }
-#undef ALNS_ROW
-    if (tid < left_cols) (out + row * ldo + ct * ALN_THREADS)[tid] = (OUT)(d - Z);
-  }
+    int yl, const void *__restrict__ score, u32 gap, u32 open, int obias, OUT *__restrict__ out, long long ldo, long long colTiles) {
+  aln_short_frame<AlnSemiglobal>(xt, n, xnpad, xl, yt, m, ynpad, yl, score, gap, open, obias, out, ldo, colTiles);
 }
 
-// Beyond 128 positions: pg_aln_long.hip's loop over (column tile, row group) items, one Y row at a time, its strips in
-// groups of eight profile slots, the boundary column of workgroup b in slice b of the workspace.
 template <typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) void pg_aln_semiglobal_long_dense_kernel(
     const u32 *__restrict__ xt, long long n, long long xnpad, int xl, const u32 *__restrict__ yt, long long m, long long ynpad,
-    int yl, const signed char *__restrict__ score, u32 gap, u32 open, OUT *__restrict__ out, long long ldo, int colTiles,
+    int yl, const void *__restrict__ score, u32 gap, u32 open, int obias, OUT *__restrict__ out, long long ldo, int colTiles,
     int items, u32 *ws) {
-  __shared__ __attribute__((aligned(16))) unsigned char Q[ALN_ROWS * ALN_QBYTES];
-  __shared__ u32 yrow[ALNG_MAX_L / 4];
-  __shared__ unsigned char cs[32 * ALN_CSTRIDE];
-  __shared__ int ylen;
-  __shared__ int smin, smax;
-  const int tid = threadIdx.x;
-  const int xg = (xl + 3) >> 2, yg = (yl + 3) >> 2;                         // <= 512 dwords each (the host checks)
-  u32 top;
-  const u32 bias = alns_table(score, cs, &smin, &smax, tid, &top);
-  const u32 oe = open + gap, Z = (u32)min(xl, yl) * top;                    // 2 Z + 255 <= 65 535: the caller's guarantee
-
-  u32 *wsb = ws + (long long)blockIdx.x * (xg * 4 * ALN_THREADS);          // this workgroup's boundary column
-  for (int item = blockIdx.x; item < items; item += gridDim.x) {
-    const long long ct = item % colTiles, row0 = (long long)(item / colTiles) * ALN_ROWS;
-    const u32 *xb = xt + ct * ALN_THREADS;
-    const long long left_cols = n - ct * ALN_THREADS;                       // >= 1
-    int lx = 0;
-    for (int g = 0; g < xg; ++g) lx = max(lx, alns_len((xb + (long long)g * xnpad)[tid], g));
-    if (tid >= left_cols) lx = 0;
-    int lxmax = lx;
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) lxmax = max(lxmax, __shfl_xor(lxmax, s));
-    lxmax = __builtin_amdgcn_readfirstlane(lxmax);
-
-    for (int r = 0; r < ALN_ROWS; ++r) {
-      const long long row = row0 + r;
-      if (row >= m) break;
-      __syncthreads();                                                    // the previous row's readers of Q / yrow / ylen are done
-      if (tid == 0) ylen = 0;
-      __syncthreads();
-      for (int g = tid; g < ALNG_MAX_L / 4; g += ALN_THREADS) {
-        const u32 w = g < yg ? yt[(long long)g * ynpad + row] : 0u;
-        yrow[g] = w;
-        if (w) atomicMax(&ylen, alns_len(w, g));
-      }
-      __syncthreads();
-      const int ly = __builtin_amdgcn_readfirstlane(ylen);
-      const int ns = (ly + ALN_STRIP - 1) / ALN_STRIP;                    // strips that hold a position of the row
-      u32 best = Z;                                                       // carried from strip to strip
-      for (int s0 = 0; s0 < ns; s0 += ALN_ROWS) {
-        const int nb = min(ALN_ROWS, ns - s0);
-        if (s0) __syncthreads();                                          // the previous eight strips' profiles are read
-        for (int i = tid; i < nb * 32 * 32; i += ALN_THREADS) {
-          const int g = i & 31, a = (i >> 5) & 31, slot = i >> 10;
-          const int gy = (s0 + slot) * (ALN_STRIP / 4) + g;               // < 512
-          *(u32 *)(Q + slot * ALN_QBYTES + a * ALN_QSTRIDE + 4 * g) = alns_profile(cs + a * ALN_CSTRIDE, yrow[gy], ly - 4 * gy);
-        }
-        __syncthreads();
-        for (int s = s0; s < s0 + nb; ++s) {
-          const unsigned char *q = Q + (s - s0) * ALN_QBYTES;
-          const int j0 = s * ALN_STRIP;
-          if (s < ns - 1) {
-            best = alns_strip<8, false, true>(q, xb, wsb, tid, xnpad, lx, lxmax, j0, 0, gap, oe, bias, Z, best);
-            continue;
-          }
-          const int rest = ly - j0, jl = rest - ((rest - 1) & ~15);       // 1..128, 1..16
-#define ALNS_LAST(NC) alns_strip<NC, true, true>(q, xb, wsb, tid, xnpad, lx, lxmax, j0, jl, gap, oe, bias, Z, best)
-          switch ((rest + 15) >> 4) {
-            case 1: best = ALNS_LAST(1); break;
-            case 2: best = ALNS_LAST(2); break;
-            case 3: best = ALNS_LAST(3); break;
-            case 4: best = ALNS_LAST(4); break;
-            case 5: best = ALNS_LAST(5); break;
-            case 6: best = ALNS_LAST(6); break;
-            case 7: best = ALNS_LAST(7); break;
-            default: best = ALNS_LAST(8); break;
-          }
-#undef ALNS_LAST
-        }
-      }
-      if (tid < left_cols) (out + row * ldo + ct * ALN_THREADS)[tid] = (OUT)(best - Z);
-    }
-  }
+  aln_long_frame<AlnSemiglobal>(xt, n, xnpad, xl, yt, m, ynpad, yl, score, gap, open, obias, out, ldo, colTiles, items, ws);
 }
 
 extern "C" {
@@ -306,58 +68,18 @@ extern "C" {
 int pg_alignment_semiglobal_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
                                   int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out, int64_t ldo,
                                   int out_elem_bytes, void *stream) {
-  if (!x_packed || !y_packed || !score_i8 || !out || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 || ldo < n)
-    return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: bad argument");
-  if (xl > ALN_MAX_L || yl > ALN_MAX_L) return pg_fail(PG_E_TOOLONG, "pg_alignment_semiglobal_dense: at most 128 positions");
-  if (gap < 1 || gap > 255) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: gap must be in 1..255");
-  if (gap_open < 0 || gap_open > 255) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: gap_open must be in 0..255");
-  if (x_npad < n || x_npad % 256 || y_npad < m) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: bad npad");
-  if (out_elem_bytes != 2 && out_elem_bytes != 8)
-    return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: out_elem_bytes must be 2 (fp16) or 8");
-  const long long colTiles = (n + ALN_THREADS - 1) / ALN_THREADS;
-  const long long blocks = colTiles * ((m + ALN_ROWS - 1) / ALN_ROWS);
-  if (blocks > 0x7fffffffll) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_dense: too many pairs for one launch");
-  const dim3 grid((unsigned)blocks), block(ALN_THREADS);
-  if (out_elem_bytes == 2)
-    pg_aln_semiglobal_dense_kernel<_Float16><<<grid, block, 0, (hipStream_t)stream>>>(
-        (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, (const signed char *)score_i8, (u32)gap,
-        (u32)gap_open, (_Float16 *)out, ldo, colTiles);
-  else
-    pg_aln_semiglobal_dense_kernel<long long><<<grid, block, 0, (hipStream_t)stream>>>(
-        (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, (const signed char *)score_i8, (u32)gap,
-        (u32)gap_open, (long long *)out, ldo, colTiles);
-  return pg_launched("pg_alignment_semiglobal_dense");
+  const AlnCall c = {x_packed, n, x_npad, xl, y_packed, m, y_npad, yl, score_i8, gap, gap_open, 0, out, ldo, out_elem_bytes, nullptr, 0, stream};
+  return aln_launch_short("pg_alignment_semiglobal_dense", c, pg_aln_semiglobal_dense_kernel<_Float16>,
+                          pg_aln_semiglobal_dense_kernel<long long>);
 }
 
 int pg_alignment_semiglobal_long_dense(const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
                                        int64_t y_npad, int yl, const int8_t *score_i8, int gap, int gap_open, void *out,
                                        int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes, void *stream) {
-  if (!x_packed || !y_packed || !score_i8 || !out || !workspace || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 || ldo < n)
-    return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: bad argument");
-  if (xl > ALNG_MAX_L || yl > ALNG_MAX_L) return pg_fail(PG_E_TOOLONG, "pg_alignment_semiglobal_long_dense: at most 2048 positions");
-  if (gap < 1 || gap > 255) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: gap must be in 1..255");
-  if (gap_open < 0 || gap_open > 255) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: gap_open must be in 0..255");
-  if (x_npad < n || x_npad % 256 || y_npad < m) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: bad npad");
-  if (out_elem_bytes != 4 && out_elem_bytes != 8)
-    return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: out_elem_bytes must be 4 (int32) or 8");
-  const long long one = (long long)ALN_THREADS * (((xl + 3) / 4) * 4) * 4;  // pg_alignment_long_workspace's share
-  if (workspace_bytes < one)
-    return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: the workspace is smaller than one workgroup's share");
-  const long long colTiles = (n + ALN_THREADS - 1) / ALN_THREADS;
-  const long long items = colTiles * ((m + ALN_ROWS - 1) / ALN_ROWS);
-  long long blocks = workspace_bytes / one;                                 // as many workgroups as the workspace holds
-  if (items > 0x7fffffffll) return pg_fail(PG_E_BADARG, "pg_alignment_semiglobal_long_dense: too many pairs for one launch");
-  if (blocks > items) blocks = items;
-  const dim3 grid((unsigned)blocks), block(ALN_THREADS);
-  if (out_elem_bytes == 4)
-    pg_aln_semiglobal_long_dense_kernel<int><<<grid, block, 0, (hipStream_t)stream>>>(
-        (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, (const signed char *)score_i8, (u32)gap,
-        (u32)gap_open, (int *)out, ldo, (int)colTiles, (int)items, (u32 *)workspace);
-  else
-    pg_aln_semiglobal_long_dense_kernel<long long><<<grid, block, 0, (hipStream_t)stream>>>(
-        (const u32 *)x_packed, n, x_npad, xl, (const u32 *)y_packed, m, y_npad, yl, (const signed char *)score_i8, (u32)gap,
-        (u32)gap_open, (long long *)out, ldo, (int)colTiles, (int)items, (u32 *)workspace);
-  return pg_launched("pg_alignment_semiglobal_long_dense");
+  const AlnCall c = {x_packed, n,   x_npad,         xl,        y_packed,        m,     y_npad, yl, score_i8, gap, gap_open, 0,
+                     out,      ldo, out_elem_bytes, workspace, workspace_bytes, stream};
+  return aln_launch_long("pg_alignment_semiglobal_long_dense", c, pg_aln_semiglobal_long_dense_kernel<int>,
+                         pg_aln_semiglobal_long_dense_kernel<long long>);
 }
 
 }  // extern "C"

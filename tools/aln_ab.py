@@ -59,14 +59,14 @@ from prograph_amd.distance import alignment, fit_alignment, local_alignment, sem
 
 # VALU instructions of one outer step (one X symbol against 16 * chunks cells) in the gfx950 ISA of pg_aln_dense_kernel.
 # Counted by hand from the compiler's assembly (`--save-temps`; the table is in profiles/aln_dense.txt).  Nothing keeps it
-# in step with the kernel: after any change to csrc/pg_aln.hip, its build flags or the compiler, count again and update
-# both places, or `share_of_valu_issue` below is wrong without a sign of it.
+# in step with the kernel: after any change to csrc/pg_aln.hip, csrc/pg_aln_frame.h, their build flags or the compiler, count
+# again and update both places, or `share_of_valu_issue` below is wrong without a sign of it.
 VALU_PER_STEP = {1: 69, 2: 134, 3: 199, 4: 264, 5: 329, 6: 394, 7: 459, 8: 523}
 # The same for pg_aln_affine_dense_kernel (profiles/aln_affine_dense.txt; here every v_* of the loop is counted), kept by
 # hand in the same way.
 AFFINE_VALU_PER_STEP = {1: 131, 2: 260, 3: 389, 4: 518, 5: 647, 6: 775, 7: 905, 8: 1033}
 # The same for pg_aln_local_dense_kernel (profiles/aln_local_dense.txt), kept by hand in the same way.
-LOCAL_VALU_PER_STEP = {1: 152, 2: 305, 3: 458, 4: 611, 5: 764, 6: 917, 7: 1070, 8: 1222}
+LOCAL_VALU_PER_STEP = {1: 153, 2: 305, 3: 458, 4: 611, 5: 764, 6: 917, 7: 1070, 8: 1222}
 # The same for pg_aln_semiglobal_dense_kernel (profiles/aln_semiglobal_dense.txt), kept by hand in the same way.
 SEMIGLOBAL_VALU_PER_STEP = {1: 179, 2: 324, 3: 470, 4: 616, 5: 762, 6: 908, 7: 1054, 8: 1198}
 ISSUE_RATE = 256 * 4 * 2.4e9
