@@ -529,58 +529,79 @@ class Prograph:
             raise ValueError("queries must be a non-empty string, list of strings or 1-D / 2-D array")
         else:
             Y = None
+        route = self._route(distance, comp if eps is not None else operator.le, k)      # a `k` search does not consult `comp`
         g = None
-        if eps is not None:
-            if distance is hamming and comp in _CMP_CODE:
-                g = self._search_eps_hamming(strings, Y, eps, comp, similarity, representation)
-            elif distance in (minkowski, cosine, euclidean) and comp in _CMP_CODE and strings is None:
-                g = self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
-            elif isinstance(distance, spectrum) and comp in _CMP_CODE:
-                g = self._search_spectrum(strings, Y, None, eps, comp, similarity, representation, distance)
-            elif distance is levenshtein and comp in _CMP_CODE:
-                g = self._search_levenshtein(strings, Y, None, eps, comp, similarity, representation)
-            elif isinstance(distance, substitution) and comp in _CMP_CODE:
-                g = self._search_substitution(strings, Y, None, eps, comp, similarity, representation, distance)
-            elif isinstance(distance, alignment) and comp in _CMP_CODE:
-                g = self._search_alignment(strings, Y, None, eps, comp, similarity, representation, distance)
-            elif isinstance(distance, _SCORES):
-                g = self._search_local(strings, Y, None, eps, comp, representation, distance)
-            if g is None:
-                g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
-            return g if output == "csr" else g.to_tuples()
-        if distance is hamming and k <= _native.MAX_K_ROUNDS:
-            g = self._search_hamming(strings, Y, k, similarity, representation)
-        elif distance in (minkowski, cosine, euclidean) and k <= _native.MAX_K_ROUNDS and strings is None:
-            g = self._search_embedding(Y, k, similarity, representation, distance)
-        elif isinstance(distance, spectrum) and k <= _native.MAX_K_ROUNDS:
-            g = self._search_spectrum(strings, Y, k, None, None, similarity, representation, distance)
-        elif distance is levenshtein and k <= _native.MAX_K_ROUNDS:
-            g = self._search_levenshtein(strings, Y, k, None, None, similarity, representation)
-        elif isinstance(distance, substitution) and k <= _native.MAX_K_ROUNDS:
-            g = self._search_substitution(strings, Y, k, None, None, similarity, representation, distance)
-        elif isinstance(distance, alignment) and k <= _native.MAX_K_ROUNDS:
-            g = self._search_alignment(strings, Y, k, None, None, similarity, representation, distance)
-        elif isinstance(distance, _SCORES):
-            g = self._search_local(strings, Y, k, None, None, representation, distance)
+        if route is not None and route[1]:
+            g = getattr(self, route[1])(strings, Y, k, eps, comp, similarity, representation, distance)
+        if g is None and eps is None:
+            return self._search_generic(strings, Y, k, similarity, representation, distance, output)     # tuples itself
         if g is None:
-            return self._search_generic(strings, Y, k, similarity, representation, distance, output)
+            g = self._search_eps_generic(strings, Y, eps, comp, similarity, representation, distance)
         return g if output == "csr" else g.to_tuples()
+
+    # The device routes in the order `build_graph` and `search` ask them: (does `distance` take it; does it need `comp`
+    # among the five orderings and k within the selection's rounds; build_graph's method; search's method).  The methods
+    # are looked up by name on `self` at every call; a method's None means "the generic loop".  Graph methods are called
+    # (idxs, eps, k, similarity, representation, comp, cap=, distance=), search methods (strings, Y, k, eps, comp,
+    # similarity, representation, distance).  Hamming graphs have no entry of their own: `build_graph` tries the fused
+    # engine and `_build_graph_long` after this list.
+    _ROUTES = (
+        (lambda d: d is hamming, True, None, "_search_hamming"),
+        (lambda d: d is minkowski, True, "_build_graph_minkowski", "_search_embedded"),
+        (lambda d: d is cosine, True, "_build_graph_cosine", "_search_embedded"),
+        (lambda d: d is euclidean, True, "_build_graph_euclidean", "_search_embedded"),
+        (lambda d: isinstance(d, spectrum), True, "_build_graph_spectrum", "_search_spectrum"),
+        (lambda d: d is levenshtein, True, "_build_graph_levenshtein", "_search_levenshtein"),
+        (lambda d: isinstance(d, substitution), True, "_build_graph_substitution", "_search_substitution"),
+        (lambda d: isinstance(d, alignment), True, "_build_graph_alignment", "_search_alignment"),
+        (lambda d: isinstance(d, _SCORES), False, "_build_graph_local", "_search_local"),
+    )
+
+    def _route(self, distance, comp, k):
+        """(build_graph's method, search's method) of the entry of `_ROUTES` that takes `distance`; None when there is
+        none, or when it needs the device selection and `comp` or `k` is outside what that covers."""
+        for takes, limited, graph, query in self._ROUTES:
+            if takes(distance):
+                if limited and not (comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS)):
+                    return None
+                return graph, query
+        return None
 
     def _dataset_matrix(self, representation):
         return self.tokenized if representation == "Tokenized" else np.vstack(self(representation))
 
-    def _search_hamming(self, strings, Y, k, similarity, representation):
-        """Byte-token queries on the device: the fused query kernel within one record, the staged dense + fp16 selection
-        path up to 2048 positions.  None when dataset or queries are not byte tokens (the generic loop then)."""
-        ops = self._hamming_operands(strings, Y, representation, _native.MAX_N_KNN)
+    def _query_tokens(self, strings, Y):
+        """The queries as an integer token matrix: strings through the dataset's letter table at their own width (unknown
+        letters and padding -> 0), an array or tensor as a host array."""
+        if strings is not None:
+            raw, table = self._byte_view(strings)
+            return table[raw]
+        return Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+
+    def _search_hamming(self, strings, Y, k, eps, comp, similarity, representation, distance=None):
+        """Byte-token queries on the device: the fused query kernels within one record (`pg_query_knn_hamming`,
+        `pg_query_eps_*`: uint8 weights), the staged frame on `_hamming_segments` up to 2048 positions (int16 weights, as
+        `_build_graph_long` gives them).  Similarities: comp(1/(1+eps), 1/(1+d)) is the same integer test on d (as in
+        `build_graph`); the container forms them.  None when dataset or queries are not byte tokens (the generic loop)."""
+        ops = self._hamming_operands(strings, Y, representation, _native.MAX_N_KNN if k is not None else 1 << 31)
         if ops is None:
             return None
         n, bits, X, T, qp, dp = ops
-        kk = min(k, n)
         if qp is None:
-            return self._search_hamming_long(X, T, kk, bits, similarity)
-        idx, dist = _native.query_knn(qp, dp, kk)
-        return KNNGraph(idx, dist, n, similarity=similarity, first=0)
+            dev, width = _native.device(), max(X.shape[1], T.shape[1])
+            Xd = torch.zeros((X.shape[0], width), dtype=torch.uint8, device=dev)
+            Xd[:, :X.shape[1]] = torch.as_tensor(X.astype(np.uint8), device=dev)
+            Td = torch.zeros((T.shape[0], width), dtype=torch.uint8, device=dev)
+            Td[:, :T.shape[1]] = torch.as_tensor(T.astype(np.uint8), device=dev)
+            # the blocks of this route hold at least 64 queries, a graph's floor, not 1
+            return self._staged(n, Td.shape[0], self._hamming_segments(Xd, Td, bits), "f16", torch.int16, k, eps, comp,
+                                similarity, True, floor=64)
+        if k is not None:
+            idx, dist = _native.query_knn(qp, dp, min(k, n))
+            return KNNGraph(idx, dist, n, similarity=similarity, first=0)
+        eps = min(max(float(eps), -1.0), 4096.0)                         # (the same test on every d in 0..2048)
+        indptr, indices, wts = _native.query_eps(qp, dp, _CMP_CODE[comp], eps)
+        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
     def _hamming_operands(self, strings, Y, representation, max_n):
         """The staging of byte-token queries: (n, bits, X, T, query planes, dataset planes) within one record (the
@@ -598,7 +619,7 @@ class Prograph:
                 return None
             T = table[raw]
         else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+            T = self._query_tokens(None, Y)
         if X.ndim != 2 or X.shape[0] == 0 or X.shape[1] == 0 or not np.issubdtype(X.dtype, np.integer):
             return None
         if not np.issubdtype(T.dtype, np.integer) or T.min() < 0 or T.max() > 255 or X.min() < 0 or X.max() > 255:
@@ -628,38 +649,79 @@ class Prograph:
         4-byte elements (the int32 blocks of the alignment kernels beyond 128 positions) hold half as many."""
         return max(floor, min(rows, self._BLOCK_ELEMS * 2 // elem_bytes // n))
 
+    # the two kinds of staged block: the `_native` selection wrappers by name (looked up at every call) and bytes per element
+    _BLOCK_KINDS = {"f16": ("f16_knn", "f16_eps", 2), "i32": ("i32_knn", "i32_eps", 4)}
+
     @staticmethod
-    def _select_blocks(blocks, knn=None, eps=None, wdtype=None):
-        """The selection over an iterator of fp16 distance blocks (row blocks of one matrix), one block alive at a time:
-        knn = (k, first, descending) -> (idx, w) of `f16_knn`, or eps = (cmp, thr, similarity, keep_zero) -> the CSR
-        (indptr, indices, w) of `f16_eps`, the blocks' results concatenated.  wdtype: what the fp16 weights are cast to."""
+    def _select_blocks(blocks, kind, knn=None, eps=None, wdtype=None):
+        """The selection over an iterator of distance blocks (row blocks of one matrix) of one kind of `_BLOCK_KINDS`, one
+        block alive at a time: knn = (k, first, descending) -> (idx, w) of `f16_knn` / `i32_knn`, or eps = (cmp, thr,
+        similarity, keep_zero) -> the CSR (indptr, indices, w) of `f16_eps` / `i32_eps` (which takes an integer thr and no
+        similarity), the blocks' results concatenated.  wdtype: what the weights are cast to."""
+        knn_name, eps_name, _ = Prograph._BLOCK_KINDS[kind]
         parts = []
         for block in blocks:
             if knn is not None:
-                part = _native.f16_knn(block, knn[0], first=knn[1], descending=knn[2])
+                part = getattr(_native, knn_name)(block, knn[0], first=knn[1], descending=knn[2])
             else:
-                cmp, thr, similarity, keep_zero = eps                     # self graphs call f16_eps without keep_zero, as ever
-                part = _native.f16_eps(block, cmp, thr, similarity=similarity, **({"keep_zero": True} if keep_zero else {}))
+                cmp, thr, similarity, keep_zero = eps
+                kw = {"similarity": similarity} if kind == "f16" else {}
+                if keep_zero:                                             # self graphs call without keep_zero, as ever
+                    kw["keep_zero"] = True
+                part = getattr(_native, eps_name)(block, cmp, thr, **kw)
             del block
             parts.append(part if wdtype is None else part[:-1] + (part[-1].to(wdtype),))
         if knn is None:
             return _native.cat_csr(parts)
         return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
 
-    @staticmethod
-    def _select_blocks_i32(blocks, knn=None, eps=None):
-        """`_select_blocks` over int32 blocks (`pg_alignment_long_dense`): knn = (k, first, descending) -> (idx, w) of
-        `i32_knn`, or eps = (cmp, integer thr, keep_zero) -> the CSR of `i32_eps`; int32 weights as they come."""
-        parts = []
-        for block in blocks:
-            if knn is not None:
-                parts.append(_native.i32_knn(block, knn[0], first=knn[1], descending=knn[2]))
-            else:
-                parts.append(_native.i32_eps(block, eps[0], eps[1], keep_zero=eps[2]))
-            del block
-        if knn is None:
-            return _native.cat_csr(parts)
-        return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+    def _staged(self, n, q, dense, kind, wdtype, k, eps, comp, similarity, query, floor=None, raw=False, score=None):
+        """
+        The frame of every staged route: q rows against n columns, cut into row blocks that
+        `dense(r0, r1)` computes as blocks of `kind`, the selection of `_select_blocks` over them, the container.
+        `query` False is a self graph (q == n), True a search; what follows from it:
+                       self graph                                    search
+          ranks        1..min(k, n-1); none left: `_empty_knn`       0..min(k, n)-1, the container told first=0
+          d = 0        dropped                                       kept
+          eps          to `_integer_threshold` as it is              clamped to -1..4096 first
+          block rows   `_block_rows(n, n, 64, ...)`                  `_block_rows(n, q, 1, ...)` (`floor` overrides)
+          k or eps?    `if k` (`build_graph` has rejected 0)         `k is not None` (eps = 0 is a radius)
+        int32 blocks take their threshold from `_long_threshold`, which clamps to -1..2^31 for both.
+        `raw`: the blocks hold final fp16 values, similarities included (Minkowski): `eps` is the threshold as given, the
+        kernels are told `similarity` and rank similarities largest first.  Else the values are integers, thresholds are
+        integer tests and the container forms similarities.
+        `score=(K, diagonal)`: the blocks hold scores + K (`_local_select`): largest first, comp(eps, s) as the mirrored
+        test of (s + K, eps + K), clamped for graphs too; an entry of value 0 is kept iff K, K comes off the weights on
+        the device, then `s > 0` is applied (`_unshift`), and the entries (r, r) go unless `diagonal`.
+        """
+        _, _, elem_bytes = self._BLOCK_KINDS[kind]
+        first = 0 if query else 1
+        K, diagonal = (0, True) if score is None else score
+        rows = self._block_rows(n, q, floor or (1 if query else 64), elem_bytes)
+        blocks = (dense(r0, min(q, r0 + rows)) for r0 in range(0, q, rows))
+        if (k is not None) if query else k:
+            kk = min(k, n - first)
+            if not kk:
+                return self._empty_knn(n, wdtype, _native.device(), similarity)
+            descending = score is not None or (raw and similarity)
+            idx, w = self._select_blocks(blocks, kind, knn=(kk, first, descending), wdtype=wdtype)
+            return KNNGraph(idx, w - K if K else w, n, similarity=similarity, first=first)
+        cmp = _CMP_CODE[comp] if score is None else _CMP_MIRROR[_CMP_CODE[comp]]
+        if raw:
+            thr = eps
+        elif kind == "i32":
+            thr = self._long_threshold(cmp, float(eps) + K)
+        elif query or score is not None:
+            thr = self._integer_threshold(cmp, min(max(float(eps) + K, -1.0), 4096.0))
+        else:
+            thr = self._integer_threshold(cmp, eps)
+        keep_zero = query if score is None else bool(K)
+        csr = self._select_blocks(blocks, kind, eps=(cmp, thr, raw and similarity, keep_zero), wdtype=wdtype)
+        if K:
+            csr = self._unshift(*csr, K, diagonal)
+        elif not diagonal:
+            csr = self._drop_diagonal(*csr)
+        return CSRGraph(*csr, n, similarity=similarity)
 
     @staticmethod
     def _empty_knn(n, wdtype, dev, similarity, final=False):
@@ -667,33 +729,43 @@ class Prograph:
         return KNNGraph(torch.zeros((n, 0), dtype=torch.int32, device=dev), torch.zeros((n, 0), dtype=wdtype, device=dev), n,
                         similarity=similarity, final=final)
 
-    def _search_hamming_long(self, X, T, kk, bits, similarity):
-        """Sequences beyond one record (up to 2048 positions): ranks 0..kk-1 of every fp16 block of
-        `_hamming_long_blocks` (`pg_f16_knn`, first = 0; rounds beyond 64)."""
-        idx, wt = self._select_blocks(self._hamming_long_blocks(X, T, bits), knn=(kk, 0, False), wdtype=torch.int16)
-        return KNNGraph(idx, wt, X.shape[0], similarity=similarity, first=0)
+    @staticmethod
+    def _empty_csr(n, wdtype, dev, similarity):
+        """The epsilon graph without an edge."""
+        return CSRGraph(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                        torch.zeros(0, dtype=wdtype, device=dev), n, similarity=similarity)
 
-    def _hamming_long_blocks(self, X, T, bits):
-        """`_build_graph_long`'s staging for queries: the dense kernel over column segments of whole records into an
-        fp16 block (Q', N) per block of queries, one block alive at a time."""
-        dev = _native.device()
-        width = max(X.shape[1], T.shape[1])
-        Xd = torch.zeros((X.shape[0], width), dtype=torch.uint8, device=dev)
-        Xd[:, :X.shape[1]] = torch.as_tensor(X.astype(np.uint8), device=dev)
-        Td = torch.zeros((T.shape[0], width), dtype=torch.uint8, device=dev)
-        Td[:, :T.shape[1]] = torch.as_tensor(T.astype(np.uint8), device=dev)
-        n, q = Xd.shape[0], Td.shape[0]
-        w = (_native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L) // 32 * 32
+    @staticmethod
+    def _nothing_within(cmp, thr):
+        """Does the integer test (cmp, thr) of a self graph admit no distance at all: none of 1, 2, ...?"""
+        return cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr - (cmp == _native.CMP_LT) < 1
+
+    @staticmethod
+    def _hamming_segments(Xd, Yd, bits):
+        """`dense(r0, r1)` for byte tokens beyond one record of the fused engines: the fp16 block of rows r0..r1 of Yd
+        against Xd (uint8 device matrices of one width), the sequence cut into column segments of whole records and their
+        distances accumulated in place (`pg_hamming_dense`, `out=`)."""
+        width = Xd.shape[1]
+        w = (_native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L) // 32 * 32     # whole 32-token groups
         segs = [(a, min(width, a + w)) for a in range(0, width, w)]
         xs = [_native.pack(Xd[:, a:b], bits=bits) for a, b in segs]
-        rows_per_block = self._block_rows(n, q, 64)
-        for r0 in range(0, q, rows_per_block):
+
+        def dense(r0, r1):
             block = None
             for (a, b), xp in zip(segs, xs):
-                block = _native.hamming_dense(xp, _native.pack(Td[r0:r0 + rows_per_block, a:b], bits=bits), out_bytes=2, out=block)
-            yield block
+                block = _native.hamming_dense(xp, _native.pack(Yd[r0:r1, a:b], bits=bits), out_bytes=2, out=block)
+            return block
+        return dense
 
     _MINK_STAGED_ROWS = 4096      # fewer Minkowski queries: dense block + selection (the fused kernel: 16 queries per CU)
+
+    def _search_embedded(self, strings, Y, k, eps, comp, similarity, representation, distance):
+        """The embedding entries of `_ROUTES` for `search`: arrays only (strings take the generic loop)."""
+        if strings is not None:
+            return None
+        if k is not None:
+            return self._search_embedding(Y, k, similarity, representation, distance)
+        return self._search_eps_embedding(Y, eps, comp, similarity, representation, distance)
 
     def _search_embedding(self, Y, k, similarity, representation, distance):
         """Minkowski / cosine / Euclidean queries on the fused kernels with first = 0 (fp16 staging of both operands, as
@@ -711,9 +783,8 @@ class Prograph:
         if distance is minkowski:
             xp = _native.pack_f16(X)
             if Y.shape[0] < self._MINK_STAGED_ROWS:
-                idx, w = self._select_blocks(self._mink_blocks(xp, Y, similarity), knn=(kk, 0, similarity))
-            else:
-                idx, w = _native.minkowski_knn(xp, _native.pack_f16(Y), kk, first=0, similarity=similarity)
+                return self._mink_staged(xp, Y, k, None, None, similarity)
+            idx, w = _native.minkowski_knn(xp, _native.pack_f16(Y), kk, first=0, similarity=similarity)
             return KNNGraph(idx, w, n, similarity=similarity, first=0)
         xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
         if xc.nonfinite() or yc.nonfinite():
@@ -722,11 +793,11 @@ class Prograph:
         idx, w = knn(xc, yc, kk, first=0, similarity=similarity)
         return KNNGraph(idx, w, n, similarity=similarity, final=True, first=0)
 
-    def _mink_blocks(self, xp, Y, similarity):
-        """The staged Minkowski path of few queries: their dense fp16 blocks against the packed dataset."""
-        rows = self._block_rows(xp.n, Y.shape[0], 1)
-        return (_native.minkowski_dense(xp, _native.pack_f16(Y[r0:r0 + rows]), similarity=similarity)
-                for r0 in range(0, Y.shape[0], rows))
+    def _mink_staged(self, xp, Y, k, eps, comp, similarity):
+        """The staged Minkowski path of few queries: their dense fp16 blocks against the packed dataset on the frame; the
+        blocks hold the final values (`raw`), `eps` is the threshold on them."""
+        dense = lambda r0, r1: _native.minkowski_dense(xp, _native.pack_f16(Y[r0:r1]), similarity=similarity)     # noqa: E731
+        return self._staged(xp.n, Y.shape[0], dense, "f16", torch.float16, k, eps, comp, similarity, True, raw=True)
 
     def _embedding_operands(self, Y, representation):
         """The fp16 device staging of dataset and queries (X, Y), the narrower one right-padded with zeros; None when the
@@ -769,23 +840,17 @@ class Prograph:
         op = _native.lev_long_operand(torch.from_numpy(np.ascontiguousarray(mat.astype(np.uint8))))
         return op if op.valid() else None
 
-    def _search_levenshtein(self, strings, Y, k, eps, comp, similarity, representation):
-        """Edit-distance queries: Q x N blocks of `pg_levenshtein_dense` (fp16: distances are at most 128) and the fp16
-        selection with rank 0 / d = 0 kept, uint8 weights.  When the dataset or the queries are wider than 128 positions
-        (up to 2048 each, the two widths need not agree) both are staged as long operands and the blocks come from
-        `pg_levenshtein_long_dense` (fp16 holds every distance up to 2048), int16 weights.  Strings are tokenised with the
-        dataset's letter table at their own width.  None (the generic loop with the operator) when dataset or queries
+    def _search_levenshtein(self, strings, Y, k, eps, comp, similarity, representation, distance=None):
+        """Edit-distance queries: blocks of `pg_levenshtein_dense` (uint8 weights: distances are at most 128), or of
+        `pg_levenshtein_long_dense` (int16 weights) when the dataset or the queries are wider than 128 positions (up to
+        2048 each, the two widths need not agree).  None (the generic loop with the operator) when dataset or queries
         are not what the kernels take."""
         try:
             X = self._dataset_matrix(representation)
             xw = np.shape(X)[1] if np.ndim(X) == 2 else 0
         except (ValueError, TypeError):
             return None
-        if strings is not None:
-            raw, table = self._byte_view(strings)
-            T = table[raw]
-        else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        T = self._query_tokens(strings, Y)
         long = max(xw, T.shape[1]) > _native.MAX_L
         if long and not _native.lev_long_ready():
             return None
@@ -798,16 +863,8 @@ class Prograph:
         qo = stage(T) if xo is not None else None
         if qo is None:
             return None
-        n, q = xo.n, qo.n
-        rows = self._block_rows(n, q, 1)
-        blocks = (dense(xo, qo, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
-        if k is not None:
-            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=wdtype)
-            return KNNGraph(idx, w, n, similarity=similarity, first=0)
-        cmp = _CMP_CODE[comp]
-        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=wdtype)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        return self._staged(xo.n, qo.n, lambda r0, r1: dense(xo, qo, out_bytes=2, rows=(r0, r1)), "f16", wdtype, k, eps, comp,
+                            similarity, True)
 
     def _sub_tokens(self, mat, distance):
         """The uint8 form of an integer token matrix whose tokens all index the table of `distance`, else None."""
@@ -824,20 +881,14 @@ class Prograph:
         return width <= _native.SUB_MAX_L and width * distance.max_cost <= self._LONG_MAX_L
 
     def _search_substitution(self, strings, Y, k, eps, comp, similarity, representation, distance):
-        """Queries under a `substitution` distance: Q x N blocks of `pg_substitution_dense` in fp16 and the fp16 selection
-        with rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width;
-        the narrower of queries and dataset is right-padded with zeros.  None (the generic loop with the operator) when
-        dataset or queries are not integer tokens of the table, or a distance could exceed 2048."""
+        """Queries under a `substitution` distance: blocks of `pg_substitution_dense` in fp16, int16 weights; the narrower
+        of queries and dataset is right-padded with zeros.  None (the generic loop with the operator) when dataset or
+        queries are not integer tokens of the table, or a distance could exceed 2048."""
         try:
             X = self._sub_tokens(self._dataset_matrix(representation), distance)
         except (ValueError, TypeError):
             return None
-        if strings is not None:
-            raw, table = self._byte_view(strings)
-            T = table[raw]
-        else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-        T = self._sub_tokens(T, distance) if X is not None else None
+        T = self._sub_tokens(self._query_tokens(strings, Y), distance) if X is not None else None
         if T is None:
             return None
         width = max(X.shape[1], T.shape[1])
@@ -847,16 +898,8 @@ class Prograph:
         wide[0][:, :X.shape[1]], wide[1][:, :T.shape[1]] = X, T
         xo, qo = (_native.sub_operand(torch.from_numpy(M), distance.symbols) for M in wide)
         cost = distance.device_cost()
-        n, q = xo.n, qo.n
-        rows = self._block_rows(n, q, 1)
-        blocks = (_native.substitution_dense(xo, qo, cost, out_bytes=2, rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
-        if k is not None:
-            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.int16)
-            return KNNGraph(idx, w, n, similarity=similarity, first=0)
-        cmp = _CMP_CODE[comp]
-        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        dense = lambda r0, r1: _native.substitution_dense(xo, qo, cost, out_bytes=2, rows=(r0, r1))     # noqa: E731
+        return self._staged(xo.n, qo.n, dense, "f16", torch.int16, k, eps, comp, similarity, True)
 
     def _aln_native(self, width, distance):
         """Does a width take the alignment kernel route?  At most 128 positions, and every distance - at most
@@ -877,62 +920,42 @@ class Prograph:
         """`_integer_threshold` for int32 values: the same comparison with an integer threshold, clamped to -1..2^31."""
         return int(Prograph._integer_threshold(cmp, min(max(float(eps), -1.0), float(1 << 31)), top=1 << 31))
 
-    @staticmethod
-    def _aln_dense(distance, xo, yo, cost, rows):
-        """One fp16 block of the alignment kernel the distance asks for: `pg_alignment_affine_dense` with a gap-open
-        penalty, `pg_alignment_dense` without."""
-        if distance.gap_open:
-            return _native.alignment_affine_dense(xo, yo, cost, distance.gap, distance.gap_open, out_bytes=2, rows=rows)
-        return _native.alignment_dense(xo, yo, cost, distance.gap, out_bytes=2, rows=rows)
+    def _aln_staged(self, distance, X, T, k, eps, comp, similarity):
+        """The frame under an `alignment` distance, for the token matrix X against itself (T None: a self graph) or the
+        queries T against it, each at its own width.  Within `_aln_native`: fp16 blocks of `pg_alignment_dense`
+        (`pg_alignment_affine_dense` with a gap-open penalty), int16 weights.  Beyond 128 positions inside `_aln_long`:
+        int32 blocks of `pg_alignment_long_dense`, int32 weights - exact as float32 for the analytics up to 2^24, and
+        the route's distances stay below 2^16.  Else None."""
+        width = X.shape[1] if T is None else max(X.shape[1], T.shape[1])
+        if self._aln_native(width, distance):
+            kind, wdtype, operand = "f16", torch.int16, _native.aln_operand
+        elif self._aln_long(width, distance):
+            kind, wdtype, operand = "i32", torch.int32, _native.aln_long_operand
+        else:
+            return None
+        xo = operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+        yo = xo if T is None else operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+        cost, gap, gap_open = distance.device_cost(), distance.gap, distance.gap_open
+        if kind == "i32":
+            dense = lambda r0, r1: _native.alignment_long_dense(xo, yo, cost, gap, gap_open, out_bytes=4, rows=(r0, r1))     # noqa: E731
+        elif gap_open:
+            dense = lambda r0, r1: _native.alignment_affine_dense(xo, yo, cost, gap, gap_open, out_bytes=2, rows=(r0, r1))     # noqa: E731
+        else:
+            dense = lambda r0, r1: _native.alignment_dense(xo, yo, cost, gap, out_bytes=2, rows=(r0, r1))     # noqa: E731
+        return self._staged(xo.n, yo.n, dense, kind, wdtype, k, eps, comp, similarity, T is not None)
 
     def _search_alignment(self, strings, Y, k, eps, comp, similarity, representation, distance):
-        """Queries under an `alignment` distance: Q x N blocks of `pg_alignment_dense` (`pg_alignment_affine_dense` when
-        the distance has a gap-open penalty) in fp16 and the fp16 selection with
-        rank 0 / d = 0 kept (int16 weights).  Strings are tokenised with the dataset's letter table at their own width, any
-        length up to 128; dataset and queries keep their own widths.  None (the generic loop with the operator) when dataset
-        or queries are not integer tokens of the table, or a distance could exceed 2048 - unless the wider of the two has
-        129..2048 positions and `_aln_long` holds: then int32 blocks of `pg_alignment_long_dense` and the int32 selection
-        (`_select_blocks_i32`), int32 weights, everything else the same."""
+        """Queries under an `alignment` distance (`_aln_staged`): strings of any length up to the kernels'; dataset and
+        queries keep their own widths.  None (the generic loop with the operator) when dataset or queries are not integer
+        tokens of the table, or no kernel route takes the wider of the two."""
         try:
             X = self._sub_tokens(self._dataset_matrix(representation), distance)
         except (ValueError, TypeError):
             return None
-        if strings is not None:
-            raw, table = self._byte_view(strings)
-            T = table[raw]
-        else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-        T = self._sub_tokens(T, distance) if X is not None else None
+        T = self._sub_tokens(self._query_tokens(strings, Y), distance) if X is not None else None
         if T is None:
             return None
-        if not self._aln_native(max(X.shape[1], T.shape[1]), distance):
-            if not self._aln_long(max(X.shape[1], T.shape[1]), distance):
-                return None
-            # beyond 128 positions: int32 blocks of the strip-mined kernel and the int32 selection (int32 weights)
-            xo, qo = (_native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(M)), distance.symbols) for M in (X, T))
-            cost = distance.device_cost()
-            n, q = xo.n, qo.n
-            rows = self._block_rows(n, q, 1, elem_bytes=4)
-            blocks = (_native.alignment_long_dense(xo, qo, cost, distance.gap, distance.gap_open, out_bytes=4,
-                                                   rows=(r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
-            if k is not None:
-                idx, w = self._select_blocks_i32(blocks, knn=(min(k, n), 0, False))
-                return KNNGraph(idx, w, n, similarity=similarity, first=0)
-            cmp = _CMP_CODE[comp]
-            indptr, indices, wts = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, eps), True))
-            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-        xo, qo = (_native.aln_operand(torch.from_numpy(np.ascontiguousarray(M)), distance.symbols) for M in (X, T))
-        cost = distance.device_cost()
-        n, q = xo.n, qo.n
-        rows = self._block_rows(n, q, 1)
-        blocks = (self._aln_dense(distance, xo, qo, cost, (r0, min(q, r0 + rows))) for r0 in range(0, q, rows))
-        if k is not None:
-            idx, w = self._select_blocks(blocks, knn=(min(k, n), 0, False), wdtype=torch.int16)
-            return KNNGraph(idx, w, n, similarity=similarity, first=0)
-        cmp = _CMP_CODE[comp]
-        thr = self._integer_threshold(cmp, min(max(float(eps), -1.0), 4096.0))
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, True), wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        return self._aln_staged(distance, X, T, k, eps, comp, similarity)
 
     # ---- local and semi-global alignment scores (`_SCORES`): similarities - largest first, whatever `similarity` says; the
     # two share every route below and differ in the kernels their instances name (`_native_dense`, `_native_long_dense`)
@@ -952,60 +975,35 @@ class Prograph:
                              f"(0..{distance.symbols - 1})")
         return T
 
-    def _local_select(self, distance, X, T, rows, k, first, eps, comp, diagonal):
-        """The selection of `local_alignment` / `semiglobal_alignment` scores of the rows of T (all of X when T is None: a self graph) against X, in
-        row blocks of `rows`: ranks first..first+k-1 of the stable descending (score, column) order -> (idx, scores), or
-        the CSR (indptr, indices, scores) of {(r, c): s > 0, comp(eps, s)} with ascending columns, without the entries
-        c == r when `diagonal` is False.  Within `_local_native` and the device's selection limits: fp16 blocks of
-        `pg_alignment_local_dense`, `_select_blocks` (descending; the comparator mirrored: the kernels test
-        (value, threshold)), int16 scores.  Beyond 128 and up to 2048 positions, inside `_native.aln_local_long_fits`: int32
-        blocks of `pg_alignment_local_long_dense` and `_select_blocks_i32` in the same way, int32 scores.  Outside both:
-        the same selection in torch over the operator's int64 blocks.  A `semiglobal_alignment` instance takes the same
-        routes on `pg_alignment_semiglobal_dense` / `pg_alignment_semiglobal_long_dense` inside
-        `_native.aln_semiglobal_long_fits`: the instance names its kernels and its bound.
+    def _local_select(self, distance, X, T, k, eps, comp):
+        """The graph of `_SCORES` scores of the rows of T (all of X when T is None: a self graph) against X: ranks first..
+        first+k-1 (k already clamped) of the stable descending (score, column) order, or the CSR of {(r, c): s > 0,
+        comp(eps, s)} with ascending columns, a self graph without its entries c == r.  The frame in its `score` form,
+        on the kernels the instance names: within `_local_native` fp16 blocks (`_native_dense`), int16 scores; beyond 128
+        and up to 2048 positions, inside the instance's bound (`_i32_route`), int32 blocks (`_native_long_dense`), int32
+        scores - both only within the device selection's limits (k rounds, the five orderings).  Outside them: the same
+        selection in torch over the operator's int64 blocks.
         `fit_alignment` scores go below 0 and the selection kernels sort non-negative values, so such an instance names a
-        shift too (`_select_bias`: K = gap_open + gap * the rows' width, minus the least score): its kernels add K to every
-        entry of a block, the selection runs on the shifted block with the threshold shifted alike and `v = 0` kept, and K
-        comes off the returned weights on the device; `s > 0` is then applied to the compacted CSR (`_unshift`).  Its fp16
-        route holds while K + width * max(S) <= 2048, its int32 route everywhere else inside `_native.aln_fit_fits`."""
-        Y = X if T is None else T
-        n, q = X.shape[0], Y.shape[0]
+        shift too (`_select_bias`: K = gap_open + gap * the rows' width, minus the least score), which its kernels add to
+        every entry of a block and the frame takes off again.  Its fp16 route holds while K + width * max(S) <= 2048, its
+        int32 route everywhere else inside `_native.aln_fit_fits`."""
+        Y, query = (X, False) if T is None else (T, True)
+        n, q, first = X.shape[0], Y.shape[0], int(T is None)
         K = distance._select_bias(Y.shape[1])                                # 0 but for `fit_alignment`
-        bias = {"bias": K} if K else {}
-        native = self._local_native(X.shape[1], distance, Y.shape[1]) if K else \
+        on_device = k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE
+        f16 = self._local_native(X.shape[1], distance, Y.shape[1]) if K else \
             self._local_native(max(X.shape[1], Y.shape[1]), distance)
-        native = native and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)
-        if native:
-            xo = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
-            yo = xo if T is None else _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-            blocks = (distance._native_dense(xo, yo, 2, rows=(r0, min(q, r0 + rows)), **bias) for r0 in range(0, q, rows))
-            if k is not None:
-                idx, w = self._select_blocks(blocks, knn=(k, first, True), wdtype=torch.int16)
-                return idx, (w - K if K else w)
-            cmp = _CMP_MIRROR[_CMP_CODE[comp]]
-            thr = self._integer_threshold(cmp, min(max(float(eps) + K, -1.0), 4096.0))
-            csr = self._select_blocks(blocks, eps=(cmp, thr, False, bool(K)), wdtype=torch.int16)
-            if K:
-                return self._unshift(*csr, K, diagonal)
-            return csr if diagonal else self._drop_diagonal(*csr)
-        if (distance._i32_route(X.shape[1], Y.shape[1])
-                and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)):
-            # beyond 128 positions: int32 blocks of the strip-mined kernel (`pg_alignment_local_long_dense`) and the int32
-            # selection, descending and with the mirrored comparator as above; int32 scores
-            xo = _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
-            yo = xo if T is None else _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-            rows = self._block_rows(n, q, 64 if T is None else 1, elem_bytes=4)
-            blocks = (distance._native_long_dense(xo, yo, 4, rows=(r0, min(q, r0 + rows)), **bias) for r0 in range(0, q, rows))
-            if k is not None:
-                idx, w = self._select_blocks_i32(blocks, knn=(k, first, True))
-                return idx, (w - K if K else w)
-            cmp = _CMP_MIRROR[_CMP_CODE[comp]]
-            csr = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, float(eps) + K), bool(K)))
-            if K:
-                return self._unshift(*csr, K, diagonal)
-            return csr if diagonal else self._drop_diagonal(*csr)
+        if on_device and (f16 or distance._i32_route(X.shape[1], Y.shape[1])):
+            kind, wdtype, operand, kernel, out_bytes = ("f16", torch.int16, _native.aln_operand, distance._native_dense, 2) if f16 else \
+                ("i32", torch.int32, _native.aln_long_operand, distance._native_long_dense, 4)
+            xo = operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+            yo = xo if T is None else operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
+            bias = {"bias": K} if K else {}
+            return self._staged(n, q, lambda r0, r1: kernel(xo, yo, out_bytes, rows=(r0, r1), **bias), kind, wdtype, k, eps, comp,
+                                False, query, score=(K, query))
         dev = _native.device()
         Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y, device=dev)
+        rows = self._block_rows(n, q, 1 if query else 64)
         parts = []
         for r0 in range(0, q, rows):
             s = distance(Xd, Yd[r0:r0 + rows])
@@ -1014,15 +1012,15 @@ class Prograph:
                 parts.append((o[1][:, first:first + k].to(torch.int32), o[0][:, first:first + k]))
                 continue
             keep = (s > 0) & comp(eps, s)
-            if not diagonal:
+            if not query:
                 keep[torch.arange(s.shape[0], device=dev), torch.arange(r0, r0 + s.shape[0], device=dev)] = False
             loc = torch.where(keep)
             indptr = torch.zeros(s.shape[0] + 1, dtype=torch.int64, device=dev)
             indptr[1:] = torch.cumsum(keep.sum(dim=1), 0)
             parts.append((indptr, loc[1].to(torch.int32), s[loc]))
         if k is not None:
-            return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
-        return _native.cat_csr(parts)
+            return KNNGraph(torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts]), n, similarity=False, first=first)
+        return CSRGraph(*_native.cat_csr(parts), n, similarity=False)
 
     @staticmethod
     def _drop_diagonal(indptr, indices, wts):
@@ -1048,37 +1046,23 @@ class Prograph:
         out[1:] = torch.cumsum(torch.bincount(rows[keep], minlength=n), 0)
         return out, indices[keep], wts[keep]
 
-    def _search_local(self, strings, Y, k, eps, comp, representation, distance):
-        """Queries under a `local_alignment` or `semiglobal_alignment` score: `k` -> ranks 0..min(k, N)-1 of the stable descending (score, dataset
-        row) order; `eps` -> per query the dataset rows with s > 0 and comp(eps, s), ascending.  Strings are tokenised with
-        the dataset's letter table at their own width; dataset and queries keep their own widths, as in
-        `_search_alignment`.  `similarity` is not consulted.  The weights are the scores."""
+    def _search_local(self, strings, Y, k, eps, comp, similarity, representation, distance):
+        """Queries under a score of `_SCORES`: `k` -> ranks 0..min(k, N)-1 of the stable descending (score, dataset row)
+        order; `eps` -> per query the dataset rows with s > 0 and comp(eps, s), ascending.  Dataset and queries keep their
+        own widths, as in `_search_alignment`.  `similarity` is not consulted.  The weights are the scores."""
         X = self._local_tokens(self._dataset_matrix(representation), distance)
-        if strings is not None:
-            raw, table = self._byte_view(strings)
-            T = table[raw]
-        else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
-        T = self._local_tokens(T, distance)
-        n = X.shape[0]
-        rows = self._block_rows(n, T.shape[0], 1)
-        if k is not None:
-            idx, w = self._local_select(distance, X, T, rows, min(k, n), 0, None, None, True)
-            return KNNGraph(idx, w, n, similarity=False, first=0)
-        indptr, indices, wts = self._local_select(distance, X, T, rows, None, 0, eps, comp, True)
-        return CSRGraph(indptr, indices, wts, n, similarity=False)
+        T = self._local_tokens(self._query_tokens(strings, Y), distance)
+        return self._local_select(distance, X, T, None if k is None else min(k, X.shape[0]), eps, comp)
 
-    def _build_graph_local(self, idxs, eps, k, representation, comp, distance):
+    def _build_graph_local(self, idxs, eps, k, similarity, representation, comp, distance, cap=None):
         """
-        `build_graph(distance=local_alignment(S, gap[, gap_open]))` or `semiglobal_alignment(...)`.  Such a score is a similarity, so the
-        graph ranks largest first and `similarity` is not consulted; the weights are the raw scores (the containers are
-        built with similarity=False, so nothing turns them into 1/(1+w)).
+        `build_graph(distance=local_alignment(S, gap[, gap_open]))`, `semiglobal_alignment(...)` or `fit_alignment(...)`.
+        Such a score is a similarity, so the graph ranks largest first and `similarity` is not consulted; the weights are
+        the raw scores (the containers are built with similarity=False, so nothing turns them into 1/(1+w)).
         k: ranks 1..k of the stable descending (score, column) order; rank 0 is dropped, as the reference drops it for
         every distance (:761-763) - it is the row itself unless a row of lower index contains it.  eps: the reference's
         similarity form (:734) - the edges {(r, c): c != r, s > 0, comp(eps, s)}, so the default comp reads s >= eps -
-        with ascending columns.  Row blocks of `_block_rows(n, n, 64)` of `pg_alignment_local_dense` in fp16 and
-        `_select_blocks` while width <= 128 and width * max(S) <= 2048 (int16 scores); beyond, the same selection in
-        torch over the operator's blocks (`_local_select`).  Returns a KNNGraph / CSRGraph.
+        with ascending columns.  The routes are `_local_select`'s.  Returns a KNNGraph / CSRGraph.
         """
         if k is not None and k < 1:
             raise ValueError("K must be at least 1.")
@@ -1087,15 +1071,9 @@ class Prograph:
             mat = mat[np.asarray(idxs)]
         T = self._local_tokens(mat, distance)
         n = T.shape[0]
-        rows = self._block_rows(n, n, 64)
-        if k:
-            kk = min(k, n - 1)
-            if not kk:
-                return self._empty_knn(n, torch.int16, _native.device(), False)
-            idx, wt = self._local_select(distance, T, None, rows, kk, 1, None, None, True)
-            return KNNGraph(idx, wt, n, similarity=False)
-        indptr, indices, wts = self._local_select(distance, T, None, rows, None, 0, eps, comp, False)
-        return CSRGraph(indptr, indices, wts, n, similarity=False)
+        if k and not min(k, n - 1):                                          # int16 whichever route would have run
+            return self._empty_knn(n, torch.int16, _native.device(), False)
+        return self._local_select(distance, T, None, min(k, n - 1) if k else None, eps, comp)
 
     # ---- alignment tracebacks (prograph_amd/alignments.py)
     def _edge_lists(self, graph):
@@ -1227,25 +1205,6 @@ class Prograph:
                         final=g.final)
 
     # ---- radius (eps) search: a CSRGraph with one row per query, d = 0 kept
-    def _search_eps_hamming(self, strings, Y, eps, comp, similarity, representation):
-        """Byte-token queries: the fused query kernels within one record (`pg_query_eps_*`: uint8 weights), beyond it
-        the staged blocks and the fp16 selection with d = 0 kept (int16 weights, as `_build_graph_long` gives them).
-        Similarities: comp(1/(1+eps), 1/(1+d)) is the same integer test on d (as in `build_graph`); the container forms
-        the similarities.  None when dataset or queries are not byte tokens (the generic loop then)."""
-        ops = self._hamming_operands(strings, Y, representation, 1 << 31)
-        if ops is None:
-            return None
-        n, bits, X, T, qp, dp = ops
-        cmp = _CMP_CODE[comp]
-        eps = min(max(float(eps), -1.0), 4096.0)                         # (the same test on every d in 0..2048)
-        if qp is not None:
-            indptr, indices, wts = _native.query_eps(qp, dp, cmp, eps)
-        else:
-            thr = self._integer_threshold(cmp, eps)
-            indptr, indices, wts = self._select_blocks(self._hamming_long_blocks(X, T, bits), eps=(cmp, thr, False, True),
-                                                       wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-
     def _search_eps_embedding(self, Y, eps, comp, similarity, representation, distance):
         """Minkowski / cosine / Euclidean queries on the fused eps kernels with d = 0 (s = 1) kept; fewer than `_MINK_STAGED_ROWS`
         Minkowski queries take the dense block + fp16 selection, which gives the same CSR bit for bit.  None (the
@@ -1263,10 +1222,9 @@ class Prograph:
         if distance is minkowski:
             xp = _native.pack_f16(X)
             if Y.shape[0] < self._MINK_STAGED_ROWS:
-                indptr, indices, wts = self._select_blocks(self._mink_blocks(xp, Y, similarity), eps=(cmp, eps, similarity, True))
-            else:
-                indptr, indices, wts = _native.minkowski_eps(xp, _native.pack_f16(Y), cmp, eps, similarity=similarity,
-                                                             keep_zero=True)
+                return self._mink_staged(xp, Y, None, eps, comp, similarity)
+            indptr, indices, wts = _native.minkowski_eps(xp, _native.pack_f16(Y), cmp, eps, similarity=similarity,
+                                                         keep_zero=True)
             return CSRGraph(indptr, indices, wts, n, similarity=similarity)
         xc, yc = _native.cosine_prep(X), _native.cosine_prep(Y)
         if xc.nonfinite() or yc.nonfinite():
@@ -1393,24 +1351,11 @@ class Prograph:
                 idxs = np.asarray(idxs)
                 if idxs.dtype == bool:
                     idxs = np.nonzero(idxs)[0]
+        route = self._route(distance, comp, k)
         g = None
-        if distance is minkowski and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_minkowski(idxs, eps, k, similarity, representation, comp, cap)
-        if distance is cosine and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_cosine(idxs, eps, k, similarity, representation, comp, cap)
-        if distance is euclidean and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_euclidean(idxs, eps, k, similarity, representation, comp, cap)
-        if isinstance(distance, spectrum) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_spectrum(idxs, eps, k, similarity, representation, comp, cap, distance)
-        if distance is levenshtein and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_levenshtein(idxs, eps, k, similarity, representation, comp, cap)
-        if isinstance(distance, substitution) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_substitution(idxs, eps, k, similarity, representation, comp, distance)
-        if isinstance(distance, alignment) and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
-            g = self._build_graph_alignment(idxs, eps, k, similarity, representation, comp, distance)
-        if isinstance(distance, _SCORES):
-            g = self._build_graph_local(idxs, eps, k, representation, comp, distance)
-        native = g is None and distance is hamming and (comp in _CMP_CODE) and (k is None or k <= _native.MAX_K_ROUNDS)
+        if route is not None and route[0]:
+            g = getattr(self, route[0])(idxs, eps, k, similarity, representation, comp, cap=cap, distance=distance)
+        native = hamming_route = g is None and distance is hamming and route is not None
         planes = None
         if native:
             try:
@@ -1419,7 +1364,7 @@ class Prograph:
                 native = False                      # not byte tokens / L > 128: generic torch path
         if native and k and planes.n > _native.MAX_N_KNN:
             native = False
-        if g is None and not native and distance is hamming and comp in _CMP_CODE and (k is None or k <= _native.MAX_K_ROUNDS):
+        if hamming_route and not native:
             g = self._build_graph_long(idxs, eps, k, similarity, representation, comp)
         if not native and g is None:
             return self._build_graph_generic(idxs, batch_size, eps, k, similarity, representation, distance, comp)
@@ -1470,13 +1415,9 @@ class Prograph:
         """
         Graphs of byte-token sequences LONGER than one record of the fused engines (more than 255 positions,
         128 for alphabets above 31 symbols; the reference has no limit: hamming.py:32-34 is a broadcast).
-        Per block of rows the distance matrix comes from the dense kernel - the sequence cut into column
-        segments of whole records, their distances accumulated in place (`pg_hamming_dense`, fp16 output:
-        integers up to 2048 are exact) - and the selection runs on the device as for fp16 embeddings: the
-        canonical (distance, column) ranks 1..k (`pg_f16_knn`, k > 63 in rounds over the same block:
-        `pg_f16_knn_round`; :756-763) or the thresholded CSR
-        (`pg_f16_eps_*`; :734-739).  Returns a KNNGraph / CSRGraph with int16 weights, or None when the
-        representation is not byte tokens or longer than 2048 positions (the generic batch loop then).
+        The frame (`_staged`) on the fp16 blocks of `_hamming_segments`: integers up to 2048 are exact.  Returns a
+        KNNGraph / CSRGraph with int16 weights, or None when the representation is not byte tokens or longer than
+        2048 positions (the generic batch loop then).
         """
         try:
             mat = self.tokenized if representation == "Tokenized" else np.vstack(self(representation))
@@ -1489,37 +1430,13 @@ class Prograph:
             return None
         if idxs is not None:
             mat = mat[np.asarray(idxs)]
-        dev = _native.device()
-        T = torch.as_tensor(np.ascontiguousarray(mat.astype(np.uint8)), device=dev)
-        n, l = T.shape
+        T = torch.as_tensor(np.ascontiguousarray(mat.astype(np.uint8)), device=_native.device())
         bits = _native.BITS_5 if int(mat.max()) <= 31 else _native.BITS_8
-        w = (_native.MAX_L_5BIT if bits == _native.BITS_5 else _native.MAX_L) // 32 * 32   # whole 32-token groups
-        segs = [(a, min(l, a + w)) for a in range(0, l, w)]
-        xs = [_native.pack(T[:, a:b], bits=bits) for a, b in segs]
-        # comp(d, eps) on integer distances as an integer threshold (exact in fp16 whatever eps is);
-        # similarity graphs: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the same test on d (:720-721, :734)
-        cmp = _CMP_CODE[comp]
-        if eps:
-            thr = self._integer_threshold(cmp, eps)
-        rows_per_block = self._block_rows(n, n, 64)
+        # similarity graphs: comp(1/(1+eps), 1/(1+d)) & (s < 1) is the same integer test on d (:720-721, :734)
+        return self._staged(T.shape[0], T.shape[0], self._hamming_segments(T, T, bits), "f16", torch.int16, k, eps, comp,
+                            similarity, False)
 
-        def blocks():
-            for r0 in range(0, n, rows_per_block):
-                block = None
-                for (a, b), xp in zip(segs, xs):
-                    block = _native.hamming_dense(xp, _native.pack(T[r0:r0 + rows_per_block, a:b], bits=bits), out_bytes=2, out=block)
-                yield block
-
-        if k:
-            kk = min(k, n - 1)
-            if not kk:
-                return self._empty_knn(n, torch.int16, dev, similarity)
-            idx, wt = self._select_blocks(blocks(), knn=(kk, 1, False), wdtype=torch.int16)
-            return KNNGraph(idx, wt, n, similarity=similarity)
-        indptr, indices, wts = self._select_blocks(blocks(), eps=(cmp, thr, False, False), wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-
-    def _build_graph_minkowski(self, idxs, eps, k, similarity, representation, comp, cap=256):
+    def _build_graph_minkowski(self, idxs, eps, k, similarity, representation, comp, cap=256, distance=None):
         """
         `build_graph(representation=<embedding>, distance=minkowski)` on the HIP kernels:
         the fp16 staging of the reference (:726), then the fused sweeps that compute the fp16 distances
@@ -1552,7 +1469,7 @@ class Prograph:
         indptr, indices, wts = _native.minkowski_eps(xp, xp, _CMP_CODE[comp], eps, similarity=similarity, cap=cap)
         return CSRGraph(indptr, indices, wts, n, similarity=similarity)
 
-    def _build_graph_cosine(self, idxs, eps, k, similarity, representation, comp, cap=256):
+    def _build_graph_cosine(self, idxs, eps, k, similarity, representation, comp, cap=256, distance=None):
         """
         `build_graph(representation=<embedding>, distance=cosine)` on the matrix-core kernels: the fp16 staging
         (:726), norms and the non-finite check (`pg_cosine_prep`), then the fused sweeps that compute the fp32
@@ -1564,7 +1481,7 @@ class Prograph:
         """
         return self._build_graph_embed_f32("cosine", idxs, eps, k, similarity, representation, comp, cap)
 
-    def _build_graph_euclidean(self, idxs, eps, k, similarity, representation, comp, cap=256):
+    def _build_graph_euclidean(self, idxs, eps, k, similarity, representation, comp, cap=256, distance=None):
         """
         `build_graph(representation=<embedding>, distance=euclidean)`: `_build_graph_cosine` with the Euclidean
         epilogue (`pg_euclidean_knn`, `pg_euclidean_knn_round`, `pg_euclidean_eps_*`) - the same
@@ -1646,11 +1563,7 @@ class Prograph:
         tok = self._spectrum_tokens(representation)
         if tok is None:
             return None
-        if strings is not None:
-            raw, table = self._byte_view(strings)
-            T = table[raw]
-        else:
-            T = Y.cpu().numpy() if isinstance(Y, torch.Tensor) else np.asarray(Y)
+        T = self._query_tokens(strings, Y)
         if (T.ndim != 2 or T.shape[0] == 0 or not 1 <= T.shape[1] <= _native.SPECTRUM_MAX_L
                 or not np.issubdtype(T.dtype, np.integer) or T.min() < 0 or T.max() > 255):
             return None
@@ -1664,7 +1577,7 @@ class Prograph:
 
     _LEV_FUSED_MAX = _native.LEV_MAX_BAND            # thresholds the fused epsilon graph (and the banded first kNN pass) cover
 
-    def _build_graph_levenshtein(self, idxs, eps, k, similarity, representation, comp, cap=256):
+    def _build_graph_levenshtein(self, idxs, eps, k, similarity, representation, comp, cap=256, distance=None):
         """
         `build_graph(distance=levenshtein)` on the HIP kernels, for token matrices they take (tokens up to 31, zeros
         only as trailing padding; else None: the generic loop with the operator).  Up to 128 positions the routes below;
@@ -1692,8 +1605,8 @@ class Prograph:
             return None
         n, dev = op.n, op.tokens.device
         dense_only = os.environ.get("PG_LEV_ROUTE", "") == "dense"
-        block_rows = self._block_rows(n, n, 64)
         if k:
+            block_rows = self._block_rows(n, n, 64)
             kk = min(k, n - 1)
             if not kk:
                 return self._empty_knn(n, torch.uint8, dev, similarity)
@@ -1714,25 +1627,21 @@ class Prograph:
             return KNNGraph(idx, dist, n, similarity=similarity)
         cmp = _CMP_CODE[comp]
         thr = int(self._integer_threshold(cmp, eps))
-        if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr - (cmp == _native.CMP_LT) < 1:   # nothing in 1..thr
-            return CSRGraph(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
-                            torch.zeros(0, dtype=torch.uint8, device=dev), n, similarity=similarity)
+        if self._nothing_within(cmp, thr):
+            return self._empty_csr(n, torch.uint8, dev, similarity)
         if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr <= self._LEV_FUSED_MAX and not dense_only:
             indptr, indices, wts = _native.levenshtein_eps(op, cmp, thr, cap=max(int(cap), 64))
             return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-        blocks = (_native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.uint8)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        return self._staged(n, n, lambda r0, r1: _native.levenshtein_dense(op, op, out_bytes=2, rows=(r0, r1)), "f16", torch.uint8,
+                            None, eps, comp, similarity, False)
 
     def _build_graph_levenshtein_long(self, mat, eps, k, similarity, comp):
         """
         `build_graph(distance=levenshtein)` for token matrices of 129..2048 positions (tokens up to 31, zeros only as
-        trailing padding; else None: the generic loop with the operator): row blocks of `pg_levenshtein_long_dense` in
-        fp16 - a distance is at most 2048, which fp16 holds exactly - and the selection of `_select_blocks`: ranks 1..k
-        of the (d, column) order (`pg_f16_knn`, rounds beyond 63), or the thresholded CSR for every ordering
-        (`pg_f16_eps_*`).  Every pair goes through the full recurrence: no bag filter, no banded first pass and no fused
-        epsilon graph beyond 128 positions.  Returns a KNNGraph / CSRGraph with int16 weights; similarities as for
-        Hamming, formed by the container.
+        trailing padding; else None: the generic loop with the operator): the frame on blocks of
+        `pg_levenshtein_long_dense` in fp16 - a distance is at most 2048, which fp16 holds exactly.  Every pair goes
+        through the full recurrence: no bag filter, no banded first pass and no fused epsilon graph beyond 128 positions.
+        Returns a KNNGraph / CSRGraph with int16 weights; similarities as for Hamming, formed by the container.
         """
         if not _native.lev_long_ready():
             return None
@@ -1740,28 +1649,14 @@ class Prograph:
         if op is None:
             return None
         n, dev = op.n, op.tokens.device
-        block_rows = self._block_rows(n, n, 64)
-        blocks = (_native.levenshtein_long_dense(op, op, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
-                  for r0 in range(0, n, block_rows))
-        if k:
-            kk = min(k, n - 1)
-            if not kk:
-                return self._empty_knn(n, torch.int16, dev, similarity)
-            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
-            return KNNGraph(idx, wt, n, similarity=similarity)
-        cmp = _CMP_CODE[comp]
-        thr = self._integer_threshold(cmp, eps)
-        if cmp in (_native.CMP_LE, _native.CMP_LT, _native.CMP_EQ) and thr - (cmp == _native.CMP_LT) < 1:   # nothing in 1..thr
-            return CSRGraph(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
-                            torch.zeros(0, dtype=torch.int16, device=dev), n, similarity=similarity)
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, thr, False, False), wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        if not k and self._nothing_within(_CMP_CODE[comp], self._integer_threshold(_CMP_CODE[comp], eps)):
+            return self._empty_csr(n, torch.int16, dev, similarity)
+        return self._staged(n, n, lambda r0, r1: _native.levenshtein_long_dense(op, op, out_bytes=2, rows=(r0, r1)), "f16",
+                            torch.int16, k, eps, comp, similarity, False)
 
-    def _build_graph_substitution(self, idxs, eps, k, similarity, representation, comp, distance):
+    def _build_graph_substitution(self, idxs, eps, k, similarity, representation, comp, distance, cap=None):
         """
-        `build_graph(distance=substitution(C))` on the HIP kernel: row blocks of `pg_substitution_dense` in fp16 and the
-        selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
-        thresholded CSR (`pg_f16_eps_*`), as `_build_graph_long` does for long Hamming sequences.  Taken when the
+        `build_graph(distance=substitution(C))`: the frame on blocks of `pg_substitution_dense` in fp16.  Taken when the
         representation holds integer tokens of the table, at most 2048 positions, and width * max(C) <= 2048, so that
         every distance is an integer fp16 holds exactly; else None (the generic loop with the operator).  Returns a
         KNNGraph / CSRGraph with int16 weights; similarities as for Hamming: the same integer test on d, formed by the
@@ -1778,33 +1673,15 @@ class Prograph:
             return None
         op = _native.sub_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
         cost = distance.device_cost()
-        n, dev = op.n, op.buf.device
-        block_rows = self._block_rows(n, n, 64)
-        blocks = (_native.substitution_dense(op, op, cost, out_bytes=2, rows=(r0, min(n, r0 + block_rows)))
-                  for r0 in range(0, n, block_rows))
-        if k:
-            kk = min(k, n - 1)
-            if not kk:
-                return self._empty_knn(n, torch.int16, dev, similarity)
-            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
-            return KNNGraph(idx, wt, n, similarity=similarity)
-        cmp = _CMP_CODE[comp]
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, self._integer_threshold(cmp, eps), False, False),
-                                                   wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        dense = lambda r0, r1: _native.substitution_dense(op, op, cost, out_bytes=2, rows=(r0, r1))     # noqa: E731
+        return self._staged(op.n, op.n, dense, "f16", torch.int16, k, eps, comp, similarity, False)
 
-    def _build_graph_alignment(self, idxs, eps, k, similarity, representation, comp, distance):
+    def _build_graph_alignment(self, idxs, eps, k, similarity, representation, comp, distance, cap=None):
         """
-        `build_graph(distance=alignment(C, gap[, gap_open]))` on the HIP kernel: row blocks of `pg_alignment_dense`
-        (`pg_alignment_affine_dense` when the distance has a gap-open penalty) in fp16 and the
-        selection of `_select_blocks` - ranks 1..k of the (d, column) order (`pg_f16_knn`, rounds beyond 63) or the
-        thresholded CSR (`pg_f16_eps_*`), as `_build_graph_substitution` does.  Taken when the representation holds
-        integer tokens of the table, at most 128 positions, and width * max(max C, gap) + gap_open <= 2048, so that every distance
-        is an integer fp16 holds exactly.  Beyond 128 and up to 2048 positions, inside the bound of `_aln_long`: row blocks of
-        `pg_alignment_long_dense` in int32 and `_select_blocks_i32` (`pg_i32_knn`, `pg_i32_eps_*`), int32 weights - exact
-        as float32 for the analytics up to 2^24, and the route's distances stay below 2^16.  Else None (the generic loop
-        with the operator).  Returns a KNNGraph / CSRGraph with int16 (int32) weights; similarities as for Hamming: the
-        same integer test on d, formed by the container.
+        `build_graph(distance=alignment(C, gap[, gap_open]))` on the routes of `_aln_staged`, when the representation
+        holds integer tokens of the table; else None (the generic loop with the operator).  Returns a KNNGraph /
+        CSRGraph with int16 (beyond 128 positions: int32) weights; similarities as for Hamming: the same integer test on
+        d, formed by the container.
         """
         if k is not None and k < 1:
             raise ValueError("K must be at least 1.")
@@ -1817,40 +1694,7 @@ class Prograph:
             return None
         if T is None:
             return None
-        if not self._aln_native(T.shape[1], distance):
-            if not self._aln_long(T.shape[1], distance):
-                return None
-            # beyond 128 positions: int32 blocks of the strip-mined kernel and the int32 selection (int32 weights)
-            op = _native.aln_long_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-            cost = distance.device_cost()
-            n, dev = op.n, op.buf.device
-            block_rows = self._block_rows(n, n, 64, elem_bytes=4)
-            blocks = (_native.alignment_long_dense(op, op, cost, distance.gap, distance.gap_open, out_bytes=4,
-                                                   rows=(r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
-            if k:
-                kk = min(k, n - 1)
-                if not kk:
-                    return self._empty_knn(n, torch.int32, dev, similarity)
-                idx, wt = self._select_blocks_i32(blocks, knn=(kk, 1, False))
-                return KNNGraph(idx, wt, n, similarity=similarity)
-            cmp = _CMP_CODE[comp]
-            indptr, indices, wts = self._select_blocks_i32(blocks, eps=(cmp, self._long_threshold(cmp, eps), False))
-            return CSRGraph(indptr, indices, wts, n, similarity=similarity)
-        op = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(T)), distance.symbols)
-        cost = distance.device_cost()
-        n, dev = op.n, op.buf.device
-        block_rows = self._block_rows(n, n, 64)
-        blocks = (self._aln_dense(distance, op, op, cost, (r0, min(n, r0 + block_rows))) for r0 in range(0, n, block_rows))
-        if k:
-            kk = min(k, n - 1)
-            if not kk:
-                return self._empty_knn(n, torch.int16, dev, similarity)
-            idx, wt = self._select_blocks(blocks, knn=(kk, 1, False), wdtype=torch.int16)
-            return KNNGraph(idx, wt, n, similarity=similarity)
-        cmp = _CMP_CODE[comp]
-        indptr, indices, wts = self._select_blocks(blocks, eps=(cmp, self._integer_threshold(cmp, eps), False, False),
-                                                   wdtype=torch.int16)
-        return CSRGraph(indptr, indices, wts, n, similarity=similarity)
+        return self._aln_staged(distance, T, None, k, eps, comp, similarity)
 
     def _build_graph_generic(self, idxs, batch_size, eps, k, similarity, representation, distance, comp):
         """

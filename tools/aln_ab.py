@@ -320,9 +320,8 @@ def main():
     if "long_graph" in only:
         # build_graph(k=16) at N = 20 000 with lengths 200..400: the long route, and the generic loop with the operator's
         # torch expression (aln_long_ready False)
-        import pandas as pd
         import tempfile
-        from prograph_amd import Prograph, synth
+        from prograph_amd import synth             # not Prograph or pd again: a local import makes them locals of main() for every mode
         rng = np.random.default_rng(6)
         host, _ = varlen(rng, 20_000, 200, 400, a)
         with tempfile.TemporaryDirectory() as tmp:
