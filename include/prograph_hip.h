@@ -595,7 +595,7 @@ int pg_alignment_fit_long_dense(const void *x_packed, int64_t n, int64_t x_npad,
  *                      touches no operand memory and gets status 1, n_ops -1, zeros elsewhere.  workspace: at least one
  *                      wave's share (PG_E_BADARG below it); the call launches min(ceil(npairs / 64), workspace_bytes /
  *                      share) waves, which stride over the list.  Every argument check returns before any launch.
- *   pg_alignment_trace_long_workspace, pg_alignment_trace_long (pg_aln_trace_long.hip)  the same canonical alignment,
+ *   pg_alignment_trace_long_workspace, pg_alignment_trace_long (pg_aln_trace.hip)  the same canonical alignment,
  *                      arguments, outputs and checks for widths xl, yl of 1..2048 (PG_E_TOOLONG beyond; narrow operands
  *                      are accepted), the row of the tables cut into strips of 128 columns.  Cells are int32, so every
  *                      table and penalty of the three modes is exact: there is no "fits" condition.  *bytes_per_wave =

@@ -1110,29 +1110,37 @@ def alignment_semiglobal_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, r
                       out_bytes, rows, long=True)
 
 
-def aln_trace_wave_bytes(xl, yl):
-    """The direction bits of the 64 pairs of one wave of pg_alignment_trace (pg_alignment_trace_workspace)."""
+TRACE_ENTRIES = ("pg_alignment_trace", "pg_alignment_fit_trace")                    # the moded entry and its fit entry
+TRACE_LONG_ENTRIES = ("pg_alignment_trace_long", "pg_alignment_fit_trace_long")
+
+
+def _wave_bytes(entry, xl, yl):
+    """One wave's share of a traceback's workspace, from the workspace entry `entry`."""
     one = _i64(0)
-    _check(lib().pg_alignment_trace_workspace(int(xl), int(yl), ctypes.byref(one)), "pg_alignment_trace_workspace")
+    _check(getattr(lib(), entry)(int(xl), int(yl), ctypes.byref(one)), entry)
     return one.value
 
 
-def _trace_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws):
-    """One pg_alignment_trace call: pairs p0..p1-1 of the lists into rows p0..p1-1 of head and ops."""
+def aln_trace_wave_bytes(xl, yl):
+    """The direction bits of the 64 pairs of one wave of pg_alignment_trace (pg_alignment_trace_workspace)."""
+    return _wave_bytes("pg_alignment_trace_workspace", xl, yl)
+
+
+def _trace_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws, entries=TRACE_ENTRIES):
+    """One call of `entries` (the moded entry and its fit entry): pairs p0..p1-1 of the lists into rows p0..p1-1 of head and
+    ops.  ALN_TRACE_FIT goes to the fit entry, an entry of its own without `mode`."""
     ldo = ops.stride(0)
-    if int(mode) == ALN_TRACE_FIT:                                          # an entry of its own, without `mode`
-        _check(lib().pg_alignment_fit_trace(_ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
-                                            ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
-                                            p1 - p0, _ptr(table), int(gap), int(gap_open),
-                                            ctypes.c_void_p(head.data_ptr() + 32 * p0),
-                                            ctypes.c_void_p(ops.data_ptr() + ldo * p0), ldo, _ptr(ws), ws.numel(), _stream()),
-               "pg_alignment_fit_trace")
-        return
-    _check(lib().pg_alignment_trace(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
-                                    ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
-                                    p1 - p0, _ptr(table), int(gap), int(gap_open),
-                                    ctypes.c_void_p(head.data_ptr() + 32 * p0), ctypes.c_void_p(ops.data_ptr() + ldo * p0),
-                                    ldo, _ptr(ws), ws.numel(), _stream()), "pg_alignment_trace")
+    fit = int(mode) == ALN_TRACE_FIT
+    entry = entries[fit]
+    _check(getattr(lib(), entry)(*(() if fit else (int(mode),)), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad,
+                                 yo.l, ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0), p1 - p0,
+                                 _ptr(table), int(gap), int(gap_open), ctypes.c_void_p(head.data_ptr() + 32 * p0),
+                                 ctypes.c_void_p(ops.data_ptr() + ldo * p0), ldo, _ptr(ws), ws.numel(), _stream()), entry)
+
+
+def _trace_long_launch(*args):
+    """`_trace_launch` on pg_alignment_trace_long and its fit entry; a name of its own, which the test stand-ins replace."""
+    _trace_launch(*args, entries=TRACE_LONG_ENTRIES)
 
 
 def _pair_lists(name, xo, yo, xi, yi):
@@ -1192,27 +1200,7 @@ def aln_trace_long_ready():
 def aln_trace_long_wave_bytes(xl, yl):
     """One wave's share of pg_alignment_trace_long's workspace (pg_alignment_trace_long_workspace): the direction bits of
     its 64 pairs and their boundary column between strips."""
-    one = _i64(0)
-    _check(lib().pg_alignment_trace_long_workspace(int(xl), int(yl), ctypes.byref(one)), "pg_alignment_trace_long_workspace")
-    return one.value
-
-
-def _trace_long_launch(xo, yo, xi, yi, p0, p1, mode, table, gap, gap_open, head, ops, ws):
-    """One pg_alignment_trace_long call: pairs p0..p1-1 of the lists into rows p0..p1-1 of head and ops."""
-    ldo = ops.stride(0)
-    if int(mode) == ALN_TRACE_FIT:                                          # an entry of its own, without `mode`
-        _check(lib().pg_alignment_fit_trace_long(_ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
-                                                 ctypes.c_void_p(xi.data_ptr() + 4 * p0),
-                                                 ctypes.c_void_p(yi.data_ptr() + 4 * p0), p1 - p0, _ptr(table), int(gap),
-                                                 int(gap_open), ctypes.c_void_p(head.data_ptr() + 32 * p0),
-                                                 ctypes.c_void_p(ops.data_ptr() + ldo * p0), ldo, _ptr(ws), ws.numel(),
-                                                 _stream()), "pg_alignment_fit_trace_long")
-        return
-    _check(lib().pg_alignment_trace_long(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
-                                         ctypes.c_void_p(xi.data_ptr() + 4 * p0), ctypes.c_void_p(yi.data_ptr() + 4 * p0),
-                                         p1 - p0, _ptr(table), int(gap), int(gap_open),
-                                         ctypes.c_void_p(head.data_ptr() + 32 * p0), ctypes.c_void_p(ops.data_ptr() + ldo * p0),
-                                         ldo, _ptr(ws), ws.numel(), _stream()), "pg_alignment_trace_long")
+    return _wave_bytes("pg_alignment_trace_long_workspace", xl, yl)
 
 
 def alignment_trace_long(xo, yo, xi, yi, mode, table, gap, gap_open, workspace_bytes=None):

@@ -30,7 +30,7 @@ interior zero is symbol 0, padding is never aligned.
 
 Routes (`trace`).  Device byte tokens of at most 128 positions: the HIP kernel `pg_alignment_trace`
 (prograph_amd/csrc/pg_aln_trace.hip).  Wider device tokens, up to 2048 positions: `pg_alignment_trace_long`
-(pg_aln_trace_long.hip), the same tables in strips of 128 columns, the same alignment field for field.
+(pg_aln_trace.hip), the same tables in strips of 128 columns, the same alignment field for field.
 Everything else - CPU tensors, widths beyond 2048, no device - `host_trace` below: one pair at a time, the three tables
 row by row in numpy (F by the running maximum over A, as the operators' torch expressions have it), then the walk over
 the stored tables.  It is SLOW (milliseconds per pair at 128 positions, and the tables of one pair take 24 bytes per

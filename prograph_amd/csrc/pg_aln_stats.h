@@ -2,7 +2,7 @@
 // pg_aln_trace.h with, beside every H, E and F, the counts of the path the walk of §4.20 would take back from that cell in
 // that state.  No direction bits, no walk, no ops.  Plain integer code for host and device alike: pg_aln_stats.hip calls
 // it with one pair per lane (cell stride 64), tests/capi_stats/stats_check.cpp compiles it for the CPU (stride 1) beside
-// pg_tr_row + pg_tr_walk and compares every field.
+// pg_tr_row + pg_tr_walk_room and compares every field.
 //
 // A count word is four 8-bit fields in one uint32: identities, pairs, x symbols unaligned, y symbols unaligned.  A word
 // describes one real path inside a table of at most 128 x 128 positions, so every field is at most 128 and one 32-bit add
@@ -13,7 +13,8 @@
 //     F mirrors E along j;  local, H <= 0: the walk stops there          ->  wH = 0
 // Borders: global H[0][j] has j y-gaps and H[i][0] i x-gaps (the rest of the other sequence, unaligned); fit H[0][j] has j
 // y-gaps and H[i][0] none (x's prefix is free); local and semi-global none.  The end cell's word is taken with
-// pg_tr_end's (best, i, j) by the same statement, so the ties of the end cell are the trace's.
+// pg_tr_end's (best, i, j) where a larger value arrives - pg_tr_end_take's rule within one strip - so the ties of the end
+// cell are the trace's.
 // Then n_ops = pairs + xgaps + ygaps, x_begin = x_end - pairs - xgaps, y_begin = y_end - pairs - ygaps.
 #pragma once
 #include "pg_aln_trace.h"

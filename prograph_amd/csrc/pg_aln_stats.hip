@@ -3,18 +3,17 @@
 // forward recurrence carries the counts of the canonical path (pg_aln_stats.h), so there are no direction bits, no walk, no
 // ops and no workspace: 32 bytes out per pair.
 //
-// §4.20's shape: one pair per lane, one wave per workgroup.  The lane's row lives in LDS as 16-byte cells col[j][lane] =
-// (H, E, wH, wE) - one 128-bit LDS read and one write per cell, a lane's own len y is a plain address - F, the diagonal and
-// their words in registers, the lane's y tokens and the table (int32, negated for the distance) in LDS too.  The column is
-// as long as the y operand is WIDE, so the kernel is compiled for widths of up to 32, 64 and 128 positions:
-// (YMAX + 1) * 64 * 16 + YMAX / 4 * 64 * 4 + 4096 = 39 936, 74 752 and 144 384 bytes, four, two and ONE workgroup per
-// compute unit.  Lanes loop to their own lengths, which the compiler turns into wave loops to the longest under the EXEC
-// mask.  A grid smaller than the list strides over it.
-#include "pg_common.h"
+// §4.20's shape on its frame (pg_aln_pair.h): one pair per lane, one wave per workgroup.  The lane's row lives in LDS as
+// 16-byte cells col[j][lane] = (H, E, wH, wE) - one 128-bit LDS read and one write per cell, a lane's own len y is a plain
+// address - F, the diagonal and their words in registers, the lane's y tokens and the table (int32, negated for the
+// distance) in LDS too.  The column is as long as the y operand is WIDE, so the kernel is compiled for widths of up to 32,
+// 64 and 128 positions: (YMAX + 1) * 64 * 16 + YMAX / 4 * 64 * 4 + 4096 = 39 936, 74 752 and 144 384 bytes, four, two and
+// ONE workgroup per compute unit.  Lanes loop to their own lengths, which the compiler turns into wave loops to the longest
+// under the EXEC mask.  A grid smaller than the list strides over it.
+#include "pg_aln_pair.h"
 #include "pg_aln_stats.h"
-#include "../../include/prograph_hip.h"
 
-#define ST_WAVE 64
+#define ST_WAVE PG_PAIR_WAVE
 #define ST_MAX_BLOCKS 1024              // one workgroup per compute unit is resident: four rounds of the device, the rest stride
 
 template <int YMAX>
@@ -26,26 +25,16 @@ __global__ __launch_bounds__(ST_WAVE) void pg_aln_stats_kernel(
   __shared__ u32 ytok[(YMAX / 4) * ST_WAVE];
   __shared__ int T[32 * 32];
   const int lane = threadIdx.x;
-  for (int k = lane; k < 32 * 32; k += ST_WAVE)
-    T[k] = mode == PG_TR_GLOBAL ? -(int)((const unsigned char *)table)[k] : (int)((const signed char *)table)[k];
-  __syncthreads();
+  pg_pair_table(T, mode, table);
   const int xg = (xl + 3) >> 2, yg = (yl + 3) >> 2;                         // <= 32, YMAX / 4 (the host checks xl, chooses YMAX >= yl)
 
-  for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-    const long long p = chunk * ST_WAVE + lane;
-    if (p >= npairs) continue;
+  PG_PAIR_FOR(p, npairs, chunks) {
     int *hd = head + p * 8;
     const long long ix = xi[p], iy = yi[p];
-    if (ix < 0 || ix >= n || iy < 0 || iy >= m) {                           // no operand memory is touched
-      hd[0] = hd[1] = hd[2] = hd[3] = hd[4] = hd[6] = 0;
-      hd[5] = -1;
-      hd[7] = 1;
-      continue;
-    }
+    if (pg_pair_outside(ix, n, iy, m, hd, nullptr, 0)) continue;
     const u32 *xb = xt + ix, *yb = yt + iy;
     for (int g = 0; g < yg; ++g) ytok[g * ST_WAVE + lane] = yb[(long long)g * ynpad];
-    // pg_sub_pack zeroes positions past the width; the clamps keep a foreign buffer inside col[]
-    const int lx = min(pg_tr_length(xb, xnpad, xg), xl), ly = min(pg_tr_length(ytok + lane, ST_WAVE, yg), yl);
+    const int lx = pg_pair_length(xb, xnpad, xg, xl), ly = pg_pair_length(ytok + lane, ST_WAVE, yg, yl);
     pg_tr_end end;
     u32 endw;
     pg_st_row0(mode, lx, ly, e, oe, col + lane, ST_WAVE, &end, &endw);
@@ -67,26 +56,11 @@ int pg_alignment_stats(int mode, const void *x_packed, int64_t n, int64_t x_npad
     int64_t y_npad, int yl, const int32_t *xi, const int32_t *yi, int64_t npairs, const void *table, int gap, int gap_open,
     int32_t *head, void *stream) {
   const char *who = "pg_alignment_stats";
-  char buf[200];
-  const char *what = nullptr;
-  int code = PG_E_BADARG;
   if (mode != PG_TR_GLOBAL && mode != PG_TR_LOCAL && mode != PG_TR_SEMIGLOBAL && mode != PG_TR_FIT)
-    what = "mode must be 0 (global), 1 (local), 2 (semi-global) or 3 (fit)";
-  else if (!x_packed || !y_packed || !xi || !yi || !table || !head || n <= 0 || m <= 0 || xl <= 0 || yl <= 0 || npairs <= 0)
-    what = "bad argument";
-  else if (xl > PG_TR_MAX_L || yl > PG_TR_MAX_L) {
-    what = "at most 128 positions";
-    code = PG_E_TOOLONG;
-  } else if (gap < 1 || gap > 255)
-    what = "gap must be in 1..255";
-  else if (gap_open < 0 || gap_open > 255)
-    what = "gap_open must be in 0..255";
-  else if (x_npad < n || y_npad < m)
-    what = "bad npad";
-  if (what) {
-    snprintf(buf, sizeof(buf), "%s: %s", who, what);
-    return pg_fail(code, buf);
-  }
+    return pg_pair_fail(who, PG_E_BADARG, "mode must be 0 (global), 1 (local), 2 (semi-global) or 3 (fit)");
+  const int rc = pg_pair_check(who, x_packed && y_packed && xi && yi && table && head, n, x_npad, xl, m, y_npad, yl, npairs, gap,
+                               gap_open, PG_TR_MAX_L);
+  if (rc) return rc;
   const long long chunks = (npairs + ST_WAVE - 1) / ST_WAVE;
   const long long blocks = chunks < ST_MAX_BLOCKS ? chunks : ST_MAX_BLOCKS;
 #define ST_LAUNCH(YMAX)                                                                                                   \

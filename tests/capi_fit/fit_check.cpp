@@ -1,7 +1,7 @@
 // Host-side check of the traceback routines in mode PG_TR_FIT (prograph_amd/csrc/pg_aln_trace.h: all of y within any
-// substring of x).  Each pair runs twice: as pg_aln_trace.hip runs it (pg_tr_row0, pg_tr_row, pg_tr_walk) and as
-// pg_aln_trace_long.hip does (pg_tr_end0 + pg_tr_end0_fit, pg_tr_strip_row0, pg_tr_row_strip with pg_tr_border_x on the
-// left edge, pg_tr_walk_room), and is held against
+// substring of x; pg_tr_end0, pg_tr_row0, pg_tr_row with pg_tr_border_x on the left edge, pg_tr_walk_room).  Each pair
+// runs twice: as pg_aln_trace.hip's instance for up to 128 positions runs it (the single strip j0 = 0, buffers of exactly
+// len y cells, at most 256 codes) and as its long instance does (strips with a boundary column), and is held against
 //   * a BRUTE FORCE on small pairs: every substring of x, every alignment path of all of y against it;
 //   * the plain full-table DP with the canonical walk on pairs of up to 300 positions (strips of 128 columns), and the
 //     replayed score of the returned codes.
@@ -148,21 +148,26 @@ static bool both(int tag, const int T[32][32], int e, int o, const std::vector<i
   for (int a = 0; a < 32; ++a)
     for (int b = 0; b < 32; ++b) Tm[a * 32 + b] = T[a][b];
   const long long ldo = lx + ly + slack;
-  if (lx <= PG_TR_MAX_L && ly <= PG_TR_MAX_L) {                             // pg_aln_trace.hip's sweep
+  if (lx <= PG_TR_MAX_L && ly <= PG_TR_MAX_L) {                             // the one strip of up to 128 positions
     std::vector<uint32_t> dir((size_t)xl * nd, 0xdeadbeefu);
-    std::vector<int> colH(ly + 1, 0x5a5a5a5a), colE(ly + 1, 0x5a5a5a5a);
+    std::vector<int> colH(ly, 0x5a5a5a5a), colE(ly, 0x5a5a5a5a);           // the strip's cells, not one more
     pg_tr_end end;
-    pg_tr_row0(mode, lx, ly, e, oe, colH.data(), colE.data(), 1, &end);
-    for (int i = 1; i <= lx; ++i)
-      pg_tr_row(mode, i, lx, ly, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
-                dir.data() + (size_t)(i - 1) * nd, 1, &end);
+    pg_tr_end0(mode, lx, ly, &end);
+    pg_tr_end0_fit(ly, e, oe, &end);
+    pg_tr_row0(mode, 0, ly, e, oe, colH.data(), colE.data(), 1);
+    for (int i = 1; i <= lx; ++i) {
+      int rh, rf;
+      pg_tr_row(mode, i, lx, ly, 0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
+                dir.data() + (size_t)(i - 1) * nd, 1, &end, pg_tr_border_x(mode, i, e, oe), PG_TR_NEG,
+                pg_tr_border_x(mode, i - 1, e, oe), &rh, &rf);
+    }
     std::vector<unsigned char> ops(ldo, 0xee);
     int32_t head[8] = {0};
     head[0] = end.best;
-    pg_tr_walk(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), ldo, head);
+    pg_tr_walk_room(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), ldo, 2 * PG_TR_MAX_L, head);
     ok &= same("row", tag, head, ops, want, lx, ly);
   }
-  {                                                                         // pg_aln_trace_long.hip's sweep
+  {                                                                         // the long instance's sweep
     std::vector<uint32_t> dir((size_t)xl * nd, 0xdeadbeefu);
     std::vector<int> bh(lx, 0x5a5a5a5a), bf(lx, 0x5a5a5a5a);                // the boundary column: H[i][j0], F[i][j0]
     pg_tr_end end;
@@ -171,13 +176,13 @@ static bool both(int tag, const int T[32][32], int e, int o, const std::vector<i
     for (int j0 = 0; j0 < ly; j0 += PG_TR_STRIP) {
       const int width = std::min(PG_TR_STRIP, ly - j0);
       std::vector<int> colH(width, 0x5a5a5a5a), colE(width, 0x5a5a5a5a);   // the strip's cells, not one more
-      pg_tr_strip_row0(mode, j0, ly, e, oe, colH.data(), colE.data(), 1);
+      pg_tr_row0(mode, j0, ly, e, oe, colH.data(), colE.data(), 1);
       int diag = pg_tr_border(mode, j0, e, oe);
       for (int i = 1; i <= lx; ++i) {
         const int left = j0 ? bh[i - 1] : pg_tr_border_x(mode, i, e, oe), fin = j0 ? bf[i - 1] : PG_TR_NEG;
         int rh, rf;
-        pg_tr_row_strip(mode, i, lx, ly, j0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt + (j0 >> 2) * ys, ys, colH.data(),
-                        colE.data(), 1, dir.data() + (size_t)(i - 1) * nd, 1, &end, left, fin, diag, &rh, &rf);
+        pg_tr_row(mode, i, lx, ly, j0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt + (j0 >> 2) * ys, ys, colH.data(),
+                  colE.data(), 1, dir.data() + (size_t)(i - 1) * nd, 1, &end, left, fin, diag, &rh, &rf);
         diag = left;
         bh[i - 1] = rh;
         bf[i - 1] = rf;

@@ -1,5 +1,5 @@
 // Host-side check of the statistics kernel's routines (prograph_amd/csrc/pg_aln_stats.h: pg_st_row0, pg_st_row, pg_st_head)
-// against the traceback's own (pg_aln_trace.h: pg_tr_row0, pg_tr_row, pg_tr_walk): the seven fields of the canonical
+// against the traceback's own (pg_aln_trace.h: pg_tr_row0, pg_tr_row, pg_tr_walk_room): the seven fields of the canonical
 // alignment, counted forwards, must be the seven fields the walk back over the direction bits gives.  Exhaustive where
 // ties are the rule - every pair of sequences over 2 and 3 symbols at all lengths 0..6 under tables of -1..1 (costs 1..2),
 // four modes, gap_open 0 and 1 - then random pairs at the lengths around the dwords and at the ends of the range, with the
@@ -49,17 +49,23 @@ static void compare(int mode, const int *Tm, int e, int o, const std::vector<int
 
   int32_t want[8] = {0}, got[8] = {0};
   {                                                                         // the traceback: rows, direction bits, the walk
-    block(colH, ly + 1, 0, exact);
-    block(colE, ly + 1, 0, exact);
+    block(colH, ly, 0, exact);                                              // the one strip's cells, not one more
+    block(colE, ly, 0, exact);
     block(dir, (size_t)std::max(lx, 1) * nd, 0xdeadbeefu, exact);
     pg_tr_end end;
-    pg_tr_row0(mode, lx, ly, e, oe, colH.data(), colE.data(), 1, &end);
-    for (int i = 1; i <= lx; ++i)
-      pg_tr_row(mode, i, lx, ly, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
-                dir.data() + (size_t)(i - 1) * nd, 1, &end);
+    pg_tr_end0(mode, lx, ly, &end);
+    if (mode == PG_TR_FIT) pg_tr_end0_fit(ly, e, oe, &end);
+    pg_tr_row0(mode, 0, ly, e, oe, colH.data(), colE.data(), 1);
+    int last = 0;
+    for (int i = 1; i <= lx; ++i) {
+      int rf;
+      pg_tr_row(mode, i, lx, ly, 0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
+                dir.data() + (size_t)(i - 1) * nd, 1, &end, pg_tr_border_x(mode, i, e, oe), PG_TR_NEG,
+                pg_tr_border_x(mode, i - 1, e, oe), &last, &rf);
+    }
     block(ops, lx + ly, (unsigned char)0xee, exact);
-    want[0] = mode == PG_TR_GLOBAL ? -colH[ly] : end.best;
-    pg_tr_walk(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), lx + ly, want);
+    want[0] = mode == PG_TR_GLOBAL ? pg_tr_global(lx, ly, e, oe, last) : end.best;
+    pg_tr_walk_room(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), lx + ly, 2 * PG_TR_MAX_L, want);
   }
   {                                                                         // the statistics: rows with their count words
     block(col, ly + 1, pg_st_cell(), exact);

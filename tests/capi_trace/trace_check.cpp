@@ -1,7 +1,8 @@
-// Host-side check of the traceback kernel's routines (prograph_amd/csrc/pg_aln_trace.h: pg_tr_row0, pg_tr_row, pg_tr_walk)
-// against a plain DP that keeps the three tables whole and walks them by comparing entries - the distance minimising over
-// its costs, no negated table, no direction bits.  Every buffer the routines get is a heap block of exactly the size they
-// may touch, so the address sanitizer sees a step outside.  Test infrastructure; no GPU.
+// Host-side check of the traceback kernel's routines (prograph_amd/csrc/pg_aln_trace.h: pg_tr_end0, pg_tr_row0, pg_tr_row,
+// pg_tr_walk_room) as the instance for up to 128 positions runs them - the single strip j0 = 0 - against a plain DP that
+// keeps the three tables whole and walks them by comparing entries - the distance minimising over its costs, no negated
+// table, no direction bits.  Every buffer the routines get is a heap block of exactly the size they may touch - the strip's
+// len y cells, not one more - so the address sanitizer sees a step outside.  Test infrastructure; no GPU.
 #include "pg_aln_trace.h"
 #include <algorithm>
 #include <cstdio>
@@ -130,18 +131,23 @@ int main() {
     int Tm[32 * 32];
     for (int a = 0; a < 32; ++a)
       for (int b = 0; b < 32; ++b) Tm[a * 32 + b] = mode == PG_TR_GLOBAL ? -T[a][b] : T[a][b];
-    std::vector<int> colH(ly + 1), colE(ly + 1);
+    std::vector<int> colH(ly, 0x5a5a5a5a), colE(ly, 0x5a5a5a5a);           // the strip's cells, not one more
     std::vector<uint32_t> dir((size_t)std::max(lx, 1) * nd, 0xdeadbeefu);
     pg_tr_end end;
-    pg_tr_row0(mode, lx, ly, e, o + e, colH.data(), colE.data(), 1, &end);
-    for (int i = 1; i <= lx; ++i)
-      pg_tr_row(mode, i, lx, ly, e, o + e, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
-                dir.data() + (size_t)(i - 1) * nd, 1, &end);
+    pg_tr_end0(mode, lx, ly, &end);
+    pg_tr_row0(mode, 0, ly, e, o + e, colH.data(), colE.data(), 1);
+    int last = 0;
+    for (int i = 1; i <= lx; ++i) {
+      int rf;
+      pg_tr_row(mode, i, lx, ly, 0, e, o + e, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt, ys, colH.data(), colE.data(), 1,
+                dir.data() + (size_t)(i - 1) * nd, 1, &end, pg_tr_border_x(mode, i, e, o + e), PG_TR_NEG,
+                pg_tr_border_x(mode, i - 1, e, o + e), &last, &rf);
+    }
     const long long ldo = lx + ly + (it % 3);                               // the least the walk may be given, and a little more
     std::vector<unsigned char> ops(ldo, 0xee);
     int32_t head[8] = {0};
-    head[0] = mode == PG_TR_GLOBAL ? -colH[ly] : end.best;
-    pg_tr_walk(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), ldo, head);
+    head[0] = mode == PG_TR_GLOBAL ? pg_tr_global(lx, ly, e, o + e, last) : end.best;
+    pg_tr_walk_room(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), ldo, 2 * PG_TR_MAX_L, head);
     bool ok = head[0] == want.score && head[1] == want.xb && head[2] == want.xe && head[3] == want.yb && head[4] == want.ye &&
               head[5] == want.n && head[6] == want.ident;
     for (long long k = 0; ok && k < ldo; ++k) ok = ops[k] == (k < want.n ? want.ops[k] : 0);

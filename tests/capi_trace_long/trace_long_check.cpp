@@ -1,5 +1,5 @@
-// Host-side check of the long traceback's routines (prograph_amd/csrc/pg_aln_trace.h: pg_tr_end0, pg_tr_strip_row0,
-// pg_tr_row_strip, pg_tr_end_take, pg_tr_walk_room) swept as pg_aln_trace_long.hip sweeps them - strip s over all rows,
+// Host-side check of the traceback's routines (prograph_amd/csrc/pg_aln_trace.h: pg_tr_end0, pg_tr_row0, pg_tr_row,
+// pg_tr_end_take, pg_tr_walk_room) swept as pg_aln_trace.hip's long instance sweeps them - strip s over all rows,
 // then strip s + 1, one boundary column in between - against the plain full-table DP of tests/capi_trace/trace_check.cpp
 // (`plain`, `pack` and the generator are that file's, its main renamed).  Every buffer the routines get is a heap block of
 // exactly the size they may touch, so the address sanitizer sees a step outside.  Test infrastructure; no GPU.
@@ -28,13 +28,13 @@ static bool strips(int tag, int mode, const int T[32][32], int e, int o, const s
   for (int j0 = 0; j0 < ly; j0 += PG_TR_STRIP) {
     const int width = std::min(PG_TR_STRIP, ly - j0);
     std::vector<int> colH(width, 0x5a5a5a5a), colE(width, 0x5a5a5a5a);     // the strip's cells, not one more
-    pg_tr_strip_row0(mode, j0, ly, e, oe, colH.data(), colE.data(), 1);
+    pg_tr_row0(mode, j0, ly, e, oe, colH.data(), colE.data(), 1);
     int diag = pg_tr_border(mode, j0, e, oe);
     for (int i = 1; i <= lx; ++i) {
       const int left = j0 ? bh[i - 1] : pg_tr_border(mode, i, e, oe), fin = j0 ? bf[i - 1] : PG_TR_NEG;
       int rh, rf;
-      pg_tr_row_strip(mode, i, lx, ly, j0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt + (j0 >> 2) * ys, ys, colH.data(),
-                      colE.data(), 1, dir.data() + (size_t)(i - 1) * nd, 1, &end, left, fin, diag, &rh, &rf);
+      pg_tr_row(mode, i, lx, ly, j0, e, oe, Tm + 32 * pg_tr_token(xt, xs, i - 1), yt + (j0 >> 2) * ys, ys, colH.data(),
+                colE.data(), 1, dir.data() + (size_t)(i - 1) * nd, 1, &end, left, fin, diag, &rh, &rf);
       diag = left;
       last = rh;
       bh[i - 1] = rh;
@@ -44,7 +44,7 @@ static bool strips(int tag, int mode, const int T[32][32], int e, int o, const s
   const long long ldo = lx + ly + slack;                                    // the least the walk may be given, and a little more
   std::vector<unsigned char> ops(ldo, 0xee);
   int32_t head[8] = {0};
-  head[0] = mode != PG_TR_GLOBAL ? end.best : -(lx == 0 ? pg_tr_border(mode, ly, e, oe) : ly == 0 ? pg_tr_border(mode, lx, e, oe) : last);
+  head[0] = mode == PG_TR_GLOBAL ? pg_tr_global(lx, ly, e, oe, last) : end.best;
   pg_tr_walk_room(mode, lx, ly, end.i, end.j, xt, xs, yt, ys, dir.data(), nd, 1, ops.data(), ldo, 2 * PG_TR_LONG_MAX_L, head);
   bool ok = head[0] == want.score && head[1] == want.xb && head[2] == want.xe && head[3] == want.yb && head[4] == want.ye &&
             head[5] == want.n && head[6] == want.ident;

@@ -10,6 +10,11 @@ shared frame puts all modes at risk at once, so for every kernel instance found:
     LDS per block  at most the figure measured before the frame was shared (profiles/aln_frame_resources.txt) plus 8 bytes,
                    the room of an smin / smax pair
 
+The per-pair kernels on pg_aln_pair.h (the traceback template of pg_aln_trace.hip, two instances; the statistics kernel of
+pg_aln_stats.hip, three) are LDS-bound at one wave per SIMD, nowhere near a register cliff: for them scratch 0, the number
+of instances, and LDS per block at most the figure measured before they shared a frame
+(profiles/aln_pair_frame_resources.txt); their VGPRs are printed, not asserted.
+
 Only the remarks are read, nothing else of the assembly.  Skipped where hipcc is absent.
 """
 import os
@@ -35,6 +40,11 @@ LDS = {
 }
 LDS_LONG_GLOBAL = 40068
 INSTANCES = {"pg_aln_long_dense_kernel": 4}                     # two modes x two output types; every other kernel: two output types
+# the per-pair units: kernel name -> template argument -> LDS bytes per block before the frame was shared
+PAIR_LDS = {
+    "pg_aln_trace": {"pg_aln_trace_kernel": {"Lb0": 78336, "Lb1": 77824}},      # up to 128 positions, the strip loop
+    "pg_aln_stats": {"pg_aln_stats_kernel": {"Li32": 39936, "Li64": 74752, "Li128": 144384}},
+}
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
 
@@ -45,7 +55,7 @@ def remarks(unit, tmp):
     assert p.returncode == 0, p.stderr[-2000:]
     kernels, cur = [], None
     for line in p.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
+        m = re.search(r"remark:\s+(Function Name|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         if m.group(1) == "Function Name":
@@ -77,3 +87,24 @@ def test_alignment_kernel_resources(usage, unit):
         lds = LDS_LONG_GLOBAL if "AlnGlobalLong" in k["name"] else LDS[unit][name]
         assert k["LDS"] <= lds + 8, k
     assert found == {k: INSTANCES.get(k, 2) for k in LDS[unit]}, found
+
+
+@pytest.fixture(scope="module")
+def pair_usage(tmp_path_factory):
+    tmp = str(tmp_path_factory.mktemp("aln_pair_resources"))
+    with ThreadPoolExecutor(max_workers=2) as pool:
+        return dict(zip(PAIR_LDS, pool.map(lambda u: remarks(u, tmp), PAIR_LDS)))
+
+
+@pytest.mark.parametrize("unit", sorted(PAIR_LDS))
+def test_pair_kernel_resources(pair_usage, unit):
+    found = []
+    for k in pair_usage[unit]:
+        base = re.match(r"_Z\d+([a-z0-9_]+?)I(L[bi]\d+)E", k["name"])
+        assert base and base.group(2) in PAIR_LDS[unit].get(base.group(1), {}), f"{unit}.hip: a kernel this test does not know: {k['name']}"
+        found.append(base.group(2))
+        print(unit, k)                                                      # the VGPRs among them: recorded, not asserted
+        assert k["ScratchSize"] == 0, k
+        assert k["LDS"] <= PAIR_LDS[unit][base.group(1)][base.group(2)], k
+    (instances,) = PAIR_LDS[unit].values()
+    assert sorted(found) == sorted(instances), found

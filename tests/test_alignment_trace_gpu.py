@@ -2,6 +2,8 @@
 The traceback kernel (`pg_alignment_trace`, prograph_amd/csrc/pg_aln_trace.hip) on the GPU: every field of every pair
 against `definition` of tests/trace_testdata.py, exactly, and the scores of a graph's edges against the graph's weights.
 One list of 200 pairs per (mode, gap, gap_open, widths) serves every list length: the reference is computed once.
+The kernel is the one-strip instance of the strip template: the narrow and odd widths, where the strip, its dwords of
+direction bits and its dwords of tokens end early, run in four modes against `alignments.host_trace`.
 """
 import functools
 
@@ -82,6 +84,42 @@ def test_every_field_is_the_definition(xw, yw, mode, gap_open, pairs):
     head, ops = _native.alignment_trace(xo, yo, xi[:pairs], yi[:pairs], mode, device_table(mode, T), 2, gap_open)
     assert xo.valid() and yo.valid()
     check(head, ops, want[:pairs], xw, yw)
+
+
+@functools.lru_cache(maxsize=None)
+def narrow(mode, gap_open, xw, yw):
+    """65 pairs (two waves, the second of one lane) over rows of every length 0..width that fits in 24 rows, the widths
+    themselves and an all-zero row on either side among them; pairs 0..2 meet the empty rows.  The host's answer, once."""
+    rng = np.random.default_rng(100 * xw + yw)
+    def rows(w):
+        M = np.zeros((24, w), dtype=np.uint8)
+        for r, l in enumerate([0, w] + [int(v) for v in rng.integers(0, w + 1, 22)]):
+            M[r, :l] = rng.integers(0, A, l)
+            if l:
+                M[r, l - 1] = rng.integers(1, A)
+        return M
+    X, Y = rows(xw), rows(yw)
+    xi, yi = rng.integers(0, 24, 65), rng.integers(0, 24, 65)
+    xi[:3], yi[:3] = (0, 0, 1), (0, 1, 0)                                   # len x = len y = 0; len x = 0; len y = 0
+    T = table(mode)
+    return X, Y, xi, yi, T, alignments.host_trace(mode, T, 2, gap_open, X, Y, xi, yi)
+
+
+@pytest.mark.parametrize("gap_open", [0, 11])
+@pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL, alignments.FIT])
+@pytest.mark.parametrize("xw,yw", [(1, 1), (128, 1), (1, 128), (7, 9), (127, 121)])
+def test_narrow_and_odd_widths_are_the_host_trace(xw, yw, mode, gap_open):
+    """A y width that is no multiple of 8 or of 4, an x of one dword, one column, one row: the single strip against
+    `host_trace`, field for field; fit through its own entry."""
+    X, Y, xi, yi, T, (*fields, hops) = narrow(mode, gap_open, xw, yw)
+    assert not X[0].any() and not Y[0].any()
+    xo, yo = _native.aln_operand(torch.from_numpy(X), A), _native.aln_operand(torch.from_numpy(Y), A)
+    head, ops = _native.alignment_trace(xo, yo, xi, yi, mode, device_table(mode, T), 2, gap_open)
+    head, ops = head.cpu().numpy(), ops.cpu().numpy()
+    assert head.shape == (65, 8) and ops.shape == (65, xw + yw) and ops.dtype == np.uint8
+    for c, f in enumerate(FIELDS):
+        assert np.array_equal(head[:, c], fields[c]), (f, head[:, c], fields[c])
+    assert not head[:, 7].any() and np.array_equal(ops, hops)
 
 
 @pytest.mark.parametrize("mode", [GLOBAL, LOCAL, SEMIGLOBAL])

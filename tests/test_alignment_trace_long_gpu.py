@@ -1,5 +1,5 @@
 """
-The strip traceback kernel (`pg_alignment_trace_long`, prograph_amd/csrc/pg_aln_trace_long.hip) on the GPU:
+The strip traceback kernel (`pg_alignment_trace_long`, the long instance of prograph_amd/csrc/pg_aln_trace.hip) on the GPU:
 every field of every pair against `definition` of tests/trace_testdata.py, exactly - lengths mixed within a wave around the
 strip boundaries 128 and 256, so that lanes differ in their number of strips - the cross-strip tie by hand, the full width
 against the host expression, the 128-position kernel bit for bit, and the scores of a graph's edges against its weights.

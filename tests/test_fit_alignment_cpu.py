@@ -373,7 +373,7 @@ def test_argument_checks_of_the_c_entries_without_a_gpu():
 
 
 def test_trace_routines_in_fit_mode_under_the_sanitizers():
-    """tests/capi_fit/fit_check.cpp: pg_aln_trace.h's row routine, strip routine and walk in mode PG_TR_FIT, compiled for
+    """tests/capi_fit/fit_check.cpp: pg_aln_trace.h's row routine, as one strip and as several, and walk in mode PG_TR_FIT, compiled for
     the host with the address and undefined-behaviour sanitizers, against a brute force over substrings and paths on
     random pairs, strips included, and the hand-made pairs of its header.  Runs on the CPU."""
     capi = os.path.join(REPO, "tests", "capi_fit")
