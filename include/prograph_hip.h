@@ -573,6 +573,38 @@ int pg_alignment_fit_long_dense(const void *x_packed, int64_t n, int64_t x_npad,
                                 int64_t ldo, int out_elem_bytes, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * PROFILE (PSSM) queries - BUILD DEFINED (pg_aln_profile.hip); SIMILARITIES: larger is nearer.  A profile is a table P of
+ * L positions by A <= 32 symbols, entries -128..127; P[j][a] scores its position j against symbol a.  The recurrences are
+ * those of pg_alignment_local_dense (mode 0), pg_alignment_semiglobal_dense (mode 1) and pg_alignment_fit_dense (mode 2)
+ * with S[x_i][y_j] replaced by P[j][x_i]: the profile is the Y operand, all of its L positions count, and in mode 2 ALL of
+ * it is placed within any stretch of the X row (scores may be negative).  No symmetry is asked of P.
+ *   The operand.  profiles: bytes P[j][a] + bias, [m][32][lpad] with j contiguous, lpad a multiple of 128 that covers yl;
+ *   bytes at j >= a profile's length and rows a >= A are 0.  lengths: int32[m] on the device, clamped to 0..yl by the
+ *   kernels (nothing is found from bytes); yl: the longest length, which stands for the Y width in the modes' cell
+ *   offsets.  bias = -min(0, min P) in 0..128 and top = max(0, max P) in 0..127 over the call's profiles: the caller
+ *   computes them, there is no reduction on the device.  Row offsets: profiles + r0 * 32 * lpad, lengths + r0.
+ *   pg_alignment_profile_dense  out[r * ldo + c] = s(profile r, X row c) + out_bias.  X as for pg_alignment_dense
+ *                      (pg_sub_pack's order, x_npad a multiple of 256); xl, yl <= 128 (PG_E_TOOLONG beyond); gap in 1..255,
+ *                      gap_open in 0..255; out_bias >= 0 is the shift of pg_alignment_fit_dense and is added in mode 2
+ *                      alone; out_elem_bytes 8 (int64) or 2 (fp16).  mode outside 0..2, a bad lpad, bias or top:
+ *                      PG_E_BADARG; the other checks and codes are pg_alignment_fit_dense's.  Every check returns before
+ *                      any launch.  The caller guarantees the 16-bit cells with max P for max S - mode 0:
+ *                      min(xl, yl) * top + 255 <= 65 535, mode 1: 2 * min(xl, yl) * top + 255 <= 65 535 (both always true
+ *                      here), mode 2: gap_open + yl * (gap + 2 top) + 255 <= 65 535 - and, for the fp16 output, that every
+ *                      out value is an integer within 0..2048; the kernel tests neither.  Does not allocate; LDS only.
+ *   pg_alignment_profile_long_dense  the same up to PG_ALN_LONG_MAX_L positions on either side: the workspace of
+ *                      pg_alignment_long_workspace(xl), out_elem_bytes 8 (int64) or 4 (int32), the checks and codes of
+ *                      pg_alignment_fit_long_dense, the caller's guarantees as above.
+ */
+int pg_alignment_profile_dense(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *profiles,
+                               const int32_t *lengths, int64_t m, int lpad, int yl, int bias, int top, int gap, int gap_open,
+                               int out_bias, void *out, int64_t ldo, int out_elem_bytes, void *stream);
+int pg_alignment_profile_long_dense(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *profiles,
+                                    const int32_t *lengths, int64_t m, int lpad, int yl, int bias, int top, int gap,
+                                    int gap_open, int out_bias, void *out, int64_t ldo, int out_elem_bytes, void *workspace,
+                                    int64_t workspace_bytes, void *stream);
+
+/*
  * Alignment TRACEBACK - BUILD DEFINED (pg_aln_trace.hip, pg_aln_trace.h): the canonical alignment of a list of pairs under
  * the tables H, E, F of pg_alignment_affine_dense (mode PG_ALN_TRACE_GLOBAL, table = cost_u8, gap_open = 0: the linear
  * form), pg_alignment_local_dense (PG_ALN_TRACE_LOCAL, table = score_i8) or pg_alignment_semiglobal_dense

@@ -30,6 +30,7 @@ ALN_LOCAL_MIN, ALN_LOCAL_MAX = -128, 127    # pg_alignment_local_dense: the entr
 ALN_LONG_MAX_L = 2048             # pg_alignment_long_dense / ..._local_long_dense / ..._semiglobal_long_dense: positions per operand
 ALN_TRACE_GLOBAL, ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL = 0, 1, 2     # pg_alignment_trace / pg_alignment_trace_long: the modes
 ALN_TRACE_FIT = 3                 # pg_aln_trace.h's PG_TR_FIT: pg_alignment_fit_trace / _long, which take no mode
+ALN_PROFILE_MODES = ("local", "semiglobal", "fit")      # pg_alignment_profile_dense / _long_dense: mode 0, 1, 2
 ALN_TRACE_LONG_WORKSPACE = 2 << 30  # alignment_trace_long: the most workspace it takes unasked
 LEV_LONG_MAX_L = 2048             # pg_levenshtein_long_dense: positions per operand
 SPECTRUM_MAX_L, SPECTRUM_MAX_K, SPECTRUM_MAX_D = 2048, 6, 32768   # pg_spectrum_profile: positions per row, window length, profile width
@@ -48,6 +49,7 @@ SYMBOLS = [
     "pg_alignment_local_dense", "pg_alignment_long_workspace", "pg_alignment_long_dense", "pg_alignment_local_long_dense",
     "pg_alignment_semiglobal_dense", "pg_alignment_semiglobal_long_dense",
     "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
+    "pg_alignment_profile_dense", "pg_alignment_profile_long_dense",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
     "pg_alignment_stats",
     "pg_spectrum_dims", "pg_spectrum_profile",
@@ -165,6 +167,9 @@ def _load():
                                                _i32, _vp]
         lib.pg_alignment_fit_long_dense.argtypes = [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32, _vp,
                                                     _i64, _i32, _vp, _i64, _vp]
+        lib.pg_alignment_profile_dense.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                   _i32, _vp, _i64, _i32, _vp]
+        lib.pg_alignment_profile_long_dense.argtypes = lib.pg_alignment_profile_dense.argtypes[:-1] + [_vp, _i64, _vp]
         lib.pg_alignment_trace_workspace.argtypes = [_i32, _i32, ctypes.POINTER(_i64)]
         lib.pg_alignment_trace.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _i32,
                                            _vp, _vp, _i64, _vp, _i64, _vp]
@@ -1067,6 +1072,77 @@ def alignment_fit_long_dense(xo, yo, score, gap, gap_open, out_bytes=8, rows=Non
     Allocates the call's workspace."""
     return _aln_dense("pg_alignment_fit_long_dense", "alignment_fit_long_dense", xo, yo, score, (gap, gap_open, bias), out_bytes,
                       rows, long=True)
+
+
+class ProfileOperand:
+    """Profiles staged for pg_alignment_profile_dense / _long_dense: `buf` uint8 (Q, 32, lpad), byte P[j][a] + bias at
+    [q][a][j], zeros past a profile's length and for symbols it does not have; `lengths` int32 (Q,) on the device; `l` the
+    longest length, `lpad` it rounded up to 128; `bias` = -min(0, min P) and `top` = max(0, max P) over all Q profiles."""
+    __slots__ = ("buf", "lengths", "n", "l", "lpad", "bias", "top")
+
+    def __init__(self, buf, lengths, l, bias, top):
+        self.buf, self.lengths, self.n, self.l, self.lpad = buf, lengths, int(buf.shape[0]), int(l), int(buf.shape[2])
+        self.bias, self.top = int(bias), int(top)
+
+
+def profile_pack(profiles):
+    """A list of (L_q, A) integer arrays (1 <= L_q <= 2048, 2 <= A <= 32, entries -128..127) -> the host arrays of a
+    ProfileOperand: (buf uint8 (Q, 32, lpad), lengths int32 (Q,), longest length, bias, top).  Host numpy: it is not hot."""
+    lengths = np.array([p.shape[0] for p in profiles], dtype=np.int32)
+    l = int(lengths.max())
+    if l > ALN_LONG_MAX_L or lengths.min() < 1 or any(p.ndim != 2 or not 2 <= p.shape[1] <= SUB_MAX_A for p in profiles):
+        raise ValueError(f"profile_pack: (L, A) profiles of 1..{ALN_LONG_MAX_L} positions and 2..{SUB_MAX_A} symbols")
+    lo, hi = min(int(p.min()) for p in profiles), max(int(p.max()) for p in profiles)
+    if lo < ALN_LOCAL_MIN or hi > ALN_LOCAL_MAX:
+        raise ValueError("profile_pack: entries in -128..127")
+    bias, top = -min(0, lo), max(0, hi)
+    buf = np.zeros((len(profiles), SUB_MAX_A, ((l + 127) // 128) * 128), dtype=np.uint8)
+    for q, p in enumerate(profiles):
+        buf[q, :p.shape[1], :p.shape[0]] = (np.asarray(p, dtype=np.int64) + bias).T
+    return buf, lengths, l, bias, top
+
+
+def profile_operand(profiles):
+    """`profile_pack` on the current HIP device."""
+    buf, lengths, l, bias, top = profile_pack(profiles)
+    dev = device()
+    return ProfileOperand(torch.from_numpy(buf).to(dev), torch.from_numpy(lengths).to(dev), l, bias, top)
+
+
+def _profile_dense(entry, name, mode, xo, po, gap, gap_open, out_bytes, rows, bias, long=False):
+    """One profile entry: the profiles (r0, r1) of `po` against every row of `xo`, as `_aln_dense`."""
+    small = 4 if long else 2
+    if out_bytes not in (small, 8):
+        raise ValueError(f"{name}: out_bytes 8 (int64) or {small} ({'int32' if long else 'fp16'})")
+    r0, r1 = (0, po.n) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= r0 < r1 <= po.n:
+        raise ValueError("row range outside the operand")
+    out = torch.empty((r1 - r0, xo.n), dtype=_TORCH_OUT[out_bytes], device=xo.buf.device)
+    tail = ()
+    if long:
+        ws = aln_long_workspace(xo, r1 - r0)
+        tail = (_ptr(ws), ws.numel())
+    _check(getattr(lib(), entry)(ALN_PROFILE_MODES.index(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l,
+                                 ctypes.c_void_p(po.buf.data_ptr() + r0 * SUB_MAX_A * po.lpad),
+                                 ctypes.c_void_p(po.lengths.data_ptr() + 4 * r0), r1 - r0, po.lpad, po.l, po.bias, po.top, int(gap),
+                                 int(gap_open), int(bias), _ptr(out), out.stride(0), out_bytes, *tail, _stream()), entry)
+    return out
+
+
+def alignment_profile_dense(mode, xo, po, gap, gap_open, out_bytes=8, rows=None, bias=0):
+    """(Q, N) profile alignment SCORES of the profiles of ProfileOperand `po` (rows = (r0, r1): only those) against every row
+    of AlnOperand `xo` (pg_alignment_profile_dense; both at most 128 positions); `mode` one of ALN_PROFILE_MODES, `gap`
+    1..255, `gap_open` 0..255, `bias` >= 0 the shift of `alignment_fit_dense` (fit alone).  int64 (out_bytes 8) or the fp16
+    block f16_knn / f16_eps select from (2: exact while every value lies in 0..2048).  The caller checks the mode's cell
+    bound (`aln_local_long_fits`, `aln_semiglobal_long_fits`, `aln_fit_fits` with po.top for max S)."""
+    return _profile_dense("pg_alignment_profile_dense", "alignment_profile_dense", mode, xo, po, gap, gap_open, out_bytes, rows, bias)
+
+
+def alignment_profile_long_dense(mode, xo, po, gap, gap_open, out_bytes=8, rows=None, bias=0):
+    """`alignment_profile_dense` up to ALN_LONG_MAX_L positions on either side (pg_alignment_profile_long_dense): int64 (8) or
+    the int32 block i32_knn / i32_eps select from (4).  Allocates the call's workspace."""
+    return _profile_dense("pg_alignment_profile_long_dense", "alignment_profile_long_dense", mode, xo, po, gap, gap_open, out_bytes,
+                          rows, bias, long=True)
 
 
 def aln_long_operand(tokens, a):

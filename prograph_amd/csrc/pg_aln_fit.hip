@@ -30,37 +30,8 @@
 // cells of lower or equal j only, so the cells j > len y of the last chunk feed no cell j <= len y; they are never folded,
 // and the boundary column is written by strips that lie wholly inside len y.  A lane past its own len x keeps its cells
 // under the EXEC mask (`i < lx`).
+// The mode itself, AlnFit, is in pg_aln_score.h: pg_aln_profile.hip runs it on profiles.
 #include "pg_aln_score.h"
-
-struct AlnFit : AlnModeBase {
-  static constexpr bool SCORE = true, TOP = true, ROWFOLD = false;           // row len x is NOT folded: all of y must align
-  static constexpr int ROW0 = ALN_ROW0_FIT, FOLD = ALN_FOLD_LASTCOL;
-  u32 e, o, bias, Z;
-  int obias;
-  u32 zr, first_r;                                                          // this row's Z and H[0][len y] (short frame)
-  // o + yl (e + 2 top) + 255 <= 65 535: the guarantee of either entry's caller, who tests it on the host
-  __device__ __forceinline__ AlnFit(const AlnParams &p)
-      : e(p.gap), o(p.open), bias(p.bias), Z(p.open + (u32)p.yl * (p.gap + p.top)), obias(p.obias), zr(0), first_r(0) {}
-  __device__ __forceinline__ u32 first(int ly, int) const { return aln_fit_row0(Z, o, e, ly); }      // H[0][len y]; Z for an empty y: 0
-  // Row 0 differs from column to column but not from row to row of Y: left to itself the compiler forms all 129 values
-  // once, ahead of the loop over the rows, and keeps them alive across it - beyond the 168 registers of three waves per
-  // SIMD.  The empty statement makes this row's Z a value of its own, so row 0 is formed where it is used.
-  __device__ __forceinline__ void begin_row(int ly) {
-    zr = Z;
-    asm volatile("" : "+s"(zr));
-    first_r = aln_fit_row0(zr, o, e, ly);
-  }
-  template <int NC>
-  __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const {
-    return aln_score_strip<AlnFit, NC, true, false>(q, x, nullptr, 0, ly - ((ly - 1) & ~15), e, o + e, bias, zr, first_r);
-  }
-  template <int NC, bool LAST>
-  __device__ __forceinline__ u32 strip(const unsigned char *q, const AlnX &x, u32 *wsb, int j0, int rest, u32 best) const {
-    return aln_score_strip<AlnFit, NC, LAST, true>(q, x, wsb, j0, rest - ((rest - 1) & ~15), e, o + e, bias, Z, best);
-  }
-  template <typename OUT>
-  __device__ __forceinline__ OUT value(u32 d) const { return (OUT)((int)d - (int)Z + obias); }
-};
 
 template <typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void pg_aln_fit_dense_kernel(

@@ -13,7 +13,8 @@
 // Two frames.  aln_short_frame (up to ALN_MAX_L positions): the 8 profile slots hold 8 Y rows, the whole row is one strip.
 // aln_long_frame (up to ALNG_MAX_L): a workgroup loops over (column tile, row group) items and takes one Y row at a time,
 // cut into strips of ALN_STRIP positions, 8 strips to the 8 slots; the left edge of strip s > 0 is the boundary column that
-// strip s - 1 wrote to workgroup b's slice of the caller's workspace, one dword per (outer step, lane).
+// strip s - 1 wrote to workgroup b's slice of the caller's workspace, one dword per (outer step, lane).  Each has a twin
+// whose Y side is a profile operand (aln_short_profile_frame, aln_long_profile_frame; pg_aln_profile.hip).
 //
 // A mode M is a struct built once per workgroup from AlnParams; it supplies
 //     M::SCORE, M::TOP           the table: costs as they are | scores + bias as bytes, with top = max(0, max S) if asked for
@@ -242,6 +243,116 @@ __device__ __forceinline__ void aln_long_frame(const u32 *__restrict__ xt, long 
           const int g = i & 31, a = (i >> 5) & 31, slot = i >> 10;
           const int gy = (s0 + slot) * (ALN_STRIP / 4) + g;               // < 512
           *(u32 *)(Q + slot * ALN_QBYTES + a * ALN_QSTRIDE + 4 * g) = aln_profile<M::SCORE>(cs + a * ALN_CSTRIDE, yrow[gy], ly - 4 * gy);
+        }
+        __syncthreads();
+        for (int s = s0; s < s0 + nb; ++s) {
+          const unsigned char *q = Q + (s - s0) * ALN_QBYTES;
+          const int j0 = s * ALN_STRIP;
+          if (s < ns - 1) {
+            best = mode.template strip<8, false>(q, x, wsb, j0, 0, best);
+            continue;
+          }
+          const int rest = ly - j0;                                       // 1..128
+#define ALN_LAST(NC) best = mode.template strip<NC, true>(q, x, wsb, j0, rest, best)
+          ALN_NC_SWITCH((rest + 15) >> 4, (void)0, ALN_LAST)
+#undef ALN_LAST
+        }
+      }
+      if (tid < left_cols) (out + row * ldo + ct * ALN_THREADS)[tid] = mode.template value<OUT>(best);
+    }
+  }
+}
+
+// ---- the profile source (pg_aln_profile.hip): the Y side is a position-specific score matrix, so its
+// query profile is not gathered from tokens and a table but copied from global memory.  Frames of their own: the token
+// frames above, which sit on the register cliff, stay as they are ----
+
+struct AlnProfiles {               // wave-uniform
+  const u32 *p;                    // bytes P + bias, [profile][32 symbols][4 * lpad4 positions]
+  const int *len;                  // positions of every profile: lengths are given, never found from bytes
+  int lpad4;                       // dwords per symbol row: a multiple of ALN_STRIP / 4 that covers the longest profile
+};
+
+// a profile's length as the frames use it: inside the operand, whatever the array holds
+__device__ __forceinline__ int aln_profile_len(const AlnProfiles &pf, long long row, int yl, int max_l) {
+  return min(max(pf.len[row], 0), min(yl, max_l));
+}
+
+// dword g of symbol a of profile `row` (g < lpad4); positions from ly on are byte 0, a score of -bias
+__device__ __forceinline__ u32 aln_profile_word(const AlnProfiles &pf, long long row, int a, int g, int ly) {
+  const int keep = ly - 4 * g;
+  const u32 d = pf.p[(row * 32 + a) * pf.lpad4 + g];
+  return d & (keep >= 4 ? 0xffffffffu : keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
+}
+
+// aln_short_frame with 8 profiles in the 8 slots: a coalesced dword copy into the ALN_QSTRIDE rows, no ytile, no table.
+// bias = -min(0, min P) and top = max(0, max P) over the call's profiles come from the host.
+template <class M, typename OUT>
+__device__ __forceinline__ void aln_short_profile_frame(const u32 *__restrict__ xt, long long n, long long xnpad, int xl,
+                                                        const AlnProfiles pf, long long m, int yl, u32 gap, u32 open, int obias,
+                                                        u32 bias, u32 top, OUT *__restrict__ out, long long ldo, long long colTiles) {
+  __shared__ __attribute__((aligned(16))) unsigned char Q[ALN_ROWS * ALN_QBYTES];
+  __shared__ int ylen[ALN_ROWS];
+  const int tid = threadIdx.x;
+  const long long ct = (long long)blockIdx.x % colTiles, rg = (long long)blockIdx.x / colTiles;
+  const long long row0 = rg * ALN_ROWS;
+  const int xg = (xl + 3) >> 2;                                             // <= 32 dwords (the host checks)
+
+  if (tid < ALN_ROWS) ylen[tid] = row0 + tid < m ? aln_profile_len(pf, row0 + tid, yl, ALN_MAX_L) : 0;
+  __syncthreads();
+  for (int i = tid; i < ALN_ROWS * 32 * 32; i += ALN_THREADS) {
+    const int g = i & 31, a = (i >> 5) & 31, r = i >> 10;                   // a workgroup reads 4 KiB runs: lpad4 = 32 here
+    *(u32 *)(Q + r * ALN_QBYTES + a * ALN_QSTRIDE + 4 * g) = row0 + r < m ? aln_profile_word(pf, row0 + r, a, g, ylen[r]) : 0u;
+  }
+  __syncthreads();
+
+  const long long left_cols = n - ct * ALN_THREADS;
+  const AlnX x = aln_x(xt + ct * ALN_THREADS, xnpad, xg, tid, left_cols);
+  M mode(AlnParams{gap, open, xl, yl, obias, bias, top});
+  for (int r = 0; r < ALN_ROWS; ++r) {
+    const long long row = row0 + r;
+    if (row >= m) break;
+    const int ly = __builtin_amdgcn_readfirstlane(ylen[r]);
+    const unsigned char *q = Q + r * ALN_QBYTES;
+    mode.begin_row(ly);
+    u32 d;
+#define ALN_ROW(NC) d = mode.template row<NC>(q, x, ly)
+    ALN_NC_SWITCH((ly + 15) >> 4, d = mode.first(0, x.lx), ALN_ROW)
+#undef ALN_ROW
+    if (tid < left_cols) (out + row * ldo + ct * ALN_THREADS)[tid] = mode.template value<OUT>(d);
+  }
+}
+
+// aln_long_frame with the 8 strips of one profile in the 8 slots, read straight from global memory: no yrow, no table
+template <class M, typename OUT>
+__device__ __forceinline__ void aln_long_profile_frame(const u32 *__restrict__ xt, long long n, long long xnpad, int xl,
+                                                       const AlnProfiles pf, long long m, int yl, u32 gap, u32 open, int obias,
+                                                       u32 bias, u32 top, OUT *__restrict__ out, long long ldo, int colTiles,
+                                                       int items, u32 *ws) {
+  __shared__ __attribute__((aligned(16))) unsigned char Q[ALN_ROWS * ALN_QBYTES];
+  const int tid = threadIdx.x;
+  const int xg = (xl + 3) >> 2;                                             // <= 512 dwords (the host checks)
+  const M mode(AlnParams{gap, open, xl, yl, obias, bias, top});
+
+  u32 *wsb = ws + (long long)blockIdx.x * (xg * 4 * ALN_THREADS);          // this workgroup's boundary column
+  for (int item = blockIdx.x; item < items; item += gridDim.x) {
+    const long long ct = item % colTiles, row0 = (long long)(item / colTiles) * ALN_ROWS;
+    const long long left_cols = n - ct * ALN_THREADS;
+    const AlnX x = aln_x(xt + ct * ALN_THREADS, xnpad, xg, tid, left_cols);
+
+    for (int r = 0; r < ALN_ROWS; ++r) {
+      const long long row = row0 + r;
+      if (row >= m) break;
+      const int ly = __builtin_amdgcn_readfirstlane(aln_profile_len(pf, row, yl, ALNG_MAX_L));      // <= yl <= 4 * lpad4 (the host checks)
+      const int ns = (ly + ALN_STRIP - 1) / ALN_STRIP;                    // strips that hold a position of the profile
+      u32 best = mode.first(ly, x.lx);                                    // carried from strip to strip
+      for (int s0 = 0; s0 < ns; s0 += ALN_ROWS) {
+        const int nb = min(ALN_ROWS, ns - s0);
+        __syncthreads();                                                  // the previous eight strips', or profile's, readers are done
+        for (int i = tid; i < nb * 32 * 32; i += ALN_THREADS) {
+          const int g = i & 31, a = (i >> 5) & 31, slot = i >> 10;
+          const int gy = (s0 + slot) * (ALN_STRIP / 4) + g;               // < 32 ns <= lpad4
+          *(u32 *)(Q + slot * ALN_QBYTES + a * ALN_QSTRIDE + 4 * g) = aln_profile_word(pf, row, a, gy, ly);
         }
         __syncthreads();
         for (int s = s0; s < s0 + nb; ++s) {

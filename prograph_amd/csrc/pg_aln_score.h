@@ -118,3 +118,58 @@ struct AlnLocal : AlnModeBase {
     return aln_score_strip<AlnLocal, NC, LAST, true>(q, x, wsb, j0, 0, e, oe, bias, 0u, best);
   }
 };
+
+// The semi-global mode (pg_aln_semiglobal.hip says why it is exact and where its result is read), here because two files
+// run it: pg_aln_semiglobal.hip on tokens, pg_aln_profile.hip on profiles.  Z = min(xl, yl) * top of the operand WIDTHS.
+struct AlnSemiglobal : AlnModeBase {
+  static constexpr bool SCORE = true, TOP = true, ROWFOLD = true;
+  static constexpr int ROW0 = ALN_ROW0_Z, FOLD = ALN_FOLD_LASTCOL;
+  u32 e, oe, bias, Z;
+  // Z <= 128 * 127 in the short kernel; 2 Z + 255 <= 65 535 is the guarantee of the long entry's caller
+  __device__ __forceinline__ AlnSemiglobal(const AlnParams &p)
+      : e(p.gap), oe(p.open + p.gap), bias(p.bias), Z((u32)min(p.xl, p.yl) * p.top) {}
+  __device__ __forceinline__ u32 first(int, int) const { return Z; }        // H[0][len y] = 0
+  // rest = len y - j0 >= 1; its index inside the last chunk is rest - ((rest - 1) & ~15), 1..16
+  template <int NC>
+  __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const {
+    return aln_score_strip<AlnSemiglobal, NC, true, false>(q, x, nullptr, 0, ly - ((ly - 1) & ~15), e, oe, bias, Z, Z);
+  }
+  template <int NC, bool LAST>
+  __device__ __forceinline__ u32 strip(const unsigned char *q, const AlnX &x, u32 *wsb, int j0, int rest, u32 best) const {
+    return aln_score_strip<AlnSemiglobal, NC, LAST, true>(q, x, wsb, j0, rest - ((rest - 1) & ~15), e, oe, bias, Z, best);
+  }
+  template <typename OUT>
+  __device__ __forceinline__ OUT value(u32 d) const { return (OUT)(d - Z); }
+};
+
+// The fit mode (pg_aln_fit.hip says why it is exact and where its result is read), here for the same two reasons.
+// Z = o + yl (e + top), yl the WIDTH of the Y operand.
+struct AlnFit : AlnModeBase {
+  static constexpr bool SCORE = true, TOP = true, ROWFOLD = false;           // row len x is NOT folded: all of y must align
+  static constexpr int ROW0 = ALN_ROW0_FIT, FOLD = ALN_FOLD_LASTCOL;
+  u32 e, o, bias, Z;
+  int obias;
+  u32 zr, first_r;                                                          // this row's Z and H[0][len y] (short frame)
+  // o + yl (e + 2 top) + 255 <= 65 535: the guarantee of either entry's caller, who tests it on the host
+  __device__ __forceinline__ AlnFit(const AlnParams &p)
+      : e(p.gap), o(p.open), bias(p.bias), Z(p.open + (u32)p.yl * (p.gap + p.top)), obias(p.obias), zr(0), first_r(0) {}
+  __device__ __forceinline__ u32 first(int ly, int) const { return aln_fit_row0(Z, o, e, ly); }      // H[0][len y]; Z for an empty y: 0
+  // Row 0 differs from column to column but not from row to row of Y: left to itself the compiler forms all 129 values
+  // once, ahead of the loop over the rows, and keeps them alive across it - beyond the 168 registers of three waves per
+  // SIMD.  The empty statement makes this row's Z a value of its own, so row 0 is formed where it is used.
+  __device__ __forceinline__ void begin_row(int ly) {
+    zr = Z;
+    asm volatile("" : "+s"(zr));
+    first_r = aln_fit_row0(zr, o, e, ly);
+  }
+  template <int NC>
+  __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const {
+    return aln_score_strip<AlnFit, NC, true, false>(q, x, nullptr, 0, ly - ((ly - 1) & ~15), e, o + e, bias, zr, first_r);
+  }
+  template <int NC, bool LAST>
+  __device__ __forceinline__ u32 strip(const unsigned char *q, const AlnX &x, u32 *wsb, int j0, int rest, u32 best) const {
+    return aln_score_strip<AlnFit, NC, LAST, true>(q, x, wsb, j0, rest - ((rest - 1) & ~15), e, o + e, bias, Z, best);
+  }
+  template <typename OUT>
+  __device__ __forceinline__ OUT value(u32 d) const { return (OUT)((int)d - (int)Z + obias); }
+};

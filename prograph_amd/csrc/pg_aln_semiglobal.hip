@@ -25,28 +25,8 @@
 // so a masked-out cell is 0 <= best.  An interior cell (j < len y, i < len x) is never folded.  (3) Padding: profile
 // bytes at j >= len y are 0 (a score of -bias <= 0), so a padded cell is at most a last-column cell of the same or an
 // earlier step - the fold after the loop may include them.
+// The mode itself, AlnSemiglobal, is in pg_aln_score.h: pg_aln_profile.hip runs it on profiles.
 #include "pg_aln_score.h"
-
-struct AlnSemiglobal : AlnModeBase {
-  static constexpr bool SCORE = true, TOP = true, ROWFOLD = true;
-  static constexpr int ROW0 = ALN_ROW0_Z, FOLD = ALN_FOLD_LASTCOL;
-  u32 e, oe, bias, Z;
-  // Z <= 128 * 127 in the short kernel; 2 Z + 255 <= 65 535 is the guarantee of the long entry's caller
-  __device__ __forceinline__ AlnSemiglobal(const AlnParams &p)
-      : e(p.gap), oe(p.open + p.gap), bias(p.bias), Z((u32)min(p.xl, p.yl) * p.top) {}
-  __device__ __forceinline__ u32 first(int, int) const { return Z; }        // H[0][len y] = 0
-  // rest = len y - j0 >= 1; its index inside the last chunk is rest - ((rest - 1) & ~15), 1..16
-  template <int NC>
-  __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const {
-    return aln_score_strip<AlnSemiglobal, NC, true, false>(q, x, nullptr, 0, ly - ((ly - 1) & ~15), e, oe, bias, Z, Z);
-  }
-  template <int NC, bool LAST>
-  __device__ __forceinline__ u32 strip(const unsigned char *q, const AlnX &x, u32 *wsb, int j0, int rest, u32 best) const {
-    return aln_score_strip<AlnSemiglobal, NC, LAST, true>(q, x, wsb, j0, rest - ((rest - 1) & ~15), e, oe, bias, Z, best);
-  }
-  template <typename OUT>
-  __device__ __forceinline__ OUT value(u32 d) const { return (OUT)(d - Z); }
-};
 
 template <typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void pg_aln_semiglobal_dense_kernel(

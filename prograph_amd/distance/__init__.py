@@ -7,6 +7,7 @@ from .hamming import hamming
 from .levenshtein import levenshtein, levenshtein_knn
 from .local_alignment import local_alignment
 from .minkowski import minkowski
+from .profile_alignment import profile_alignment
 from .semiglobal_alignment import semiglobal_alignment
 from .spectrum import spectrum
 from .substitution import substitution

@@ -34,8 +34,9 @@ import torch
 
 from . import _native
 from . import alignments as _alignments
-from .distance import (alignment, cosine, euclidean, fit_alignment, hamming, levenshtein, local_alignment, minkowski, semiglobal_alignment,
-                       spectrum, substitution)
+from .distance import (alignment, cosine, euclidean, fit_alignment, hamming, levenshtein, local_alignment, minkowski, profile_alignment,
+                       semiglobal_alignment, spectrum, substitution)
+from .distance.profile_alignment import Profiles
 
 _EMBED_F32 = {cosine: "cosine", euclidean: "euclidean"}      # fp32 embedding metrics of pg_cos.hip -> their _native prefix
 
@@ -491,6 +492,10 @@ class Prograph:
         does a `fit_alignment` instance (`pg_alignment_fit_dense`), which is NOT symmetric: the QUERY is aligned whole within
         any stretch of a dataset row - a hit (q, c) reads "query q, whole, placed in row c" -, its scores may be negative
         (a `k` list ranks them), and `eps` keeps `s > 0`.
+        A `profile_alignment` instance takes PROFILES as `queries` - one (L, A) array, a (Q, L, A) array or a list of (L_q, A)
+        arrays (distance/profile_alignment.py) - and otherwise behaves as the score of its mode: largest first, `eps` keeps
+        `s > 0 and comp(eps, s)`, the weights are the scores, in fit mode a hit (q, c) reads "profile q, whole, in row c"
+        (blocks of `pg_alignment_profile_dense` / `pg_alignment_profile_long_dense`); it takes no identity cut.
         `min_identity=` (0..1) / `min_columns=`: as in `build_graph` - the hits are found as above, each is aligned with
         its query (`align(..., queries=, ops=False)`), and those below the cut are dropped; the result is a `CSRGraph`
         (`output="csr"`, also for `k`: a query may keep fewer than k hits) or the filtered tuple list.
@@ -514,6 +519,9 @@ class Prograph:
                 raise TypeError("Epsilon must be provided as a number.")
             if eps != eps:
                 raise ValueError("Epsilon must not be NaN.")
+        if isinstance(distance, profile_alignment):                        # the queries are profiles, not sequences
+            g = self._search_profile(queries, k, eps, comp, representation, distance)
+            return g if output == "csr" else g.to_tuples()
         strings = None
         if isinstance(queries, str):
             strings = [queries]
@@ -988,7 +996,7 @@ class Prograph:
         every entry of a block and the frame takes off again.  Its fp16 route holds while K + width * max(S) <= 2048, its
         int32 route everywhere else inside `_native.aln_fit_fits`."""
         Y, query = (X, False) if T is None else (T, True)
-        n, q, first = X.shape[0], Y.shape[0], int(T is None)
+        n, q = X.shape[0], Y.shape[0]
         K = distance._select_bias(Y.shape[1])                                # 0 but for `fit_alignment`
         on_device = k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE
         f16 = self._local_native(X.shape[1], distance, Y.shape[1]) if K else \
@@ -1003,10 +1011,16 @@ class Prograph:
                                 False, query, score=(K, query))
         dev = _native.device()
         Xd, Yd = torch.as_tensor(X, device=dev), torch.as_tensor(Y, device=dev)
+        return self._score_select_torch(n, q, lambda r0, r1: distance(Xd, Yd[r0:r1]), k, eps, comp, query, dev)
+
+    def _score_select_torch(self, n, q, scores, k, eps, comp, query, dev):
+        """`_local_select`'s selection in torch over the int64 blocks `scores(r0, r1)` of the operator, for what the device
+        selection does not cover."""
+        first = 0 if query else 1
         rows = self._block_rows(n, q, 1 if query else 64)
         parts = []
         for r0 in range(0, q, rows):
-            s = distance(Xd, Yd[r0:r0 + rows])
+            s = scores(r0, min(q, r0 + rows))
             if k is not None:
                 o = torch.sort(s, dim=1, descending=True, stable=True)
                 parts.append((o[1][:, first:first + k].to(torch.int32), o[0][:, first:first + k]))
@@ -1053,6 +1067,37 @@ class Prograph:
         X = self._local_tokens(self._dataset_matrix(representation), distance)
         T = self._local_tokens(self._query_tokens(strings, Y), distance)
         return self._local_select(distance, X, T, None if k is None else min(k, X.shape[0]), eps, comp)
+
+    def _search_profile(self, queries, k, eps, comp, representation, distance):
+        """Profiles as queries under a `profile_alignment`: the contract of `_search_local` - `k` -> ranks 0..min(k, N)-1 of
+        the stable descending (score, dataset row) order, `eps` -> the rows with s > 0 and comp(eps, s), ascending, the weights
+        the scores - on the routes of `_local_select`: fp16 blocks of `pg_alignment_profile_dense` up to 128 positions while
+        the shifted values stay within 0..2048 (`_f16_route`), int32 blocks of `pg_alignment_profile_long_dense` beyond
+        (`_i32_route`), fit scores shifted by `_select_bias` and taken back by the frame; outside the device selection's
+        limits, and without a device, the same selection in torch over the operator's int64 blocks."""
+        prof = Profiles(queries)
+        X = self._sub_tokens(self._dataset_matrix(representation), prof)
+        if X is None:
+            raise ValueError(f"profile_alignment: the tokens must be integers of the profiles' symbols (0..{prof.symbols - 1})")
+        n, q, wx, wy = X.shape[0], len(prof), X.shape[1], prof.width
+        k = None if k is None else min(k, n)
+        device = _native.aln_long_ready()
+        on_device = device and (k <= _native.MAX_K_ROUNDS if k is not None else comp in _CMP_CODE)
+        f16 = on_device and distance._f16_route(wx, wy, prof.top)
+        if f16 or (on_device and distance._i32_route(wx, wy, prof.top)):
+            K = distance._select_bias(wy)
+            kind, wdtype, operand, kernel, out_bytes = ("f16", torch.int16, _native.aln_operand, distance._native_dense, 2) if f16 else \
+                ("i32", torch.int32, _native.aln_long_operand, distance._native_long_dense, 4)
+            xo = operand(torch.from_numpy(np.ascontiguousarray(X)), prof.symbols)
+            po = _native.profile_operand(prof.list)
+            return self._staged(n, q, lambda r0, r1: kernel(xo, po, out_bytes, rows=(r0, r1), bias=K), kind, wdtype, k, eps, comp,
+                                False, True, score=(K, True))
+        dev = _native.device() if device else torch.device("cpu")
+        Xd = torch.as_tensor(X, device=dev)
+        return self._score_select_torch(n, q, lambda r0, r1: distance(Xd, prof.list[r0:r1]), k, eps, comp, True, dev)
+
+    _PROFILE_QUERIES_ONLY = ("{}: a profile_alignment scores profiles, and profiles are queries only: pass them to "
+                             "search(profiles, k= | eps=, distance=...)")
 
     def _build_graph_local(self, idxs, eps, k, similarity, representation, comp, distance, cap=None):
         """
@@ -1121,6 +1166,8 @@ class Prograph:
         nothing (32 bytes per edge, no workspace); 129..2048 positions the strip kernel in slices of the edge list with
         one ops buffer of at most 256 MiB.
         """
+        if isinstance(distance, profile_alignment):                         # no traceback against a profile
+            raise ValueError(self._PROFILE_QUERIES_ONLY.format("align"))
         mode = _alignments._mode_of(distance)                               # TypeError for anything else
         X = self._local_tokens(self._dataset_matrix(representation), distance)
         if graph is not None:
@@ -1171,6 +1218,8 @@ class Prograph:
         """False for the defaults (nothing changes); else the checks of `min_identity=` / `min_columns=`."""
         if min_identity is None and not min_columns:
             return False
+        if isinstance(distance, profile_alignment):
+            raise ValueError(Prograph._PROFILE_QUERIES_ONLY.format(f"{who}(min_identity= / min_columns=)"))
         _alignments._mode_of(distance)                                      # TypeError for anything but the four operators
         if min_identity is not None and not 0 <= float(min_identity) <= 1:
             raise ValueError(f"{who}: min_identity must be in 0..1")
@@ -1321,6 +1370,7 @@ class Prograph:
         profiles from `pg_spectrum_profile`, then the run of a stored embedding under the operator's metric - final fp32
         weights, k up to 1023, `eps` under the five orderings; sequences with equal k-mer multisets are at distance 0 and
         are dropped from `eps` graphs like duplicates.
+        A `profile_alignment` instance raises `ValueError`: profiles are queries only (`search`).
         `min_identity=` (0..1) and `min_columns=` cut the graph by PERCENT IDENTITY; `distance` must then be one of the four
         alignment operators (`TypeError`).  The graph is built exactly as without them; then every edge is aligned
         (`align(..., ops=False)`: `pg_alignment_stats` at up to 128 positions) and kept iff its canonical alignment has
@@ -1329,6 +1379,8 @@ class Prograph:
         (`output="csr"`, also for `k`: a row may keep fewer than k edges) or the filtered tuple list, and `store=` stores
         the filtered graph.
         """
+        if isinstance(distance, profile_alignment):
+            raise ValueError(self._PROFILE_QUERIES_ONLY.format("build_graph"))
         if self._identity_cut_asked("build_graph", distance, min_identity, min_columns):
             g = self.build_graph(idxs=idxs, batch_size=batch_size, eps=eps, k=k, weighted=weighted, similarity=similarity,
                                  representation=representation, distance=distance, comp=comp, output="csr", cap=cap)
