@@ -580,8 +580,9 @@ int pg_alignment_fit_long_dense(const void *x_packed, int64_t n, int64_t x_npad,
  * it is placed within any stretch of the X row (scores may be negative).  No symmetry is asked of P.
  *   The operand.  profiles: bytes P[j][a] + bias, [m][32][lpad] with j contiguous, lpad a multiple of 128 that covers yl;
  *   bytes at j >= a profile's length and rows a >= A are 0.  lengths: int32[m] on the device, clamped to 0..yl by the
- *   kernels (nothing is found from bytes); yl: the longest length, which stands for the Y width in the modes' cell
- *   offsets.  bias = -min(0, min P) in 0..128 and top = max(0, max P) in 0..127 over the call's profiles: the caller
+ *   kernels (nothing is found from bytes): an entry above yl counts yl positions, those behind the profile's own scoring
+ *   -bias for every symbol (their bytes are 0); an entry of 0 or less is the empty profile, s = 0 in every mode (out_bias
+ *   alone in mode 2).  yl: the longest length, which stands for the Y width in the modes' cell offsets.  bias = -min(0, min P) in 0..128 and top = max(0, max P) in 0..127 over the call's profiles: the caller
  *   computes them, there is no reduction on the device.  Row offsets: profiles + r0 * 32 * lpad, lengths + r0.
  *   pg_alignment_profile_dense  out[r * ldo + c] = s(profile r, X row c) + out_bias.  X as for pg_alignment_dense
  *                      (pg_sub_pack's order, x_npad a multiple of 256); xl, yl <= 128 (PG_E_TOOLONG beyond); gap in 1..255,
