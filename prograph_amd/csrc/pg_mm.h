@@ -174,7 +174,8 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
                       // folded tiles, 6 candidates queued, 7 flushes, 8 insertions / eps matches, 9 resweep super-tiles, 10 passes,
                       // 11 folded tiles; x64 cycles (s_memtime) of this wave: 12 in flush, 13 in its insertion part, 14 in folded tiles,
                       // 15 in passes, 16 in scan() (the hot loop), 17 in slow_mfma (queueing, its flushes included), 18 scan() calls,
-                      // 19 bias refreshes, 20 queueing turns, 21 x64 cycles from a pass's start to its first super-tile
+                      // 19 bias refreshes, 20 queueing turns, 21 x64 cycles from a pass's start to its first super-tile, 22 in scan()'s exit code
+                      // (a stopped super-tile's sign words: part of 16), 23 in the flushes of the lane-parallel queueing (part of 17 and of 12)
 #define PG_ST(i, n) st[i] += (u32)(n)
 #define PG_T0(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
 #define PG_T1(i, v) st[i] += (u32)((__builtin_amdgcn_s_memtime() - v) >> 6)
@@ -577,11 +578,20 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
     u32 am0 = 0, am1 = 0, am2 = 0, am3 = 0;
     u32 amMask = 0;                                         // bit t = tile t is flagged
     auto push_signs = [&](int S) {
-      u32 tm = amMask;
+      // (short-list kNN: the tile mask as a SCALAR - it is wave uniform, but left to the compiler it lives in a VGPR and the
+      //  tile loop and the choice of the sign word are vector compares with a branch each, six VALU -> VCC -> branch round
+      //  trips per flagged tile; from a scalar they are scalar compares and selects)
+      u32 tm = kPar ? (u32)__builtin_amdgcn_readfirstlane((int)amMask) : amMask;
       while (tm) {
         const int t = __builtin_ctz(tm);
         tm &= tm - 1u;
-        u32 a = t == 1 ? am1 : (t == 2 ? am2 : (t == 3 ? am3 : am0));
+        u32 a;
+        if constexpr (kPar) {                               // (masks of a scalar index: no branch decides between the words)
+          const u32 k0 = t == 0 ? ~0u : 0u, k1 = t == 1 ? ~0u : 0u, k2 = t == 2 ? ~0u : 0u, k3 = t == 3 ? ~0u : 0u;
+          a = (am0 & k0) | (am1 & k1) | (am2 & k2) | (am3 & k3);
+        } else {
+          a = t == 1 ? am1 : (t == 2 ? am2 : (t == 3 ? am3 : am0));
+        }
         const u32 ebase = ((u32)(4 * (lane >> 5)) << SH) | (u32)((S * 4 + t) * 32 + (lane & 31));
         if (MODE == PG_MODE_KNN || !epsOrdered) {
           u64 mb = __builtin_amdgcn_ballot_w64(a != 0u);
@@ -594,7 +604,11 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
             PG_ST(20, 1);
             qn += n;
             a &= a - 1u;
-            if (qn >= 64) flush();                          // (at most 63 + 64 entries before it)
+            if (qn >= 64) {                                 // (at most 63 + 64 entries before it)
+              PG_T0(tg0);
+              flush();
+              PG_T1(23, tg0);
+            }
             mb = __builtin_amdgcn_ballot_w64(a != 0u);
           }
         } else {
@@ -736,6 +750,7 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
         return 0;
       }
       PG_ST(1, 1);
+      PG_T0(tx0);
       // The flagged chains' MFMAs again, from the ring, unscaled and from zero: the sign word of every MFMA (bit r =
       // result register r holds a candidate).  From these: the MFMAs with a candidate, the lane slots (column x 16-row
       // half) that hold one, and the tiles' sign words.  Which links of a chain are evaluated again: a negative field 0
@@ -783,6 +798,7 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(
 #else
       if (nslots >= R * PG_MM_DENSE_L1) return 2;
 #endif
+      PG_T1(22, tx0);
       am0 = sw0; am1 = sw1; am2 = sw2; am3 = sw3;
       if constexpr (R == 1) amMask = mask;
       else amMask = ((mask & 3u) ? 1u : 0u) | ((mask & 12u) ? 2u : 0u) | ((mask & 48u) ? 4u : 0u) | ((mask & 192u) ? 8u : 0u);

@@ -13,7 +13,7 @@ NAMES = ["L1 super-tiles", "with candidates", "dense tiles, every distance", "de
          "candidates queued", "flushes", "insertions/matches", "resweep super-tiles", "passes", "dense tiles, folded bound",
          "x64 cycles in flush", "x64 cycles in kNN insertion loops", "x64 cycles in folded tiles (incl. their flushes)", "x64 cycles in passes",
          "x64 cycles in scan (hot loop)", "x64 cycles in slow_mfma (incl. its flushes)", "scan calls", "bias refreshes", "queueing turns",
-         "x64 cycles of pass setup", "-", "-"]
+         "x64 cycles of pass setup", "x64 cycles in scan's exit code (part of scan)", "x64 cycles in flushes inside slow_mfma"]
 NST = 24
 lib = nat.lib()
 def stats(reset=True):
