@@ -17,7 +17,10 @@
  *     bytes: launch-private device state (the pass counters of the engine's persistent waves,
  *     the data probe's counts and decision words, and - kNN calls of more than 65 536 rows,
  *     5.2 MB - the partial neighbour lists of rows swept in column pieces; one word per row for
- *     the rows a kNN launch finishes separately),
+ *     the rows a kNN launch finishes separately; from 65 536 rows on also the plan, the pass lists
+ *     and the delivered keys of the symmetric kNN sweep of a self graph, 4 * 256 bytes per row and
+ *     ~90 MB of lists at 200 000 rows - the size follows the row count alone, so every all-pairs
+ *     call of that many rows asks for it, whether its launch can be symmetric or not),
  *     initialised by the call on `stream`; ONE workspace per launch in flight - a workspace
  *     may be reused once the launch that got it has completed, or by later launches on the
  *     same stream;
@@ -230,6 +233,17 @@ int pg_knn_hamming(const void *row_planes, int64_t row_npad, int64_t row0, int64
                    const void *col_planes, int64_t col_npad, int64_t ncols,
                    int l, int bits, int k, int32_t *idx_out, uint8_t *dist_out,
                    void *workspace, void *stream);
+
+/*
+ * pg_knn_sym_plan — the pass plan of the symmetric kNN sweep (host only: no device is touched).
+ * A self graph (rows and columns the same n sequences) on the 64-row matrix-core instance evaluates every
+ * unordered pair once: row block b (64 rows) sweeps the super-tiles (128 columns) from its own, b / 2, on,
+ * cut into pieces that `slots` persistent waves fetch in the order given here.  Entry i of `out` (four int32:
+ * row block, first super-tile, end super-tile, piece number within the block); at most max_passes entries
+ * are written (out may be NULL); returns the number of passes.  piece > 0: pieces of that many super-tiles
+ * (tests); piece = 0: the guided rule, pieces of at least piece_min super-tiles (0: the library's default).
+ */
+int64_t pg_knn_sym_plan(int64_t n, int64_t slots, int piece, int piece_min, int32_t *out, int64_t max_passes);
 
 /*
  * pg_knn_hamming_round — kNN beyond 63 neighbours, 63/64 ranks per all-pairs round.

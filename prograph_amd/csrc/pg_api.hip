@@ -68,8 +68,10 @@ int64_t pg_planes_bytes(int64_t n, int l, int bits) { return ((int64_t)pg_nchunk
 // launch-private device state of an all-pairs call, sized by the row count:
 //   [0, 64)      pass counters of the engine's persistent waves (words 0 and 8: a call's main launch and its gated 32-row
 //                alternative) and, word 1, the number of evicted rows                        - zeroed by the call
-//   [64, 576)    (reserved; zeroed with the counters)
-//   [576, 640)   the probe's decision words (gates)
+//   [64, 576)    word 16 (byte 64): the pass counter of the symmetric kNN sweep; the rest reserved - zeroed with the counters
+//   [576, 640)   decision words (gates): [0], [1] the probe's (pg_decide_kernel); [2] the word the launches BEHIND a
+//                symmetric kNN sweep test (pg_knn_sym_decide_kernel: the probe's gate[0] - 0 without a probe - or 3 =
+//                the sweep's results stand, only pg_knn_rows_kernel still runs)
 //   [640, ...)   the probe's counts (8 * PG_PROBE_ROWS * PG_PROBE_WAVES bytes)
 //   from PG_WS_PARTIAL on, launches of more than PG_SPLIT_MIN_ROWS rows: the lists of the column pieces - at most
 //                PG_SPLIT_MAX_ROWS rows x 8 pieces (or half of them x 16) x PG_MM_KL keys; then the evicted rows (below)
@@ -79,12 +81,155 @@ int64_t pg_planes_bytes(int64_t n, int l, int bits) { return ((int64_t)pg_nchunk
 #define PG_WS_PARTIAL (PG_WS_COUNTS + 8 * 64 * 128)
 #define PG_SPLIT_MAX_ROWS 8192       // 128 row blocks of 64
 #define PG_SPLIT_MIN_ROWS 65536     // (launches up to here never split)
+#define PG_SYM_MIN_N 65536          // the symmetric kNN sweep is not chosen below (= PG_PROBE_MIN_N: launches that are probed)
 #define PG_WS_PARTIAL_BYTES ((int64_t)PG_SPLIT_MAX_ROWS * 8 * PG_MM_KL * 4)
 // ... and behind that (every launch) one word per row: the rows a kNN launch of the MFMA engine evicts (NsqParams::mmEvict;
 // their number: word 1 of the counter line)
 static int64_t ws_evict_offset(int64_t nrows) { return PG_WS_PARTIAL + (nrows > PG_SPLIT_MIN_ROWS ? PG_WS_PARTIAL_BYTES : 0); }
-int64_t pg_workspace_bytes(int64_t nrows) { return ws_evict_offset(nrows) + 4 * (nrows > 0 ? nrows : 0) + 64; }
+static int64_t ws_sym_offset(int64_t nrows) { return (ws_evict_offset(nrows) + 4 * (nrows > 0 ? nrows : 0) + 64 + 255) / 256 * 256; }
+static int64_t sym_ws_bytes(int64_t n);
+// ... and behind that, launches the symmetric kNN sweep may take (knn_launch: self graphs from PG_PROBE_MIN_N rows on): its
+// plan, the lists of its passes and the delivered keys (sym_ws_bytes below: N x capL x 4 bytes the largest part)
+int64_t pg_workspace_bytes(int64_t nrows) { return ws_sym_offset(nrows) + sym_ws_bytes(nrows); }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------
+// The plan of the symmetric kNN sweep (pg_mm_knn_sym_kernel): row block b (64 rows) sweeps the super-tiles from its own,
+// b >> 1, to the last one - a triangle of about half the rectangular sweep's visits - and the persistent grid holds one
+// wave per slot, so the blocks are cut into PIECES and handed out through the pass counter in block order, longest
+// first.  The cut is guided: a block's pieces are about (visits still to hand out) / slots long, at least `pmin` - long
+// pieces while there is much left to balance with, short ones at the end, where the waves' finishing times are evened
+// out (a fixed length needs ~6 pieces per wave for a makespan within 10 % of the mean; this rule is within 2 % at 200 000
+// rows with half as many).  piece > 0: every block in pieces of that length (tests, experiments).  Boundaries inside a
+// block fall on even super-tiles (the folded form's tiles are pairs); a piece is at least three super-tiles before
+// that rounding, so none is empty.  The same code runs on the host (pg_knn_sym_plan: tests, sizes) and in
+// pg_knn_sym_plan_kernel, which writes the plan of a launch into its workspace.
+// ---------------------------------------------------------------------------------------
+__host__ __device__ static inline int sym_block_pieces(long long b, long long nst, long long slots, int piece, int pmin) {
+  const long long len = nst - (b >> 1);
+  // visits of the blocks from b on (two blocks per super-tile; a missing last block does not matter to a length rule)
+  const long long rem = len * (len + 1) - ((b & 1) ? len : 0);
+  long long P = piece > 0 ? piece : (rem / (slots > 0 ? slots : 1)) & ~1ll;
+  if (piece <= 0 && P < pmin) P = pmin;
+  if (P < 3) P = 3;
+  if (P > len) P = len > 3 ? len : 3;
+  unsigned np = ((unsigned)len + (unsigned)P - 1u) / (unsigned)P;      // (32-bit: len < 2^17)
+  if (np > (unsigned)len / 3u) np = (unsigned)len / 3u;
+  if (np > PG_SYM_MAX_PIECES) np = PG_SYM_MAX_PIECES;
+  return np < 1 ? 1 : (int)np;
+}
+// piece q of np of block b: super-tiles [first, end)
+__host__ __device__ static inline void sym_piece_range(long long b, long long nst, int np, int q, int *first, int *end) {
+  // (32-bit: nst < 2^17 super-tiles at 2^24 columns, np <= 16)
+  const unsigned s0 = (unsigned)(b >> 1), len = (unsigned)nst - s0, unp = (unsigned)np, uq = (unsigned)q;
+  *first = q == 0 ? (int)s0 : (int)(2u * ((s0 + len * uq / unp + 1u) / 2u));
+  *end = q + 1 == np ? (int)nst : (int)(2u * ((s0 + len * (uq + 1u) / unp + 1u) / 2u));
+}
+static long long sym_plan_host(long long n, long long slots, int piece, int pmin, int32_t *out, long long cap) {
+  const long long nb = (n + 63) / 64, nst = (n + PG_MM_ST - 1) / PG_MM_ST;
+  // the number of passes alone (every call sizes its workspace by it): the last few answers are kept - a walk over all
+  // row blocks costs tens of microseconds on the host at 200 000 rows, which a short launch would show
+  struct Memo { long long n, slots, count; int piece, pmin; };
+  static std::mutex memoLock;
+  static Memo memo[4] = {};
+  static int memoNext = 0;
+  if (!out) {
+    std::lock_guard<std::mutex> g(memoLock);
+    for (const Memo &m : memo)
+      if (m.n == n && m.slots == slots && m.piece == piece && m.pmin == pmin && m.count > 0) return m.count;
+  }
+  long long at = 0;
+  for (long long b = 0; b < nb; ++b) {
+    const int np = sym_block_pieces(b, nst, slots, piece, pmin);
+    for (int q = 0; q < np; ++q, ++at) {
+      if (!out || at >= cap) continue;
+      int f, e;
+      sym_piece_range(b, nst, np, q, &f, &e);
+      out[4 * at] = (int)b; out[4 * at + 1] = f; out[4 * at + 2] = e; out[4 * at + 3] = q;
+    }
+  }
+  if (!out) {
+    std::lock_guard<std::mutex> g(memoLock);
+    memo[memoNext] = Memo{n, slots, at, piece, pmin};
+    memoNext = (memoNext + 1) % 4;
+  }
+  return at;
+}
+// one workgroup: thread t takes a contiguous run of blocks - their piece counts, a scan over the threads, then the
+// entries and pieceStart[b] = the first pass of block b (pieceStart[nb] = passes in all)
+__global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(long long nb, long long nst, long long slots, int piece, int pmin,
+                                                                int4 *plan, u32 *pieceStart) {
+  __shared__ u32 sums[1024];
+  const int t = threadIdx.x;
+  const long long per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
+  u32 mine = 0;
+  for (long long b = b0; b < b1; ++b) mine += (u32)sym_block_pieces(b, nst, slots, piece, pmin);
+  sums[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const u32 x = t >= o ? sums[t - o] : 0u;
+    __syncthreads();
+    sums[t] += x;
+    __syncthreads();
+  }
+  u32 at = sums[t] - mine;
+  for (long long b = b0; b < b1; ++b) {
+    const int np = sym_block_pieces(b, nst, slots, piece, pmin);
+    pieceStart[b] = at;
+    for (int q = 0; q < np; ++q, ++at) {
+      int f, e;
+      sym_piece_range(b, nst, np, q, &f, &e);
+      plan[at] = make_int4((int)b, f, e, q);
+    }
+  }
+  if (t == 1023) pieceStart[nb] = sums[1023];
+}
+// knobs of the symmetric kNN sweep: PG_KNN_SYM = 0 off / 1 forced wherever the MFMA engine runs the short-list kNN;
+// PG_KNN_SYM_CAPL delivered keys per row (8..256); PG_KNN_SYM_PIECE fixed piece length in super-tiles (default: guided);
+// PG_KNN_SYM_PIECE_MIN the guided rule's shortest piece; PG_KNN_SYM_OCC waves per SIMD the plan counts on
+static int sym_env() { return getenv("PG_KNN_SYM") ? atoi(getenv("PG_KNN_SYM")) : -1; }
+static u32 sym_capl() {
+  const int v = getenv("PG_KNN_SYM_CAPL") ? atoi(getenv("PG_KNN_SYM_CAPL")) : PG_SYM_MAX_CAPL;
+  return (u32)(v < 8 ? 8 : (v > PG_SYM_MAX_CAPL ? PG_SYM_MAX_CAPL : v));
+}
+static int sym_piece() { return getenv("PG_KNN_SYM_PIECE") ? atoi(getenv("PG_KNN_SYM_PIECE")) : 0; }
+static int sym_piece_min() {
+  const int v = getenv("PG_KNN_SYM_PIECE_MIN") ? atoi(getenv("PG_KNN_SYM_PIECE_MIN")) : 32;
+  return v < 4 ? 4 : v;
+}
+static long long sym_slots(int occ) {
+  if (const char *e = getenv("PG_KNN_SYM_OCC")) { if (atoi(e) >= 1 && atoi(e) <= 4) occ = atoi(e); }
+  return (long long)(cu_count() > 0 ? cu_count() : 256) * 4 * (occ < 1 ? 1 : (occ > 4 ? 4 : occ));
+}
+// workspace of the symmetric sweep behind ws_sym_offset: plan (16 bytes a pass), pieceStart, lowCount, the passes' lists
+// (sized for the most waves per SIMD the instance can hold, PG_MM_KL keys a row), lowKeys.  0: no such launch at n rows
+struct SymWs { int64_t plan, pieceStart, lowCount, partial, lowKeys, bytes; long long maxPasses; };
+static SymWs sym_ws(int64_t n) {
+  SymWs w = {0, 0, 0, 0, 0, 0, 0};
+  const int env = sym_env();
+  if (n <= 0 || n > PG_MAX_N_KNN || env == 0 || (env != 1 && n < PG_SYM_MIN_N)) return w;
+  auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+  const long long nb = (n + 63) / 64;
+  w.maxPasses = sym_plan_host(n, sym_slots(4), sym_piece(), sym_piece_min(), nullptr, 0);
+  w.plan = 0;
+  w.pieceStart = up(w.plan + 16 * w.maxPasses);
+  w.lowCount = up(w.pieceStart + 4 * (nb + 1));
+  w.partial = up(w.lowCount + 4 * n);
+  w.lowKeys = up(w.partial + w.maxPasses * 64 * PG_MM_KL * 4);
+  w.bytes = up(w.lowKeys + n * (int64_t)sym_capl() * 4);
+  return w;
+}
+static int64_t sym_ws_bytes(int64_t n) { return sym_ws(n).bytes; }
+
+extern "C" {
+// the plan of the symmetric kNN sweep of an n x n self graph for `slots` waves (host only, no device needed): up to
+// max_passes entries (row block, first super-tile, end super-tile, piece of the block) to out[4 * i ..]; returns the
+// number of passes.  piece > 0: fixed piece length; piece_min: the guided rule's shortest piece (0: the default)
+int64_t pg_knn_sym_plan(int64_t n, int64_t slots, int piece, int piece_min, int32_t *out, int64_t max_passes) {
+  if (n <= 0 || slots <= 0) return pg_fail(PG_E_BADARG, "pg_knn_sym_plan: bad argument");
+  return sym_plan_host(n, slots, piece, piece_min > 0 ? piece_min : sym_piece_min(), out, max_passes);
+}
 }  // extern "C"
 
 // =======================================================================================
@@ -428,6 +573,10 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 //   gate[1]  whole-square eps graph: 0 = every unordered pair once (symmetric slots), 1 = rectangular VALU sweep.
 //            Dense graphs (more than 4 % of all pairs match) pay more for the symmetric path's atomics and
 //            unsorted back parts than it saves (one cluster, eps <= 2: 39.6 vs 29.4 ms)
+//   gate[2]  (not the probe's: pg_knn_sym_decide_kernel writes it behind the merge of a symmetric kNN sweep) what the
+//            rectangular kNN launches and pg_knn_rows_kernel of that call test instead of gate[0]: gate[0]'s value where
+//            the probe chose another engine or instance, 0 where the sweep evicted more rows than its limit (the
+//            rectangular launch runs), 3 where its results stand (pg_knn_rows_kernel alone runs, for its evicted rows)
 // ---------------------------------------------------------------------------------------
 #define PG_PROBE_ROWS 64        // sample rows
 #define PG_PROBE_WAVES 128      // waves per sample row: every 8th column tile (PG_PROBE_STRIDE), one turn of four tiles each at N = 200k
@@ -513,6 +662,109 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
       head = pos < k1 ? keys[wv][g][b * k1 + pos] : 0xFFFFFFFFu;
     }
   }
+}
+
+// kNN of the symmetric sweep (pg_mm_knn_sym_kernel): a row's lists of k + 1 keys - one per piece of its block, passes
+// pieceStart[block] .. pieceStart[block + 1] - and its min(lowCount, capL) delivered keys -> its k + 1 smallest keys in
+// (distance << 24 | index) order, the order of the rectangular sweep; ranks 1..k written out.  Sixteen lanes per row, four
+// rows per wave.  Three steps: (A) the pieces' sorted lists, lane b at the head of list b: k + 1 rounds of "smallest head
+// wins and advances" give the row's own k + 1 smallest keys and with the last of them a bound T on its final threshold;
+// (B) the delivered keys are read once and only those below T are kept, packed, in LDS - a row receives about as many keys
+// as it has cluster mates below it, a handful of them can still enter its list; (C) k + 1 rounds over the own keys (a
+// pointer) and the kept ones ("the smallest above the last one": keys are unique; 0xFFFFFFFF = no entry).
+// Every list is complete below the cap only: a row whose (k+1)-th distance is not below it, or whose slot of delivered keys
+// overflowed, joins the evicted rows (pg_knn_rows_kernel finishes them).
+__global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
+                                                                         const u32 *lowKeys, u32 capL, long long nrows, int k, int *idx,
+                                                                         unsigned char *dist, u32 cap, u32 *evictCount, u32 *evictRows,
+                                                                         const u32 *gate, u32 gateMask) {
+  constexpr int kOwn = PG_SYM_MAX_PIECES * PG_MM_KL, kKeys = PG_MM_KL + kOwn + PG_SYM_MAX_CAPL;
+  __shared__ u32 keys[PG_WG_WAVES][4][kKeys];
+  if (gate && !((gateMask >> __builtin_nontemporal_load(gate)) & 1u)) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, b = lane & 15;
+  const long long row0 = ((long long)blockIdx.x * PG_WG_WAVES + wv) * 4;
+  if (row0 >= nrows) return;                               // (whole wave; no workgroup barrier below)
+  const int k1 = k + 1;
+  const long long blk = row0 >> 6;                         // (four consecutive rows from a multiple of four: one block)
+  const u32 s0 = pieceStart[blk];
+  u32 np = pieceStart[blk + 1] - s0;
+  np = np > PG_SYM_MAX_PIECES ? PG_SYM_MAX_PIECES : np;
+  const long long row = row0 + g;
+  const bool mine = row < nrows;
+  const u32 cnt = mine ? lowCount[row] : 0u;
+  const int nl = (int)(cnt < capL ? cnt : capL);
+  u32 *top = &keys[wv][g][0], *own = top + PG_MM_KL, *kept = own + kOwn;
+  auto sync = []() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  auto group_min = [](u32 m) {
+    for (int o = 8; o > 0; o >>= 1) {
+      const u32 x = (u32)__shfl_xor((int)m, o, 16);
+      m = x < m ? x : m;
+    }
+    return m;
+  };
+  // (A) the four rows at once: lane b stages list b and merges from its head
+  const bool has = mine && b < (int)np;
+  if (has) {
+    const u32 *src = partial + (((long long)s0 + b) * 64 + (row & 63)) * k1;
+    for (int j = 0; j < k1; ++j) own[b * k1 + j] = src[j];
+  }
+  sync();
+  int pos = 0;
+  u32 head = has ? own[b * k1] : 0xFFFFFFFFu, T = 0xFFFFFFFFu;
+  for (int r = 0; r <= k; ++r) {
+    T = group_min(head);
+    if (b == 0) top[r] = T;
+    if (has && head == T && T != 0xFFFFFFFFu) {            // the winner (unique key) moves on in its list
+      ++pos;
+      head = pos < k1 ? own[b * k1 + pos] : 0xFFFFFFFFu;
+    }
+  }
+  // (B) the delivered keys below the own (k+1)-th key, packed (ranks among the group's sixteen lanes)
+  const u32 *low = lowKeys + (mine ? row : 0) * (long long)capL;
+  int nk = 0;
+  for (int e0 = 0; e0 < nl; e0 += 16) {
+    const int e = e0 + b;
+    const u32 x = e < nl ? low[e] : 0xFFFFFFFFu;
+    const bool keep = x < T;
+    const u32 m16 = (u32)(__builtin_amdgcn_ballot_w64(keep) >> (16 * g)) & 0xFFFFu;
+    if (keep) kept[nk + __builtin_popcount(m16 & ((1u << b) - 1u))] = x;
+    nk += __builtin_popcount(m16);
+  }
+  sync();
+  // (C) own keys by pointer, kept keys by rounds
+  int tpos = 0;
+  u32 last = 0;
+  for (int r = 0; r <= k; ++r) {
+    u32 m = 0xFFFFFFFFu;
+    for (int e = b; e < nk; e += 16) {
+      const u32 x = kept[e];
+      m = ((r == 0 || x > last) && x < m) ? x : m;
+    }
+    m = group_min(m);
+    const u32 t = top[tpos];                                // (tpos <= r <= k < PG_MM_KL)
+    if (t < m) { m = t; ++tpos; }
+    if (b == 0 && mine) {
+      if (r >= 1) {
+        idx[row * k + r - 1] = m == 0xFFFFFFFFu ? -1 : (int)(m & 0x00FFFFFFu);
+        dist[row * k + r - 1] = (unsigned char)(m >> 24);
+      }
+      if (r == k && ((m >> 24) >= cap || cnt > capL)) evictRows[atomicAdd(evictCount, 1u)] = (u32)row;   // (0xFFFFFFFF, no entry, reads 255)
+    }
+    last = m;
+  }
+}
+// behind the merge: too many evicted rows (clusters much larger than the slots of delivered keys, data without neighbours
+// below the cap) - the rectangular launch behind this kernel runs instead and starts from no evicted rows.  gate2: what the
+// launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the probe's word (0 without one)
+__global__ void pg_knn_sym_decide_kernel(const u32 *gate, u32 *gate2, u32 *evictCount, u32 limit) {
+  const u32 g = gate ? *gate : 0u;
+  if (g != 0u) { *gate2 = g; return; }
+  if (*evictCount > limit) { *evictCount = 0u; *gate2 = 0u; }
+  else *gate2 = 3u;
 }
 
 typedef int (*probe_fn)(int, const ProbeParams &, hipStream_t);
@@ -749,6 +1001,9 @@ extern "C" int pg_debug_stats(unsigned long long *out12, int reset) {   // debug
   return 0;
 }
 #endif
+typedef int (*mm_sym_fn)(const NsqParams &, int, hipStream_t);
+static const mm_sym_fn kMmSym[8] = {pg_launch_mm_knn_sym_g1, pg_launch_mm_knn_sym_g2, pg_launch_mm_knn_sym_g3, pg_launch_mm_knn_sym_g4,
+                                    pg_launch_mm_knn_sym_g5, pg_launch_mm_knn_sym_g6, pg_launch_mm_knn_sym_g7, pg_launch_mm_knn_sym_g8};
 static const nsq_fn kMm[8] = {pg_launch_mm_g1, pg_launch_mm_g2, pg_launch_mm_g3, pg_launch_mm_g4,
                               pg_launch_mm_g5, pg_launch_mm_g6, pg_launch_mm_g7, pg_launch_mm_g8};
 // resident workgroups per CU of an MFMA-engine instance (launcher mode codes 0..4), asked once from the runtime
@@ -1123,15 +1378,74 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
       p.mmEvict = (u32 *)workspace + 1;                     // (word 1 of the counter line: zeroed by pass_counter)
       p.mmEvictRows = (u32 *)((char *)workspace + ws_evict_offset(nrows));
     }
+    bool symOn = false;                                      // the symmetric sweep runs in front (below)
     auto finish_evicted = [&]() -> int {
       if (!evict) return 0;
       KnnRowsParams kr;
       kr.rowPlanes = p.rowPlanes; kr.colPlanes = p.colPlanes; kr.rowNpad = p.rowNpad; kr.colNpad = p.colNpad; kr.ncols = p.ncols;
       kr.count = p.mmEvict; kr.rows = p.mmEvictRows; kr.baseRow = row0; kr.k = k;
-      kr.knnIdx = idx_out; kr.knnDist = dist_out; kr.gate = p.gate; kr.gateMask = p.gateMask;
+      kr.knnIdx = idx_out; kr.knnDist = dist_out; kr.gate = p.gate; kr.gateMask = p.gateMask | (symOn ? 1u << 3 : 0u);
       const long long cap = (long long)(cu_count() > 0 ? cu_count() : 256) * 8;   // (one workgroup per row, the rows in turns)
       return pg_launched(kKnnRows[ng - 1](bits, kr, (int)(nrows < cap ? nrows : cap), (hipStream_t)stream), "pg_knn_rows_kernel");
     };
+    // A self graph on the 64-row instance: every unordered pair ONCE (pg_mm.h KS; plan, merge and fallback above).  The
+    // sweep, its merge and a decision run in front of the rectangular launch, which then tests a word of its own: it
+    // runs only where the merge evicted more rows than pg_knn_rows_kernel finishes for less than a rectangular sweep
+    // costs - a sixteenth of them (one row there is one exact sweep of all columns by a workgroup: 12 500 rows x 200 000
+    // columns are 2.5e9 exact distances, ~1.4 ms at the VALU engine's direct-form rate, the price of cfg3's whole step).
+    const SymWs sw = sym_ws(nrows);
+    const bool sym = shortList && evict && bits == PG_BITS_5 && pg_nchunks(l, bits) <= 3 && row_planes == col_planes && row_npad == col_npad &&
+                     row0 == 0 && nrows == ncols && p.filter != 0 && sw.bytes > 0 && (sym_env() == 1 || two);
+    long long symSlots = 0, symPasses = 0;
+    if (sym) {
+      static std::atomic<int> occCache[8];
+      int occS = occCache[ng - 1].load(std::memory_order_relaxed);
+      if (occS == 0) {
+        const int n = kMmSym[ng - 1](NsqParams(), -1, nullptr);
+        occS = n < 1 ? 4 : (n > 4 ? 4 : n);
+        occCache[ng - 1].store(occS, std::memory_order_relaxed);
+      }
+      symSlots = sym_slots(occS);
+      symPasses = sym_plan_host(nrows, symSlots, sym_piece(), sym_piece_min(), nullptr, 0);
+    }
+    // (a plan the workspace was not sized for - it is sized for the most slots the instance can have - is not taken:
+    //  the rectangular launch below stands on its own)
+    if (sym && symPasses <= sw.maxPasses) {
+      char *base = (char *)workspace + ws_sym_offset(nrows);
+      const long long slots = symSlots, npass = symPasses, nbk = (nrows + 63) / 64, nstk = (nrows + PG_MM_ST - 1) / PG_MM_ST;
+      const int piece = sym_piece(), pmin = sym_piece_min();
+      NsqParams s = p;
+      s.nrows = nrows;
+      s.gateMask = 1u << 0;
+      SymArgs sa;
+      sa.plan = (const int4 *)(base + sw.plan); sa.partial = (u32 *)(base + sw.partial);
+      sa.lowCount = (u32 *)(base + sw.lowCount); sa.lowKeys = (u32 *)(base + sw.lowKeys);
+      sa.capL = sym_capl();
+      sa.deliver = !(getenv("PG_KNN_SYM_DELIVER") && atoi(getenv("PG_KNN_SYM_DELIVER")) == 0);   // (0: timing experiments, wrong results)
+      pg_sym_set(&s, sa);
+      s.mmEvict = nullptr; s.mmEvictRows = nullptr; s.mmPieces = 0; s.mmPieceFrom = 0; s.mmPartial = nullptr;
+      s.rowsPerWave = 2 * PG_MM_RB; s.rowsPerPass = 2 * PG_MM_RB; s.mmTailFrom = npass; s.mmTailRows = 2 * PG_MM_RB;
+      s.mmPasses = npass;
+      s.mmGridWaves = ((npass < slots ? npass : slots) + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
+      s.mmPassCounter = p.mmPassCounter + 16;
+      u32 *pieceStart = (u32 *)(base + sw.pieceStart), *gate2 = (u32 *)((char *)workspace + PG_WS_GATES) + 2;
+      if (getenv("PG_DEBUG_PLAN")) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots\n", (long long)nrows, npass, slots);
+      const hipError_t me = hipMemsetAsync(sa.lowCount, 0, 4 * (size_t)nrows, (hipStream_t)stream);
+      if (me != hipSuccess) return pg_launched((int)me, "workspace: hipMemsetAsync");
+      pg_knn_sym_plan_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(nbk, nstk, slots, piece, pmin, (int4 *)(base + sw.plan), pieceStart);
+      if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
+      if (int rc = pg_launched(kMmSym[ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), (hipStream_t)stream), "pg_mm_knn_sym_kernel")) return rc;
+      pg_knn_sym_merge_kernel<<<dim3((unsigned)((nrows + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES))), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
+          sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, nrows, k, idx_out, dist_out, p.knnGuess, p.mmEvict,
+          p.mmEvictRows, s.gate, s.gateMask);
+      if (int rc = pg_launched("pg_knn_sym_merge_kernel")) return rc;
+      const long long limit = getenv("PG_KNN_SYM_EVICT_LIMIT") ? atoll(getenv("PG_KNN_SYM_EVICT_LIMIT")) : nrows / 16;
+      pg_knn_sym_decide_kernel<<<dim3(1), dim3(1), 0, (hipStream_t)stream>>>(p.gate, gate2, p.mmEvict, (u32)(limit < 0 ? 0 : limit));
+      if (int rc = pg_launched("pg_knn_sym_decide_kernel")) return rc;
+      if (!p.gate) p.gateMask = (1u << 0) | (1u << 2);
+      p.gate = gate2;
+      symOn = true;
+    }
     if (mainRows < nrows) {
       const long long rem = nrows - mainRows, nb = (rem + rbm - 1) / rbm;
       const long long simds = (long long)(cu_count() > 0 ? cu_count() : 256) * 4;

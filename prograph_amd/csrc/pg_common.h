@@ -447,6 +447,24 @@ struct NsqParams {
   int *knnIdx;
   unsigned char *knnDist;
 };
+// pg_mm_knn_sym_kernel (pg_mm.h, KS): the symmetric kNN sweep of a self graph.  Pass i is plan[i] = (row block of 64,
+// first super-tile, end super-tile, -) and leaves its rows' lists (k + 1 keys) at partial[(i * 64 + row) * (k + 1)];
+// a pair (row, col), col > row, below the cap is delivered to lowKeys[col * capL + atomicAdd(lowCount[col])] as
+// distance << 24 | row.  deliver = 0: no delivery (timing experiments: wrong results).
+// The launch carries them in fields of NsqParams that only eps launches read (the struct, and with it the argument
+// segment and the code of every other instance, stays what it was): slotIdx, counts, countsLo, slotAux, cap, epsOrdered
+struct SymArgs {
+  const int4 *plan;
+  u32 *partial, *lowCount, *lowKeys;
+  u32 capL;
+  int deliver;
+};
+static inline void pg_sym_set(NsqParams *p, const SymArgs &a) {
+  p->slotIdx = (int *)a.plan; p->counts = a.partial; p->countsLo = a.lowCount; p->slotAux = (int *)a.lowKeys;
+  p->cap = a.capL; p->epsOrdered = a.deliver;
+}
+#define PG_SYM_MAX_PIECES 16   // symmetric kNN: pieces of a row block's columns at most (the merge holds their lists in LDS)
+#define PG_SYM_MAX_CAPL 256    // ... and delivered keys per row at most
 
 // Probe of the data in front of an all-pairs launch (pg_api.hip): exact distances of `nsample` evenly spaced rows of the
 // launch against all columns, counted per sample row: columns nearer than `near` and columns inside the eps interval.
@@ -542,6 +560,7 @@ static inline int pg_launched(const char *where) { return pg_launched((int)hipGe
   int pg_launch_nsq_g##G(int mode, int bits, const NsqParams &p, int grid, hipStream_t s);   \
   int pg_occ_nsq_g##G(int mode, int bits); /* resident workgroups per CU of that instance */ \
   int pg_launch_mm_g##G(int mode, int bits, const NsqParams &p, int grid, hipStream_t s); /* MFMA stage 1 (pg_mm.h) */ \
+  int pg_launch_mm_knn_sym_g##G(const NsqParams &p, int grid, hipStream_t s); /* symmetric kNN sweep, 5 planes, G <= 2 */ \
   int pg_launch_dense_g##G(int bits, const DenseParams &p, hipStream_t s);                    \
   int pg_launch_compact_g##G(int bits, const CompactParams &p, hipStream_t s);                \
   int pg_launch_probe_g##G(int bits, const ProbeParams &p, hipStream_t s);                    \

@@ -89,6 +89,21 @@ int PG_CAT(pg_launch_mm_g, PG_G)(int mode, int bits, const NsqParams &p, int gri
   return bits == 5 ? launch_mm<5, PG_MODE_KNN>(p, grid, s) : launch_mm<8, PG_MODE_KNN>(p, grid, s);
 }
 
+// the symmetric kNN sweep of a self graph: 5 planes, records of up to three chunks (L <= 64); grid < 0 as above
+int PG_CAT(pg_launch_mm_knn_sym_g, PG_G)(const NsqParams &p, int grid, hipStream_t s) {
+  if constexpr (Rec<PG_G, 5>::Q <= 3) {
+    if (grid < 0) {
+      int n = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, pg_mm_knn_sym_kernel<HammingMetric<PG_G, 5>>, PG_WG_THREADS, 0) != hipSuccess) n = 0;
+      return n;
+    }
+    pg_mm_knn_sym_kernel<HammingMetric<PG_G, 5>><<<dim3(grid), dim3(PG_WG_THREADS), 0, s>>>(p);
+    return (int)hipGetLastError();
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
+}
+
 template <int B>
 static int launch_dense(const DenseParams &p, hipStream_t s) {
   if constexpr (!Cols<B>::kBuilt) return (int)hipErrorInvalidValue;

@@ -2,13 +2,19 @@
 (global_load_dwordx4 with a scalar base inside an ASMSTART block) and the s_waitcnt that covers it, no instruction may
 read or write a register the load is still filling (the compiler does not know the load is in flight: a copy or spill
 there would move stale data).  Every path through a kernel is walked (branches followed both ways), so the layout of the basic
-blocks in the file does not matter.  usage: tools/check_ring_asm.py [G ...]   (compiles pg_nsq_inst.hip -S per group count)"""
+blocks in the file does not matter.  usage: tools/check_ring_asm.py [G ...] [--kernel PREFIX]   (compiles pg_nsq_inst.hip -S per
+group count; PREFIX: the kernels whose mangled name starts with it, default _Z12pg_mm_kernel)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "prograph_amd", "csrc")
 FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -Wno-pass-failed -Wno-unused-variable -mllvm -amdgpu-mfma-vgpr-form=1".split()
-extra = [a for a in sys.argv[1:] if a.startswith("-D")]
-gs = [int(a) for a in sys.argv[1:] if a.isdigit()] or list(range(1, 9))
+argv = sys.argv[1:]
+PREFIX = "_Z12pg_mm_kernel"
+if "--kernel" in argv:
+    PREFIX = argv[argv.index("--kernel") + 1]
+    del argv[argv.index("--kernel"):argv.index("--kernel") + 2]
+extra = [a for a in argv if a.startswith("-D")]
+gs = [int(a) for a in argv if a.isdigit()] or list(range(1, 9))
 
 def regs(tok):
     m = re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
@@ -73,7 +79,7 @@ for g in gs:
     kernel, instrs, labels, in_asm, nloads, nk = None, [], {}, False, 0, 0
     for ln, line in enumerate(open(out), 1):
         t = line.strip()
-        if t.startswith("_Z12pg_mm_kernel") and ":" in t and not t.endswith('"'):
+        if t.startswith(PREFIX) and ":" in t and not t.endswith('"'):
             kernel, instrs, labels, in_asm = t.split(":")[0], [], {}, False
             nk += 1
             continue
@@ -93,6 +99,6 @@ for g in gs:
             b, n = check_kernel(kernel, instrs, labels, g)
             bad += b; nloads += n
             kernel = None
-    print(f"G={g}: {nk} pg_mm_kernel instances, {nloads} inline fragment loads checked")
+    print(f"G={g}: {nk} {PREFIX[PREFIX.index('pg_'):] if 'pg_' in PREFIX else PREFIX} instances, {nloads} inline fragment loads checked")
 print("RULE violations:", bad)
 sys.exit(1 if bad else 0)

@@ -5,19 +5,20 @@ candidates, the test for the end of the stretch).  Counted per step: MFMAs, VALU
 lane-spill instructions (v_readlane / v_writelane), scratch accesses, and the chain heads - MFMAs that do not accumulate
 onto their own result - with whether their addend is an inline constant (a register there means the compiler keeps a
 splat alive: 16 VGPRs refilled in every iteration).
-usage: tools/check_scan_loop.py [G ...] [--src DIR] [--json]     (compiles DIR/pg_nsq_inst.hip -S per group count;
-DIR defaults to prograph_amd/csrc).  Exit status 1 if a step holds spill or scratch code or a head with a register addend."""
+usage: tools/check_scan_loop.py [G ...] [--src DIR] [--json] [--kernel PREFIX]     (compiles DIR/pg_nsq_inst.hip -S per group
+count; DIR defaults to prograph_amd/csrc; PREFIX: the kernels whose mangled name starts with it, default _Z12pg_mm_kernel -
+_Z20pg_mm_knn_sym_kernel is the symmetric kNN sweep).  Exit status 1 if a step holds spill or scratch code or a head with a register addend."""
 import json, os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = "-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wno-unused-function -Wno-pass-failed -Wno-unused-variable -mllvm -amdgpu-mfma-vgpr-form=1".split()
 
 
-def instances(path):
-    """{kernel: [(text, in_asm, is_label)]} for every pg_mm_kernel of an assembly file"""
+def instances(path, prefix="_Z12pg_mm_kernel"):
+    """{kernel: [(text, in_asm, is_label)]} for every kernel of an assembly file whose name starts with prefix"""
     out, kernel, in_asm = {}, None, False
     for line in open(path):
         t = line.strip()
-        if t.startswith("_Z12pg_mm_kernel") and ":" in t and not t.endswith('"'):
+        if t.startswith(prefix) and ":" in t and not t.endswith('"'):
             kernel, in_asm = t.split(":")[0], False
             out[kernel] = []
             continue
@@ -83,6 +84,10 @@ def main():
     if "--src" in args:
         src = os.path.abspath(args[args.index("--src") + 1])
         del args[args.index("--src"):args.index("--src") + 2]
+    prefix = "_Z12pg_mm_kernel"
+    if "--kernel" in args:
+        prefix = args[args.index("--kernel") + 1]
+        del args[args.index("--kernel"):args.index("--kernel") + 2]
     as_json = "--json" in args
     gs = [int(a) for a in args if a.isdigit()] or list(range(1, 9))
     bad, report = 0, {}
@@ -91,7 +96,7 @@ def main():
         out = os.path.join(tmp.name, f"scan_g{g}.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + [f"-DPG_G={g}", "-S", "--cuda-device-only", "pg_nsq_inst.hip", "-o", out],
                               cwd=src, stderr=subprocess.DEVNULL)
-        for name, instrs in instances(out).items():
+        for name, instrs in instances(out, prefix).items():
             cs = [census(s) for s in steps(instrs)]
             if not cs:
                 continue
