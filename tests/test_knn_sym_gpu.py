@@ -52,21 +52,26 @@ def case(n, kind):
     return _cache[(n, kind)]
 
 
-def check(monkeypatch, n, kind, env, ks=KS):
+def check(monkeypatch, capfd, n, kind, env, ks=KS):
+    """... and the planner's debug line says which launch ran: the forced call is the symmetric one, PG_KNN_SYM=0 is not"""
     from prograph_amd import _native as nat
     tok, ref = case(n, kind)
     monkeypatch.setenv("PG_ENGINE", "mfma")
+    monkeypatch.setenv("PG_DEBUG_PLAN", "1")
     monkeypatch.setenv("PG_MM_R", "2")
     planes = nat.pack(torch.from_numpy(tok), bits=5)
     for k in ks:
         monkeypatch.setenv("PG_KNN_SYM", "0")
+        capfd.readouterr()
         ridx, rdist = [x.cpu().numpy() for x in nat.knn_graph(planes, planes, k)]
+        assert "[pg plan sym]" not in capfd.readouterr().err, (n, kind, k, "PG_KNN_SYM=0 took the symmetric path")
         monkeypatch.setenv("PG_KNN_SYM", "1")
         for key, value in env.items():
             monkeypatch.setenv(key, value)
         idx, dist = [x.cpu().numpy() for x in nat.knn_graph(planes, planes, k)]
         for key in env:
             monkeypatch.delenv(key)
+        assert f"[pg plan sym] rows={n}:" in capfd.readouterr().err, (n, kind, k, env, "the forced call declined the symmetric path")
         assert np.array_equal(idx, ref[k][0]) and np.array_equal(dist, ref[k][1]), (n, kind, k, env, "oracle")
         assert idx.tobytes() == ridx.tobytes() and dist.tobytes() == rdist.tobytes(), (n, kind, k, env, "rectangular path")
 
@@ -74,38 +79,38 @@ def check(monkeypatch, n, kind, env, ks=KS):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("n", NS)
-def test_symmetric_sweep_against_oracle_and_rectangular_path(monkeypatch, n, kind):
+def test_symmetric_sweep_against_oracle_and_rectangular_path(monkeypatch, capfd, n, kind):
     """the eviction limit out of reach: the gated rectangular launch never runs, what is compared is the merge's own
     output (and pg_knn_rows_kernel's for the rows the merge evicts)"""
-    check(monkeypatch, n, kind, {"PG_KNN_SYM_EVICT_LIMIT": "100000000"})
+    check(monkeypatch, capfd, n, kind, {"PG_KNN_SYM_EVICT_LIMIT": "100000000"})
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["strided64", "strided12"])
 @pytest.mark.parametrize("n", NS)
-def test_default_eviction_limit(monkeypatch, n, kind):
+def test_default_eviction_limit(monkeypatch, capfd, n, kind):
     """N / 16 evicted rows at most: clusters of 12 lose the cap in every row - the rectangular fallback; clusters of 64 stay"""
-    check(monkeypatch, n, kind, {}, ks=(16,))
+    check(monkeypatch, capfd, n, kind, {}, ks=(16,))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", ["strided64", "contiguous"])
 @pytest.mark.parametrize("n", [1000, 3000])
-def test_slots_of_eight_delivered_keys_overflow(monkeypatch, n, kind):
+def test_slots_of_eight_delivered_keys_overflow(monkeypatch, capfd, n, kind):
     """capL = 8 against clusters of 64: most rows receive more keys than their slot holds.  First the evicted rows are
     finished one by one (limit out of reach), then the limit of 0 sends the launch to the gated rectangular sweep."""
-    check(monkeypatch, n, kind, {"PG_KNN_SYM_CAPL": "8", "PG_KNN_SYM_EVICT_LIMIT": "100000000"})
-    check(monkeypatch, n, kind, {"PG_KNN_SYM_CAPL": "8", "PG_KNN_SYM_EVICT_LIMIT": "0"})
+    check(monkeypatch, capfd, n, kind, {"PG_KNN_SYM_CAPL": "8", "PG_KNN_SYM_EVICT_LIMIT": "100000000"})
+    check(monkeypatch, capfd, n, kind, {"PG_KNN_SYM_CAPL": "8", "PG_KNN_SYM_EVICT_LIMIT": "0"})
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("piece", ["12", "3"])
 @pytest.mark.parametrize("kind", ["strided256", "contiguous"])
-def test_blocks_cut_into_two_and_seven_pieces(monkeypatch, kind, piece):
+def test_blocks_cut_into_two_and_seven_pieces(monkeypatch, capfd, kind, piece):
     """N = 3000: 24 super-tiles.  Pieces of 12 cut the first blocks' columns in 2, pieces of 3 the blocks with 21..23
     super-tiles in 7 (pg_knn_sym_plan; checked on the CPU in test_knn_sym_cpu.py)"""
-    check(monkeypatch, 3000, kind, {"PG_KNN_SYM_PIECE": piece})
-    check(monkeypatch, 1000, kind, {"PG_KNN_SYM_PIECE": "4"}, ks=(16,))
+    check(monkeypatch, capfd, 3000, kind, {"PG_KNN_SYM_PIECE": piece})
+    check(monkeypatch, capfd, 1000, kind, {"PG_KNN_SYM_PIECE": "4"}, ks=(16,))
 
 
 @pytest.mark.gpu
