@@ -68,9 +68,10 @@ int64_t pg_planes_bytes(int64_t n, int l, int bits) { return ((int64_t)pg_nchunk
 // launch-private device state of an all-pairs call, sized by the row count:
 //   [0, 64)      pass counters of the engine's persistent waves (words 0 and 8: a call's main launch and its gated 32-row
 //                alternative) and, word 1, the number of evicted rows                        - zeroed by the call
-//   [64, 576)    word 16 (byte 64): the pass counter of the symmetric kNN sweep; the rest reserved - zeroed with the counters
+//   [64, 576)    word 16 (byte 64): the pass counter of the symmetric kNN sweep; word 17: the ticket of its merge's
+//                workgroups (the last one decides); the rest reserved - zeroed with the counters
 //   [576, 640)   decision words (gates): [0], [1] the probe's (pg_decide_kernel); [2] the word the launches BEHIND a
-//                symmetric kNN sweep test (pg_knn_sym_decide_kernel: the probe's gate[0] - 0 without a probe - or 3 =
+//                symmetric kNN sweep test (pg_knn_sym_merge_kernel's last workgroup: the probe's gate[0] - 0 without a probe - or 3 =
 //                the sweep's results stand, only pg_knn_rows_kernel still runs)
 //   [640, ...)   the probe's counts (8 * PG_PROBE_ROWS * PG_PROBE_WAVES bytes)
 //   from PG_WS_PARTIAL on, launches of more than PG_SPLIT_MIN_ROWS rows: the lists of the column pieces - at most
@@ -156,12 +157,17 @@ static long long sym_plan_host(long long n, long long slots, int piece, int pmin
   }
   return at;
 }
-// one workgroup: thread t takes a contiguous run of blocks - their piece counts, a scan over the threads, then the
-// entries and pieceStart[b] = the first pass of block b (pieceStart[nb] = passes in all)
+// workgroup 0: thread t takes a contiguous run of blocks - their piece counts, a scan over the threads, then the
+// entries and pieceStart[b] = the first pass of block b (pieceStart[nb] = passes in all).  The workgroups behind it zero
+// the rows' counts of delivered keys meanwhile (`zero4` uint4 of lowCount: the launch's memset, folded in)
 __global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(long long nb, long long nst, long long slots, int piece, int pmin,
-                                                                int4 *plan, u32 *pieceStart) {
+                                                                int4 *plan, u32 *pieceStart, uint4 *zero, long long zero4) {
   __shared__ u32 sums[1024];
   const int t = threadIdx.x;
+  if (blockIdx.x > 0) {
+    for (long long i = (long long)(blockIdx.x - 1) * 1024 + t; i < zero4; i += (long long)(gridDim.x - 1) * 1024) zero[i] = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
   const long long per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
   u32 mine = 0;
   for (long long b = b0; b < b1; ++b) mine += (u32)sym_block_pieces(b, nst, slots, piece, pmin);
@@ -187,7 +193,8 @@ __global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(long long nb, lon
 }
 // knobs of the symmetric kNN sweep: PG_KNN_SYM = 0 off / 1 forced wherever the MFMA engine runs the short-list kNN;
 // PG_KNN_SYM_CAPL delivered keys per row (8..256); PG_KNN_SYM_PIECE fixed piece length in super-tiles (default: guided);
-// PG_KNN_SYM_PIECE_MIN the guided rule's shortest piece; PG_KNN_SYM_OCC waves per SIMD the plan counts on
+// PG_KNN_SYM_PIECE_MIN the guided rule's shortest piece; PG_KNN_SYM_OCC waves per SIMD the plan counts on;
+// PG_KNN_SYM_MERGE_WGS workgroups of the merge at most (default: eight a CU)
 static int sym_env() { return getenv("PG_KNN_SYM") ? atoi(getenv("PG_KNN_SYM")) : -1; }
 static u32 sym_capl() {
   const int v = getenv("PG_KNN_SYM_CAPL") ? atoi(getenv("PG_KNN_SYM_CAPL")) : PG_SYM_MAX_CAPL;
@@ -573,7 +580,7 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 //   gate[1]  whole-square eps graph: 0 = every unordered pair once (symmetric slots), 1 = rectangular VALU sweep.
 //            Dense graphs (more than 4 % of all pairs match) pay more for the symmetric path's atomics and
 //            unsorted back parts than it saves (one cluster, eps <= 2: 39.6 vs 29.4 ms)
-//   gate[2]  (not the probe's: pg_knn_sym_decide_kernel writes it behind the merge of a symmetric kNN sweep) what the
+//   gate[2]  (not the probe's: the merge of a symmetric kNN sweep, pg_knn_sym_merge_kernel, writes it) what the
 //            rectangular kNN launches and pg_knn_rows_kernel of that call test instead of gate[0]: gate[0]'s value where
 //            the probe chose another engine or instance, 0 where the sweep evicted more rows than its limit (the
 //            rectangular launch runs), 3 where its results stand (pg_knn_rows_kernel alone runs, for its evicted rows)
@@ -664,107 +671,137 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
   }
 }
 
-// kNN of the symmetric sweep (pg_mm_knn_sym_kernel): a row's lists of k + 1 keys - one per piece of its block, passes
-// pieceStart[block] .. pieceStart[block + 1] - and its min(lowCount, capL) delivered keys -> its k + 1 smallest keys in
-// (distance << 24 | index) order, the order of the rectangular sweep; ranks 1..k written out.  Sixteen lanes per row, four
-// rows per wave.  Three steps: (A) the pieces' sorted lists, lane b at the head of list b: k + 1 rounds of "smallest head
-// wins and advances" give the row's own k + 1 smallest keys and with the last of them a bound T on its final threshold;
-// (B) the delivered keys are read once and only those below T are kept, packed, in LDS - a row receives about as many keys
-// as it has cluster mates below it, a handful of them can still enter its list; (C) k + 1 rounds over the own keys (a
-// pointer) and the kept ones ("the smallest above the last one": keys are unique; 0xFFFFFFFF = no entry).
+// kNN of the symmetric sweep (pg_mm_knn_sym_kernel): a row's records - one per piece of its block, passes
+// pieceStart[block] .. pieceStart[block + 1], PG_MM_KL keys each with the sorted list of k + 1 keys at the end - and its
+// min(lowCount, capL) delivered keys -> its k + 1 smallest keys in (distance << 24 | index) order, the order of the
+// rectangular sweep; ranks 1..k written out.  Sixteen lanes per row, four rows per wave.
+// Two memory levels: pieceStart, lowCount and the first 64 keys of the slot (inside the workspace whatever the count is;
+// masked to 0xFFFFFFFF from min(lowCount, capL) on) are asked for at once, then lane b's record b (five 16-byte loads)
+// and the rest of the slot, lane b entries b, b + 16, ... - the delivered keys stay in registers.
+// Selection: every lane sorts its sixteen delivered keys once (a network of 63 compare-exchanges in registers), then k + 1
+// rounds of "smallest head wins and advances" over the sixteen lanes' two heads - list b's, a pointer into the staged
+// record, and the lane's delivered keys', which move down one register when they win: one reduction a round, nothing is
+// scanned twice (keys are unique; equal heads advance together; 0xFFFFFFFF = no entry).  LDS holds the records only,
+// 20 KB a workgroup.
 // Every list is complete below the cap only: a row whose (k+1)-th distance is not below it, or whose slot of delivered keys
 // overflowed, joins the evicted rows (pg_knn_rows_kernel finishes them).
+// The decision behind the merge is taken by the workgroup that finishes last (a ticket: `ticket`, a zeroed word of the
+// counter block, left at 0 again): too many evicted rows (clusters much larger than the slots of delivered keys, data
+// without neighbours below the cap) - the rectangular launch behind this kernel runs instead and starts from no evicted
+// rows.  gate2: what the launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the
+// probe's word (0 without one).  Workgroups that have no rows, or leave at the gate, take their ticket all the same.
+// lane i of a row of sixteen reads lane (i + N) & 15
+#define PG_SYM_ROR(x, N) ((u32)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (N), 0xF, 0xF, false))
+#define PG_SYM_CE(a, b) { const u32 x_ = a, y_ = b; a = x_ < y_ ? x_ : y_; b = x_ < y_ ? y_ : x_; }
 __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
                                                                          const u32 *lowKeys, u32 capL, long long nrows, int k, int *idx,
                                                                          unsigned char *dist, u32 cap, u32 *evictCount, u32 *evictRows,
-                                                                         const u32 *gate, u32 gateMask) {
-  constexpr int kOwn = PG_SYM_MAX_PIECES * PG_MM_KL, kKeys = PG_MM_KL + kOwn + PG_SYM_MAX_CAPL;
-  __shared__ u32 keys[PG_WG_WAVES][4][kKeys];
-  if (gate && !((gateMask >> __builtin_nontemporal_load(gate)) & 1u)) return;
+                                                                         const u32 *gate, u32 gateMask, u32 *gate2, u32 *ticket, u32 limit) {
+  constexpr int kRec = PG_MM_KL, kOwn = PG_SYM_MAX_PIECES * kRec, kLane = PG_SYM_MAX_CAPL / 16;
+  static_assert(kRec == 20 && kLane == 16, "records of whole uint4; sixteen delivered keys a lane");
+  __shared__ __attribute__((aligned(16))) u32 keys[PG_WG_WAVES][4][kOwn];
+  const u32 gv = gate ? __builtin_nontemporal_load(gate) : 0u;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, b = lane & 15;
-  const long long row0 = ((long long)blockIdx.x * PG_WG_WAVES + wv) * 4;
-  if (row0 >= nrows) return;                               // (whole wave; no workgroup barrier below)
-  const int k1 = k + 1;
-  const long long blk = row0 >> 6;                         // (four consecutive rows from a multiple of four: one block)
-  const u32 s0 = pieceStart[blk];
-  u32 np = pieceStart[blk + 1] - s0;
-  np = np > PG_SYM_MAX_PIECES ? PG_SYM_MAX_PIECES : np;
-  const long long row = row0 + g;
-  const bool mine = row < nrows;
-  const u32 cnt = mine ? lowCount[row] : 0u;
-  const int nl = (int)(cnt < capL ? cnt : capL);
-  u32 *top = &keys[wv][g][0], *own = top + PG_MM_KL, *kept = own + kOwn;
-  auto sync = []() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-  auto group_min = [](u32 m) {
-    for (int o = 8; o > 0; o >>= 1) {
-      const u32 x = (u32)__shfl_xor((int)m, o, 16);
-      m = x < m ? x : m;
+  const bool open = !gate || ((gateMask >> gv) & 1u);
+  // (whole waves; the grid is a few workgroups a CU, every wave takes four rows in turns: few tickets on one word)
+  for (long long row0 = ((long long)blockIdx.x * PG_WG_WAVES + wv) * 4; open && row0 < nrows; row0 += (long long)gridDim.x * PG_WG_WAVES * 4) {
+    const int k1 = k + 1, off = kRec - k1;
+    const long long blk = row0 >> 6;                         // (four consecutive rows from a multiple of four: one block)
+    const long long row = row0 + g;
+    const bool mine = row < nrows;
+    const long long rowIn = mine ? row : row0;               // (idle groups read the wave's first row: in bounds, unused)
+    const u32 *low = lowKeys + rowIn * (long long)capL + b;  // (lane b: entries b, b + 16, ...)
+    // The loads of level 1 and the records are unconditional, from addresses inside the workspace - a lane without a piece
+    // reads record 0 of its block - and masked afterwards; the rest of the slot is loaded up to the count.  The LDS
+    // stores stand behind the last load, so no load waits for another.
+    // level 1: the block's passes, the row's count and the head of its slot
+    const u32 s0 = pieceStart[blk], s1 = pieceStart[blk + 1];
+    u32 cnt = lowCount[rowIn];
+    // (the sixteen delivered keys of a lane are sixteen names, not an array: every one stays in its register)
+    u32 d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15;
+#define PG_SYM_EARLY(j, d) d = (u32)(16 * j + b) < capL ? low[16 * j] : 0xFFFFFFFFu;
+    if (capL >= 64) { d0 = low[0]; d1 = low[16]; d2 = low[32]; d3 = low[48]; }   // (the production slot: no test)
+    else { PG_SYM_EARLY(0, d0) PG_SYM_EARLY(1, d1) PG_SYM_EARLY(2, d2) PG_SYM_EARLY(3, d3) }
+    __builtin_amdgcn_sched_barrier(0);
+    cnt = mine ? cnt : 0u;
+    u32 np = s1 - s0;
+    np = np > PG_SYM_MAX_PIECES ? PG_SYM_MAX_PIECES : np;
+    const int nl = (int)(cnt < capL ? cnt : capL);
+    u32 *own = &keys[wv][g][0];
+    // level 2: record b and the rest of the slot
+    const bool has = mine && b < (int)np;
+    const uint4 *rec = reinterpret_cast<const uint4 *>(partial) + (((long long)s0 + (b < (int)np ? b : 0)) * 64 + (row & 63)) * (kRec / 4);
+    const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
+#define PG_SYM_LATE(j, d) d = 16 * j + b < nl ? low[16 * j] : 0xFFFFFFFFu;
+    PG_SYM_LATE(4, d4) PG_SYM_LATE(5, d5) PG_SYM_LATE(6, d6) PG_SYM_LATE(7, d7) PG_SYM_LATE(8, d8) PG_SYM_LATE(9, d9)
+    PG_SYM_LATE(10, d10) PG_SYM_LATE(11, d11) PG_SYM_LATE(12, d12) PG_SYM_LATE(13, d13) PG_SYM_LATE(14, d14) PG_SYM_LATE(15, d15)
+    __builtin_amdgcn_sched_barrier(0);
+    {
+      uint4 *st = reinterpret_cast<uint4 *>(own + b * kRec);  // (a lane without a piece stages what it read: never its head)
+      st[0] = r0; st[1] = r1; st[2] = r2; st[3] = r3; st[4] = r4;
     }
-    return m;
-  };
-  // (A) the four rows at once: lane b stages list b and merges from its head
-  const bool has = mine && b < (int)np;
-  if (has) {
-    const u32 *src = partial + (((long long)s0 + b) * 64 + (row & 63)) * k1;
-    for (int j = 0; j < k1; ++j) own[b * k1 + j] = src[j];
-  }
-  sync();
-  int pos = 0;
-  u32 head = has ? own[b * k1] : 0xFFFFFFFFu, T = 0xFFFFFFFFu;
-  for (int r = 0; r <= k; ++r) {
-    T = group_min(head);
-    if (b == 0) top[r] = T;
-    if (has && head == T && T != 0xFFFFFFFFu) {            // the winner (unique key) moves on in its list
-      ++pos;
-      head = pos < k1 ? own[b * k1 + pos] : 0xFFFFFFFFu;
+#define PG_SYM_MASK(j, d) d = 16 * j + b < nl ? d : 0xFFFFFFFFu;
+    PG_SYM_MASK(0, d0) PG_SYM_MASK(1, d1) PG_SYM_MASK(2, d2) PG_SYM_MASK(3, d3)
+    // the lane's delivered keys in ascending order (no entries last: Batcher's odd-even merge sort of sixteen); rows of
+    // up to sixteen keys hold one a lane, as it stands
+    if (__builtin_amdgcn_ballot_w64(nl > 16) != 0) {
+      PG_SYM_CE(d0, d1) PG_SYM_CE(d2, d3) PG_SYM_CE(d4, d5) PG_SYM_CE(d6, d7) PG_SYM_CE(d8, d9) PG_SYM_CE(d10, d11) PG_SYM_CE(d12, d13) PG_SYM_CE(d14, d15)
+      PG_SYM_CE(d0, d2) PG_SYM_CE(d1, d3) PG_SYM_CE(d4, d6) PG_SYM_CE(d5, d7) PG_SYM_CE(d8, d10) PG_SYM_CE(d9, d11) PG_SYM_CE(d12, d14) PG_SYM_CE(d13, d15)
+      PG_SYM_CE(d1, d2) PG_SYM_CE(d5, d6) PG_SYM_CE(d9, d10) PG_SYM_CE(d13, d14) PG_SYM_CE(d0, d4) PG_SYM_CE(d1, d5) PG_SYM_CE(d2, d6) PG_SYM_CE(d3, d7)
+      PG_SYM_CE(d8, d12) PG_SYM_CE(d9, d13) PG_SYM_CE(d10, d14) PG_SYM_CE(d11, d15) PG_SYM_CE(d2, d4) PG_SYM_CE(d3, d5) PG_SYM_CE(d10, d12) PG_SYM_CE(d11, d13)
+      PG_SYM_CE(d1, d2) PG_SYM_CE(d3, d4) PG_SYM_CE(d5, d6) PG_SYM_CE(d9, d10) PG_SYM_CE(d11, d12) PG_SYM_CE(d13, d14) PG_SYM_CE(d0, d8) PG_SYM_CE(d1, d9)
+      PG_SYM_CE(d2, d10) PG_SYM_CE(d3, d11) PG_SYM_CE(d4, d12) PG_SYM_CE(d5, d13) PG_SYM_CE(d6, d14) PG_SYM_CE(d7, d15) PG_SYM_CE(d4, d8) PG_SYM_CE(d5, d9)
+      PG_SYM_CE(d6, d10) PG_SYM_CE(d7, d11) PG_SYM_CE(d2, d4) PG_SYM_CE(d3, d5) PG_SYM_CE(d6, d8) PG_SYM_CE(d7, d9) PG_SYM_CE(d10, d12) PG_SYM_CE(d11, d13)
+      PG_SYM_CE(d1, d2) PG_SYM_CE(d3, d4) PG_SYM_CE(d5, d6) PG_SYM_CE(d7, d8) PG_SYM_CE(d9, d10) PG_SYM_CE(d11, d12) PG_SYM_CE(d13, d14)
     }
-  }
-  // (B) the delivered keys below the own (k+1)-th key, packed (ranks among the group's sixteen lanes)
-  const u32 *low = lowKeys + (mine ? row : 0) * (long long)capL;
-  int nk = 0;
-  for (int e0 = 0; e0 < nl; e0 += 16) {
-    const int e = e0 + b;
-    const u32 x = e < nl ? low[e] : 0xFFFFFFFFu;
-    const bool keep = x < T;
-    const u32 m16 = (u32)(__builtin_amdgcn_ballot_w64(keep) >> (16 * g)) & 0xFFFFu;
-    if (keep) kept[nk + __builtin_popcount(m16 & ((1u << b) - 1u))] = x;
-    nk += __builtin_popcount(m16);
-  }
-  sync();
-  // (C) own keys by pointer, kept keys by rounds
-  int tpos = 0;
-  u32 last = 0;
-  for (int r = 0; r <= k; ++r) {
-    u32 m = 0xFFFFFFFFu;
-    for (int e = b; e < nk; e += 16) {
-      const u32 x = kept[e];
-      m = ((r == 0 || x > last) && x < m) ? x : m;
-    }
-    m = group_min(m);
-    const u32 t = top[tpos];                                // (tpos <= r <= k < PG_MM_KL)
-    if (t < m) { m = t; ++tpos; }
-    if (b == 0 && mine) {
-      if (r >= 1) {
-        idx[row * k + r - 1] = m == 0xFFFFFFFFu ? -1 : (int)(m & 0x00FFFFFFu);
-        dist[row * k + r - 1] = (unsigned char)(m >> 24);
+    // heads of the own list (a pointer: the lane reads what it staged itself) and of the delivered keys (d0); lane r - 1
+    // keeps rank r (ranks from 17 on: lane 0 writes)
+    int pos = 0;
+    u32 head = has ? own[b * kRec + off] : 0xFFFFFFFFu, res = 0xFFFFFFFFu;
+    for (int r = 0; r <= k; ++r) {
+      u32 m = head < d0 ? head : d0, x;
+      x = PG_SYM_ROR(m, 8); m = x < m ? x : m;
+      x = PG_SYM_ROR(m, 4); m = x < m ? x : m;
+      x = PG_SYM_ROR(m, 2); m = x < m ? x : m;
+      x = PG_SYM_ROR(m, 1); m = x < m ? x : m;
+      const bool any = m != 0xFFFFFFFFu;
+      if (any && head == m) {                                // the winner moves on in its list
+        ++pos;
+        head = pos < k1 ? own[b * kRec + off + pos] : 0xFFFFFFFFu;
       }
-      if (r == k && ((m >> 24) >= cap || cnt > capL)) evictRows[atomicAdd(evictCount, 1u)] = (u32)row;   // (0xFFFFFFFF, no entry, reads 255)
+      const bool dwin = any && d0 == m;                      // ... or its delivered keys move down a register
+      d0 = dwin ? d1 : d0; d1 = dwin ? d2 : d1; d2 = dwin ? d3 : d2; d3 = dwin ? d4 : d3;
+      d4 = dwin ? d5 : d4; d5 = dwin ? d6 : d5; d6 = dwin ? d7 : d6; d7 = dwin ? d8 : d7;
+      d8 = dwin ? d9 : d8; d9 = dwin ? d10 : d9; d10 = dwin ? d11 : d10; d11 = dwin ? d12 : d11;
+      d12 = dwin ? d13 : d12; d13 = dwin ? d14 : d13; d14 = dwin ? d15 : d14; d15 = dwin ? 0xFFFFFFFFu : d15;
+      if (b == r - 1) res = m;
+      if (b == 0 && mine) {
+        if (r > 16) {
+          idx[row * k + r - 1] = m == 0xFFFFFFFFu ? -1 : (int)(m & 0x00FFFFFFu);
+          dist[row * k + r - 1] = (unsigned char)(m >> 24);
+        }
+        if (r == k && ((m >> 24) >= cap || cnt > capL)) evictRows[atomicAdd(evictCount, 1u)] = (u32)row;   // (0xFFFFFFFF, no entry, reads 255)
+      }
     }
-    last = m;
+#undef PG_SYM_EARLY
+#undef PG_SYM_LATE
+#undef PG_SYM_MASK
+    if (mine && b < k) {
+      idx[row * k + b] = res == 0xFFFFFFFFu ? -1 : (int)(res & 0x00FFFFFFu);
+      dist[row * k + b] = (unsigned char)(res >> 24);
+    }
   }
-}
-// behind the merge: too many evicted rows (clusters much larger than the slots of delivered keys, data without neighbours
-// below the cap) - the rectangular launch behind this kernel runs instead and starts from no evicted rows.  gate2: what the
-// launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the probe's word (0 without one)
-__global__ void pg_knn_sym_decide_kernel(const u32 *gate, u32 *gate2, u32 *evictCount, u32 limit) {
-  const u32 g = gate ? *gate : 0u;
-  if (g != 0u) { *gate2 = g; return; }
-  if (*evictCount > limit) { *evictCount = 0u; *gate2 = 0u; }
-  else *gate2 = 3u;
+  __syncthreads();                                           // (every wave of the workgroup: its rows' evictions are counted)
+  // (the ticket releases what the workgroup counted - the barrier orders its other waves' atomics before thread 0 -
+  //  and the workgroup that draws the last one acquires them all; a few thousand tickets, so the fences do not show)
+  if (threadIdx.x == 0) {
+    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+      *ticket = 0u;
+      if (gv != 0u) *gate2 = gv;
+      else if (__hip_atomic_load(evictCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > limit) { *evictCount = 0u; *gate2 = 0u; }
+      else *gate2 = 3u;
+    }
+  }
 }
 
 typedef int (*probe_fn)(int, const ProbeParams &, hipStream_t);
@@ -1430,18 +1467,21 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
       s.mmPassCounter = p.mmPassCounter + 16;
       u32 *pieceStart = (u32 *)(base + sw.pieceStart), *gate2 = (u32 *)((char *)workspace + PG_WS_GATES) + 2;
       if (getenv("PG_DEBUG_PLAN")) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots\n", (long long)nrows, npass, slots);
-      const hipError_t me = hipMemsetAsync(sa.lowCount, 0, 4 * (size_t)nrows, (hipStream_t)stream);
-      if (me != hipSuccess) return pg_launched((int)me, "workspace: hipMemsetAsync");
-      pg_knn_sym_plan_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(nbk, nstk, slots, piece, pmin, (int4 *)(base + sw.plan), pieceStart);
+      // (lowCount: 256-byte aligned and padded to it, so whole uint4 stay inside)
+      const long long zero4 = (nrows + 3) / 4, zeroWgs = (zero4 + 1023) / 1024 < 64 ? (zero4 + 1023) / 1024 : 64;
+      pg_knn_sym_plan_kernel<<<dim3((unsigned)(1 + zeroWgs)), dim3(1024), 0, (hipStream_t)stream>>>(nbk, nstk, slots, piece, pmin, (int4 *)(base + sw.plan),
+                                                                                              pieceStart, (uint4 *)sa.lowCount, zero4);
       if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
       if (int rc = pg_launched(kMmSym[ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), (hipStream_t)stream), "pg_mm_knn_sym_kernel")) return rc;
-      pg_knn_sym_merge_kernel<<<dim3((unsigned)((nrows + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES))), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
-          sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, nrows, k, idx_out, dist_out, p.knnGuess, p.mmEvict,
-          p.mmEvictRows, s.gate, s.gateMask);
-      if (int rc = pg_launched("pg_knn_sym_merge_kernel")) return rc;
       const long long limit = getenv("PG_KNN_SYM_EVICT_LIMIT") ? atoll(getenv("PG_KNN_SYM_EVICT_LIMIT")) : nrows / 16;
-      pg_knn_sym_decide_kernel<<<dim3(1), dim3(1), 0, (hipStream_t)stream>>>(p.gate, gate2, p.mmEvict, (u32)(limit < 0 ? 0 : limit));
-      if (int rc = pg_launched("pg_knn_sym_decide_kernel")) return rc;
+      // (PG_KNN_SYM_MERGE_WGS: tests - a few workgroups take the rows of a small graph in turns)
+      const long long mergeWgs = (nrows + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES);
+      long long mergeCap = (long long)(cu_count() > 0 ? cu_count() : 256) * 8;
+      if (const char *e = getenv("PG_KNN_SYM_MERGE_WGS")) { if (atoll(e) >= 1 && atoll(e) < mergeCap) mergeCap = atoll(e); }
+      pg_knn_sym_merge_kernel<<<dim3((unsigned)(mergeWgs < mergeCap ? mergeWgs : mergeCap)), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
+          sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, nrows, k, idx_out, dist_out, p.knnGuess, p.mmEvict,
+          p.mmEvictRows, s.gate, s.gateMask, gate2, p.mmPassCounter + 17, (u32)(limit < 0 ? 0 : limit));
+      if (int rc = pg_launched("pg_knn_sym_merge_kernel")) return rc;
       if (!p.gate) p.gateMask = (1u << 0) | (1u << 2);
       p.gate = gate2;
       symOn = true;

@@ -448,7 +448,8 @@ struct NsqParams {
   unsigned char *knnDist;
 };
 // pg_mm_knn_sym_kernel (pg_mm.h, KS): the symmetric kNN sweep of a self graph.  Pass i is plan[i] = (row block of 64,
-// first super-tile, end super-tile, -) and leaves its rows' lists (k + 1 keys) at partial[(i * 64 + row) * (k + 1)];
+// first super-tile, end super-tile, -) and leaves its rows' records (PG_MM_KL keys, 16-byte aligned; the sorted list of
+// k + 1 keys is their end) at partial[(i * 64 + row) * PG_MM_KL];
 // a pair (row, col), col > row, below the cap is delivered to lowKeys[col * capL + atomicAdd(lowCount[col])] as
 // distance << 24 | row.  deliver = 0: no delivery (timing experiments: wrong results).
 // The launch carries them in fields of NsqParams that only eps launches read (the struct, and with it the argument

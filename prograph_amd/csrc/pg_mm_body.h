@@ -245,8 +245,17 @@
         const auto &kd = K();                               // (cold arguments: read where they are used)
         if (on && kd.epsOrdered) {
           const u32 capL = kd.cap;
+#if defined(PG_KNN_SYM_DELIVER_TIMING) && PG_KNN_SYM_DELIVER_TIMING == 1
+          // (timing builds only, wrong results: the returning atomic without the store)
+          const u32 pos = atomicAdd(&kd.countsLo[col], 1u);
+          if (pos == 0xFFFFFFFFu) reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL] = (d << 24) | rowg;
+#elif defined(PG_KNN_SYM_DELIVER_TIMING) && PG_KNN_SYM_DELIVER_TIMING == 2
+          // (timing builds only, wrong results: the store without the atomic, at a place in the slot the sender row fixes)
+          reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL + rowg % capL] = (d << 24) | rowg;
+#else
           const u32 pos = atomicAdd(&kd.countsLo[col], 1u);
           if (pos < capL) reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL + pos] = (d << 24) | rowg;
+#endif
         }
       }
     };
@@ -1117,12 +1126,11 @@
       if constexpr (kPar) {
         const int kk = kr.k;
         if constexpr (KS) {
-          // the lists as they stand (k + 1 keys, rank 0 included), pass by pass, for the merge
-          const int k1 = kk + 1;
-          for (int e = lane; e < nr * k1; e += 64) {
-            const int rr = e / k1, j = e - rr * k1;
-            kr.counts[((long long)pass * RB + rr) * k1 + j] = lstbuf[wv][rr][KL - k1 + j];
-          }
+          // the rows' whole records as they stand (KL keys, 16 bytes at a time: the list of k + 1 keys, rank 0 included,
+          // is their end), pass by pass, for the merge
+          uint4 *dst = reinterpret_cast<uint4 *>(kr.counts) + (long long)pass * RB * (KL / 4);
+          const uint4 *src = reinterpret_cast<const uint4 *>(&lstbuf[wv][0][0]);
+          for (int e = lane; e < nr * (KL / 4); e += 64) dst[e] = src[e];
         } else if (npieces > 1) {
           // a column piece: the list as it stands (k + 1 keys, rank 0 included) for the merge
           const int k1 = kk + 1;
