@@ -696,6 +696,28 @@ int pg_alignment_stats(int mode, const void *x_packed, int64_t n, int64_t x_npad
                        int gap_open, int32_t *head, void *stream);
 
 /*
+ * Alignment values of an EDGE LIST - BUILD DEFINED (pg_aln_list.hip, pg_aln_list.h): the
+ * value of every edge of a CSR list, on the row routines of the dense kernels - what rescoring a pool of candidate pairs
+ * needs.
+ *   pg_alignment_list_scores  mode 0 (global), 1 (local), 2 (semi-global) or 3 (fit), the numbering and the tables of
+ *                      pg_alignment_stats (cost_u8 for mode 0, score_i8 otherwise); operands in pg_sub_pack's order at
+ *                      widths xl, yl of 1..128 (PG_E_TOOLONG beyond); gap in 1..255, gap_open in 0..255.  indptr:
+ *                      int64[m + 1], non-decreasing, indptr[0] = 0, one row per Y sequence; indices: int32[indptr[m]], X
+ *                      column numbers.  scores[e], for e in indptr[r]..indptr[r + 1], is the value the dense entry of the
+ *                      mode - pg_alignment_affine_dense (gap_open 0: the linear distance), _local_dense, _semiglobal_dense,
+ *                      _fit_dense with bias 0 (true, possibly negative scores) - writes at out[r * ldo + indices[e]] with
+ *                      out_elem_bytes 8.  An entry outside 0..n-1 (the -1 of an unfilled kNN slot) touches no operand
+ *                      memory of its own and gets INT32_MIN.  Fit is exact while gap_open + yl * (gap + 2 * max S) + 255
+ *                      <= 65 535, which the caller tests on the host as for pg_alignment_fit_dense.  One workgroup per 8
+ *                      rows; a wave serves one row at a time, 64 entries a pass.  No workspace, no allocation.  A bad
+ *                      mode, gap or gap_open, NULL pointers, non-positive sizes and npad < n are PG_E_BADARG; every
+ *                      argument check returns before any launch.
+ */
+int pg_alignment_list_scores(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed, int64_t m,
+                             int64_t y_npad, int yl, const int64_t *indptr, const int32_t *indices, const void *table, int gap,
+                             int gap_open, int32_t *scores, void *stream);
+
+/*
  * k-mer SPECTRUM profiles - BUILD DEFINED (pg_spectrum.hip, pg_spectrum.h): the k-mer count vector of
  * every row of a token matrix, as the fp16 matrix pg_pack_f16 -> pg_cosine_prep -> pg_cosine_* / pg_euclidean_* take.
  * Tokens are 1..symbols; 0 is padding or an unknown letter and may stand anywhere.  Window i (0 <= i <= l - k) of a row

@@ -51,7 +51,7 @@ SYMBOLS = [
     "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
     "pg_alignment_profile_dense", "pg_alignment_profile_long_dense",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
-    "pg_alignment_stats",
+    "pg_alignment_stats", "pg_alignment_list_scores",
     "pg_spectrum_dims", "pg_spectrum_profile",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
@@ -180,6 +180,7 @@ def _load():
         lib.pg_alignment_fit_trace.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_fit_trace_long.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_stats.argtypes = lib.pg_alignment_trace.argtypes[:16] + [_vp]
+        lib.pg_alignment_list_scores.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]
         lib.pg_spectrum_dims.argtypes = [_i32, _i32, _i32]
         lib.pg_spectrum_profile.argtypes = [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
@@ -1333,6 +1334,40 @@ def alignment_stats(xo, yo, xi, yi, mode, table, gap, gap_open):
     head = torch.empty((xi.numel(), 8), dtype=torch.int32, device=xo.buf.device)
     _stats_launch(xo, yo, xi, yi, mode, table, gap, gap_open, head)
     return head
+
+
+def aln_list_ready():
+    """Can `alignment_list_scores` run?  True only with a HIP device.  `Prograph.rescore` asks this before it leaves the
+    scores of `align(..., ops=False)` for the list kernel."""
+    try:
+        return device().type == "cuda"
+    except NativeUnavailable:
+        return False
+
+
+INT32_MIN = -(1 << 31)              # alignment_list_scores: the value of an entry that names no column
+
+
+def alignment_list_scores(xo, yo, indptr, indices, mode, table, gap, gap_open):
+    """The alignment value of every edge of a CSR list (pg_alignment_list_scores): int32 [nnz] on the
+    device, entry e of row r = the value of Y row r against X column indices[e] - what `alignment_affine_dense`,
+    `alignment_local_dense`, `alignment_semiglobal_dense` or `alignment_fit_dense` (bias 0) holds at [r, indices[e]].
+    `indptr` int64 [yo.n + 1] from 0, non-decreasing, `indices` int32 (cast and moved to the device when they are not);
+    `mode` ALN_TRACE_GLOBAL (`table` from sub_cost), ALN_TRACE_LOCAL, ALN_TRACE_SEMIGLOBAL or ALN_TRACE_FIT (`table` from
+    aln_local_score; exact while `aln_fit_fits` holds, which the caller checks); operands from aln_operand; `gap` 1..255,
+    `gap_open` 0..255.  An entry outside 0..xo.n-1 (the -1 of an unfilled kNN slot) gets INT32_MIN.  No host sync, no
+    workspace: `indptr` is the caller's word for the length of `indices`."""
+    dev = xo.buf.device
+    indptr = torch.as_tensor(indptr).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    indices = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if indptr.numel() != yo.n + 1:
+        raise ValueError("alignment_list_scores: indptr must have one entry per row of yo, and one more")
+    scores = torch.empty(indices.numel(), dtype=torch.int32, device=dev)
+    if indices.numel():
+        _check(lib().pg_alignment_list_scores(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
+                                              _ptr(indptr), _ptr(indices), _ptr(table), int(gap), int(gap_open), _ptr(scores),
+                                              _stream()), "pg_alignment_list_scores")
+    return scores
 
 
 def spectrum_profile(tokens, k, symbols, dims=None, rows=None):

@@ -142,6 +142,8 @@ struct AlnAffine : AlnModeBase {
   __device__ __forceinline__ u32 row(const unsigned char *q, const AlnX &x, int ly) const { return alna_row<NC>(q, x, ly, gap, open); }
 };
 
+// pg_aln_list.hip includes this file for the mode above alone (its list instance needs AlnAffine, which lives here)
+#ifndef ALN_AFFINE_MODE_ONLY
 template <typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) void pg_aln_affine_dense_kernel(const u32 *__restrict__ xt, long long n, long long xnpad,
                                                                           int xl, const u32 *__restrict__ yt, long long m,
@@ -161,3 +163,4 @@ int pg_alignment_affine_dense(const void *x_packed, int64_t n, int64_t x_npad, i
 }
 
 }  // extern "C"
+#endif

@@ -459,7 +459,7 @@ class Prograph:
         return self[idx], np.min(distances)
 
     def search(self, queries, k=None, eps=None, distance=hamming, representation="Tokenized", similarity=False,
-               output="tuples", comp=operator.le, min_identity=None, min_columns=0):
+               output="tuples", comp=operator.le, min_identity=None, min_columns=0, candidates=None, pool=None):
         """
         The k nearest dataset rows (`k`), or the dataset rows within a radius (`eps`), of sequences or embeddings that
         need not be in the dataset; exactly one of the two.
@@ -499,12 +499,18 @@ class Prograph:
         `min_identity=` (0..1) / `min_columns=`: as in `build_graph` - the hits are found as above, each is aligned with
         its query (`align(..., queries=, ops=False)`), and those below the cut are dropped; the result is a `CSRGraph`
         (`output="csr"`, also for `k`: a query may keep fewer than k hits) or the filtered tuple list.
+        `candidates=` / `pool=`: FILTER AND REFINE, as in `build_graph` - `distance` must be one of the four alignment
+        operators, the pool of a query is `search(queries, k=pool, distance=candidates)` (or `candidates` is a ready search
+        result and `pool` None), and `rescore(..., queries=queries)` ranks it: exact within the pool, approximate overall.
+        `similarity=True` raises `ValueError`.
         """
         if self._identity_cut_asked("search", distance, min_identity, min_columns):
             g = self.search(queries, k=k, eps=eps, distance=distance, representation=representation, similarity=similarity,
-                            output="csr", comp=comp)
+                            output="csr", comp=comp, candidates=candidates, pool=pool)
             g = self._identity_cut(g, distance, min_identity, min_columns, representation, queries=queries)
             return g if output == "csr" else g.to_tuples()
+        if candidates is not None or pool is not None:
+            return self._search_candidates(queries, k, eps, comp, similarity, representation, distance, output, candidates, pool)
         if eps is None:
             if not k:                                                      # build_graph's errors for k
                 raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
@@ -1143,6 +1149,17 @@ class Prograph:
             return np.repeat(np.arange(len(graph), dtype=np.int64), counts), c
         raise TypeError("align: graph must be a CSRGraph, a KNNGraph, the name of a stored graph or a list of (indices, weights) tuples")
 
+    def _edge_queries(self, queries, distance):
+        """What `search` was given, as the token matrix whose rows a search result's rows name (`align`, `rescore`)."""
+        if isinstance(queries, str) or (isinstance(queries, (list, tuple)) and len(queries)
+                                        and all(isinstance(q, str) for q in queries)):
+            raw, table = self._byte_view([queries] if isinstance(queries, str) else list(queries))
+            Q = table[raw]
+        else:
+            Q = queries.cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
+            Q = Q.reshape(1, -1) if Q.ndim == 1 else Q
+        return self._local_tokens(Q, distance)
+
     def align(self, graph=None, rows=None, cols=None, queries=None, idxs=None, distance=None, representation="Tokenized",
               workspace_bytes=None, ops=True):
         """
@@ -1189,14 +1206,7 @@ class Prograph:
         if queries is None:
             Q = X
         else:
-            if isinstance(queries, str) or (isinstance(queries, (list, tuple)) and len(queries)
-                                            and all(isinstance(q, str) for q in queries)):
-                raw, table = self._byte_view([queries] if isinstance(queries, str) else list(queries))
-                Q = table[raw]
-            else:
-                Q = queries.cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
-                Q = Q.reshape(1, -1) if Q.ndim == 1 else Q
-            Q = self._local_tokens(Q, distance)
+            Q = self._edge_queries(queries, distance)
         if len(r) and (r.min() < 0 or r.max() >= Q.shape[0] or c.min() < 0 or c.max() >= X.shape[0]):
             raise IndexError("align: an edge names a row outside the data")
         letters = "?" + "".join(self.amino_acids) if all(len(a) == 1 for a in self.amino_acids) else None
@@ -1211,6 +1221,246 @@ class Prograph:
                                      letters=letters, native=native, native_long=native_long, ops=ops)
         return _alignments.trace(distance, Qt, Xt, torch.from_numpy(r), torch.from_numpy(c), workspace_bytes=workspace_bytes,
                                  letters=letters, native=native, native_long=native_long, ops=ops)
+
+    # ---- filter and refine: the alignment values of candidate edges
+    def _candidate_csr(self, graph):
+        """A candidate graph - what `_edge_lists` takes - as CSR tensors where the graph lives (a device graph stays on the
+        device): (indptr int64 [nrows + 1], columns int64, row0).  kNN slots without a neighbour (-1) are no edges."""
+        if isinstance(graph, str):
+            graph = self._device_graph_any(graph) or graph
+        if isinstance(graph, KNNGraph):
+            graph = graph.as_csr()
+        if isinstance(graph, CSRGraph):
+            indptr, c = graph.indptr.to(torch.int64), graph.indices.to(torch.int64)
+            real = c >= 0
+            if not bool(real.all()):
+                rows = torch.repeat_interleave(torch.arange(graph.nrows, device=c.device), indptr[1:] - indptr[:-1])
+                indptr = torch.zeros_like(indptr)
+                indptr[1:] = torch.cumsum(torch.bincount(rows[real], minlength=graph.nrows), 0)
+                c = c[real]
+            return indptr, c, graph.row0
+        r, c = self._edge_lists(graph)                                      # a name without a device graph, a tuple list
+        nrows = len(self) if isinstance(graph, str) else len(graph)
+        if len(r) and (r.min() < 0 or r.max() >= nrows or np.any(np.diff(r) < 0)):
+            raise ValueError("rescore: the graph's edges must come row by row")
+        indptr = np.zeros(nrows + 1, dtype=np.int64)
+        indptr[1:] = np.cumsum(np.bincount(r, minlength=nrows))
+        return torch.from_numpy(indptr), torch.from_numpy(c), 0
+
+    @staticmethod
+    def _rescore_knn_torch(rs, cs, ss, indptr, nrows, k, descending):
+        """`rescore`'s kNN selection in torch: edges (rs, cs, ss) sorted by (row, column) -> (idx, w) (nrows, k), per row the
+        first k of the stable (value, column) order, -1 / 0 beyond a row's candidates."""
+        dev = ss.device
+        by_value = torch.sort(ss, stable=True, descending=descending)[1]
+        order = by_value[torch.sort(rs[by_value], stable=True)[1]]         # by (row, value, column)
+        rank = torch.arange(order.numel(), device=dev) - indptr[rs]       # rs is sorted: the sorted rows are rs itself
+        keep = rank < k
+        idx = torch.full((nrows, k), -1, dtype=torch.int32, device=dev)
+        w = torch.zeros((nrows, k), dtype=torch.int32, device=dev)
+        idx[rs[keep], rank[keep]] = cs[order][keep].to(torch.int32)
+        w[rs[keep], rank[keep]] = ss[order][keep]
+        return idx, w
+
+    def _rescore_select_device(self, rs, cs, ss, indptr, indptr_host, nrows, k, eps, cmp, K, keep_zero, descending):
+        """`rescore`'s selection on the int32 selection kernels: (rows, P) blocks whose columns are a row's candidates in
+        column order - so that a tie of positions is a tie of columns -, P the longest list (k if that is more), the rest of
+        a row padded with what takes no rank from an edge (behind the edges a tie goes to the edge: 0 under largest first,
+        2^31 - 1 under smallest first; -1, which no radius admits).  Values are shifted by K >= 0 (`fit_alignment`: the
+        blocks of `_local_select`).  Selected positions go back to columns by a gather; a position past its row's list is
+        no neighbour.  Returns (idx, w) or the CSR triple."""
+        dev = ss.device
+        lens_host = np.diff(indptr_host)
+        lens = indptr[1:] - indptr[:-1]
+        P = max(int(lens_host.max()) if nrows else 1, k or 1, 1)
+        pos = torch.arange(ss.numel(), device=dev) - indptr[rs]
+        pad = -1 if k is None else (0 if descending else (1 << 31) - 1)
+        per = max(1, self._BLOCK_ELEMS // 2 // P)
+        parts = []
+        for r0 in range(0, nrows, per):
+            r1 = min(nrows, r0 + per)
+            e0, e1 = int(indptr_host[r0]), int(indptr_host[r1])
+            block = torch.full((r1 - r0, P), pad, dtype=torch.int32, device=dev)
+            block[rs[e0:e1] - r0, pos[e0:e1]] = ss[e0:e1] + K
+            base, ln = indptr[r0:r1], lens[r0:r1]
+            if k is not None:
+                at, w = _native.i32_knn(block, k, first=0, descending=descending)
+                at = at.to(torch.int64)
+                real = (at >= 0) & (at < ln[:, None])
+                col = cs[(base[:, None] + at.clamp(min=0)).clamp(max=max(cs.numel() - 1, 0))] if cs.numel() else at
+                parts.append((torch.where(real, col, torch.full_like(col, -1)).to(torch.int32),
+                              torch.where(real, w - K, torch.zeros_like(w))))
+                continue
+            ip, at, w = _native.i32_eps(block, cmp, self._long_threshold(cmp, float(eps) + K), keep_zero=keep_zero)
+            at = at.to(torch.int64)
+            rows = torch.repeat_interleave(torch.arange(r1 - r0, device=dev), ip[1:] - ip[:-1])
+            w = w - K
+            real = at < ln[rows]
+            if K:
+                real &= w > 0
+            out = torch.zeros_like(ip)
+            out[1:] = torch.cumsum(torch.bincount(rows[real], minlength=r1 - r0), 0)
+            parts.append((out, cs[base[rows[real]] + at[real]].to(torch.int32), w[real]))
+        if k is not None:
+            return torch.cat([p_[0] for p_ in parts]), torch.cat([p_[1] for p_ in parts])
+        return _native.cat_csr(parts)
+
+    def rescore(self, graph, distance, k=None, eps=None, comp=operator.le, queries=None, idxs=None,
+                representation="Tokenized", output="csr", store=None):
+        """
+        The REFINE half of filter-and-refine: the edges of a candidate graph scored with an alignment operator, and the best
+        of every row kept.  `graph`: a `CSRGraph`, a `KNNGraph`, a stored graph's name or a tuple list, read as `align`
+        reads it (`row0` honoured, kNN slots of -1 are no edges; with `idxs`, the selection the graph was built over, rows
+        and columns go through it; with `queries`, what `search` was given, the rows are the queries).  `distance`: an
+        `alignment`, `local_alignment`, `semiglobal_alignment` or `fit_alignment` instance (`TypeError` otherwise; a
+        `profile_alignment` raises the queries-only `ValueError`).  Every edge (r, c) gets the operator's value
+        `distance(T, T[r:r+1])[0, c]` (with `queries` the query row against T; `fit_alignment`: the row or query whole,
+        within column c, as in `build_graph`).
+        Neither `k` nor `eps`: a `CSRGraph` of the same edges in the same order with int32 weights.  `k`: a `KNNGraph` with
+        int32 values - per row the first k candidates of the stable (value, column) order, largest first for the scores,
+        smallest first for `alignment`; idx -1, weight 0 where a row has fewer than k candidates (built with first=1, with
+        `queries` first=0).  `eps`: a `CSRGraph` with ascending columns under `build_graph`'s contract - distances
+        `comp(d, eps) & d > 0`, scores `s > 0 & comp(eps, s)` - or with `queries` under `search`'s, which keeps d = 0.
+        Nothing is dropped on its own: an edge c == r is scored like any other.  `output="tuples"` and `store=` as in
+        `build_graph`.
+        Exact within the candidates, approximate as a graph: an edge the candidate graph lacks is never found.
+        On the device, at up to 128 positions and for `fit_alignment` inside its 16-bit bound, the values come from
+        `pg_alignment_list_scores` - the dense kernels' row routines over the edge list, one launch - and the selection
+        from the int32 selection kernels over (rows, longest list) blocks.  Wider operands (129..2048 positions and the
+        host expression beyond), a fit outside its bound, a `comp` outside the five orderings, k beyond the selection's
+        rounds, or no device: the scores of `align(..., ops=False)` and the same selection in torch - the same graph.
+        """
+        if isinstance(distance, profile_alignment):
+            raise ValueError(self._PROFILE_QUERIES_ONLY.format("rescore"))
+        mode = _alignments._mode_of(distance)                               # TypeError for anything else
+        if k is not None and eps is not None:
+            raise ValueError("rescore: k or eps, not both")
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer))):
+            raise TypeError("K must be provided as an integer.")
+        if k is not None and k < 1:
+            raise ValueError("K must be at least 1.")
+        if eps is not None and (isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating))):
+            raise TypeError("Epsilon must be provided as a number.")
+        if eps is not None and eps != eps:
+            raise ValueError("Epsilon must not be NaN.")
+        k = None if k is None else int(k)
+        X = self._local_tokens(self._dataset_matrix(representation), distance)
+        if idxs is not None:
+            idxs = np.arange(len(self))[idxs] if isinstance(idxs, slice) else np.asarray(idxs)
+            idxs = np.nonzero(idxs)[0] if idxs.dtype == bool else idxs.astype(np.int64)
+            X = X[idxs]
+        indptr, cols, row0 = self._candidate_csr(graph)
+        indptr_host = indptr.cpu().numpy()
+        nrows, n, query = len(indptr_host) - 1, X.shape[0], queries is not None
+        Q = self._edge_queries(queries, distance) if query else X
+        if row0 < 0 or row0 + nrows > Q.shape[0] or (cols.numel() and (int(cols.min()) < 0 or int(cols.max()) >= n)):
+            raise IndexError("rescore: an edge names a row outside the data")
+        whole = not query and row0 == 0 and nrows == n
+        Y = Q if whole else Q[row0:row0 + nrows]
+        score = mode != _alignments.GLOBAL
+        kernel = (_native.aln_list_ready() and nrows > 0 and max(X.shape[1], Y.shape[1]) <= _native.ALN_MAX_L
+                  and (mode != _alignments.FIT
+                       or _native.aln_fit_fits(X.shape[1], Y.shape[1], distance.max_score, distance.gap, distance.gap_open)))
+        selects = k <= _native.MAX_K_ROUNDS if k is not None else (eps is None or comp in _CMP_CODE)
+        fast = kernel and selects
+        if fast:
+            dev = _native.device()
+            xo = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+            yo = xo if whole else _native.aln_operand(torch.from_numpy(np.ascontiguousarray(Y)), distance.symbols)
+            indptr, cols = indptr.to(dev), cols.to(dev)
+            ss = _native.alignment_list_scores(xo, yo, indptr, cols.to(torch.int32), mode, _alignments._device_table(distance, mode),
+                                               distance.gap, distance.gap_open)
+        else:
+            g0 = CSRGraph(indptr.cpu(), cols.cpu().to(torch.int32), torch.zeros(cols.numel(), dtype=torch.int32), n, row0=row0)
+            tb = self.align(g0, queries=queries, idxs=idxs, distance=distance, representation=representation, ops=False)
+            ss = tb.score.to(torch.int32)
+            dev = ss.device
+            indptr, cols = indptr.to(dev), cols.to(dev)
+        if k is None and eps is None:
+            g = CSRGraph(indptr, cols.to(torch.int32), ss, n, similarity=False, row0=row0)
+            return self._graph_result(g, idxs, store, None, output)
+        rs = torch.repeat_interleave(torch.arange(nrows, device=dev), indptr[1:] - indptr[:-1])
+        order = torch.sort(rs * n + cols, stable=True)[1]                   # a row's candidates in column order
+        cs, ss = cols[order], ss[order]
+        K = distance._select_bias(Y.shape[1]) if score else 0               # 0 but for `fit_alignment`
+        if k is not None:
+            idx, w = self._rescore_select_device(rs, cs, ss, indptr, indptr_host, nrows, k, None, None, K, False, score) if fast \
+                else self._rescore_knn_torch(rs, cs, ss, indptr, nrows, k, score)
+            g = KNNGraph(idx, w, n, similarity=False, row0=row0, first=0 if query else 1)
+        else:
+            if fast:
+                cmp = _CMP_MIRROR[_CMP_CODE[comp]] if score else _CMP_CODE[comp]
+                csr = self._rescore_select_device(rs, cs, ss, indptr, indptr_host, nrows, None, eps, cmp, K,
+                                                  bool(K) if score else query, score)
+            else:
+                keep = ((ss > 0) & comp(eps, ss)) if score else (comp(ss, eps) & ((ss > 0) | query))
+                out = torch.zeros_like(indptr)
+                out[1:] = torch.cumsum(torch.bincount(rs[keep], minlength=nrows), 0)
+                csr = (out, cs[keep].to(torch.int32), ss[keep])
+            g = CSRGraph(*csr, n, similarity=False, row0=row0)
+        return self._graph_result(g, idxs, store, None, output)
+
+    _GRAPH_TYPES = (CSRGraph, KNNGraph, str, list, tuple)                   # what `candidates=` takes for a ready graph
+
+    @staticmethod
+    def _pool_checked(who, candidates, pool, k):
+        """The checks of `candidates=` / `pool=` (`build_graph`, `search`): True when `candidates` is a ready graph."""
+        if candidates is None:
+            raise ValueError(f"{who}: pool= goes with candidates=")
+        if isinstance(candidates, Prograph._GRAPH_TYPES):
+            if pool is not None:
+                raise ValueError(f"{who}: candidates= is a graph already, pool= must be None")
+            return True
+        if pool is None:
+            raise ValueError(f"{who}: candidates= is a distance, so pool= (candidates per row) must be given")
+        if isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
+            raise TypeError(f"{who}: pool must be an integer")
+        if k is not None and isinstance(k, (int, np.integer)) and pool < k:
+            raise ValueError(f"{who}: pool must be at least k")
+        if not 1 <= pool <= _native.MAX_K_ROUNDS:
+            raise ValueError(f"{who}: pool must be in max(k, 1)..{_native.MAX_K_ROUNDS}")
+        return False
+
+    def _build_graph_candidates(self, idxs, eps, k, similarity, representation, distance, comp, output, store, candidates, pool):
+        """`build_graph(candidates=, pool=)`: the pool per row - `build_graph(k=pool, distance=candidates)` over the same
+        `idxs` and `representation`, or a ready graph -, without its entries c == r, through `rescore`."""
+        if similarity:
+            raise ValueError("build_graph: candidates= ranks the values of an alignment operator; similarity=True has no meaning there")
+        if isinstance(distance, profile_alignment):
+            raise ValueError(self._PROFILE_QUERIES_ONLY.format("build_graph"))
+        _alignments._mode_of(distance)                                      # TypeError for anything but the four operators
+        if operator.xor(bool(eps), bool(k)) is False:
+            raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
+        if not self._pool_checked("build_graph", candidates, pool, k):
+            candidates = self.build_graph(idxs=idxs, k=int(pool), distance=candidates, representation=representation, output="csr")
+        indptr, c, row0 = self._candidate_csr(candidates)
+        nrows = indptr.numel() - 1
+        r = torch.repeat_interleave(torch.arange(nrows, device=c.device), indptr[1:] - indptr[:-1])
+        keep = c != r + row0
+        kept = torch.zeros_like(indptr)
+        kept[1:] = torch.cumsum(torch.bincount(r[keep], minlength=nrows), 0)
+        ncols = candidates.ncols if isinstance(candidates, (CSRGraph, KNNGraph)) else len(self) if idxs is None else \
+            len(np.arange(len(self))[idxs] if isinstance(idxs, slice) else
+                (np.nonzero(idxs)[0] if np.asarray(idxs).dtype == bool else np.asarray(idxs)))
+        pool_graph = CSRGraph(kept, c[keep].to(torch.int32), torch.zeros(int(kept[-1]), dtype=torch.int32, device=c.device), ncols,
+                              row0=row0)
+        return self.rescore(pool_graph, distance, k=k, eps=eps if eps else None, comp=comp, idxs=idxs, representation=representation,
+                            output=output, store=store)
+
+    def _search_candidates(self, queries, k, eps, comp, similarity, representation, distance, output, candidates, pool):
+        """`search(candidates=, pool=)`: the pool per query - `search(k=pool, distance=candidates)`, or a ready graph -
+        through `rescore(queries=)`."""
+        if similarity:
+            raise ValueError("search: candidates= ranks the values of an alignment operator; similarity=True has no meaning there")
+        if isinstance(distance, profile_alignment):
+            raise ValueError(self._PROFILE_QUERIES_ONLY.format("search(candidates=)"))
+        _alignments._mode_of(distance)
+        if (k is None) == (eps is None):
+            raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
+        if not self._pool_checked("search", candidates, pool, k):
+            candidates = self.search(queries, k=int(pool), distance=candidates, representation=representation, output="csr")
+        return self.rescore(candidates, distance, k=k, eps=eps, comp=comp, queries=queries, representation=representation,
+                            output=output)
 
     # ---- percent-identity cuts of a graph's edges (DESIGN.md 4.25)
     @staticmethod
@@ -1350,7 +1600,7 @@ class Prograph:
     # ------------------------------------------------------------------ graph construction
     def build_graph(self, idxs=None, batch_size=8, eps=None, k=None, weighted=False, similarity=False,
                     representation="Tokenized", distance=hamming, comp=operator.le, output="tuples", cap=256,
-                    store=None, _keep=None, min_identity=None, min_columns=0):
+                    store=None, _keep=None, min_identity=None, min_columns=0, candidates=None, pool=None):
         """
         epsilon-neighbourhood (`eps`) or kNN (`k`) graph over all pairwise distances
         (reference :656-765).  Returns the reference's list of N `(indices, weights)` tuples;
@@ -1378,17 +1628,31 @@ class Prograph:
         empty local alignment has identity 0).  Survivors keep their order and their weights; the result is a `CSRGraph`
         (`output="csr"`, also for `k`: a row may keep fewer than k edges) or the filtered tuple list, and `store=` stores
         the filtered graph.
+        `candidates=` / `pool=`: FILTER AND REFINE - an alignment graph without the quadratic dynamic programming.
+        `distance` must be one of the four alignment operators; `candidates` is any distance `build_graph(k=)` accepts
+        (`spectrum(k=3, symbols=20)` is the usual one) with `pool` = candidates per row, an integer in max(k, 1)..1023
+        (`ValueError` without it or below k), or a ready graph (`rescore` says which) with `pool` None.  The pool is
+        `build_graph(idxs=idxs, k=pool, distance=candidates, representation=representation)`; its entries c == r are
+        removed, and `rescore` scores the rest with `distance` and keeps the best `k`, or the `eps` edges, of every row.
+        EXACT WITHIN THE POOL, APPROXIMATE OVERALL: a neighbour outside a row's pool is never found (profiles/aln_list.txt
+        has a recall table).  With duplicated sequences it also differs from the exact route in what it leaves out: that
+        one drops rank 0, whatever it is; this one drops the row itself.  `similarity=True` raises `ValueError`;
+        `min_identity=` / `min_columns=` cut the rescored graph.
         """
         if isinstance(distance, profile_alignment):
             raise ValueError(self._PROFILE_QUERIES_ONLY.format("build_graph"))
         if self._identity_cut_asked("build_graph", distance, min_identity, min_columns):
             g = self.build_graph(idxs=idxs, batch_size=batch_size, eps=eps, k=k, weighted=weighted, similarity=similarity,
-                                 representation=representation, distance=distance, comp=comp, output="csr", cap=cap)
+                                 representation=representation, distance=distance, comp=comp, output="csr", cap=cap,
+                                 candidates=candidates, pool=pool)
             if idxs is not None:                                            # the positions `align` maps edges through
                 idxs = np.arange(len(self))[idxs] if isinstance(idxs, slice) else np.asarray(idxs)
                 idxs = np.nonzero(idxs)[0] if idxs.dtype == bool else idxs
             g = self._identity_cut(g, distance, min_identity, min_columns, representation, idxs=idxs)
             return self._graph_result(g, idxs, store, _keep, output)
+        if candidates is not None or pool is not None:
+            return self._build_graph_candidates(idxs, eps, k, similarity, representation, distance, comp, output, store, candidates,
+                                                pool)
         if operator.xor(bool(eps), bool(k)) is False:
             raise ValueError("Epsilon or K must be provided, but both cannot be as they are different methods of graph construction.")
         if k is not None and not isinstance(k, int):
