@@ -748,6 +748,9 @@ int pg_spectrum_profile(const uint8_t *tokens, int64_t n, int l, int64_t ld, con
  *   prograph.py:894-896),  col_sum[c] += w_rc (in-degree, `mode="indegree"`; caller zeroes it).
  * weights: uint8 distances OR float32 (exactly one non-NULL; both NULL = boolean weights 1);
  * f = per-node values (double[ncols]); any output may be NULL.
+ * An entry whose column is negative (the empty slot of a kNN table, idx = -1) is no edge: it adds to none of
+ * deg, sum_f, sum_wf, self_w, col_sum, and neither f nor col_sum is read or written for it.  A column at or
+ * past the length of f / col_sum is the caller's error and is not checked.
  */
 int pg_csr_row_stats(const int64_t *indptr, const int32_t *indices, const uint8_t *weights_u8,
                      const float *weights_f32, int64_t nrows, int64_t row0, const double *f, double *deg,

@@ -493,6 +493,7 @@ __global__ __launch_bounds__(256) void pg_index_kernel(const u32 *__restrict__ p
 //   sf[r]   = sum_j f[col_j]        (local_variance, :924-946:  mean_j (f_r - f_j) = f_r - sf/cnt)
 //   swf[r]  = sum_j w_rj f[col_j]   (dirichlet, :899-922:  f^T L f = sum_r f_r (deg_r f_r - swf_r))
 // one wave per row, coalesced reads of the row's slice, DPP/shuffle tree reduction.
+// An entry with a negative column (an empty kNN slot) is no edge: it enters no sum, and neither f nor colsum is touched.
 // =======================================================================================
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -514,6 +515,7 @@ __global__ __launch_bounds__(256) void pg_csr_row_stats_kernel(const long long *
   for (long long e = a + lane; e < b; e += 64) {
     const double w = w8 ? (double)w8[e] : (wf ? (double)wf[e] : 1.0);
     const int col = indices[e];
+    if (col < 0) continue;                                // an empty kNN slot: no edge, nothing is read or added for it
     const double fj = f ? f[col] : 0.0;
     d += w; s1 += fj; s2 += w * fj;
     if (col == row0 + row) sw += w;                       // the row's own node among its neighbours

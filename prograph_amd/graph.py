@@ -136,13 +136,15 @@ class KNNGraph:
     """k nearest neighbours: idx int32 (n,k), dist uint8|int16|int32 (n,k) or fp16 Minkowski values; canonical (distance, index)
     order (descending values for Minkowski similarities).  final=True: the values are final (cosine / Euclidean fp32) whatever
     their dtype.  first: the rank of column 0 - 1 for self-graphs (rank 0 dropped, ranks beyond N-1 do not exist), 0 for
-    query results (`Prograph.search`: rank 0 kept, min(k, N) ranks)."""
+    query results (`Prograph.search`: rank 0 kept, min(k, N) ranks).  idx < 0: an empty slot, no edge (`host`, `to_tuples`
+    and `as_csr` leave it out; `_without_empty_slots`)."""
 
     def __init__(self, idx, dist, ncols, similarity=False, row0=0, final=False, first=1):
         self.idx, self.dist = idx, dist
         self.ncols, self.similarity, self.row0 = int(ncols), bool(similarity), int(row0)
         self.final = bool(final)
         self.first = int(first)
+        self._csr = None             # the CSR without the empty slots, once `_without_empty_slots` has looked
 
     @property
     def nrows(self):
@@ -151,7 +153,31 @@ class KNNGraph:
     def _ranks(self):
         return min(self.idx.shape[1], max(self.ncols - self.first, 0))   # ranks beyond N-1 do not exist ([:,1:k+1])
 
+    def _without_empty_slots(self):
+        """A slot with idx < 0 holds no neighbour (`rescore(k=)`: a row with fewer than k candidates) and is no edge for
+        any consumer.  False when the ranks that exist are all filled - the usual table; one device reduction, made
+        once -, else the CSRGraph of the filled slots: `indptr` from the per-row counts, order and weights as in the
+        table."""
+        if self._csr is None:
+            kk = self._ranks()
+            idx = self.idx[:, :kk]
+            real = idx >= 0
+            if not idx.numel() or bool(real.all()):
+                self._csr = False
+            else:
+                indptr = torch.zeros(self.nrows + 1, dtype=torch.int64, device=idx.device)
+                indptr[1:] = torch.cumsum(real.sum(dim=1), 0)
+                self._csr = CSRGraph(indptr, idx[real], self.dist[:, :kk][real], self.ncols, similarity=self.similarity,
+                                     row0=self.row0, final=self.final)
+        return self._csr
+
     def host(self):
+        """(idx int64, weights in the reference's dtype) as numpy, (n, ranks) each; a table with empty slots: two lists
+        of n ragged rows without them (views into two flat arrays)."""
+        g = self._without_empty_slots()
+        if g:
+            indptr, idx, w = g.host()
+            return np.split(idx, indptr[1:-1]), np.split(w, indptr[1:-1])
         kk = self._ranks()
         idx = self.idx[:, :kk].to(torch.int64).cpu().numpy()
         if self.final or self.dist.dtype == torch.float16:
@@ -165,7 +191,11 @@ class KNNGraph:
         return list(zip(list(idx), list(w)))
 
     def as_csr(self):
-        """The same graph as a CSRGraph view (k entries per row; ranks beyond N-1 do not exist)."""
+        """The same graph as a CSRGraph: a view of the table (k entries per row; ranks beyond N-1 do not exist), or,
+        where the table has empty slots, the CSR without them."""
+        g = self._without_empty_slots()
+        if g:
+            return g
         kk = self._ranks()
         n = self.nrows
         indptr = torch.arange(0, n * kk + 1, kk, dtype=torch.int64, device=self.idx.device) if kk else \

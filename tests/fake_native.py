@@ -120,6 +120,8 @@ def _csr_row_stats(indptr, indices, weights, f=None, want=("deg",), row0=0, ncol
     ip = indptr.numpy(); ix = indices.numpy().astype(np.int64)
     w = np.ones(len(ix)) if weights is None else weights.numpy().astype(np.float64)
     rows = np.repeat(np.arange(len(ip) - 1), np.diff(ip))
+    real = ix >= 0                                                        # the kernel's rule: a negative column is no edge
+    ix, w, rows = ix[real], w[real], rows[real]
     fv = None if f is None else f.numpy().astype(np.float64)
     out = {}
     for key in want:

@@ -134,7 +134,7 @@ def test_build_graph_generic_on_cpu(monkeypatch, tmp_path, capsys):
 INDPTR = np.array([0, 2, 2, 5, 6], dtype=np.int64)
 INDICES = np.array([1, 3, 0, 1, 3, 2], dtype=np.int32)
 F32 = np.array([0.25, 1.5, 0.0999, 2.0, 1e-7, 0.33333334], dtype=np.float32)
-KIDX = np.array([[1, 2], [0, 3], [3, 1], [2, -1]], dtype=np.int32)
+KIDX = np.array([[1, 2], [0, 3], [3, 1], [2, 0]], dtype=np.int32)      # every slot filled (empty ones: test_graph_containers_cpu.py)
 KF32 = np.array([[0.5, 0.79], [0.5, 1.25], [1.0, 1.75], [1.0, 0.0]], dtype=np.float32)
 
 

@@ -20,7 +20,7 @@ from prograph_amd.graph import CSRGraph, KNNGraph, load_graphs, save_graphs
 INDPTR = np.array([0, 2, 2, 5, 6], dtype=np.int64)
 INDICES = np.array([1, 3, 0, 1, 3, 2], dtype=np.int32)
 F16 = np.array([0.79052734, 1.5, 0.0999, 65504.0, np.inf, 0.33325195], dtype=np.float16)
-KIDX = np.array([[1, 2], [0, 3], [3, 1], [2, -1]], dtype=np.int32)
+KIDX = np.array([[1, 2], [0, 3], [3, 1], [2, 0]], dtype=np.int32)      # every slot filled (empty ones: test_graph_containers_cpu.py)
 KF16 = np.array([[0.5, 0.79052734], [0.5, 2.25], [1.0, 3.0], [1.0, 0.0]], dtype=np.float16)
 
 
