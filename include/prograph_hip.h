@@ -718,6 +718,27 @@ int pg_alignment_list_scores(int mode, const void *x_packed, int64_t n, int64_t 
                              int gap_open, int32_t *scores, void *stream);
 
 /*
+ * The same BEYOND 128 positions - BUILD DEFINED (pg_aln_list_long.hip, pg_aln_list_long.h): the strip
+ * routines of the long dense kernels over the edge list.
+ *   pg_alignment_list_long_scores  the arguments, the results and the errors of pg_alignment_list_scores, with two
+ *                      differences: widths xl, yl of 1..2048 (PG_E_TOOLONG beyond), and a caller-owned workspace laid out
+ *                      as the long dense entries' - a boundary column per lane of every workgroup in flight, shares sized
+ *                      by pg_alignment_long_workspace(xl, &one, &full).  scores[e] is the value the LONG dense entry of
+ *                      the mode - pg_alignment_long_dense, _local_long_dense, _semiglobal_long_dense, _fit_long_dense with
+ *                      bias 0 - writes at out[r * ldo + indices[e]].  min(m, workspace_bytes / one) workgroups are
+ *                      launched; they stride over the rows, and a row without a list costs two words of indptr.  A NULL
+ *                      workspace, or one below a single share, is PG_E_BADARG.  The kernel does not test the 16-bit cell
+ *                      bounds of the long dense entries (global: W * max(max C, gap) + 2 gap_open + 2 gap; local:
+ *                      min(xl, yl) * max S + 255; semi-global: 2 * min(xl, yl) * max S + 255; fit: gap_open + yl * (gap +
+ *                      2 * max S) + 255; each <= 65 535): the caller does.  Every argument check returns before any
+ *                      launch; the entry never allocates.
+ */
+int pg_alignment_list_long_scores(int mode, const void *x_packed, int64_t n, int64_t x_npad, int xl, const void *y_packed,
+                                  int64_t m, int64_t y_npad, int yl, const int64_t *indptr, const int32_t *indices,
+                                  const void *table, int gap, int gap_open, int32_t *scores, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
+
+/*
  * k-mer SPECTRUM profiles - BUILD DEFINED (pg_spectrum.hip, pg_spectrum.h): the k-mer count vector of
  * every row of a token matrix, as the fp16 matrix pg_pack_f16 -> pg_cosine_prep -> pg_cosine_* / pg_euclidean_* take.
  * Tokens are 1..symbols; 0 is padding or an unknown letter and may stand anywhere.  Window i (0 <= i <= l - k) of a row

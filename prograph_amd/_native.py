@@ -51,7 +51,7 @@ SYMBOLS = [
     "pg_alignment_fit_dense", "pg_alignment_fit_long_dense", "pg_alignment_fit_trace", "pg_alignment_fit_trace_long",
     "pg_alignment_profile_dense", "pg_alignment_profile_long_dense",
     "pg_alignment_trace_workspace", "pg_alignment_trace", "pg_alignment_trace_long_workspace", "pg_alignment_trace_long",
-    "pg_alignment_stats", "pg_alignment_list_scores",
+    "pg_alignment_stats", "pg_alignment_list_scores", "pg_alignment_list_long_scores",
     "pg_spectrum_dims", "pg_spectrum_profile",
     "pg_i32_knn", "pg_i32_knn_round", "pg_i32_eps_count", "pg_i32_eps_fill",
     "pg_comm_available", "pg_comm_unique_id", "pg_comm_init", "pg_comm_destroy", "pg_allgather_tokens",
@@ -181,6 +181,8 @@ def _load():
         lib.pg_alignment_fit_trace_long.argtypes = lib.pg_alignment_trace.argtypes[1:]
         lib.pg_alignment_stats.argtypes = lib.pg_alignment_trace.argtypes[:16] + [_vp]
         lib.pg_alignment_list_scores.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp]
+        lib.pg_alignment_list_long_scores.argtypes = [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp,
+                                                      _vp, _i64, _vp]
         lib.pg_spectrum_dims.argtypes = [_i32, _i32, _i32]
         lib.pg_spectrum_profile.argtypes = [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp]
         lib.pg_i32_knn.argtypes = [_vp, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp]
@@ -1367,6 +1369,41 @@ def alignment_list_scores(xo, yo, indptr, indices, mode, table, gap, gap_open):
         _check(lib().pg_alignment_list_scores(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
                                               _ptr(indptr), _ptr(indices), _ptr(table), int(gap), int(gap_open), _ptr(scores),
                                               _stream()), "pg_alignment_list_scores")
+    return scores
+
+
+def aln_list_long_ready():
+    """Can `alignment_list_long_scores` run?  True only with a HIP device.  `Prograph.rescore` asks this, not `aln_list_ready`
+    or `aln_long_ready`, before it leaves the scores of `align(..., ops=False)` for the long list kernel at 129..2048
+    positions."""
+    try:
+        return device().type == "cuda"
+    except NativeUnavailable:
+        return False
+
+
+def alignment_list_long_scores(xo, yo, indptr, indices, mode, table, gap, gap_open, workspace_bytes=None):
+    """`alignment_list_scores` for operands of up to ALN_LONG_MAX_L positions (pg_alignment_list_long_scores, DESIGN.md
+    §4.29; `xo`, `yo` from aln_long_operand): int32 [nnz], entry e of row r = what `alignment_long_dense`,
+    `alignment_local_long_dense`, `alignment_semiglobal_long_dense` or `alignment_fit_long_dense` (bias 0) holds at
+    [r, indices[e]], INT32_MIN for an entry outside 0..xo.n-1.  Exact while the mode's 16-bit bound holds (`aln_long_fits`,
+    `aln_local_long_fits`, `aln_semiglobal_long_fits`, `aln_fit_fits`), which the caller checks.  The boundary-column
+    workspace - min(the whole device's, a share per row) bytes, or `workspace_bytes` of it, at least one share - is
+    allocated here, once per call.  No host sync."""
+    dev = xo.buf.device
+    indptr = torch.as_tensor(indptr).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    indices = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if indptr.numel() != yo.n + 1:
+        raise ValueError("alignment_list_long_scores: indptr must have one entry per row of yo, and one more")
+    scores = torch.empty(indices.numel(), dtype=torch.int32, device=dev)
+    if indices.numel():
+        one, full = _i64(0), _i64(0)
+        _check(lib().pg_alignment_long_workspace(xo.l, ctypes.byref(one), ctypes.byref(full)), "pg_alignment_long_workspace")
+        nbytes = min(full.value, yo.n * one.value) if workspace_bytes is None else int(workspace_bytes)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _check(lib().pg_alignment_list_long_scores(int(mode), _ptr(xo.buf), xo.n, xo.npad, xo.l, _ptr(yo.buf), yo.n, yo.npad, yo.l,
+                                                   _ptr(indptr), _ptr(indices), _ptr(table), int(gap), int(gap_open), _ptr(scores),
+                                                   _ptr(ws), ws.numel(), _stream()), "pg_alignment_list_long_scores")
     return scores
 
 

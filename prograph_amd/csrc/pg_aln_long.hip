@@ -110,6 +110,8 @@ struct AlnGlobalLong : AlnModeBase {
   }
 };
 
+// pg_aln_list_long.hip includes this file for the mode above alone (its list instance needs AlnGlobalLong, which lives here)
+#ifndef ALN_LONG_MODE_ONLY
 template <class MODE, typename OUT>
 __global__ __launch_bounds__(ALN_THREADS) void pg_aln_long_dense_kernel(
     const u32 *__restrict__ xt, long long n, long long xnpad, int xl, const u32 *__restrict__ yt, long long m, long long ynpad,
@@ -155,3 +157,4 @@ int pg_alignment_local_long_dense(const void *x_packed, int64_t n, int64_t x_npa
 }
 
 }  // extern "C"
+#endif  // ALN_LONG_MODE_ONLY

@@ -1326,9 +1326,12 @@ class Prograph:
         Exact within the candidates, approximate as a graph: an edge the candidate graph lacks is never found.
         On the device, at up to 128 positions and for `fit_alignment` inside its 16-bit bound, the values come from
         `pg_alignment_list_scores` - the dense kernels' row routines over the edge list, one launch - and the selection
-        from the int32 selection kernels over (rows, longest list) blocks.  Wider operands (129..2048 positions and the
-        host expression beyond), a fit outside its bound, a `comp` outside the five orderings, k beyond the selection's
-        rounds, or no device: the scores of `align(..., ops=False)` and the same selection in torch - the same graph.
+        from the int32 selection kernels over (rows, longest list) blocks.  At 129..2048 positions, inside the mode's
+        16-bit bound (`aln_long_fits`, `aln_local_long_fits`, `aln_semiglobal_long_fits`, `aln_fit_fits`), the values come
+        from `pg_alignment_list_long_scores` - the long dense kernels' strip routines over the edge list - and the
+        selection is the same.  Wider operands still, a mode outside its bound, a `comp` outside the five orderings, k
+        beyond the selection's rounds, or no device: the scores of `align(..., ops=False)` and the same selection in torch
+        - the same graph.
         """
         if isinstance(distance, profile_alignment):
             raise ValueError(self._PROFILE_QUERIES_ONLY.format("rescore"))
@@ -1358,18 +1361,25 @@ class Prograph:
         whole = not query and row0 == 0 and nrows == n
         Y = Q if whole else Q[row0:row0 + nrows]
         score = mode != _alignments.GLOBAL
-        kernel = (_native.aln_list_ready() and nrows > 0 and max(X.shape[1], Y.shape[1]) <= _native.ALN_MAX_L
+        width = max(X.shape[1], Y.shape[1])
+        kernel = (_native.aln_list_ready() and nrows > 0 and width <= _native.ALN_MAX_L
                   and (mode != _alignments.FIT
                        or _native.aln_fit_fits(X.shape[1], Y.shape[1], distance.max_score, distance.gap, distance.gap_open)))
+        # 129..2048 positions: the long list kernel, inside the mode's own 16-bit bound (the long dense kernels')
+        long = (nrows > 0 and _native.ALN_MAX_L < width <= _native.ALN_LONG_MAX_L and _native.aln_list_long_ready()
+                and (_native.aln_long_fits(width, distance.max_cost, distance.gap, distance.gap_open) if mode == _alignments.GLOBAL
+                     else distance._long_fits(X.shape[1], Y.shape[1])))
         selects = k <= _native.MAX_K_ROUNDS if k is not None else (eps is None or comp in _CMP_CODE)
-        fast = kernel and selects
+        fast = (kernel or long) and selects
         if fast:
             dev = _native.device()
-            xo = _native.aln_operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
-            yo = xo if whole else _native.aln_operand(torch.from_numpy(np.ascontiguousarray(Y)), distance.symbols)
+            operand, scores = (_native.aln_long_operand, _native.alignment_list_long_scores) if long else \
+                (_native.aln_operand, _native.alignment_list_scores)
+            xo = operand(torch.from_numpy(np.ascontiguousarray(X)), distance.symbols)
+            yo = xo if whole else operand(torch.from_numpy(np.ascontiguousarray(Y)), distance.symbols)
             indptr, cols = indptr.to(dev), cols.to(dev)
-            ss = _native.alignment_list_scores(xo, yo, indptr, cols.to(torch.int32), mode, _alignments._device_table(distance, mode),
-                                               distance.gap, distance.gap_open)
+            ss = scores(xo, yo, indptr, cols.to(torch.int32), mode, _alignments._device_table(distance, mode), distance.gap,
+                        distance.gap_open)
         else:
             g0 = CSRGraph(indptr.cpu(), cols.cpu().to(torch.int32), torch.zeros(cols.numel(), dtype=torch.int32), n, row0=row0)
             tb = self.align(g0, queries=queries, idxs=idxs, distance=distance, representation=representation, ops=False)
