@@ -7,6 +7,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "_build", "liboracle.so")
+_SRC = os.path.join(_HERE, "oracle.c")
 _lib = None
 
 
@@ -17,7 +18,8 @@ def build():
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(_SO):
+        # a library older than its source would lack what the source has gained since: make knows the dependency
+        if not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(_SRC):
             build()
         # a bounded team: the GPU boxes show hundreds of CPUs but grant a share of them
         os.environ.setdefault("OMP_NUM_THREADS", str(min(32, os.cpu_count() or 1)))
@@ -84,3 +86,18 @@ def lev_knn(T, k, band=8, row0=0, nrows=None):
     lib().orc_lev_knn(_p(T), ctypes.c_int64(n), ctypes.c_int(l), ctypes.c_int64(row0), ctypes.c_int64(nrows),
                       ctypes.c_int(band), ctypes.c_int(k), _p(idx), _p(d))
     return idx, d
+
+
+def lev_matrix(X, Y, dtype=np.int64):
+    """(M, N) unbanded edit distances of the non-zero prefixes of the rows of Y against those of the rows of X
+    (orc_lev_matrix): zero-right-padded uint8 rows, the two operands at their own widths of up to 2048; int32 or int64."""
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.uint8); Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=np.uint8)
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise TypeError("lev_matrix: int32 or int64")
+    if X.shape[1] > 2048 or Y.shape[1] > 2048:
+        raise ValueError("lev_matrix: at most 2048 positions per operand")
+    out = np.empty((Y.shape[0], X.shape[0]), dtype=dtype)
+    lib().orc_lev_matrix(_p(X), ctypes.c_int64(X.shape[0]), ctypes.c_int(X.shape[1]), _p(Y), ctypes.c_int64(Y.shape[0]),
+                         ctypes.c_int(Y.shape[1]), _p(out), ctypes.c_int(dtype.itemsize))
+    return out

@@ -238,3 +238,42 @@ void orc_lev_knn(const uint8_t *T, int64_t n, int l, int64_t row0, int64_t nrows
   }
   free(lens);
 }
+
+/* ---------------------------------------------------------------------------------------
+ * Unbanded Levenshtein matrix — BUILD DEFINED (no reference counterpart).
+ * out[r * n + c] = edit distance (unit costs) of the non-zero prefix of Y row r against the
+ * non-zero prefix of X row c: the plain Wagner–Fischer table kept as two rows.  X is (n, lx),
+ * Y is (m, ly), zero right-padded, lx and ly up to 2048.  out is int32 (out_bytes 4) or int64 (8).
+ * Pinned against the numpy references in tests/test_levenshtein_every_length_cpu.py.
+ * ------------------------------------------------------------------------------------- */
+#define ORC_LEV_MATRIX_MAX 2048
+void orc_lev_matrix(const uint8_t *X, int64_t n, int lx, const uint8_t *Y, int64_t m, int ly, void *out, int out_bytes) {
+  if (lx > ORC_LEV_MATRIX_MAX || ly > ORC_LEV_MATRIX_MAX || lx < 0 || ly < 0) return;
+  int *xlens = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
+  for (int64_t c = 0; c < n; ++c) xlens[c] = seq_len(X + c * lx, lx);
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int64_t r = 0; r < m; ++r) {
+    const uint8_t *a = Y + r * ly;
+    const int la = seq_len(a, ly);
+    int rowa[ORC_LEV_MATRIX_MAX + 1], rowb[ORC_LEV_MATRIX_MAX + 1];
+    for (int64_t c = 0; c < n; ++c) {
+      const uint8_t *b = X + c * lx;
+      const int lb = xlens[c];
+      int *prev = rowa, *cur = rowb;
+      for (int j = 0; j <= lb; ++j) prev[j] = j;
+      for (int i = 1; i <= la; ++i) {
+        cur[0] = i;
+        for (int j = 1; j <= lb; ++j) {
+          int v = prev[j - 1] + (a[i - 1] != b[j - 1]);
+          if (prev[j] + 1 < v) v = prev[j] + 1;
+          if (cur[j - 1] + 1 < v) v = cur[j - 1] + 1;
+          cur[j] = v;
+        }
+        int *t = prev; prev = cur; cur = t;
+      }
+      if (out_bytes == 8) ((int64_t *)out)[r * n + c] = prev[lb];
+      else ((int32_t *)out)[r * n + c] = prev[lb];
+    }
+  }
+  free(xlens);
+}

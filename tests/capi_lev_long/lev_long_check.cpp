@@ -2,7 +2,8 @@
 // (prograph_amd/csrc/pg_lev_long.h) compiled for the host and driven exactly as pg_levenshtein_long_dense_kernel drives
 // them - operand blocks of five bit planes, the text in chunks of 128 positions with a mask table of 129 entries, the
 // pattern blocks inside, four shift-register pairs between two blocks - at every block count the kernel is instantiated
-// for, against a plain Wagner-Fischer written here.  Built with the address and undefined-behaviour sanitizers.
+// for, against a plain Wagner-Fischer written here: boundary lengths up to 2048 in every family, and every text and every
+// pattern length 0..260 against a set of lengths.  Built with the address and undefined-behaviour sanitizers.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -186,6 +187,33 @@ static int check_pair(int fam, int la, int lb) {
   return 0;
 }
 
+// One pair of the every-length sweep: the pattern at its own width, at every instance that width admits, the wave
+// running the pattern's own blocks and every block of the instance.
+static int sweep_pair(int fam, int la, int lb) {
+  Seq x, y;
+  make_pair(fam, la, lb, x, y);
+  const int want = wagner_fischer(y, x);
+  ++checked;
+  const int need = pg_ll::blocks_of(lb);
+  const Packed px = pack(x, std::max(lb, 1)), py = pack(y, std::max(la, 1));
+  const int inst = pg_ll::instance_of(pg_ll::blocks_of(px.width));
+  static const int NBS[] = {1, 2, 4, 8, 16};
+  for (int nb : NBS) {
+    if (nb < inst) continue;
+    const int nbws[2] = {need, nb};
+    for (int t = 0; t < 2; ++t) {
+      const int got = distance_at(nb, px, py, nbws[t]);
+      ++runs;
+      if (got != want) {
+        printf("FAIL sweep %s la=%d lb=%d width=%d NB=%d blocks run=%d: got %d, want %d\n", FAMILY[fam], la, lb, px.width, nb,
+               nbws[t], got, want);
+        return 1;
+      }
+    }
+  }
+  return 0;
+}
+
 int main() {
   parent.resize(PG_LEV_LONG_MAX_L);
   for (auto &t : parent) t = (unsigned char)(1 + rnd(31));
@@ -215,6 +243,16 @@ int main() {
   // the closed forms at full length
   for (int fam = 0; fam < NFAM; ++fam)
     if (check_pair(fam, 2048, 2048) || check_pair(fam, 0, 2048) || check_pair(fam, 2048, 0)) return 1;
+  // every text length 0..260 against a set of pattern lengths, every pattern length 0..260 against the same set as text
+  // lengths: every tail and trip count of segment(), every (dword, bit) of the read-off in the first three blocks
+  static const int SWEEP[] = {0, 1, 31, 32, 33, 127, 128, 129, 200, 257};
+  int turn = 0;
+  for (int l = 0; l <= 260; ++l)
+    for (int o : SWEEP) {                                           // the families in turn, each way through all of them
+      if (sweep_pair(turn % NFAM, l, o) || sweep_pair((turn + 3) % NFAM, o, l)) return 1;
+      ++turn;
+    }
+  printf("every-length sweep: lengths 0..260 against %d lengths, both ways\n", (int)(sizeof(SWEEP) / sizeof(SWEEP[0])));
   printf("lev_long host check OK: %ld pairs, %ld kernel-order evaluations, block counts 1 2 4 8 16\n", checked, runs);
   return 0;
 }
