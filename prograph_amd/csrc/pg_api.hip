@@ -2,6 +2,7 @@
 // plane packing, exclusive scan, flag compaction and the fused 1xN indexing pass.
 #include "pg_common.h"
 #include "pg_mm.h"
+#include "pg_plan.h"   // host-only: the planners, the workspace layout, the knobs
 #include "../../include/prograph_hip.h"
 
 #include <dlfcn.h>
@@ -17,8 +18,9 @@ static thread_local char g_err[256] = "";
 
 void pg_set_error(const char *msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
-// stage-1 lower-bound filter of the engine: adaptive by default; PG_LB_FILTER=0 disables, =2 forces it on
-static int lb_filter_mode() { return getenv("PG_LB_FILTER") ? atoi(getenv("PG_LB_FILTER")) : 1; }
+// the PG_* knobs of a C-ABI call (table and reader: pg_plan.h), read from the environment once per call
+extern char **environ;
+static PgKnobs read_knobs() { return pg_knobs_read(environ); }
 
 // compute units of the CURRENT device (cached per device: a process may drive several)
 #define PG_MAX_DEVICES 64
@@ -32,15 +34,6 @@ static int cu_count() {
   if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
   if (cached) cus[dev].store(prop.multiProcessorCount, std::memory_order_relaxed);
   return prop.multiProcessorCount;
-}
-
-// waves per CU the all-pairs engine is sized for (PG_WAVES_PER_CU overrides; multiples of 4)
-static int waves_per_cu() {
-  const char *e = getenv("PG_WAVES_PER_CU");
-  int w = e ? atoi(e) : 32;
-  if (w < 4) w = 4;
-  if (w > 128) w = 128;
-  return (w / 4) * 4;
 }
 
 extern "C" {
@@ -62,101 +55,15 @@ int pg_device_info(int *cus, int *wave, char *arch, int arch_len) {
 }
 
 int64_t pg_npad(int64_t n) { return n <= 0 ? 256 : ((n + 255) / 256) * 256; }
-int pg_ngroups(int l) { return l <= 0 ? 1 : (l + 31) / 32; }
-int pg_nchunks(int l, int bits) { return (pg_ngroups(l) * bits + 3) / 4; }
+int pg_ngroups(int l) { return plan_ngroups(l); }
+int pg_nchunks(int l, int bits) { return plan_nchunks(l, bits); }
 int64_t pg_planes_bytes(int64_t n, int l, int bits) { return ((int64_t)pg_nchunks(l, bits) * 16 + PG_AUX_BYTES) * pg_npad(n); }
-// launch-private device state of an all-pairs call, sized by the row count:
-//   [0, 64)      pass counters of the engine's persistent waves (words 0 and 8: a call's main launch and its gated 32-row
-//                alternative) and, word 1, the number of evicted rows                        - zeroed by the call
-//   [64, 576)    word 16 (byte 64): the pass counter of the symmetric kNN sweep; word 17: the ticket of its merge's
-//                workgroups (the last one decides); the rest reserved - zeroed with the counters
-//   [576, 640)   decision words (gates): [0], [1] the probe's (pg_decide_kernel); [2] the word the launches BEHIND a
-//                symmetric kNN sweep test (pg_knn_sym_merge_kernel's last workgroup: the probe's gate[0] - 0 without a probe - or 3 =
-//                the sweep's results stand, only pg_knn_rows_kernel still runs)
-//   [640, ...)   the probe's counts (8 * PG_PROBE_ROWS * PG_PROBE_WAVES bytes)
-//   from PG_WS_PARTIAL on, launches of more than PG_SPLIT_MIN_ROWS rows: the lists of the column pieces - at most
-//                PG_SPLIT_MAX_ROWS rows x 8 pieces (or half of them x 16) x PG_MM_KL keys; then the evicted rows (below)
-#define PG_WS_FLAGS 64
-#define PG_WS_GATES 576
-#define PG_WS_COUNTS 640
-#define PG_WS_PARTIAL (PG_WS_COUNTS + 8 * 64 * 128)
-#define PG_SPLIT_MAX_ROWS 8192       // 128 row blocks of 64
-#define PG_SPLIT_MIN_ROWS 65536     // (launches up to here never split)
-#define PG_SYM_MIN_N 65536          // the symmetric kNN sweep is not chosen below (= PG_PROBE_MIN_N: launches that are probed)
-#define PG_WS_PARTIAL_BYTES ((int64_t)PG_SPLIT_MAX_ROWS * 8 * PG_MM_KL * 4)
-// ... and behind that (every launch) one word per row: the rows a kNN launch of the MFMA engine evicts (NsqParams::mmEvict;
-// their number: word 1 of the counter line)
-static int64_t ws_evict_offset(int64_t nrows) { return PG_WS_PARTIAL + (nrows > PG_SPLIT_MIN_ROWS ? PG_WS_PARTIAL_BYTES : 0); }
-static int64_t ws_sym_offset(int64_t nrows) { return (ws_evict_offset(nrows) + 4 * (nrows > 0 ? nrows : 0) + 64 + 255) / 256 * 256; }
-static int64_t sym_ws_bytes(int64_t n);
-// ... and behind that, launches the symmetric kNN sweep may take (knn_launch: self graphs from PG_PROBE_MIN_N rows on): its
-// plan, the lists of its passes and the delivered keys (sym_ws_bytes below: N x capL x 4 bytes the largest part)
-int64_t pg_workspace_bytes(int64_t nrows) { return ws_sym_offset(nrows) + sym_ws_bytes(nrows); }
+// launch-private device state of an all-pairs call, sized by the row count (the layout: pg_plan.h)
+int64_t pg_workspace_bytes(int64_t nrows) { return workspace_bytes(nrows, cu_count(), read_knobs()); }
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------------
-// The plan of the symmetric kNN sweep (pg_mm_knn_sym_kernel): row block b (64 rows) sweeps the super-tiles from its own,
-// b >> 1, to the last one - a triangle of about half the rectangular sweep's visits - and the persistent grid holds one
-// wave per slot, so the blocks are cut into PIECES and handed out through the pass counter in block order, longest
-// first.  The cut is guided: a block's pieces are about (visits still to hand out) / slots long, at least `pmin` - long
-// pieces while there is much left to balance with, short ones at the end, where the waves' finishing times are evened
-// out (a fixed length needs ~6 pieces per wave for a makespan within 10 % of the mean; this rule is within 2 % at 200 000
-// rows with half as many).  piece > 0: every block in pieces of that length (tests, experiments).  Boundaries inside a
-// block fall on even super-tiles (the folded form's tiles are pairs); a piece is at least three super-tiles before
-// that rounding, so none is empty.  The same code runs on the host (pg_knn_sym_plan: tests, sizes) and in
-// pg_knn_sym_plan_kernel, which writes the plan of a launch into its workspace.
-// ---------------------------------------------------------------------------------------
-__host__ __device__ static inline int sym_block_pieces(long long b, long long nst, long long slots, int piece, int pmin) {
-  const long long len = nst - (b >> 1);
-  // visits of the blocks from b on (two blocks per super-tile; a missing last block does not matter to a length rule)
-  const long long rem = len * (len + 1) - ((b & 1) ? len : 0);
-  long long P = piece > 0 ? piece : (rem / (slots > 0 ? slots : 1)) & ~1ll;
-  if (piece <= 0 && P < pmin) P = pmin;
-  if (P < 3) P = 3;
-  if (P > len) P = len > 3 ? len : 3;
-  unsigned np = ((unsigned)len + (unsigned)P - 1u) / (unsigned)P;      // (32-bit: len < 2^17)
-  if (np > (unsigned)len / 3u) np = (unsigned)len / 3u;
-  if (np > PG_SYM_MAX_PIECES) np = PG_SYM_MAX_PIECES;
-  return np < 1 ? 1 : (int)np;
-}
-// piece q of np of block b: super-tiles [first, end)
-__host__ __device__ static inline void sym_piece_range(long long b, long long nst, int np, int q, int *first, int *end) {
-  // (32-bit: nst < 2^17 super-tiles at 2^24 columns, np <= 16)
-  const unsigned s0 = (unsigned)(b >> 1), len = (unsigned)nst - s0, unp = (unsigned)np, uq = (unsigned)q;
-  *first = q == 0 ? (int)s0 : (int)(2u * ((s0 + len * uq / unp + 1u) / 2u));
-  *end = q + 1 == np ? (int)nst : (int)(2u * ((s0 + len * (uq + 1u) / unp + 1u) / 2u));
-}
-static long long sym_plan_host(long long n, long long slots, int piece, int pmin, int32_t *out, long long cap) {
-  const long long nb = (n + 63) / 64, nst = (n + PG_MM_ST - 1) / PG_MM_ST;
-  // the number of passes alone (every call sizes its workspace by it): the last few answers are kept - a walk over all
-  // row blocks costs tens of microseconds on the host at 200 000 rows, which a short launch would show
-  struct Memo { long long n, slots, count; int piece, pmin; };
-  static std::mutex memoLock;
-  static Memo memo[4] = {};
-  static int memoNext = 0;
-  if (!out) {
-    std::lock_guard<std::mutex> g(memoLock);
-    for (const Memo &m : memo)
-      if (m.n == n && m.slots == slots && m.piece == piece && m.pmin == pmin && m.count > 0) return m.count;
-  }
-  long long at = 0;
-  for (long long b = 0; b < nb; ++b) {
-    const int np = sym_block_pieces(b, nst, slots, piece, pmin);
-    for (int q = 0; q < np; ++q, ++at) {
-      if (!out || at >= cap) continue;
-      int f, e;
-      sym_piece_range(b, nst, np, q, &f, &e);
-      out[4 * at] = (int)b; out[4 * at + 1] = f; out[4 * at + 2] = e; out[4 * at + 3] = q;
-    }
-  }
-  if (!out) {
-    std::lock_guard<std::mutex> g(memoLock);
-    memo[memoNext] = Memo{n, slots, at, piece, pmin};
-    memoNext = (memoNext + 1) % 4;
-  }
-  return at;
-}
+// The plan of the symmetric kNN sweep on the device (sym_block_pieces, sym_piece_range: pg_plan.h - the same code as the host's).
 // workgroup 0: thread t takes a contiguous run of blocks - their piece counts, a scan over the threads, then the
 // entries and pieceStart[b] = the first pass of block b (pieceStart[nb] = passes in all).  The workgroups behind it zero
 // the rows' counts of delivered keys meanwhile (`zero4` uint4 of lowCount: the launch's memset, folded in)
@@ -191,51 +98,13 @@ __global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(long long nb, lon
   }
   if (t == 1023) pieceStart[nb] = sums[1023];
 }
-// knobs of the symmetric kNN sweep: PG_KNN_SYM = 0 off / 1 forced wherever the MFMA engine runs the short-list kNN;
-// PG_KNN_SYM_CAPL delivered keys per row (8..256); PG_KNN_SYM_PIECE fixed piece length in super-tiles (default: guided);
-// PG_KNN_SYM_PIECE_MIN the guided rule's shortest piece; PG_KNN_SYM_OCC waves per SIMD the plan counts on;
-// PG_KNN_SYM_MERGE_WGS workgroups of the merge at most (default: eight a CU)
-static int sym_env() { return getenv("PG_KNN_SYM") ? atoi(getenv("PG_KNN_SYM")) : -1; }
-static u32 sym_capl() {
-  const int v = getenv("PG_KNN_SYM_CAPL") ? atoi(getenv("PG_KNN_SYM_CAPL")) : PG_SYM_MAX_CAPL;
-  return (u32)(v < 8 ? 8 : (v > PG_SYM_MAX_CAPL ? PG_SYM_MAX_CAPL : v));
-}
-static int sym_piece() { return getenv("PG_KNN_SYM_PIECE") ? atoi(getenv("PG_KNN_SYM_PIECE")) : 0; }
-static int sym_piece_min() {
-  const int v = getenv("PG_KNN_SYM_PIECE_MIN") ? atoi(getenv("PG_KNN_SYM_PIECE_MIN")) : 32;
-  return v < 4 ? 4 : v;
-}
-static long long sym_slots(int occ) {
-  if (const char *e = getenv("PG_KNN_SYM_OCC")) { if (atoi(e) >= 1 && atoi(e) <= 4) occ = atoi(e); }
-  return (long long)(cu_count() > 0 ? cu_count() : 256) * 4 * (occ < 1 ? 1 : (occ > 4 ? 4 : occ));
-}
-// workspace of the symmetric sweep behind ws_sym_offset: plan (16 bytes a pass), pieceStart, lowCount, the passes' lists
-// (sized for the most waves per SIMD the instance can hold, PG_MM_KL keys a row), lowKeys.  0: no such launch at n rows
-struct SymWs { int64_t plan, pieceStart, lowCount, partial, lowKeys, bytes; long long maxPasses; };
-static SymWs sym_ws(int64_t n) {
-  SymWs w = {0, 0, 0, 0, 0, 0, 0};
-  const int env = sym_env();
-  if (n <= 0 || n > PG_MAX_N_KNN || env == 0 || (env != 1 && n < PG_SYM_MIN_N)) return w;
-  auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
-  const long long nb = (n + 63) / 64;
-  w.maxPasses = sym_plan_host(n, sym_slots(4), sym_piece(), sym_piece_min(), nullptr, 0);
-  w.plan = 0;
-  w.pieceStart = up(w.plan + 16 * w.maxPasses);
-  w.lowCount = up(w.pieceStart + 4 * (nb + 1));
-  w.partial = up(w.lowCount + 4 * n);
-  w.lowKeys = up(w.partial + w.maxPasses * 64 * PG_MM_KL * 4);
-  w.bytes = up(w.lowKeys + n * (int64_t)sym_capl() * 4);
-  return w;
-}
-static int64_t sym_ws_bytes(int64_t n) { return sym_ws(n).bytes; }
-
 extern "C" {
 // the plan of the symmetric kNN sweep of an n x n self graph for `slots` waves (host only, no device needed): up to
 // max_passes entries (row block, first super-tile, end super-tile, piece of the block) to out[4 * i ..]; returns the
 // number of passes.  piece > 0: fixed piece length; piece_min: the guided rule's shortest piece (0: the default)
 int64_t pg_knn_sym_plan(int64_t n, int64_t slots, int piece, int piece_min, int32_t *out, int64_t max_passes) {
   if (n <= 0 || slots <= 0) return pg_fail(PG_E_BADARG, "pg_knn_sym_plan: bad argument");
-  return sym_plan_host(n, slots, piece, piece_min > 0 ? piece_min : sym_piece_min(), out, max_passes);
+  return sym_plan_host(n, slots, piece, piece_min > 0 ? piece_min : (int)read_knobs().symPieceMin.v, out, max_passes);
 }
 }  // extern "C"
 
@@ -587,10 +456,7 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 //            the probe chose another engine or instance, 0 where the sweep evicted more rows than its limit (the
 //            rectangular launch runs), 3 where its results stand (pg_knn_rows_kernel alone runs, for its evicted rows)
 // ---------------------------------------------------------------------------------------
-#define PG_PROBE_ROWS 64        // sample rows
-#define PG_PROBE_WAVES 128      // waves per sample row: every 8th column tile (PG_PROBE_STRIDE), one turn of four tiles each at N = 200k
-                                // (a turn = one L2 / Infinity-Cache round trip, ~2 us: 1 x 1 wave 206 us, 64 x 4 67 us, 64 x 32 22 us)
-#define PG_PROBE_MIN_N 65536    // launches below this are not probed: the probe (~20 us) would show, and the size rules hold
+// (PG_PROBE_ROWS, PG_PROBE_WAVES, PG_PROBE_MIN_N: pg_plan.h)
 // one workgroup: 16 threads per sample row (a quarter wave) sum the row's per-wave counts, the wave of a row then the
 // workgroup combine the verdicts
 __global__ __launch_bounds__(1024) void pg_decide_kernel(const u32 *counts, int nsample, int wavesPerRow, u32 need, long long ncols,
@@ -812,28 +678,23 @@ static const knn_rows_fn kKnnRows[8] = {pg_launch_knn_rows_g1, pg_launch_knn_row
                                         pg_launch_knn_rows_g5, pg_launch_knn_rows_g6, pg_launch_knn_rows_g7, pg_launch_knn_rows_g8};
 static const probe_fn kProbe[8] = {pg_launch_probe_g1, pg_launch_probe_g2, pg_launch_probe_g3, pg_launch_probe_g4,
                                    pg_launch_probe_g5, pg_launch_probe_g6, pg_launch_probe_g7, pg_launch_probe_g8};
-// PG_PROBE=0: no probe (the size rules alone); PG_GATE_FORCE=<bits>: the decision is forced (tests): bit 0 gate[0], bit 1 gate[1]
-static bool probe_enabled() {
-  const char *e = getenv("PG_PROBE");
-  return !(e && atoi(e) == 0) && !getenv("PG_ENGINE") && !getenv("PG_ENGINE_MIN_ROWS");
-}
+// (whether a launch is probed: probe_enabled, pg_plan.h; PG_GATE_FORCE=<bits>: the decision is forced (tests): bit 0 gate[0], bit 1 gate[1])
 // zeroes workspace[0, 576) (the counter block: pass_counter issues no fill behind a probe) and fills workspace[576, ...):
 // returns the gate words through *gate
 static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 span, u32 need, void *workspace, hipStream_t s,
-                     const u32 **gate) {
+                     const PgKnobs &kn, const u32 **gate) {
   if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
   u32 *gates = (u32 *)((char *)workspace + PG_WS_GATES), *counts = (u32 *)((char *)workspace + PG_WS_COUNTS);
-  static_assert(PG_WS_COUNTS + 8 * PG_PROBE_ROWS * PG_PROBE_WAVES <= PG_WS_PARTIAL, "pg_workspace_bytes");
   ProbeParams pp;
   pp.rowPlanes = e.rowPlanes; pp.colPlanes = e.colPlanes; pp.rowNpad = e.rowNpad; pp.colNpad = e.colNpad;
   pp.row0 = e.row0; pp.nrows = e.nrows; pp.ncols = e.ncols;
   pp.nsample = e.nrows < PG_PROBE_ROWS ? (int)e.nrows : PG_PROBE_ROWS;
   pp.wavesPerRow = PG_PROBE_WAVES;
-  if (const char *es = getenv("PG_PROBE_S")) { if (atoi(es) > 0 && atoi(es) <= PG_PROBE_ROWS) pp.nsample = atoi(es); }   // (experiments)
-  if (const char *ew = getenv("PG_PROBE_W")) { if (atoi(ew) > 0 && atoi(ew) <= PG_PROBE_WAVES) pp.wavesPerRow = atoi(ew); }
+  if (kn.probeS.v > 0) pp.nsample = (int)kn.probeS.v;       // (experiments)
+  if (kn.probeW.v > 0) pp.wavesPerRow = (int)kn.probeW.v;
   pp.near = near; pp.lo = lo; pp.span = span; pp.counts = counts;
   if (int rc = pg_launched(kProbe[pg_ngroups(l) - 1](bits, pp, s), "pg_probe_kernel")) return rc;
-  const int force = getenv("PG_GATE_FORCE") ? atoi(getenv("PG_GATE_FORCE")) : -1;
+  const int force = (int)kn.gateForce.v;
   // (counts of a short sample: pg_decide_kernel reads counts[nsample + s] - same layout as the probe wrote)
   static_assert(PG_WS_GATES / 4 <= 1024, "pg_decide_kernel zeroes one word per thread");
   pg_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates, (u32 *)workspace,
@@ -869,62 +730,17 @@ static const compact_fn kCompact[8] = {pg_launch_compact_g1, pg_launch_compact_g
                                        pg_launch_compact_g4, pg_launch_compact_g5, pg_launch_compact_g6,
                                        pg_launch_compact_g7, pg_launch_compact_g8};
 
-// Static, even split of the rows over the waves: every row costs the same (one sweep over all
-// columns), so equal row counts are equal work.  The kernel is VALU-issue bound and a workgroup
-// puts one wave on each SIMD of its CU, so the run time follows the busiest SIMD:
-//     makespan ~ (rows_per_wave + 1) * sum over rounds of T(waves in the round),
-//     n = ceil(workgroups / CUs) waves per SIMD run in rounds of `occ` residents (the instance's
-//     occupancy), T(1..8) = 2.2, 3.1, 3.7, 4.3, 5.1, 6, 7, 8
-// (the +1 is the per-wave cost of streaming the column tiles, ~1 row-equivalent; T(m) reflects
-// that fewer than ~5 waves cannot keep the VALU issuing: one wave alone issues under half of the
-// time.  Fitted to tools/sweep_rpw.py at N = 50k and 200k, within ~8 %).  rows_per_wave is chosen
-// among the multiples of 4 up to one pass (PG_RB) to minimise that; ties go to the larger value
-// (fewer column re-reads).  More than PG_RB rows per wave (only with the PG_WAVES_PER_CU /
-// PG_ROWS_PER_WAVE overrides) are walked in passes of nearly equal size.
-// Second term: every wave streams the whole column matrix (ncols * Q * 16 bytes).  While that fits
-// the L2s the stream is hidden; beyond (cfg4: 48 MB) the sweep becomes bound by L2-miss traffic
-// served from the Infinity Cache: measured 11.5-15 TB/s aggregate at 48 MB, ~18-20 at 24 MB
-// (tools/sweep_rpw_big.py; N = 1M, 125k rows: 16 rows per wave 28.8 ms, 24 rows 20.5 ms).  The plan
-// minimises max(VALU makespan, streamed bytes / bandwidth) with bandwidth = 13 TB/s * (48 MB / bytes)^0.65
-// (capped at 4x) and 1.21e-11 s per makespan unit and column.
-static int plan_rows(int64_t nrows, NsqParams *p, int *grid, int occ, double recBytes, int maxRows = PG_RB) {
+// The row split of a VALU-engine launch (plan_rows, pg_plan.h) goes into its parameters
+static void set_rows_plan(NsqParams *p, int *grid, const PassPlan &pl, const PgKnobs &kn) {
+  if (kn.debugPlan.set) fprintf(stderr, "[pg plan] rows=%lld occ=%d rows_per_wave=%lld waves=%lld\n", (long long)p->nrows, pl.occ, (long long)pl.rowsPerWave, pl.passes);
+  p->rowsPerWave = pl.rowsPerWave; p->rowsPerPass = pl.rowsPerPass;
+  *grid = pl.grid;
+}
+// ... planned here, for the device of the call; no device, no launch
+static int plan_rows_here(NsqParams *p, int *grid, int occ, double recBytes, const PgKnobs &kn, int maxRows = PG_RB) {
   const int cus = cu_count();
   if (cus <= 0) return pg_fail(PG_E_NODEV, "no HIP device");
-  long long rpw = 4;
-  if (getenv("PG_WAVES_PER_CU")) {
-    const long long maxWaves = (long long)cus * waves_per_cu();
-    rpw = (nrows + maxWaves - 1) / maxWaves;
-    if (rpw < 1) rpw = 1;
-    // the filtered sweep takes rows four at a time: whole groups waste no stage-1 work
-    if (rpw >= 4) rpw = (rpw + 3) / 4 * 4;
-  } else {
-    static const long long kRound[9] = {0, 22, 31, 37, 43, 51, 60, 70, 80};   // T(m) x 10
-    if (occ < 1) occ = 1;
-    if (occ > 8) occ = 8;
-    const double matBytes = recBytes * (double)p->ncols;
-    double bw = 13e12;
-    if (matBytes > 0 && matBytes < 48e6) bw *= fmin(4.0, pow(48e6 / matBytes, 0.65));
-    double best = -1;
-    for (long long r = 4; r <= maxRows; r += 4) {
-      const long long nw = (nrows + r - 1) / r;
-      const long long wgs = (nw + PG_WG_WAVES - 1) / PG_WG_WAVES;
-      const long long n = (wgs + cus - 1) / cus;             // waves the busiest SIMD runs
-      const double valu = 1.21e-11 * (double)(((n / occ) * kRound[occ] + kRound[n % occ]) * (r + 1));
-      const double stream = (double)nw * recBytes / bw;      // both per column
-      const double cost = valu > stream ? valu : stream;
-      if (best < 0 || cost <= best * 1.0000001) { best = cost; rpw = r; }
-    }
-  }
-  if (const char *e = getenv("PG_ROWS_PER_WAVE")) { if (atoi(e) > 0) rpw = atoi(e); }   // tuning sweeps
-  const long long waves = (nrows + rpw - 1) / rpw;
-  if (getenv("PG_DEBUG_PLAN")) fprintf(stderr, "[pg plan] rows=%lld occ=%d rows_per_wave=%lld waves=%lld\n", (long long)nrows, occ, rpw, waves);
-  const long long passes = (rpw + maxRows - 1) / maxRows;
-  p->rowsPerWave = (int)rpw;
-  long long rpp = (rpw + passes - 1) / passes;
-  if (rpp >= 4) rpp = (rpp + 3) / 4 * 4;
-  if (rpp > maxRows) rpp = maxRows;
-  p->rowsPerPass = (int)rpp;
-  *grid = (int)((waves + PG_WG_WAVES - 1) / PG_WG_WAVES);
+  set_rows_plan(p, grid, plan_rows(p->nrows, p->ncols, cus, occ, recBytes, kn, maxRows), kn);
   return 0;
 }
 
@@ -997,14 +813,14 @@ int pg_hamming_dense(const void *x_planes, int64_t n, int64_t x_npad, const void
 }
 
 static int fill_nsq(NsqParams *p, const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows,
-                    const void *col_planes, int64_t col_npad, int64_t ncols, int l, int bits) {
+                    const void *col_planes, int64_t col_npad, int64_t ncols, int l, int bits, const PgKnobs &kn) {
   if (!row_planes || !col_planes || row0 < 0 || nrows <= 0 || ncols <= 0) return pg_fail(PG_E_BADARG, "bad argument");
   if (int rc = check_bits(bits)) return rc;
   if (int rc = check_l(l, bits)) return rc;
   if (col_npad < ncols || col_npad % 256 || row_npad < row0 + nrows) return pg_fail(PG_E_BADARG, "bad npad");
   if (ncols > 0x7fffffffLL) return pg_fail(PG_E_TOOMANY, "ncols exceeds int32 indices");
   memset(p, 0, sizeof(*p));
-  p->filter = lb_filter_mode();
+  p->filter = (int)kn.lbFilter.v;   // stage-1 lower-bound filter: adaptive by default; PG_LB_FILTER=0 disables, =2 forces it on
   p->rowPlanes = (const uint4 *)row_planes; p->rowNpad = row_npad; p->row0 = row0; p->nrows = nrows;
   p->colPlanes = (const uint4 *)col_planes; p->colNpad = col_npad; p->ncols = ncols;
   p->colSig = p->colPlanes + (long long)pg_nchunks(l, bits) * col_npad;
@@ -1013,23 +829,6 @@ static int fill_nsq(NsqParams *p, const void *row_planes, int64_t row_npad, int6
   return 0;
 }
 
-// Which all-pairs engine runs a Hamming launch: pg_mm.h (stage 1 on the matrix cores, passes of 32
-// rows per wave) or pg_nsq.h (stage 1 on the VALU, 4..32 rows per wave).  PG_ENGINE=mfma / valu forces one.
-// Auto: the MFMA engine from 8 waves per SIMD-column on, i.e. once 32-row passes fill the chip; below
-// that the VALU engine's finer row split keeps more CUs busy.
-static bool use_mm_engine(int64_t nrows, int l = 64, bool knn = true) {
-  if (const char *e = getenv("PG_ENGINE")) {
-    if (!strcmp(e, "mfma")) return true;
-    if (!strcmp(e, "valu")) return false;
-  }
-  // Since the MFMA engine queues its candidates lane-parallel (kNN, and eps slots too: pg_mm.h push_signs) it wins from
-  // ~20k rows for kNN (profiles/r03_engine_crossover.txt: N = 16k L = 64 0.24 vs 0.29 ms, L = 32 0.24 vs 0.20) and from
-  // ~28k for eps (N = 24k: 0.34 vs 0.27; 32k: 0.41 vs 0.53), ~36k for sequences of one group (L <= 32: only 32 signature
-  // bits; N = 50k L = 32 symmetric: 0.43 vs 0.53).  Round 2: 40k / 60k.
-  const long long dflt = knn ? 20000 : (l <= 32 ? 36000 : 28000);
-  const long long thr = getenv("PG_ENGINE_MIN_ROWS") ? atoll(getenv("PG_ENGINE_MIN_ROWS")) : dflt;
-  return nrows >= thr;
-}
 #ifdef PG_MM_STATS
 static unsigned long long *g_stats = nullptr;
 extern "C" int pg_debug_stats(unsigned long long *out12, int reset) {   // debug builds only (tools/mm_stats.py); PG_NSTAT counters
@@ -1057,75 +856,21 @@ static int mm_occupancy(int groups, int mode, int bits) {
   }
   return v;
 }
-// One pass per wave.  A pass takes up to 32 rows (the M of the MFMA tile) and the CU holds 16 waves (four
-// workgroups: LDS and VGPR bound), so the grid runs in rounds of `slots` passes.  When 32-row passes would not
-// even fill one round, the rows are spread over ~97 % of the slots in smaller passes, down to 16 rows (N=50k L=32
-// kNN 1.03 -> 0.90 ms, N=100k L=128 2.40 -> 2.16 ms; tools/rows_sweep.py, profiles/r02_rows_per_pass.txt).
-// PG_MM_TAIL=1 also shrinks the passes of the LAST round of a longer grid (mmTailFrom / mmTailRows): measured
-// slower (dense 200k: 12.5 -> 14.1 ms, cfg3 3.81 -> 3.90) - a round of 2154 full passes on half-empty SIMDs runs
-// faster per pass than 3830 passes of 18 rows on full ones - and therefore off.
-// PG_ROWS_PER_WAVE = uniform passes of that many rows (tuning sweeps).
-// occ: resident workgroups per CU of the instance (= waves per SIMD), mm_occupancy().
-// Single round (every pass gets a wave slot at once): what a launch takes follows the waves on its busiest SIMD, not the
-// rows per wave - every wave streams all column fragments through the matrix pipe whatever its row count (measured at
-// 200 000 columns, tools/dbg/balance*.py: one wave per SIMD 0.70 ms, two 0.79, three 0.94, four 1.10-1.14 with 32-row
-// passes; 1.26 / 1.52 / 1.87 for two / three / four waves of 64-row passes, the same for 48..64 rows).  So: the fewest
-// waves per SIMD that hold the rows, the rows spread evenly over exactly that many waves on every SIMD.  (Round 2 spread
-// the rows over ~97 % of ALL slots: 65 536 rows took 1.11 ms as 4096 passes of 16 rows, 0.79 as 2048 of 32.)
-static void plan_mm(int64_t nrows, NsqParams *p, int *grid, int rb = PG_MM_RB, int occ = 4, bool knn = false, int uniformRows = 0) {   // rb: rows per pass of the instance (32 or 64)
-  long long rpw = rb, tailFrom = (nrows + rb - 1) / rb, tailRows = rb;
-  const long long simds = (long long)(cu_count() > 0 ? cu_count() : 256) * 4;
-  const long long slots = simds * (occ < 1 ? 1 : occ);
-  const char *e = getenv("PG_ROWS_PER_WAVE");
-  const char *t = getenv("PG_MM_TAIL");
-  // eps launches keep round 2's spreading rule: their passes are not equal work (symmetric: a pass sweeps the columns
-  // above its rows only; matches cost per row) - tools/dbg/plan_ab.py: N = 50k eps <= 2 symmetric 0.58 ms against 0.79
-  const int planEnv = getenv("PG_MM_PLAN") ? atoi(getenv("PG_MM_PLAN")) : 0;               // (A/B: 2 = round 2's rule, 1 = the new one for eps too)
-  const bool oldPlan = planEnv == 2 || (!knn && planEnv != 1);
-  if ((e && atoi(e) > 0) || uniformRows > 0) {
-    const int want = e && atoi(e) > 0 ? atoi(e) : uniformRows;
-    rpw = want < rb ? want : rb;                            // (a wave sweeps one pass of at most rb rows at a time)
-    tailFrom = (nrows + rpw - 1) / rpw; tailRows = rpw;
-  } else if (!oldPlan) {
-    if (tailFrom <= slots) {
-      const long long w = (tailFrom + simds - 1) / simds;               // waves per SIMD
-      long long r = (nrows + w * simds - 1) / (w * simds);
-      r = (r + 1) / 2 * 2;
-      if (r < 4) r = 4;
-      if (r > rb) r = rb;
-      rpw = r; tailFrom = (nrows + r - 1) / r; tailRows = r;
-    }
-  } else {
-    const long long full = nrows / (slots * rb) * slots;                // passes of the full rounds
-    const long long rest = nrows - full * rb;
-    if (rest > 0 && (full == 0 || (t && atoi(t) == 1))) {
-      long long r = (long long)((double)rest / (0.97 * (double)slots)) + 1;
-      r = (r + 1) / 2 * 2;
-      if (r < 4) r = 4;
-      if (r > rb) r = rb;
-      if (full == 0 && r < 16) r = 16;                                  // a single round: at least half-filled MFMA tiles
-      tailFrom = full; tailRows = r;
-    }
-  }
-  p->rowsPerWave = (int)rpw; p->rowsPerPass = rb;
-  p->mmTailFrom = tailFrom; p->mmTailRows = (int)tailRows;
-  const long long headRows = tailFrom * rpw < nrows ? tailFrom * rpw : nrows;
-  const long long waves = tailFrom + (nrows - headRows + tailRows - 1) / tailRows;
-  if (getenv("PG_DEBUG_PLAN")) fprintf(stderr, "[pg plan mm] rows=%lld: %lld passes of %lld rows + %lld of %lld\n", (long long)nrows, tailFrom, rpw, waves - tailFrom, tailRows);
-  p->mmDenseL1 = getenv("PG_MM_L1") ? atoi(getenv("PG_MM_L1")) : PG_MM_DENSE_L1;
-  p->mmDenseL2 = getenv("PG_MM_L2") ? atoi(getenv("PG_MM_L2")) : PG_MM_DENSE_L2;
-  p->mmDirectRun = getenv("PG_MM_RUN") ? atoi(getenv("PG_MM_RUN")) : PG_MM_DIRECT_RUN;
-  if (p->mmDirectRun < 1) p->mmDirectRun = 1;
+// The pass plan of an MFMA-engine launch over `nrows` rows (plan_mm, pg_plan.h) goes into its parameters, with the
+// engine's tuning knobs (*grid: its workgroups, where the caller has no plan of its own to read them from)
+static void set_mm_plan(NsqParams *p, int *grid, int64_t nrows, const PassPlan &pl, const PgKnobs &kn) {
+  p->rowsPerWave = pl.rowsPerWave; p->rowsPerPass = pl.rowsPerPass;
+  p->mmTailFrom = pl.tailFrom; p->mmTailRows = pl.tailRows;
+  if (kn.debugPlan.set) fprintf(stderr, "[pg plan mm] rows=%lld: %lld passes of %lld rows + %lld of %lld\n", (long long)nrows, pl.tailFrom, (long long)pl.rowsPerWave, pl.passes - pl.tailFrom, (long long)pl.tailRows);
+  p->mmDenseL1 = (int)kn.mmL1.v;
+  p->mmDenseL2 = (int)kn.mmL2.v;
+  p->mmDirectRun = (int)kn.mmRun.v;
 #ifdef PG_MM_STATS
   if (!g_stats) pg_debug_stats(nullptr, 1);
   p->stats = g_stats;
 #endif
-  // persistent waves: at most one per slot of the chip (whole workgroups), the rest of the passes through the counter
-  long long gridWaves = waves < slots ? waves : slots;
-  if (const char *pe = getenv("PG_MM_PERSISTENT")) { if (atoi(pe) == 0) gridWaves = waves; }
-  gridWaves = (gridWaves + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
-  p->mmPasses = waves; p->mmGridWaves = gridWaves;
-  *grid = (int)(gridWaves / PG_WG_WAVES);
+  p->mmPasses = pl.passes; p->mmGridWaves = pl.gridWaves;
+  if (grid) *grid = pl.grid;
 }
 // The pass counter of a launch lives in the caller's workspace (pg_workspace_bytes): zeroed on the launch's stream
 // right before the kernel.  Launch-private by contract, so concurrent launches - other streams, other devices,
@@ -1146,20 +891,21 @@ int pg_eps_slots(const void *row_planes, int64_t row_npad, int64_t row0, int64_t
                  int64_t col_npad, int64_t ncols, int l, int bits, int cmp, double eps, int cap, int32_t *slot_idx,
                  uint8_t *slot_w, uint32_t *counts, void *workspace, void *stream) {
   NsqParams p;
-  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
+  const PgKnobs kn = read_knobs();
+  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits, kn)) return rc;
   if (!slot_idx || !slot_w || !counts || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
     return pg_fail(PG_E_BADARG, "pg_eps_slots: bad argument");
   eps_interval(cmp, eps, &p.lo, &p.span);
   p.hi1 = (p.lo > 0xFFFFFF00u - 1u) ? 0u : p.lo + p.span + 1u;   // empty interval: nothing can match
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.counts = counts;
   int grid = 0;
-  p.epsOrdered = getenv("PG_EPS_ORDERED") && atoi(getenv("PG_EPS_ORDERED")) != 0;
-  if (use_mm_engine(nrows, l, false)) {
-    plan_mm(nrows, &p, &grid);
+  p.epsOrdered = kn.epsOrdered.v != 0;
+  if (use_mm_engine(nrows, kn, l, false)) {
+    set_mm_plan(&p, &grid, nrows, plan_mm(nrows, cu_count(), kn), kn);
     if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
     return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps)");
   }
-  if (int rc = plan_rows(nrows, &p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits))) return rc;
+  if (int rc = plan_rows_here(&p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits), kn)) return rc;
   return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps)");
 }
 
@@ -1170,7 +916,8 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
                      int32_t *slot_idx, uint8_t *slot_w, uint32_t *counts_up, uint32_t *counts_lo, void *workspace,
                      void *stream) {
   NsqParams p;
-  if (int rc = fill_nsq(&p, planes, npad, 0, n, planes, npad, n, l, bits)) return rc;
+  const PgKnobs kn = read_knobs();
+  if (int rc = fill_nsq(&p, planes, npad, 0, n, planes, npad, n, l, bits, kn)) return rc;
   if (!slot_idx || !slot_w || !counts_up || !counts_lo || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
     return pg_fail(PG_E_BADARG, "pg_eps_slots_sym: bad argument");
   if (n >= (1ll << 27)) return pg_fail(PG_E_TOOMANY, "pg_eps_slots_sym: n must be below 2^27");
@@ -1182,14 +929,14 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
   int grid = 0;
   // Large graphs: the data decide (probe above) between this path and a plain rectangular sweep on the VALU engine,
   // which writes the same slots (every match at the front of its row, counts_lo stays zero): dense graphs.
-  if (probe_enabled() && n >= PG_PROBE_MIN_N) {
+  if (probe_enabled(kn) && n >= PG_PROBE_MIN_N) {
     const u32 *gate = nullptr;
-    if (int rc = run_probe(p, l, bits, 0u, p.lo, p.span, 1u, workspace, (hipStream_t)stream, &gate)) return rc;
+    if (int rc = run_probe(p, l, bits, 0u, p.lo, p.span, 1u, workspace, (hipStream_t)stream, kn, &gate)) return rc;
     NsqParams r = p;
     r.countsLo = nullptr;
     r.gate = gate + 1; r.gateMask = 1u << 1;
     int rgrid = 0;
-    if (int rc = plan_rows(n, &r, &rgrid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits))) return rc;
+    if (int rc = plan_rows_here(&r, &rgrid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS, bits), 16.0 * pg_nchunks(l, bits), kn)) return rc;
     if (int rc = pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS, bits, r, rgrid, (hipStream_t)stream), "pg_nsq_kernel(eps, gated)")) return rc;
     p.gate = gate + 1; p.gateMask = 1u << 0;
   }
@@ -1197,8 +944,8 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
   // dispatched in row order, i.e. longest first, which balances by itself once there are a few
   // waves per resident slot.  Measured (tools/eps_sym_probe.py): 8 rows per wave at N = 50k, 16 at
   // N = 100k .. 200k (more rows: too few waves to balance; fewer: the per-wave column stream shows).
-  p.epsOrdered = getenv("PG_EPS_ORDERED") && atoi(getenv("PG_EPS_ORDERED")) != 0;
-  if (use_mm_engine(n, l, false)) {
+  p.epsOrdered = kn.epsOrdered.v != 0;
+  if (use_mm_engine(n, kn, l, false)) {
     // the symmetric sweep's passes are not equal work (a pass sweeps the columns above its rows): about one and a half
     // rounds of passes balance best (tools/dbg/eps_plan.py: N = 50k 8 rows per pass 0.40 ms against 0.43 / 0.59 for 14 / 32;
     // N = 100k 16 rows 0.61 against 0.66 / 0.71 for 26 / 32; N = 200k 32 rows 1.12 against 1.62 for 16)
@@ -1206,16 +953,16 @@ int pg_eps_slots_sym(const void *planes, int64_t npad, int64_t n, int l, int bit
     rs = (rs + 1) / 2 * 2;
     rs = rs < 8 ? 8 : (rs > PG_MM_RB ? PG_MM_RB : rs);
     // (records of up to three chunks - four waves per SIMD; longer ones, N = 100k L = 128: 0.75 against 0.67 with the old rule)
-    const bool fine = pg_nchunks(l, bits) <= 3 && !(getenv("PG_MM_PLAN") && atoi(getenv("PG_MM_PLAN")) == 2);
-    plan_mm(n, &p, &grid, PG_MM_RB, 4, false, fine ? (int)rs : 0);
+    const bool fine = pg_nchunks(l, bits) <= 3 && kn.mmPlan.v != 2;
+    set_mm_plan(&p, &grid, n, plan_mm(n, cu_count(), kn, PG_MM_RB, 4, false, fine ? (int)rs : 0), kn);
     if (int rc = pass_counter(&p, workspace, (hipStream_t)stream, p.gate != nullptr)) return rc;
     return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps sym)");
   }
-  if (!getenv("PG_ROWS_PER_WAVE") && !getenv("PG_WAVES_PER_CU")) {
+  if (!kn.rowsPerWave.set && !kn.wavesPerCu.set) {
     const long long r = n >= 80000 ? 16 : 8;
     p.rowsPerWave = (int)r; p.rowsPerPass = (int)r;
     grid = (int)(((n + r - 1) / r + PG_WG_WAVES - 1) / PG_WG_WAVES);
-  } else if (int rc = plan_rows(n, &p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS_SYM, bits), 16.0 * pg_nchunks(l, bits), 16)) {
+  } else if (int rc = plan_rows_here(&p, &grid, nsq_occupancy(pg_ngroups(l), PG_MODE_EPS_SYM, bits), 16.0 * pg_nchunks(l, bits), kn, 16)) {
     return rc;
   }
   return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_EPS_SYM, bits, p, grid, (hipStream_t)stream), "pg_nsq_kernel(eps sym)");
@@ -1227,7 +974,7 @@ int pg_eps_compact_sym(const void *planes, int64_t npad, int64_t n, int l, int b
                        int leave_overflow, void *stream) {
   CompactParams c;
   c.skipOverflow = leave_overflow ? 1 : 0;
-  if (int rc = fill_nsq(&c.e, planes, npad, 0, n, planes, npad, n, l, bits)) return rc;
+  if (int rc = fill_nsq(&c.e, planes, npad, 0, n, planes, npad, n, l, bits, read_knobs())) return rc;
   if (!slot_idx || !slot_w || !counts_up || !counts_lo || !indptr || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
     return pg_fail(PG_E_BADARG, "pg_eps_compact_sym: bad argument");
   eps_interval(cmp, eps, &c.e.lo, &c.e.span);
@@ -1263,7 +1010,7 @@ int pg_eps_compact(const void *row_planes, int64_t row_npad, int64_t row0, int64
                    int32_t *indices, uint8_t *weights, int leave_overflow, void *stream) {
   CompactParams c;
   c.skipOverflow = leave_overflow ? 1 : 0;
-  if (int rc = fill_nsq(&c.e, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
+  if (int rc = fill_nsq(&c.e, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits, read_knobs())) return rc;
   if (!slot_idx || !slot_w || !counts || !indptr || cap < 0 || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
     return pg_fail(PG_E_BADARG, "pg_eps_compact: bad argument");
   eps_interval(cmp, eps, &c.e.lo, &c.e.span);
@@ -1285,7 +1032,8 @@ int pg_eps_fill_rows(const void *row_planes, int64_t row_npad, int64_t row0, con
                      void *stream) {
   NsqParams p;
   if (!row_list || n_list <= 0) return pg_fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
-  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, n_list, col_planes, col_npad, ncols, l, bits)) return rc;
+  const PgKnobs kn = read_knobs();
+  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, n_list, col_planes, col_npad, ncols, l, bits, kn)) return rc;
   if (!indptr || !indices || !weights || !scratch_counts || cmp < PG_CMP_LE || cmp > PG_CMP_GT)
     return pg_fail(PG_E_BADARG, "pg_eps_fill_rows: bad argument");
   eps_interval(cmp, eps, &p.lo, &p.span);
@@ -1294,244 +1042,173 @@ int pg_eps_fill_rows(const void *row_planes, int64_t row_npad, int64_t row0, con
   p.rowList = (const long long *)row_list; p.fillIndptr = (const long long *)indptr;
   p.slotIdx = indices; p.slotW = weights; p.counts = scratch_counts;
   int grid = 0;
-  plan_mm(n_list, &p, &grid);
+  set_mm_plan(&p, &grid, n_list, plan_mm(n_list, cu_count(), kn), kn);
   if (int rc = pass_counter(&p, workspace, (hipStream_t)stream)) return rc;
   return pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_EPS, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(eps fill)");
 }
 
-// What a kNN launch of `nrows` rows x `ncols` columns takes (ms) on the 32-row (rb = 32) or the 64-row (rb = 64) short-list
-// instance, and which rows go into plain passes (*mainRows; the rest: column pieces, knn_launch).  A round of waves costs
-//     T(w, ncols) = S[w] + H[w] * ncols / 100 000,     w = waves on the busiest SIMD
-// (it follows the waves per SIMD, not the rows per wave: profiles/r03_pass_plan.txt).  S is what does not grow with the
-// columns - the candidates of a row's cluster mates, pass set-up, the tail - H the sweep itself; calibrated at 300 000
-// and 900 000 columns of cfg3-like data (tools/dbg/calib.py).  The 64-row instance sweeps twice the rows per fragment
-// (H per row 0.6 x) but pays more per pass: 131 072 rows x 200 000 columns 1.07 ms (32-row passes) against 1.27, x
-// 1 000 000 columns 4.9 against 3.6 (BASELINE configs[3]: one GPU's 125 000 x 1M block 5.5 -> 3.6 ms).
-//   one round   : T(w); with w >= 3 and at most 128 row blocks beyond w - 1 full waves: T(w - 1) + the pieces
-//   more rounds : whole rounds of full occupancy + (a last round: T(its waves) | at most 128 row blocks: the pieces)
-static double knn_plan_cost(long long nrows, long long ncols, int rb, int occ, bool canSplit, long long *mainRows) {
-  static const double S1[4] = {0.43, 0.42, 0.37, 0.12}, H1[4] = {0.148, 0.200, 0.294, 0.477};
-  static const double S2[4] = {0.64, 0.69, 0.64, 0.54}, H2[4] = {0.229, 0.292, 0.404, 0.557};
-  const bool big = rb > PG_MM_RB;
-  const double c = (double)ncols / 1e5, kPieces = 0.04 * c;
-  auto T = [&](long long w) { return (big ? S2 : S1)[w - 1] + (big ? H2 : H1)[w - 1] * c; };
-  const long long simds = (long long)(cu_count() > 0 ? cu_count() : 256) * 4;
-  occ = occ < 1 ? 1 : (occ > 4 ? 4 : occ);
-  const long long passes = (nrows + rb - 1) / rb, slots = simds * occ, maxRem = 128ll * rb;
-  *mainRows = nrows;
-  if (passes <= slots) {
-    const long long w = (passes + simds - 1) / simds;
-    if (canSplit && w >= 3 && nrows - (w - 1) * simds * rb <= maxRem) {
-      *mainRows = (w - 1) * simds * rb;
-      return T(w - 1) + kPieces;
-    }
-    return T(w);
+// ---------------------------------------------------------------------------------------
+// A kNN launch: check, gather the hardware numbers, read the knobs, plan (knn_plan, pg_plan.h: every decision and the
+// reasons), then run the plan's launches in order.  KnnRun is what the launches share; each launch_* below copies what
+// its KnnPlan says into parameters and issues one launch - none of them decides anything.
+// ---------------------------------------------------------------------------------------
+struct KnnRun {
+  const KnnPlan &pl;
+  const PgKnobs &kn;
+  NsqParams p;               // the main launch's parameters; the other launches start from a copy
+  int l, bits, ng, k;
+  int64_t row0, nrows;
+  int32_t *idx;
+  uint8_t *dist;
+  void *workspace;
+  hipStream_t stream;
+  u32 *gates() const { return (u32 *)((char *)workspace + PG_WS_GATES); }
+};
+// resident workgroups per CU of the instances a launch of this shape may use
+static KnnHw knn_hw(const KnnShape &s, const PgKnobs &kn) {
+  const int ng = pg_ngroups(s.l);
+  const bool shortList = knn_short_list(s, kn);
+  KnnHw hw;
+  hw.cus = cu_count();
+  hw.occValu = nsq_occupancy(ng, PG_MODE_KNN, s.bits);
+  hw.occMm32 = mm_occupancy(ng, shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN, s.bits);
+  hw.occMm64 = shortList ? mm_occupancy(ng, PG_MODE_KNN_SHORT2, s.bits) : 0;
+  static std::atomic<int> occCache[8];
+  int occS = occCache[ng - 1].load(std::memory_order_relaxed);
+  if (occS == 0) {
+    const int n = kMmSym[ng - 1](NsqParams(), -1, nullptr);
+    occS = n < 1 ? 4 : (n > 4 ? 4 : n);
+    occCache[ng - 1].store(occS, std::memory_order_relaxed);
   }
-  const long long full = nrows / (slots * rb), rem = nrows - full * slots * rb;
-  double t = (double)full * T(occ);
-  if (rem > 0) {
-    if (canSplit && rem <= maxRem) {
-      *mainRows = full * slots * rb;
-      t += kPieces;
-    } else {
-      t += T(((rem + rb - 1) / rb + simds - 1) / simds);
-    }
-  }
-  return t;
+  hw.occSym = occS;
+  return hw;
+}
+// the VALU engine: the whole launch, or the alternative behind a probe (gated on gate[0] bit 1)
+static int launch_valu(const KnnRun &r, bool gated) {
+  NsqParams q = r.p;
+  if (gated) { q.knnGuess = r.pl.guessValu; q.gate = r.gates(); q.gateMask = 1u << 1; }
+  if (r.pl.valu.grid <= 0) return pg_fail(PG_E_NODEV, "no HIP device");   // (knn_plan plans no VALU launch for a device of no CUs)
+  int grid = 0;
+  set_rows_plan(&q, &grid, r.pl.valu, r.kn);
+  return pg_launched(kNsq[r.ng - 1](PG_MODE_KNN, r.bits, q, grid, r.stream), "pg_nsq_kernel(knn)");
+}
+// the symmetric sweep of a self graph, in front of the rectangular launch: its plan kernel, the sweep, its merge
+static int launch_sym(const KnnRun &r) {
+  const KnnPlan &pl = r.pl;
+  char *base = (char *)r.workspace + pl.symBase;
+  NsqParams s = r.p;
+  s.nrows = r.nrows;
+  s.gateMask = pl.symGateMask;
+  SymArgs sa;
+  sa.plan = (const int4 *)(base + pl.symWs.plan); sa.partial = (u32 *)(base + pl.symWs.partial);
+  sa.lowCount = (u32 *)(base + pl.symWs.lowCount); sa.lowKeys = (u32 *)(base + pl.symWs.lowKeys);
+  sa.capL = pl.symCapL;
+  sa.deliver = pl.symDeliver;
+  pg_sym_set(&s, sa);
+  s.mmEvict = nullptr; s.mmEvictRows = nullptr; s.mmPieces = 0; s.mmPieceFrom = 0; s.mmPartial = nullptr;
+  s.rowsPerWave = 2 * PG_MM_RB; s.rowsPerPass = 2 * PG_MM_RB; s.mmTailFrom = pl.symPasses; s.mmTailRows = 2 * PG_MM_RB;
+  s.mmPasses = pl.symPasses;
+  s.mmGridWaves = pl.symGridWaves;
+  s.mmPassCounter = r.p.mmPassCounter + 16;
+  u32 *pieceStart = (u32 *)(base + pl.symWs.pieceStart), *gate2 = r.gates() + 2;
+  if (r.kn.debugPlan.set) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots\n", (long long)r.nrows, pl.symPasses, pl.symSlots);
+  pg_knn_sym_plan_kernel<<<dim3(pl.symPlanGrid), dim3(1024), 0, r.stream>>>(pl.symNb, pl.symNst, pl.symSlots, pl.symPiece, pl.symPieceMin, (int4 *)(base + pl.symWs.plan),
+                                                                            pieceStart, (uint4 *)sa.lowCount, pl.symZero4);
+  if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
+  if (int rc = pg_launched(kMmSym[r.ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), r.stream), "pg_mm_knn_sym_kernel")) return rc;
+  pg_knn_sym_merge_kernel<<<dim3(pl.symMergeGrid), dim3(PG_WG_THREADS), 0, r.stream>>>(
+      sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, r.nrows, r.k, r.idx, r.dist, r.p.knnGuess, r.p.mmEvict,
+      r.p.mmEvictRows, s.gate, s.gateMask, gate2, r.p.mmPassCounter + 17, (u32)(pl.symLimit < 0 ? 0 : pl.symLimit));
+  return pg_launched("pg_knn_sym_merge_kernel");
+}
+// the main launch of the MFMA engine (r.p: the plain passes, the gate and the eviction are set), with the column pieces
+// of the rows beyond mainRows and their merge when the plan splits
+static int launch_main(KnnRun &r) {
+  const KnnPlan &pl = r.pl;
+  NsqParams &p = r.p;
+  if (!pl.split) return pg_launched(kMm[r.ng - 1](pl.mode, r.bits, p, pl.launch.grid, r.stream), "pg_mm_kernel(knn)");
+  const long long rem = r.nrows - pl.mainRows;
+  p.nrows = r.nrows;
+  p.mmPieces = pl.pieces; p.mmPieceFrom = pl.main.passes; p.mmPartial = (u32 *)((char *)r.workspace + PG_WS_PARTIAL);
+  p.mmPasses = pl.launch.passes;
+  p.mmTailFrom = pl.launch.tailFrom; p.mmTailRows = pl.launch.tailRows;
+  p.mmGridWaves = pl.launch.gridWaves;
+  if (int rc = pg_launched(kMm[r.ng - 1](pl.mode, r.bits, p, pl.launch.grid, r.stream), "pg_mm_kernel(knn + column pieces)")) return rc;
+  pg_knn_merge_kernel<<<dim3(pl.pieceMergeGrid), dim3(PG_WG_THREADS), 0, r.stream>>>(
+      p.mmPartial, rem, pl.pieces, r.k, r.idx + pl.mainRows * r.k, r.dist + pl.mainRows * r.k, p.knnGuess, p.mmEvict, p.mmEvictRows,
+      (long long)r.row0 + pl.mainRows, p.gate, p.gateMask);
+  return pg_launched("pg_knn_merge_kernel");
+}
+// the probe may say "one cluster" (gate 2): the same engine with 32-row passes over all rows, as a third alternative
+static int launch_alt32(const KnnRun &r) {
+  NsqParams q = r.p;
+  q.nrows = r.nrows;
+  q.mmPieces = 0; q.mmPieceFrom = 0; q.mmPartial = nullptr;
+  q.mmEvict = nullptr; q.mmEvictRows = nullptr;             // (one cluster: every row has its neighbours; the second phase if not)
+  set_mm_plan(&q, nullptr, r.nrows, r.pl.alt, r.kn);
+  q.mmPassCounter = r.p.mmPassCounter + 8;
+  q.gateMask = 1u << 2;
+  return pg_launched(kMm[r.ng - 1](PG_MODE_KNN_SHORT, r.bits, q, r.pl.alt.grid, r.stream), "pg_mm_kernel(knn, 32-row passes, gated)");
+}
+// the evicted rows, behind everything else: one exact sweep of all columns per row
+static int launch_evicted(const KnnRun &r) {
+  const NsqParams &p = r.p;
+  KnnRowsParams kr;
+  kr.rowPlanes = p.rowPlanes; kr.colPlanes = p.colPlanes; kr.rowNpad = p.rowNpad; kr.colNpad = p.colNpad; kr.ncols = p.ncols;
+  kr.count = p.mmEvict; kr.rows = p.mmEvictRows; kr.baseRow = r.row0; kr.k = r.k;
+  kr.knnIdx = r.idx; kr.knnDist = r.dist; kr.gate = p.gate; kr.gateMask = r.pl.evictGateMask;
+  return pg_launched(kKnnRows[r.ng - 1](r.bits, kr, r.pl.evictGrid, r.stream), "pg_knn_rows_kernel");
 }
 
 static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows, const void *col_planes,
                       int64_t col_npad, int64_t ncols, int l, int bits, int k, int first, const uint32_t *floor_keys,
                       uint32_t *last_keys, int32_t *idx_out, uint8_t *dist_out, void *workspace, void *stream) {
+  const PgKnobs kn = read_knobs();
   NsqParams p;
-  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits)) return rc;
+  if (int rc = fill_nsq(&p, row_planes, row_npad, row0, nrows, col_planes, col_npad, ncols, l, bits, kn)) return rc;
   if (!idx_out || !dist_out) return pg_fail(PG_E_BADARG, "pg_knn_hamming: bad argument");
   if (k < 1 || first < 0 || first > 1 || first + k > 64) return pg_fail(PG_E_BADARG, "pg_knn_hamming: k out of range");
   if (ncols > PG_MAX_N_KNN) return pg_fail(PG_E_TOOMANY, "pg_knn_hamming: ncols exceeds 2^24");
+  KnnShape shape;
+  shape.nrows = nrows; shape.ncols = ncols; shape.row0 = row0;
+  shape.samePlanes = row_planes == col_planes && row_npad == col_npad;
+  shape.l = l; shape.bits = bits; shape.k = k; shape.first = first;
+  shape.floorKeys = floor_keys != nullptr; shape.lastKeys = last_keys != nullptr; shape.workspace = workspace != nullptr;
+  const KnnPlan pl = knn_plan(shape, knn_hw(shape, kn), kn);
+
   p.k = k; p.knnFirst = first; p.floorKeys = floor_keys; p.lastKeys = last_keys;
-  // optimistic stage-1 cap.  pg_nsq.h: 8 = half of what unrelated sequences show in its 32-bit plane-0 bound.
-  // pg_mm.h: 10 with the 54-bit signature (L > 32) - unrelated pairs below it are one in 3e6, kNN time is flat from
-  // 7 to 12 on every shape tried (tools/guess_sweep.py) and rows whose k-th distance reaches 9 keep their cap;
-  // 7 where the signature is the 32 plane-0 bits of a single group (L <= 32: one in 4e3 at 7, one in 400 at 10)
-  const bool mm = use_mm_engine(nrows);
-  const u32 guessMm = l > 32 ? 10u : 7u, guessValu = 8u;
-  p.knnGuess = getenv("PG_KNN_GUESS") ? (u32)atoi(getenv("PG_KNN_GUESS")) : (mm ? guessMm : guessValu);
-  if (p.filter == 0) p.knnGuess = 0;                       // no stage 1, nothing to cap
+  p.knnGuess = pl.guess;
   p.knnIdx = idx_out; p.knnDist = dist_out;
-  int grid = 0;
-  auto launch_valu = [&](NsqParams &q) -> int {
-    int g = 0;
-    if (int rc = plan_rows(nrows, &q, &g, nsq_occupancy(pg_ngroups(l), PG_MODE_KNN, bits), 16.0 * pg_nchunks(l, bits), PG_RB_KNN)) return rc;
-    return pg_launched(kNsq[pg_ngroups(l) - 1](PG_MODE_KNN, bits, q, g, (hipStream_t)stream), "pg_nsq_kernel(knn)");
-  };
-  if (mm) {
-    // Large launches: the data decide between the engines (probe above): unclustered data -> the VALU engine
-    if (probe_enabled() && ncols >= PG_PROBE_MIN_N && nrows >= PG_PROBE_MIN_N / 2 && p.filter != 0 && !getenv("PG_KNN_GUESS")) {
-      const u32 *gate = nullptr;
-      if (int rc = run_probe(p, l, bits, p.knnGuess, 1u, 0u, (u32)(first + k), workspace, (hipStream_t)stream, &gate)) return rc;
-      NsqParams v = p;
-      v.knnGuess = guessValu;
-      v.gate = gate; v.gateMask = 1u << 1;
-      if (int rc = launch_valu(v)) return rc;
-      p.gate = gate; p.gateMask = (1u << 0) | (1u << 2);   // (2 = one cluster: the 32-row alternative below takes it over where it exists)
-    }
-    // short lists (the usual k): the instance that inserts a whole batch of candidates at once (pg_mm.h, KL).
-    // PG_MM_SHORT=0 keeps the 64-lane lists (A/B runs)
-    const bool shortList = first == 1 && k + 1 <= PG_MM_KL && !floor_keys && !last_keys &&
-                           !(getenv("PG_MM_SHORT") && atoi(getenv("PG_MM_SHORT")) == 0);
-    // ... with 64 rows per pass (every column fragment feeds two MFMAs: half the vector-memory traffic per pair) where
-    // that is the cheaper plan (knn_plan_cost; PG_MM_R=1 / 2 forces either).  5-bit L = 64: 64-row passes from 131 073
-    // rows on (131 072 rows 1.14 ms against 1.26; 147 456: 1.55 / 1.47; 196 608: 1.84 / 1.57); L = 128 (three waves per
-    // SIMD) N = 100k: 32-row passes 0.75 against 0.97; byte alphabets (64-row instance: two waves per SIMD): 32-row passes.
-    // One wave more on every SIMD for a few rows more costs the launch as much as a full round of them (plan_mm), and
-    // so does a last round of the persistent waves that only a few passes are left for.  The rows that whole rounds
-    // hold go into plain passes; the few beyond - at most 128 row blocks - are swept in PIECES of the columns (as many
-    // pieces as give every SIMD about one wave: short passes, a sixteenth or an eighth of a sweep each), and
-    // pg_knn_merge_kernel makes the rows' lists of the pieces'.
-    // cfg3 (200 000 rows = 3 x 65 536 + 3 392): three waves per SIMD + 53 row blocks x 16 pieces.  PG_MM_SPLIT=0: off
-    const int ng = pg_ngroups(l);
-    const int occ1 = mm_occupancy(ng, shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN, bits);
-    const int occ2 = shortList ? mm_occupancy(ng, PG_MODE_KNN_SHORT2, bits) : 0;
-    const bool evictOn = !(getenv("PG_MM_EVICT") && atoi(getenv("PG_MM_EVICT")) == 0);
-    const bool canSplit = shortList && workspace && evictOn && p.knnGuess > 0 && ncols >= 65536 && nrows > PG_SPLIT_MIN_ROWS &&
-                          !getenv("PG_ROWS_PER_WAVE") && !(getenv("PG_MM_SPLIT") && atoi(getenv("PG_MM_SPLIT")) == 0);
-    long long main1 = nrows, main2 = nrows;
-    const double t1 = knn_plan_cost(nrows, ncols, PG_MM_RB, occ1, canSplit, &main1);
-    const double t2 = shortList ? knn_plan_cost(nrows, ncols, 2 * PG_MM_RB, occ2, canSplit, &main2) : 1e30;
-    bool two = shortList && t2 < t1;
-    if (const char *e = getenv("PG_MM_R")) two = shortList && atoi(e) == 2;
-    const int rbm = two ? 2 * PG_MM_RB : PG_MM_RB, occm = two ? occ2 : occ1;
-    const int modeM = two ? PG_MODE_KNN_SHORT2 : (shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN);
-    const long long mainRows = two ? main2 : main1;
-    // the probe's "one cluster" (gate value 2) goes to the 32-row alternative where one is launched (below); elsewhere
-    // the main launch takes it as well
-    const bool alt32 = two && p.gate && !getenv("PG_MM_R");
-    if (p.gate) p.gateMask = alt32 ? (1u << 0) : ((1u << 0) | (1u << 2));
-    plan_mm(mainRows, &p, &grid, rbm, occm, true);
-    p.nrows = mainRows;
-    if (int rc = pass_counter(&p, workspace, (hipStream_t)stream, p.gate != nullptr)) return rc;
-    // rows that lose their optimistic cap are evicted from their passes and finished by pg_knn_rows_kernel behind the
-    // launch (NsqParams::mmEvict; PG_MM_EVICT=0: the second phase inside the pass, as before)
-    const bool evict = first == 1 && !floor_keys && !last_keys && p.knnGuess > 0 && evictOn;
-    if (evict) {
-      p.mmEvict = (u32 *)workspace + 1;                     // (word 1 of the counter line: zeroed by pass_counter)
-      p.mmEvictRows = (u32 *)((char *)workspace + ws_evict_offset(nrows));
-    }
-    bool symOn = false;                                      // the symmetric sweep runs in front (below)
-    auto finish_evicted = [&]() -> int {
-      if (!evict) return 0;
-      KnnRowsParams kr;
-      kr.rowPlanes = p.rowPlanes; kr.colPlanes = p.colPlanes; kr.rowNpad = p.rowNpad; kr.colNpad = p.colNpad; kr.ncols = p.ncols;
-      kr.count = p.mmEvict; kr.rows = p.mmEvictRows; kr.baseRow = row0; kr.k = k;
-      kr.knnIdx = idx_out; kr.knnDist = dist_out; kr.gate = p.gate; kr.gateMask = p.gateMask | (symOn ? 1u << 3 : 0u);
-      const long long cap = (long long)(cu_count() > 0 ? cu_count() : 256) * 8;   // (one workgroup per row, the rows in turns)
-      return pg_launched(kKnnRows[ng - 1](bits, kr, (int)(nrows < cap ? nrows : cap), (hipStream_t)stream), "pg_knn_rows_kernel");
-    };
-    // A self graph on the 64-row instance: every unordered pair ONCE (pg_mm.h KS; plan, merge and fallback above).  The
-    // sweep, its merge and a decision run in front of the rectangular launch, which then tests a word of its own: it
-    // runs only where the merge evicted more rows than pg_knn_rows_kernel finishes for less than a rectangular sweep
-    // costs - a sixteenth of them (one row there is one exact sweep of all columns by a workgroup: 12 500 rows x 200 000
-    // columns are 2.5e9 exact distances, ~1.4 ms at the VALU engine's direct-form rate, the price of cfg3's whole step).
-    const SymWs sw = sym_ws(nrows);
-    const bool sym = shortList && evict && bits == PG_BITS_5 && pg_nchunks(l, bits) <= 3 && row_planes == col_planes && row_npad == col_npad &&
-                     row0 == 0 && nrows == ncols && p.filter != 0 && sw.bytes > 0 && (sym_env() == 1 || two);
-    long long symSlots = 0, symPasses = 0;
-    if (sym) {
-      static std::atomic<int> occCache[8];
-      int occS = occCache[ng - 1].load(std::memory_order_relaxed);
-      if (occS == 0) {
-        const int n = kMmSym[ng - 1](NsqParams(), -1, nullptr);
-        occS = n < 1 ? 4 : (n > 4 ? 4 : n);
-        occCache[ng - 1].store(occS, std::memory_order_relaxed);
-      }
-      symSlots = sym_slots(occS);
-      symPasses = sym_plan_host(nrows, symSlots, sym_piece(), sym_piece_min(), nullptr, 0);
-    }
-    // (a plan the workspace was not sized for - it is sized for the most slots the instance can have - is not taken:
-    //  the rectangular launch below stands on its own)
-    if (sym && symPasses <= sw.maxPasses) {
-      char *base = (char *)workspace + ws_sym_offset(nrows);
-      const long long slots = symSlots, npass = symPasses, nbk = (nrows + 63) / 64, nstk = (nrows + PG_MM_ST - 1) / PG_MM_ST;
-      const int piece = sym_piece(), pmin = sym_piece_min();
-      NsqParams s = p;
-      s.nrows = nrows;
-      s.gateMask = 1u << 0;
-      SymArgs sa;
-      sa.plan = (const int4 *)(base + sw.plan); sa.partial = (u32 *)(base + sw.partial);
-      sa.lowCount = (u32 *)(base + sw.lowCount); sa.lowKeys = (u32 *)(base + sw.lowKeys);
-      sa.capL = sym_capl();
-      sa.deliver = !(getenv("PG_KNN_SYM_DELIVER") && atoi(getenv("PG_KNN_SYM_DELIVER")) == 0);   // (0: timing experiments, wrong results)
-      pg_sym_set(&s, sa);
-      s.mmEvict = nullptr; s.mmEvictRows = nullptr; s.mmPieces = 0; s.mmPieceFrom = 0; s.mmPartial = nullptr;
-      s.rowsPerWave = 2 * PG_MM_RB; s.rowsPerPass = 2 * PG_MM_RB; s.mmTailFrom = npass; s.mmTailRows = 2 * PG_MM_RB;
-      s.mmPasses = npass;
-      s.mmGridWaves = ((npass < slots ? npass : slots) + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
-      s.mmPassCounter = p.mmPassCounter + 16;
-      u32 *pieceStart = (u32 *)(base + sw.pieceStart), *gate2 = (u32 *)((char *)workspace + PG_WS_GATES) + 2;
-      if (getenv("PG_DEBUG_PLAN")) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots\n", (long long)nrows, npass, slots);
-      // (lowCount: 256-byte aligned and padded to it, so whole uint4 stay inside)
-      const long long zero4 = (nrows + 3) / 4, zeroWgs = (zero4 + 1023) / 1024 < 64 ? (zero4 + 1023) / 1024 : 64;
-      pg_knn_sym_plan_kernel<<<dim3((unsigned)(1 + zeroWgs)), dim3(1024), 0, (hipStream_t)stream>>>(nbk, nstk, slots, piece, pmin, (int4 *)(base + sw.plan),
-                                                                                              pieceStart, (uint4 *)sa.lowCount, zero4);
-      if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
-      if (int rc = pg_launched(kMmSym[ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), (hipStream_t)stream), "pg_mm_knn_sym_kernel")) return rc;
-      const long long limit = getenv("PG_KNN_SYM_EVICT_LIMIT") ? atoll(getenv("PG_KNN_SYM_EVICT_LIMIT")) : nrows / 16;
-      // (PG_KNN_SYM_MERGE_WGS: tests - a few workgroups take the rows of a small graph in turns)
-      const long long mergeWgs = (nrows + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES);
-      long long mergeCap = (long long)(cu_count() > 0 ? cu_count() : 256) * 8;
-      if (const char *e = getenv("PG_KNN_SYM_MERGE_WGS")) { if (atoll(e) >= 1 && atoll(e) < mergeCap) mergeCap = atoll(e); }
-      pg_knn_sym_merge_kernel<<<dim3((unsigned)(mergeWgs < mergeCap ? mergeWgs : mergeCap)), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
-          sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, nrows, k, idx_out, dist_out, p.knnGuess, p.mmEvict,
-          p.mmEvictRows, s.gate, s.gateMask, gate2, p.mmPassCounter + 17, (u32)(limit < 0 ? 0 : limit));
-      if (int rc = pg_launched("pg_knn_sym_merge_kernel")) return rc;
-      if (!p.gate) p.gateMask = (1u << 0) | (1u << 2);
-      p.gate = gate2;
-      symOn = true;
-    }
-    if (mainRows < nrows) {
-      const long long rem = nrows - mainRows, nb = (rem + rbm - 1) / rbm;
-      const long long simds = (long long)(cu_count() > 0 ? cu_count() : 256) * 4;
-      int pieces = (int)(simds / nb);                       // (nb <= 128: at least 8; nb * pieces <= 1024 passes = the workspace's share)
-      pieces = pieces > 16 ? 16 : (pieces < 2 ? 2 : pieces);
-      if (const char *e = getenv("PG_MM_PIECES")) { if (atoi(e) >= 2 && atoi(e) <= (nb <= 64 ? 16 : 8)) pieces = atoi(e); }   // (experiments)
-      // the pieces ride in the main launch: its passes beyond the plain ones, fetched through the counter by the waves
-      // that finish first - they run while the slower passes are still at work
-      const long long mainPasses = p.mmPasses;              // (plain passes of rbm rows: plan_mm gave whole rounds)
-      p.nrows = nrows;
-      p.mmPieces = pieces; p.mmPieceFrom = mainPasses; p.mmPartial = (u32 *)((char *)workspace + PG_WS_PARTIAL);
-      p.mmPasses = mainPasses + nb * pieces;
-      p.mmTailFrom = p.mmPasses; p.mmTailRows = rbm;
-      // ... or, where the chip has slots left beside the plain passes (one round: a wave per SIMD is free), as waves of
-      // their own from the start: short guests at four waves per SIMD instead of a tail of 886 waves on an empty chip
-      // (PG_MM_PIECES_AHEAD=0: through the counter)
-      if (mainPasses + nb * pieces <= simds * occm && !(getenv("PG_MM_PIECES_AHEAD") && atoi(getenv("PG_MM_PIECES_AHEAD")) == 0)) {
-        p.mmGridWaves = (p.mmPasses + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
-        grid = (int)(p.mmGridWaves / PG_WG_WAVES);
-      }
-      if (int rc = pg_launched(kMm[ng - 1](modeM, bits, p, grid, (hipStream_t)stream), "pg_mm_kernel(knn + column pieces)")) return rc;
-      pg_knn_merge_kernel<<<dim3((unsigned)((rem + 4 * PG_WG_WAVES - 1) / (4 * PG_WG_WAVES))), dim3(PG_WG_THREADS), 0, (hipStream_t)stream>>>(
-          p.mmPartial, rem, pieces, k, idx_out + mainRows * k, dist_out + mainRows * k, p.knnGuess, p.mmEvict, p.mmEvictRows,
-          (long long)row0 + mainRows, p.gate, p.gateMask);
-      if (int rc = pg_launched("pg_knn_merge_kernel")) return rc;
-      p.nrows = nrows;                                      // (the gated 32-row alternative below covers all rows)
-    }
-    if (alt32) {
-      // the probe may say "one cluster" (gate 2): the same engine with 32-row passes, launched as a third alternative
-      NsqParams q = p;
-      int qgrid = 0;
-      q.mmPieces = 0; q.mmPieceFrom = 0; q.mmPartial = nullptr;
-      q.mmEvict = nullptr; q.mmEvictRows = nullptr;         // (one cluster: every row has its neighbours; the second phase if not)
-      plan_mm(nrows, &q, &qgrid, PG_MM_RB, occ1, true);
-      q.mmPassCounter = p.mmPassCounter + 8;
-      q.gateMask = 1u << 2;
-      if (int rc = pg_launched(kMm[pg_ngroups(l) - 1](PG_MODE_KNN_SHORT, bits, q, qgrid, (hipStream_t)stream), "pg_mm_kernel(knn, 32-row passes, gated)")) return rc;
-    }
-    if (mainRows < nrows) return finish_evicted();          // (the main launch and the pieces are out already)
-    if (int rc = pg_launched(kMm[pg_ngroups(l) - 1](two ? PG_MODE_KNN_SHORT2 : (shortList ? PG_MODE_KNN_SHORT : PG_MODE_KNN), bits, p, grid,
-                                                 (hipStream_t)stream), "pg_mm_kernel(knn)")) return rc;
-    return finish_evicted();
+  KnnRun r = {pl, kn, p, l, bits, pg_ngroups(l), k, row0, nrows, idx_out, dist_out, workspace, (hipStream_t)stream};
+  if (!pl.mm) return launch_valu(r, false);
+  if (pl.probe) {
+    const u32 *gate = nullptr;
+    if (int rc = run_probe(r.p, l, bits, pl.guess, 1u, 0u, (u32)(first + k), workspace, r.stream, kn, &gate)) return rc;
+    if (int rc = launch_valu(r, true)) return rc;
+    r.p.gate = gate;
   }
-  return launch_valu(p);
+  r.p.gateMask = pl.mainGateMask;
+  set_mm_plan(&r.p, nullptr, pl.mainRows, pl.main, kn);
+  r.p.nrows = pl.mainRows;
+  if (int rc = pass_counter(&r.p, workspace, r.stream, pl.probe)) return rc;
+  if (pl.evict) {
+    r.p.mmEvict = (u32 *)workspace + 1;                     // (word 1 of the counter line: zeroed by pass_counter)
+    r.p.mmEvictRows = (u32 *)((char *)workspace + pl.evictOffset);
+  }
+  if (pl.sym) {
+    if (int rc = launch_sym(r)) return rc;
+    r.p.gate = r.gates() + 2;
+  }
+  if (pl.split) {                                           // (the main launch and the pieces go out before the alternative)
+    if (int rc = launch_main(r)) return rc;
+  }
+  if (pl.alt32) {
+    if (int rc = launch_alt32(r)) return rc;
+  }
+  if (!pl.split) {
+    if (int rc = launch_main(r)) return rc;
+  }
+  return pl.evict ? launch_evicted(r) : 0;
 }
 
 int pg_knn_hamming(const void *row_planes, int64_t row_npad, int64_t row0, int64_t nrows, const void *col_planes,
@@ -1781,16 +1458,17 @@ int pg_lev_candidates(const void *profiles, int64_t npad, int64_t n, int64_t row
   if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_lev_candidates: bad npad");
   if (n > 0x7fffffffLL) return pg_fail(PG_E_TOOMANY, "n exceeds int32 indices");
   NsqParams p;
+  const PgKnobs kn = read_knobs();
   memset(&p, 0, sizeof(p));
   p.rowPlanes = (const uint4 *)profiles; p.rowNpad = npad; p.row0 = row0; p.nrows = nrows;
   p.colPlanes = (const uint4 *)profiles; p.colNpad = npad; p.ncols = n;
   p.lo = 0; p.span = 2u * (u32)band; p.hi1 = p.span + 1u;
-  p.filter = lb_filter_mode();             // keep pairs with max(SAD, 2*|dlen|) <= 2*band, self included
+  p.filter = (int)kn.lbFilter.v;             // keep pairs with max(SAD, 2*|dlen|) <= 2*band, self included
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.counts = counts;
   int grid = 0;
   static int bag_occ = 0;
   if (!bag_occ) { bag_occ = pg_occ_nsq_bag(); if (bag_occ < 1) bag_occ = 4; }
-  if (int rc = plan_rows(nrows, &p, &grid, bag_occ, 48.0)) return rc;
+  if (int rc = plan_rows_here(&p, &grid, bag_occ, 48.0, kn)) return rc;
   return pg_launched(pg_launch_nsq_bag(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag)");
 }
 
@@ -1804,16 +1482,17 @@ int pg_lev_candidates_sym(const void *profiles, int64_t npad, int64_t n, int ban
   if (npad < n || npad % 256) return pg_fail(PG_E_BADARG, "pg_lev_candidates_sym: bad npad");
   if (n >= (1ll << 27)) return pg_fail(PG_E_TOOMANY, "pg_lev_candidates_sym: n must be below 2^27");
   NsqParams p;
+  const PgKnobs kn = read_knobs();
   memset(&p, 0, sizeof(p));
   p.rowPlanes = (const uint4 *)profiles; p.rowNpad = npad; p.row0 = 0; p.nrows = n;
   p.colPlanes = (const uint4 *)profiles; p.colNpad = npad; p.ncols = n;
   p.lo = 0; p.span = 2u * (u32)band; p.hi1 = p.span + 1u;
-  p.filter = lb_filter_mode();
+  p.filter = (int)kn.lbFilter.v;
   p.cap = (u32)cap; p.slotIdx = slot_idx; p.slotW = slot_w; p.slotAux = slot_aux; p.counts = counts_up; p.countsLo = counts_lo;
   hipError_t e = hipMemsetAsync(counts_lo, 0, (size_t)n * sizeof(uint32_t), (hipStream_t)stream);
   if (e != hipSuccess) return pg_launched((int)e, "hipMemsetAsync");
   long long r = n >= 80000 ? 16 : 8;                        // as pg_eps_slots_sym
-  if (const char *ev = getenv("PG_ROWS_PER_WAVE")) { if (atoi(ev) > 0) r = atoi(ev); }
+  if (kn.rowsPerWave.v > 0) r = kn.rowsPerWave.v;
   p.rowsPerWave = (int)r; p.rowsPerPass = (int)(r > PG_RB ? PG_RB : r);
   const int grid = (int)(((n + r - 1) / r + PG_WG_WAVES - 1) / PG_WG_WAVES);
   return pg_launched(pg_launch_nsq_bag_sym(p, grid, (hipStream_t)stream), "pg_nsq_kernel(bag sym)");
