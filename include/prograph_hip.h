@@ -778,6 +778,58 @@ int pg_csr_row_stats(const int64_t *indptr, const int32_t *indices, const uint8_
                      double *sum_f, double *sum_wf, double *self_w, double *col_sum, void *stream);
 
 /*
+ * Undirected graphs from a device CSR (prograph_amd/csrc/pg_graph.hip, definitions in pg_graph.h): row sort, transpose,
+ * symmetrisation.  G has nrows rows (indptr int64 [nrows + 1], indices int32 [nnz], weights of elem_bytes 1, 2 or 4), ncols
+ * columns, and row r is node row0 + r.  An entry whose column is outside 0..ncols-1 is no edge (-1, the empty kNN slot, among
+ * them): nothing is read through it or written for it.  Workspaces are the caller's (the *_workspace queries give their bytes,
+ * 8-byte aligned; -1 for a negative size); the library allocates nothing.  NULL pointers, negative sizes, more than 2^31 - 1 rows
+ * or columns, elem_bytes outside {1, 2, 4}, a bad kind / mode / combine and a workspace that is too small are PG_E_BADARG, checked
+ * before any launch; nrows == 0 and nnz == 0 are legal and launch nothing that indexes.  A row of G holds fewer than 2^32 entries.
+ *   pg_csr_sort_rows_count   counts[r] = the edges of row r; the workspace then holds the rows' keys (column << 32 | position in
+ *                            row), sorted, no-edge entries last
+ *   pg_csr_sort_rows_fill    after pg_exclusive_scan(counts) -> out_indptr: every row's edges ascending by column, equal columns
+ *                            in storage order, weights moved with them bit for bit; same workspace, untouched in between
+ *   pg_csr_histogram         counts[c] = the edges of column c (counts uint32 [ncols], zeroed here; integer atomics: exact)
+ *   pg_csr_transpose         after pg_exclusive_scan(counts) -> t_indptr [ncols + 1]: row c of T lists (row0 + r, w) for every edge
+ *                            (r, c, w) of G in G's storage order (columns of T ascending, duplicates in order); t_indices and
+ *                            t_weights hold t_indptr[ncols] entries.  The same bits every run.  row0 + nrows <= 2^31 - 1.
+ *   pg_csr_symmetrize_count  A = the sorted rows of a square G (row0 = 0, nrows = ncols), T = its transpose (nnz_a, nnz_t: the
+ *                            lengths of their arrays, at least a_indptr[nrows], t_indptr[nrows]).  Merges A[r] and T[r] into
+ *                            the workspace, combines the weights of every run of equal column - kind PG_W_UNSIGNED | PG_W_SIGNED
+ *                            | PG_W_FLOAT (2 or 4 bytes), combine PG_COMBINE_MIN | PG_COMBINE_MAX; a NaN loses to a number,
+ *                            ties (two NaNs, -0 and +0) go to the smaller bit pattern - and counts per row the columns that
+ *                            mode keeps: PG_SYM_UNION all, PG_SYM_MUTUAL those that A[r] and T[r] both hold
+ *   pg_csr_symmetrize_fill   after pg_exclusive_scan(counts) -> out_indptr: the kept columns ascending, each once, with the
+ *                            combined weight; same nnz_a, nnz_t and workspace, untouched in between
+ */
+#define PG_W_UNSIGNED 0
+#define PG_W_SIGNED 1
+#define PG_W_FLOAT 2
+#define PG_SYM_UNION 0
+#define PG_SYM_MUTUAL 1
+#define PG_COMBINE_MIN 0
+#define PG_COMBINE_MAX 1
+int64_t pg_csr_sort_workspace(int64_t nnz);
+int pg_csr_sort_rows_count(const int64_t *indptr, const int32_t *indices, int64_t nrows, int64_t nnz, int64_t ncols,
+                           uint32_t *counts, void *workspace, int64_t workspace_bytes, void *stream);
+int pg_csr_sort_rows_fill(const int64_t *indptr, const void *weights, int elem_bytes, int64_t nrows, int64_t nnz,
+                          const uint32_t *counts, const int64_t *out_indptr, int32_t *out_indices, void *out_weights,
+                          const void *workspace, int64_t workspace_bytes, void *stream);
+int pg_csr_histogram(const int32_t *indices, int64_t nnz, int64_t ncols, uint32_t *counts, void *stream);
+int64_t pg_csr_transpose_workspace(int64_t nnz, int64_t ncols);
+int pg_csr_transpose(const int64_t *indptr, const int32_t *indices, const void *weights, int elem_bytes, int64_t nrows,
+                     int64_t nnz, int64_t ncols, int64_t row0, const int64_t *t_indptr, int32_t *t_indices, void *t_weights,
+                     void *workspace, int64_t workspace_bytes, void *stream);
+int64_t pg_csr_symmetrize_workspace(int64_t nnz_a, int64_t nnz_t);
+int pg_csr_symmetrize_count(const int64_t *a_indptr, const int32_t *a_indices, const void *a_weights, int64_t nnz_a,
+                            const int64_t *t_indptr, const int32_t *t_indices, const void *t_weights, int64_t nnz_t,
+                            int elem_bytes, int kind, int mode, int combine, int64_t nrows, uint32_t *counts, void *workspace,
+                            int64_t workspace_bytes, void *stream);
+int pg_csr_symmetrize_fill(const int64_t *a_indptr, int64_t nnz_a, const int64_t *t_indptr, int64_t nnz_t, int elem_bytes,
+                           int64_t nrows, const int64_t *out_indptr, int32_t *out_indices, void *out_weights,
+                           const void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
  * pg_compact_flags — ascending indices of the non-zero flags (np.where(...)[0]).
  *   out_idx int64[n] (worst case), out_count int64[1]; scratch: pg_scan_scratch_bytes(n)
  */

@@ -62,6 +62,8 @@ SYMBOLS = [
     "pg_euclidean_dense", "pg_euclidean_knn", "pg_euclidean_knn_round", "pg_euclidean_eps_slots", "pg_euclidean_eps_fill_rows",
     "pg_query_workspace_bytes", "pg_query_knn_hamming",
     "pg_query_eps_segments", "pg_query_eps_count", "pg_query_eps_fill",
+    "pg_csr_sort_workspace", "pg_csr_sort_rows_count", "pg_csr_sort_rows_fill", "pg_csr_histogram", "pg_csr_transpose_workspace",
+    "pg_csr_transpose", "pg_csr_symmetrize_workspace", "pg_csr_symmetrize_count", "pg_csr_symmetrize_fill",
 ]
 
 
@@ -142,6 +144,16 @@ def _load():
         lib.pg_index_flags.argtypes = [_vp, _i64, _i64, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.pg_compact_flags.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp]
         lib.pg_csr_row_stats.argtypes = [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.pg_csr_sort_workspace.restype = lib.pg_csr_transpose_workspace.restype = lib.pg_csr_symmetrize_workspace.restype = _i64
+        lib.pg_csr_sort_workspace.argtypes = [_i64]
+        lib.pg_csr_transpose_workspace.argtypes = lib.pg_csr_symmetrize_workspace.argtypes = [_i64, _i64]
+        lib.pg_csr_sort_rows_count.argtypes = [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]
+        lib.pg_csr_sort_rows_fill.argtypes = [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+        lib.pg_csr_histogram.argtypes = [_vp, _i64, _i64, _vp, _vp]
+        lib.pg_csr_transpose.argtypes = [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
+        lib.pg_csr_symmetrize_count.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp,
+                                                _i64, _vp]
+        lib.pg_csr_symmetrize_fill.argtypes = [_vp, _i64, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]
         lib.pg_lev_profile.argtypes = [_vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _vp]
         lib.pg_lev_candidates.argtypes = [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
         lib.pg_lev_candidates_sym.argtypes = [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
@@ -1502,6 +1514,117 @@ def csr_row_stats(indptr, indices, weights, f=None, want=("deg",), row0=0, ncols
                                   _ptr(out.get("deg")), _ptr(out.get("sum_f")), _ptr(out.get("sum_wf")),
                                   _ptr(out.get("self_w")), _ptr(out.get("col_sum")), _stream()), "pg_csr_row_stats")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Undirected graphs from a device CSR (pg_graph.hip; definitions in include/prograph_hip.h and DESIGN.md §4.30)
+# ----------------------------------------------------------------------------------------------
+W_KINDS = {torch.uint8: (1, 0), torch.int16: (2, 1), torch.int32: (4, 1), torch.float16: (2, 2), torch.float32: (4, 2)}
+SYM_MODES, SYM_COMBINES = {"union": 0, "mutual": 1}, {"min": 0, "max": 1}
+
+
+def _w_kind(weights):
+    """(elem_bytes, kind) of the weight dtypes the graph containers carry."""
+    if weights.dtype not in W_KINDS:
+        raise TypeError(f"weights must be one of {sorted(str(d) for d in W_KINDS)}, not {weights.dtype}")
+    return W_KINDS[weights.dtype]
+
+
+def _csr_operands(indptr, indices, weights):
+    if indptr.dtype != torch.int64 or indices.dtype != torch.int32 or weights.numel() != indices.numel() or indptr.numel() < 1:
+        raise TypeError("a CSR is indptr int64 [n + 1], indices int32 [nnz], weights [nnz]")
+    if not (indptr.is_cuda and indices.is_cuda and weights.is_cuda):
+        raise NativeUnavailable("the graph operations run on device tensors; there is no CPU path")
+    return indptr.contiguous(), indices.contiguous(), weights.contiguous()
+
+
+def _bytes(n, dev):
+    return torch.empty(max(int(n), 8), dtype=torch.uint8, device=dev)
+
+
+def _scan(counts):
+    """uint32 counts (an int32 tensor) -> indptr int64 [m + 1] on the device; m = 0: [0]."""
+    m, dev = counts.numel(), counts.device
+    indptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    if m:
+        scratch = _bytes(lib().pg_scan_scratch_bytes(m), dev)
+        _check(lib().pg_exclusive_scan(_ptr(counts), m, _ptr(indptr), _ptr(scratch), _stream()), "pg_exclusive_scan")
+    return indptr
+
+
+def _csr_out(indptr, nnz_max, like, trim):
+    """The arrays of a result of at most nnz_max entries; trim: ONE host read of its nnz, else the arrays keep nnz_max entries
+    of which the first indptr[-1] are the result (a stage of `csr_symmetrize`, which reads once at its end)."""
+    nnz = int(indptr[-1].item()) if trim else int(nnz_max)
+    dev = indptr.device
+    return torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)[:nnz], torch.empty(max(nnz, 1), dtype=like.dtype, device=dev)[:nnz]
+
+
+def csr_sort_rows(indptr, indices, weights, ncols, trim=True):
+    """sorted(): every row's edges ascending by column, equal columns in storage order, entries whose column is outside
+    0..ncols-1 dropped.  Device tensors in, (indptr, indices, weights) out."""
+    indptr, indices, weights = _csr_operands(indptr, indices, weights)
+    eb, _ = _w_kind(weights)
+    L, dev = lib(), indptr.device
+    nrows, nnz = indptr.numel() - 1, indices.numel()
+    if not nnz:
+        return torch.zeros(nrows + 1, dtype=torch.int64, device=dev), indices, weights
+    counts = torch.zeros(nrows, dtype=torch.int32, device=dev)
+    nbytes = int(L.pg_csr_sort_workspace(nnz))
+    ws = _bytes(nbytes, dev)
+    _check(L.pg_csr_sort_rows_count(_ptr(indptr), _ptr(indices), nrows, nnz, int(ncols), _ptr(counts), _ptr(ws), nbytes, _stream()),
+           "pg_csr_sort_rows_count")
+    out_indptr = _scan(counts)
+    out_idx, out_w = _csr_out(out_indptr, nnz, weights, trim)
+    _check(L.pg_csr_sort_rows_fill(_ptr(indptr), _ptr(weights), eb, nrows, nnz, _ptr(counts), _ptr(out_indptr), _ptr(out_idx),
+                                   _ptr(out_w), _ptr(ws), nbytes, _stream()), "pg_csr_sort_rows_fill")
+    return out_indptr, out_idx, out_w
+
+
+def csr_transpose(indptr, indices, weights, ncols, row0=0, trim=True):
+    """transpose(): (indptr [ncols + 1], indices, weights) of T, whose row c lists (row0 + r, w) for every edge (r, c, w) in
+    storage order; the same bits every run."""
+    indptr, indices, weights = _csr_operands(indptr, indices, weights)
+    eb, _ = _w_kind(weights)
+    L, dev = lib(), indptr.device
+    nrows, nnz, ncols = indptr.numel() - 1, indices.numel(), int(ncols)
+    if not nnz or not ncols:
+        return torch.zeros(ncols + 1, dtype=torch.int64, device=dev), indices[:0], weights[:0]
+    counts = torch.zeros(ncols, dtype=torch.int32, device=dev)
+    _check(L.pg_csr_histogram(_ptr(indices), nnz, ncols, _ptr(counts), _stream()), "pg_csr_histogram")
+    t_indptr = _scan(counts)
+    t_idx, t_w = _csr_out(t_indptr, nnz, weights, trim)
+    nbytes = int(L.pg_csr_transpose_workspace(nnz, ncols))
+    ws = _bytes(nbytes, dev)
+    _check(L.pg_csr_transpose(_ptr(indptr), _ptr(indices), _ptr(weights), eb, nrows, nnz, ncols, int(row0), _ptr(t_indptr),
+                              _ptr(t_idx), _ptr(t_w), _ptr(ws), nbytes, _stream()), "pg_csr_transpose")
+    return t_indptr, t_idx, t_w
+
+
+def csr_symmetrize(indptr, indices, weights, mode="union", combine="min"):
+    """symmetrize() of a square graph over n = nrows = ncols nodes (row0 = 0): rows ascending by column, each column once;
+    union | mutual, the weight min | max over every occurrence of (r, c) and (c, r).  One host read, of the result's nnz."""
+    if mode not in SYM_MODES or combine not in SYM_COMBINES:
+        raise ValueError("mode is 'union' or 'mutual', combine is 'min' or 'max'")
+    indptr, indices, weights = _csr_operands(indptr, indices, weights)
+    eb, kind = _w_kind(weights)
+    L, dev = lib(), indptr.device
+    n, nnz = indptr.numel() - 1, indices.numel()
+    if not nnz:
+        return torch.zeros(n + 1, dtype=torch.int64, device=dev), indices, weights
+    a = csr_sort_rows(indptr, indices, weights, n, trim=False)
+    t = csr_transpose(indptr, indices, weights, n, trim=False)
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    nbytes = int(L.pg_csr_symmetrize_workspace(nnz, nnz))
+    ws = _bytes(nbytes, dev)
+    _check(L.pg_csr_symmetrize_count(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), nnz, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), nnz, eb, kind,
+                                     SYM_MODES[mode], SYM_COMBINES[combine], n, _ptr(counts), _ptr(ws), nbytes, _stream()),
+           "pg_csr_symmetrize_count")
+    out_indptr = _scan(counts)
+    out_idx, out_w = _csr_out(out_indptr, 0, weights, True)
+    _check(L.pg_csr_symmetrize_fill(_ptr(a[0]), nnz, _ptr(t[0]), nnz, eb, n, _ptr(out_indptr), _ptr(out_idx), _ptr(out_w), _ptr(ws),
+                                    nbytes, _stream()), "pg_csr_symmetrize_fill")
+    return out_indptr, out_idx, out_w
 
 
 class PackedF16:

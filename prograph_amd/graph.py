@@ -123,6 +123,42 @@ class CSRGraph:
         out = torch.where(cnt > 0, fr - st["sum_f"] / cnt.clamp(min=1), torch.full_like(fr, float("nan")))
         return out.cpu().numpy()
 
+    # ------------------------------------------------------------------ undirected graphs (pg_graph.hip)
+    # An entry whose column is outside 0..ncols-1 is no edge (the rule of `row_stats`).  The results are ordinary CSRGraphs
+    # on the device: `similarity`, `final` and the weight dtype carry over, the weights' bits are never changed.
+    def _like(self, arrays, ncols, row0):
+        return CSRGraph(*arrays, ncols, similarity=self.similarity, row0=row0, final=self.final)
+
+    def sorted(self):
+        """The same rows with each row's edges ascending by column; equal columns stay in storage order (a stable sort),
+        weights travel with their entries, no-edge entries are dropped."""
+        return self._like(_native.csr_sort_rows(self.indptr, self.indices, self.weights, self.ncols), self.ncols, self.row0)
+
+    def transpose(self):
+        """T with T.nrows = ncols, T.ncols = row0 + nrows, T.row0 = 0: row c of T lists (row0 + r, w) for every edge
+        (r, c, w), in storage order - so T's rows are ascending by column and duplicates keep their order.  The reverse
+        neighbour lists: of a `fit_alignment` graph "what does row c contain?", of `search` results "which queries hit
+        this dataset row?".  Rectangular graphs and shards (`row0 != 0`) are legal.  Bitwise reproducible."""
+        return self._like(_native.csr_transpose(self.indptr, self.indices, self.weights, self.ncols, row0=self.row0),
+                          self.row0 + self.nrows, 0)
+
+    def symmetrize(self, mode="union", combine="min"):
+        """The undirected graph S of a square graph (`row0 == 0`, `nrows == ncols`; `ValueError` otherwise): rows ascending
+        by column, each column at most once per row.  mode="union": (r, c) is in S iff (r, c) or (c, r) is an edge (the
+        undirected kNN graph); "mutual": iff both are (the mutual-kNN graph).  S[r, c] is `combine` ("min" | "max") over
+        the weights of all occurrences of (r, c) and (c, r); a self-loop is its own reverse.  "min", the default, lets the
+        nearer of two distances win; graphs of raw SCORES (`local_alignment` and the like, built with similarity=False)
+        want combine="max" - the container cannot know that larger is nearer.  Integers compare as integers, floats as
+        floats; a NaN loses to a number, and of two NaNs or of -0 and +0 the smaller bit pattern wins, so S equals
+        S.transpose() bit for bit."""
+        if mode not in _native.SYM_MODES:
+            raise ValueError("mode is 'union' or 'mutual'")
+        if combine not in _native.SYM_COMBINES:
+            raise ValueError("combine is 'min' or 'max'")
+        if self.row0 != 0 or self.nrows != self.ncols:
+            raise ValueError("symmetrize needs a square graph: row0 == 0 and nrows == ncols")
+        return self._like(_native.csr_symmetrize(self.indptr, self.indices, self.weights, mode=mode, combine=combine), self.ncols, 0)
+
     def coords(self, boolean_weights=False):
         """(I, J, V) of prograph.py:824-857 straight from CSR."""
         indptr, idx, w = self.host()
@@ -202,6 +238,18 @@ class KNNGraph:
             torch.zeros(n + 1, dtype=torch.int64, device=self.idx.device)
         return CSRGraph(indptr, self.idx[:, :kk].reshape(-1).contiguous(), self.dist[:, :kk].reshape(-1).contiguous(),
                         self.ncols, similarity=self.similarity, row0=self.row0, final=self.final)
+
+    def sorted(self):
+        """`as_csr().sorted()`: a CSRGraph, every row ascending by column."""
+        return self.as_csr().sorted()
+
+    def transpose(self):
+        """`as_csr().transpose()`: the reverse-neighbour lists, a CSRGraph."""
+        return self.as_csr().transpose()
+
+    def symmetrize(self, mode="union", combine="min"):
+        """`as_csr().symmetrize(...)`: the undirected (union) or mutual kNN graph, a CSRGraph."""
+        return self.as_csr().symmetrize(mode=mode, combine=combine)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -2121,6 +2121,29 @@ class Prograph:
             return indptr, np.zeros(0, dtype=int), np.zeros(0)
         return indptr, np.concatenate([e[0] for e in col]), np.concatenate([e[1] for e in col])
 
+    def symmetrize(self, graph, mode="union", combine="min", store=None, output="csr"):
+        """The undirected graph of a directed one, on the device (`CSRGraph.symmetrize`): mode="union" - (r, c) is an edge
+        iff (r, c) or (c, r) was, the undirected kNN graph - or "mutual" - iff both were, the mutual-kNN graph -, the weight
+        `combine` ("min" | "max") over both directions.  Graphs of scores (`local_alignment` and the like) want
+        combine="max".  `graph`: a `CSRGraph` / `KNNGraph`, or the name of a stored graph; a column without a matching device
+        graph is uploaded (integer weights as int32, others as final float32 values).  `store=` and `output=` as in
+        `build_graph`: after `symmetrize("E", mode="mutual", store="M")`, `dirichlet("M")` and `degree("M")` run on the
+        device graph."""
+        if isinstance(graph, (CSRGraph, KNNGraph)):
+            g = graph
+        else:
+            g = self._device_graph_any(graph)
+            if g is None:
+                indptr, indices, w = self._column_csr(graph)
+                dev = _native.device()
+                integer = np.issubdtype(np.asarray(w).dtype, np.integer)
+                g = CSRGraph(torch.from_numpy(np.ascontiguousarray(indptr, dtype=np.int64)).to(dev),
+                             torch.from_numpy(np.ascontiguousarray(indices, dtype=np.int32)).to(dev),
+                             torch.from_numpy(np.ascontiguousarray(w, dtype=np.int32 if integer else np.float32)).to(dev),
+                             len(self), final=not integer)
+        s = g.symmetrize(mode=mode, combine=combine)
+        return self._graph_result(s, None, store, None, output)
+
     def degree(self, graph="Neighbours", boolean_weights=False):
         g = self._device_graph(graph)
         if g is not None:
