@@ -101,3 +101,32 @@ def lev_matrix(X, Y, dtype=np.int64):
     lib().orc_lev_matrix(_p(X), ctypes.c_int64(X.shape[0]), ctypes.c_int(X.shape[1]), _p(Y), ctypes.c_int64(Y.shape[0]),
                          ctypes.c_int(Y.shape[1]), _p(out), ctypes.c_int(dtype.itemsize))
     return out
+
+
+TRACE_MAX_CELLS = 1 << 19            # oracle.c's ORC_TRACE_MAX_CELLS: (len x + 1) * (len y + 1) of one pair
+_TRACE_ERRORS = {1: "a pair's row number is outside its operand", 2: "a symbol outside the table",
+                 3: f"a pair of more than {TRACE_MAX_CELLS} cells", 4: "ldo is below len x + len y of a pair", 5: "a bad argument",
+                 6: "no memory"}
+
+
+def align_trace(X, Y, xi, yi, table, gap, gap_open, mode, ldo=None):
+    """(head int32 (P, 8), ops uint8 (P, ldo)) of the canonical alignments (orc_align_trace) of the pairs
+    (X[xi[p]], Y[yi[p]]): zero-right-padded uint8 operands at their own widths, `table` (A, A) integers read as
+    table[x symbol][y symbol], `mode` 0 global distance, 1 local, 2 semi-global, 3 fit; `ldo` defaults to the two widths
+    together.  The layout is the device's: head = score, x_begin, x_end, y_begin, y_end, n_ops, identities, 0, and ops is
+    zero from n_ops on.  A pair of more than TRACE_MAX_CELLS cells is refused (ValueError)."""
+    X = np.ascontiguousarray(np.atleast_2d(X), dtype=np.uint8); Y = np.ascontiguousarray(np.atleast_2d(Y), dtype=np.uint8)
+    xi = np.ascontiguousarray(xi, dtype=np.int32).reshape(-1); yi = np.ascontiguousarray(yi, dtype=np.int32).reshape(-1)
+    T = np.ascontiguousarray(table, dtype=np.int64)
+    if T.ndim != 2 or T.shape[0] != T.shape[1] or len(xi) != len(yi):
+        raise ValueError("align_trace: a square table and two lists of one length")
+    ldo = X.shape[1] + Y.shape[1] if ldo is None else int(ldo)
+    head = np.empty((len(xi), 8), dtype=np.int32); ops = np.empty((len(xi), ldo), dtype=np.uint8)
+    f = lib().orc_align_trace
+    f.restype = ctypes.c_int
+    rc = f(_p(X), ctypes.c_int64(X.shape[0]), ctypes.c_int(X.shape[1]), _p(Y), ctypes.c_int64(Y.shape[0]), ctypes.c_int(Y.shape[1]),
+           _p(xi), _p(yi), ctypes.c_int64(len(xi)), _p(T), ctypes.c_int(T.shape[0]), ctypes.c_int(int(gap)), ctypes.c_int(int(gap_open)),
+           ctypes.c_int(int(mode)), _p(head), _p(ops), ctypes.c_int64(ldo))
+    if rc:
+        raise ValueError(f"align_trace: {_TRACE_ERRORS.get(rc, rc)}")
+    return head, ops

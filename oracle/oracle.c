@@ -11,6 +11,7 @@
  *   orc_eps       (comp(d,eps) & (d>0)) per row, columns ascending prograph/prograph.py:731-753
  *   orc_knn       stable ascending sort by distance, ranks 1..k    prograph/prograph.py:756-764
  *   orc_synth     the deterministic generator of prograph_amd/synth.py
+ *   orc_align_trace  the canonical alignment of DESIGN.md §4.20 with whole tables (build defined, below)
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -276,4 +277,171 @@ void orc_lev_matrix(const uint8_t *X, int64_t n, int lx, const uint8_t *Y, int64
     }
   }
   free(xlens);
+}
+
+/* ---------------------------------------------------------------------------------------
+ * Canonical alignment of a list of pairs — BUILD DEFINED (no reference counterpart).
+ * The yardstick of tests/test_alignment_trace_lengths_*.py: tests/trace_testdata.definition (fit:
+ * tests/fit_testdata.canonical) restated in C, to which tests/test_alignment_trace_lengths_cpu.py pins it.  Per pair the
+ * three tables H, E, F are kept WHOLE as int64, the global distance minimising over its cost table and the three scores
+ * maximising; the end cell is found by a scan of the finished table in the canonical order (by i, then j; only a
+ * larger value replaces); the walk back compares table entries.  Nothing of the kernels' shape is here: no direction
+ * bits, no negated table, no running maximum, no strips.
+ *
+ * X (n, xw), Y (m, yw): uint8 rows, zero right-padded, a sequence is a row without its trailing zeros (an interior zero
+ * is symbol 0).  T is (A, A) int64, read as T[x symbol][y symbol].  mode 0 global distance, 1 local, 2 semi-global,
+ * 3 fit (all of y within x).  head is int32 (P, 8) = score, x_begin, x_end, y_begin, y_end, n_ops, identities, 0;
+ * ops uint8 (P, ldo): 1 pair, 2 x symbol unaligned, 3 y symbol unaligned, 0 from n_ops on.
+ * Returns 0, or 1 an index outside its operand, 2 a symbol outside the table, 3 a pair of more than
+ * ORC_TRACE_MAX_CELLS cells, 4 ldo below len x + len y, 5 a bad argument, 6 no memory; nothing is promised of head
+ * and ops then.
+ * ------------------------------------------------------------------------------------- */
+#define ORC_TRACE_MAX_CELLS (1 << 19)
+#define ORC_TRACE_NONE ((int64_t)1 << 40)
+
+static int row_len(const uint8_t *a, int w) {
+  int n = w;
+  while (n > 0 && a[n - 1] == 0) --n;
+  return n;
+}
+
+static inline int64_t orc_better(int mn, int64_t a, int64_t b) { return mn ? (a < b ? a : b) : (a > b ? a : b); }
+
+static void orc_trace_pair(int mode, const int64_t *T, int A, int64_t e, int64_t o, const uint8_t *x, int lx, const uint8_t *y,
+                           int ly, int64_t *H, int64_t *E, int64_t *F, int32_t *head, uint8_t *ops, int64_t ldo) {
+  const int mn = mode == 0, W = ly + 1;
+  const int64_t none = mn ? ORC_TRACE_NONE : -ORC_TRACE_NONE, oe = mn ? o + e : -(o + e), ee = mn ? e : -e;
+#define AT(M, i, j) M[(int64_t)(i) * W + (j)]
+  for (int i = 0; i <= lx; ++i)
+    for (int j = 0; j <= ly; ++j) {
+      AT(H, i, j) = 0;
+      AT(E, i, j) = none;
+      AT(F, i, j) = none;
+    }
+  if (mode == 0) {
+    for (int j = 1; j <= ly; ++j) AT(H, 0, j) = o + j * e;
+    for (int i = 1; i <= lx; ++i) AT(H, i, 0) = o + i * e;
+  }
+  if (mode == 3)
+    for (int j = 1; j <= ly; ++j) AT(H, 0, j) = -(o + j * e);
+  for (int i = 1; i <= lx; ++i)
+    for (int j = 1; j <= ly; ++j) {
+      AT(E, i, j) = orc_better(mn, AT(E, i - 1, j) + ee, AT(H, i - 1, j) + oe);
+      AT(F, i, j) = orc_better(mn, AT(F, i, j - 1) + ee, AT(H, i, j - 1) + oe);
+      int64_t h = orc_better(mn, AT(H, i - 1, j - 1) + T[(int64_t)x[i - 1] * A + y[j - 1]], orc_better(mn, AT(E, i, j), AT(F, i, j)));
+      if (mode == 1 && h < 0) h = 0;
+      AT(H, i, j) = h;
+    }
+  /* the end cell: the first of the largest among the mode's candidates, in the order by i, then j */
+  int bi = lx, bj = ly;
+  if (mode != 0) {
+    int first = 1;
+    for (int i = 0; i <= lx; ++i)
+      for (int j = 0; j <= ly; ++j) {
+        const int cand = mode == 1 || (mode == 2 && (i == lx || j == ly)) || (mode == 3 && j == ly);
+        if (cand && (first || AT(H, i, j) > AT(H, bi, bj))) {
+          bi = i;
+          bj = j;
+          first = 0;
+        }
+      }
+  }
+  /* the walk, codes written backwards */
+  int i = bi, j = bj, state = 0, n = 0, ident = 0;
+  for (;;) {
+    if (state == 0) {
+      if (mode == 1 && AT(H, i, j) == 0) break;
+      if (mode == 2 && (i == 0 || j == 0)) break;
+      if (mode == 0 && (i == 0 || j == 0)) {
+        for (; j > 0 && i == 0; --j) ops[n++] = 3;
+        for (; i > 0; --i) ops[n++] = 2;
+        break;
+      }
+      if (mode == 3 && j == 0) break;
+      if (mode == 3 && i == 0) {
+        for (; j > 0; --j) ops[n++] = 3;
+        break;
+      }
+      if (AT(H, i, j) == AT(H, i - 1, j - 1) + T[(int64_t)x[i - 1] * A + y[j - 1]]) {
+        ops[n++] = 1;
+        ident += x[i - 1] == y[j - 1];
+        --i;
+        --j;
+      } else if (AT(H, i, j) == AT(E, i, j)) {
+        state = 1;
+      } else {
+        state = 2;
+      }
+    } else if (state == 1) {
+      ops[n++] = 2;
+      if (AT(E, i, j) == AT(H, i - 1, j) + oe) state = 0;
+      --i;
+    } else {
+      ops[n++] = 3;
+      if (AT(F, i, j) == AT(H, i, j - 1) + oe) state = 0;
+      --j;
+    }
+  }
+  for (int a = 0, b = n - 1; a < b; ++a, --b) {
+    const uint8_t t = ops[a];
+    ops[a] = ops[b];
+    ops[b] = t;
+  }
+  for (int64_t k = n; k < ldo; ++k) ops[k] = 0;
+  head[0] = (int32_t)AT(H, bi, bj);
+  head[1] = i;
+  head[2] = bi;
+  head[3] = j;
+  head[4] = bj;
+  head[5] = n;
+  head[6] = ident;
+  head[7] = 0;
+#undef AT
+}
+
+int orc_align_trace(const uint8_t *X, int64_t n, int xw, const uint8_t *Y, int64_t m, int yw, const int32_t *xi, const int32_t *yi,
+                    int64_t npairs, const int64_t *T, int A, int gap, int gap_open, int mode, int32_t *head, uint8_t *ops, int64_t ldo) {
+  if (!X || !Y || !xi || !yi || !T || !head || !ops || xw < 1 || yw < 1 || npairs < 0 || A < 1 || A > 256 || mode < 0 || mode > 3 ||
+      gap < 0 || gap_open < 0)
+    return 5;
+  int *xlen = (int *)malloc(sizeof(int) * (size_t)(n > 0 ? n : 1)), *ylen = (int *)malloc(sizeof(int) * (size_t)(m > 0 ? m : 1));
+  if (!xlen || !ylen) { free(xlen); free(ylen); return 6; }
+  int rc = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    xlen[r] = row_len(X + r * xw, xw);
+    for (int k = 0; k < xlen[r]; ++k)
+      if (X[r * xw + k] >= A) rc = 2;
+  }
+  for (int64_t r = 0; r < m; ++r) {
+    ylen[r] = row_len(Y + r * yw, yw);
+    for (int k = 0; k < ylen[r]; ++k)
+      if (Y[r * yw + k] >= A) rc = 2;
+  }
+  int64_t most = 1;
+  for (int64_t p = 0; p < npairs && !rc; ++p) {
+    if (xi[p] < 0 || xi[p] >= n || yi[p] < 0 || yi[p] >= m) { rc = 1; break; }
+    const int64_t cells = (int64_t)(xlen[xi[p]] + 1) * (ylen[yi[p]] + 1);
+    if (cells > ORC_TRACE_MAX_CELLS) rc = 3;
+    if (xlen[xi[p]] + ylen[yi[p]] > ldo) rc = 4;
+    if (cells > most) most = cells;
+  }
+  if (!rc) {
+#pragma omp parallel
+    {
+      int64_t *tab = (int64_t *)malloc(sizeof(int64_t) * 3 * (size_t)most);       /* this thread's H, E, F */
+      if (!tab) {
+#pragma omp atomic write
+        rc = 6;
+      }
+#pragma omp for schedule(dynamic, 4)
+      for (int64_t p = 0; p < npairs; ++p)
+        if (tab)
+          orc_trace_pair(mode, T, A, gap, gap_open, X + (int64_t)xi[p] * xw, xlen[xi[p]], Y + (int64_t)yi[p] * yw, ylen[yi[p]], tab,
+                         tab + most, tab + 2 * most, head + p * 8, ops + p * ldo, ldo);
+      free(tab);
+    }
+  }
+  free(xlen);
+  free(ylen);
+  return rc;
 }
