@@ -559,9 +559,11 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
 // rows.  gate2: what the launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the
 // probe's word (0 without one).  Workgroups that have no rows, or leave at the gate, take their ticket all the same.
 // lane i of a row of sixteen reads lane (i + N) & 15
+// Held to 64 VGPRs (left alone: 72): 8 waves per SIMD, no scratch - 90 -> 83 us at cfg3 (profiles/r16_knn_sym_filter.json, which
+// also has the recipe of the other merge builds measured there)
 #define PG_SYM_ROR(x, N) ((u32)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (N), 0xF, 0xF, false))
 #define PG_SYM_CE(a, b) { const u32 x_ = a, y_ = b; a = x_ < y_ ? x_ : y_; b = x_ < y_ ? y_ : x_; }
-__global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
+__global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
                                                                          const u32 *lowKeys, u32 capL, long long nrows, int k, int *idx,
                                                                          unsigned char *dist, u32 cap, u32 *evictCount, u32 *evictRows,
                                                                          const u32 *gate, u32 gateMask, u32 *gate2, u32 *ticket, u32 limit) {
@@ -660,13 +662,26 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_sym_merge_kernel(const u
     }
   }
   __syncthreads();                                           // (every wave of the workgroup: its rows' evictions are counted)
-  // (the ticket releases what the workgroup counted - the barrier orders its other waves' atomics before thread 0 -
-  //  and the workgroup that draws the last one acquires them all; a few thousand tickets, so the fences do not show)
+  // The ticket is a RELAXED add, and no fence stands beside it.  What the workgroup that draws the last one reads of the
+  // others is the count of evicted rows alone, and that word is only ever touched by agent-scope atomic read-modify-writes,
+  // which execute at the memory side, not in an XCD's L2: (1) every evict add above is a returning atomic whose value is
+  // used - the index of the store beside it - so it has been performed when its wave arrives at the barrier; (2) thread
+  // 0's ticket add is issued behind that barrier, so it is performed after every evict add of its workgroup; (3) the last
+  // ticket is drawn after all others were performed; (4) the decider reads the count with a read-modify-write of its own,
+  // issued after its ticket came back and before any of its stores (the ticket's word shares the count's 128-byte line).
+  // That read is an add of a zero the compiler cannot see: an add of the constant 0 is folded into a load (`global_load_dword
+  // ... sc1`, served by an L2 that may have kept the line); in the ISA it is `global_atomic_add ... sc0`, the third atomic
+  // of the kernel.  Nothing cached takes part, so there is nothing to release or to acquire.  The results, evictRows and the
+  // words the decider stores (the ticket back to 0, gate2, the count) are read by the launches behind this one only.
+  // (The release/acquire pair - an L2 write-back and an L1 invalidate per workgroup, 2048 of them - cost 50 us at cfg3.)
   if (threadIdx.x == 0) {
-    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+    if (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
+      u32 zero = 0u;
+      asm volatile("" : "+v"(zero));                         // (opaque: keeps the add an atomic instruction)
+      const u32 evictedRows = __hip_atomic_fetch_add(evictCount, zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       *ticket = 0u;
       if (gv != 0u) *gate2 = gv;
-      else if (__hip_atomic_load(evictCount, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > limit) { *evictCount = 0u; *gate2 = 0u; }
+      else if (evictedRows > limit) { *evictCount = 0u; *gate2 = 0u; }
       else *gate2 = 3u;
     }
   }
