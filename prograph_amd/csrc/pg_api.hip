@@ -540,78 +540,106 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
 }
 
 // kNN of the symmetric sweep (pg_mm_knn_sym_kernel): a row's records - one per piece of its block, passes
-// pieceStart[block] .. pieceStart[block + 1], PG_MM_KL keys each with the sorted list of k + 1 keys at the end - and its
-// min(lowCount, capL) delivered keys -> its k + 1 smallest keys in (distance << 24 | index) order, the order of the
-// rectangular sweep; ranks 1..k written out.  Sixteen lanes per row, four rows per wave.
-// Two memory levels: pieceStart, lowCount and the first 64 keys of the slot (inside the workspace whatever the count is;
-// masked to 0xFFFFFFFF from min(lowCount, capL) on) are asked for at once, then lane b's record b (five 16-byte loads)
-// and the rest of the slot, lane b entries b, b + 16, ... - the delivered keys stay in registers.
-// Selection: every lane sorts its sixteen delivered keys once (a network of 63 compare-exchanges in registers), then k + 1
+// pieceStart[block] .. pieceStart[block + 1], PG_MM_KL keys each with the sorted list of k + 1 keys at the end - and the
+// keys delivered to it -> its k + 1 smallest keys in (distance << 24 | index) order, the order of the rectangular sweep;
+// ranks 1..k written out.  Sixteen lanes per row, four rows per wave, sixteen rows per workgroup and trip: one GROUP of
+// receiver rows, whose delivered keys are one append log (pg_plan.h: sym_entry; word 16 g of lowCount counts it).
+// Binning: the workgroup reads the log coalesced - min(count, sym_group_cap) entries, all 256 threads - and puts every entry,
+// expanded to distance << 24 | sender row again, into its row's bin of capL keys in LDS; a returning LDS add on the row's
+// count gives the place, places from capL on are not stored, the count runs on.  Behind a barrier lane b takes its bin's
+// entries into registers; behind another the rows' records are staged in the SAME LDS block (the bins have left it: 20 KB
+// a workgroup, not 36, and 7 waves per SIMD, not 4: 118 -> 106 us at cfg3); the next trip's first barrier stands behind the
+// last read of them.  Three barriers a trip; the counts are two sets in turn (a trip zeroes the next one's, whose last
+// readers passed the trip before's third barrier) - and every wave of a workgroup makes the same trips (the bound is the
+// workgroup's first row), so the barrier in front of the ticket is reached by all of them.
+// The loads of the block's passes and of lane b's record b (five 16-byte loads) are issued in front of the binning.
+// Selection: lane b takes entries b, b + 16, ... of its row's bin into sixteen registers and sorts them once (a network of
+// 63 compare-exchanges), then k + 1
 // rounds of "smallest head wins and advances" over the sixteen lanes' two heads - list b's, a pointer into the staged
 // record, and the lane's delivered keys', which move down one register when they win: one reduction a round, nothing is
-// scanned twice (keys are unique; equal heads advance together; 0xFFFFFFFF = no entry).  LDS holds the records only,
-// 20 KB a workgroup.
-// Every list is complete below the cap only: a row whose (k+1)-th distance is not below it, or whose slot of delivered keys
-// overflowed, joins the evicted rows (pg_knn_rows_kernel finishes them).
+// scanned twice (keys are unique; equal heads advance together; 0xFFFFFFFF = no entry).
+// Every list is complete below the cap only: a row whose (k+1)-th distance is not below it, or whose bin overflowed, joins
+// the evicted rows (pg_knn_rows_kernel finishes them) - and so do all sixteen rows of a group whose LOG overflowed: entries
+// were lost and nobody knows whose (some row of such a group is over capL anyway).
 // The decision behind the merge is taken by the workgroup that finishes last (a ticket: `ticket`, a zeroed word of the
 // counter block, left at 0 again): too many evicted rows (clusters much larger than the slots of delivered keys, data
 // without neighbours below the cap) - the rectangular launch behind this kernel runs instead and starts from no evicted
 // rows.  gate2: what the launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the
 // probe's word (0 without one).  Workgroups that have no rows, or leave at the gate, take their ticket all the same.
+// Resource line (hipcc -O3, gfx950): 72 VGPRs, no scratch, LDS 20 608 B, 7 waves per SIMD (profiles/r17_knn_sym_group_delivery.json
+// has the builds measured: the parent's per-row slots 81 us, bins beside the records 118, this form 106).
 // lane i of a row of sixteen reads lane (i + N) & 15
-// Held to 64 VGPRs (left alone: 72): 8 waves per SIMD, no scratch - 90 -> 83 us at cfg3 (profiles/r16_knn_sym_filter.json, which
-// also has the recipe of the other merge builds measured there)
 #define PG_SYM_ROR(x, N) ((u32)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (N), 0xF, 0xF, false))
 #define PG_SYM_CE(a, b) { const u32 x_ = a, y_ = b; a = x_ < y_ ? x_ : y_; b = x_ < y_ ? y_ : x_; }
-__global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
-                                                                         const u32 *lowKeys, u32 capL, long long nrows, int k, int *idx,
+__global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8))) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
+                                                                         const u32 *lowKeys, u32 capL, int rowBits, long long nrows, int k, int *idx,
                                                                          unsigned char *dist, u32 cap, u32 *evictCount, u32 *evictRows,
                                                                          const u32 *gate, u32 gateMask, u32 *gate2, u32 *ticket, u32 limit) {
   constexpr int kRec = PG_MM_KL, kOwn = PG_SYM_MAX_PIECES * kRec, kLane = PG_SYM_MAX_CAPL / 16;
   static_assert(kRec == 20 && kLane == 16, "records of whole uint4; sixteen delivered keys a lane");
+  // one LDS block in two roles a trip: the group's bins (per row its delivered keys, as they arrive) while the log is read,
+  // then - the bins are in registers - the rows' records
   __shared__ __attribute__((aligned(16))) u32 keys[PG_WG_WAVES][4][kOwn];
+  static_assert(4 * PG_WG_WAVES * PG_SYM_MAX_CAPL <= PG_WG_WAVES * 4 * kOwn, "the bins fit the records' block");
+  u32 (*bins)[PG_SYM_MAX_CAPL] = reinterpret_cast<u32 (*)[PG_SYM_MAX_CAPL]>(&keys[0][0][0]);
+  __shared__ u32 binCount[2][4 * PG_WG_WAVES];               // how many keys arrived for a row (two sets: trips in turn)
   const u32 gv = gate ? __builtin_nontemporal_load(gate) : 0u;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> 4, b = lane & 15;
   const bool open = !gate || ((gateMask >> gv) & 1u);
-  // (whole waves; the grid is a few workgroups a CU, every wave takes four rows in turns: few tickets on one word)
-  for (long long row0 = ((long long)blockIdx.x * PG_WG_WAVES + wv) * 4; open && row0 < nrows; row0 += (long long)gridDim.x * PG_WG_WAVES * 4) {
+  if (threadIdx.x < 4 * PG_WG_WAVES) binCount[0][threadIdx.x] = 0u;
+  int trip = 0;
+  // (whole workgroups; the grid is a few workgroups a CU, every one takes a group of sixteen rows in turns: few tickets on one word)
+  for (long long first = (long long)blockIdx.x * (4 * PG_WG_WAVES); open && first < nrows; first += (long long)gridDim.x * (4 * PG_WG_WAVES), trip ^= 1) {
     const int k1 = k + 1, off = kRec - k1;
-    const long long blk = row0 >> 6;                         // (four consecutive rows from a multiple of four: one block)
-    const long long row = row0 + g;
+    const long long blk = first >> 6;                        // (sixteen consecutive rows from a multiple of sixteen: one block)
+    const long long row = first + 4 * wv + g;
     const bool mine = row < nrows;
-    const long long rowIn = mine ? row : row0;               // (idle groups read the wave's first row: in bounds, unused)
-    const u32 *low = lowKeys + rowIn * (long long)capL + b;  // (lane b: entries b, b + 16, ...)
-    // The loads of level 1 and the records are unconditional, from addresses inside the workspace - a lane without a piece
-    // reads record 0 of its block - and masked afterwards; the rest of the slot is loaded up to the count.  The LDS
-    // stores stand behind the last load, so no load waits for another.
-    // level 1: the block's passes, the row's count and the head of its slot
+    const long long rowIn = mine ? row : first;              // (idle lanes read the group's first row: in bounds, unused)
+    // level 1: the block's passes and the group's count; then record b - unconditional loads from addresses inside the
+    // workspace (a lane without a piece reads record 0 of its block), masked afterwards
     const u32 s0 = pieceStart[blk], s1 = pieceStart[blk + 1];
-    u32 cnt = lowCount[rowIn];
-    // (the sixteen delivered keys of a lane are sixteen names, not an array: every one stays in its register)
-    u32 d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15;
-#define PG_SYM_EARLY(j, d) d = (u32)(16 * j + b) < capL ? low[16 * j] : 0xFFFFFFFFu;
-    if (capL >= 64) { d0 = low[0]; d1 = low[16]; d2 = low[32]; d3 = low[48]; }   // (the production slot: no test)
-    else { PG_SYM_EARLY(0, d0) PG_SYM_EARLY(1, d1) PG_SYM_EARLY(2, d2) PG_SYM_EARLY(3, d3) }
-    __builtin_amdgcn_sched_barrier(0);
-    cnt = mine ? cnt : 0u;
+    const u32 logged = lowCount[first];
     u32 np = s1 - s0;
     np = np > PG_SYM_MAX_PIECES ? PG_SYM_MAX_PIECES : np;
-    const int nl = (int)(cnt < capL ? cnt : capL);
     u32 *own = &keys[wv][g][0];
-    // level 2: record b and the rest of the slot
     const bool has = mine && b < (int)np;
-    const uint4 *rec = reinterpret_cast<const uint4 *>(partial) + (((long long)s0 + (b < (int)np ? b : 0)) * 64 + (row & 63)) * (kRec / 4);
+    const uint4 *rec = reinterpret_cast<const uint4 *>(partial) + (((long long)s0 + (b < (int)np ? b : 0)) * 64 + (rowIn & 63)) * (kRec / 4);
     const uint4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3], r4 = rec[4];
-#define PG_SYM_LATE(j, d) d = 16 * j + b < nl ? low[16 * j] : 0xFFFFFFFFu;
-    PG_SYM_LATE(4, d4) PG_SYM_LATE(5, d5) PG_SYM_LATE(6, d6) PG_SYM_LATE(7, d7) PG_SYM_LATE(8, d8) PG_SYM_LATE(9, d9)
-    PG_SYM_LATE(10, d10) PG_SYM_LATE(11, d11) PG_SYM_LATE(12, d12) PG_SYM_LATE(13, d13) PG_SYM_LATE(14, d14) PG_SYM_LATE(15, d15)
-    __builtin_amdgcn_sched_barrier(0);
+    // the group's log into the rows' bins
+    const u32 capG = sym_group_cap((u32)nrows, (u32)first, capL);
+    const u32 nlog = logged < capG ? logged : capG;
+    const u32 *log = lowKeys + first * (long long)capL;
+    __syncthreads();                                         // (the last trip's records are read; this trip's counts are zero)
+    for (u32 e0 = threadIdx.x; e0 < nlog; e0 += 4 * PG_WG_THREADS) {   // (four loads of a thread in flight)
+      u32 en[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) en[j] = e0 + j * PG_WG_THREADS < nlog ? log[e0 + j * PG_WG_THREADS] : 0u;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (e0 + j * PG_WG_THREADS < nlog) {
+          const u32 place = sym_entry_place(en[j]);
+          const u32 at = atomicAdd(&binCount[trip][place], 1u);
+          if (at < capL) bins[place][at] = sym_entry_key(en[j], rowBits);
+        }
+      }
+    }
+    if (threadIdx.x < 4 * PG_WG_WAVES) binCount[trip ^ 1][threadIdx.x] = 0u;   // (last read before the last trip's third barrier)
+    __syncthreads();
+    // lane b: entries b, b + 16, ... of its row's bin
+    // (the sixteen delivered keys of a lane are sixteen names, not an array: every one stays in its register)
+    const u32 cnt = mine ? binCount[trip][4 * wv + g] : 0u;
+    const int nl = (int)(cnt < capL ? cnt : capL);
+    const u32 *low = &bins[4 * wv + g][b];
+    u32 d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15;
+#define PG_SYM_BIN(j, d) d = 16 * j + b < nl ? low[16 * j] : 0xFFFFFFFFu;
+    PG_SYM_BIN(0, d0) PG_SYM_BIN(1, d1) PG_SYM_BIN(2, d2) PG_SYM_BIN(3, d3) PG_SYM_BIN(4, d4) PG_SYM_BIN(5, d5) PG_SYM_BIN(6, d6) PG_SYM_BIN(7, d7)
+    PG_SYM_BIN(8, d8) PG_SYM_BIN(9, d9) PG_SYM_BIN(10, d10) PG_SYM_BIN(11, d11) PG_SYM_BIN(12, d12) PG_SYM_BIN(13, d13) PG_SYM_BIN(14, d14) PG_SYM_BIN(15, d15)
+#undef PG_SYM_BIN
+    __syncthreads();                                         // (the bins are in registers: the block takes the records)
     {
       uint4 *st = reinterpret_cast<uint4 *>(own + b * kRec);  // (a lane without a piece stages what it read: never its head)
       st[0] = r0; st[1] = r1; st[2] = r2; st[3] = r3; st[4] = r4;
     }
-#define PG_SYM_MASK(j, d) d = 16 * j + b < nl ? d : 0xFFFFFFFFu;
-    PG_SYM_MASK(0, d0) PG_SYM_MASK(1, d1) PG_SYM_MASK(2, d2) PG_SYM_MASK(3, d3)
     // the lane's delivered keys in ascending order (no entries last: Batcher's odd-even merge sort of sixteen); rows of
     // up to sixteen keys hold one a lane, as it stands
     if (__builtin_amdgcn_ballot_w64(nl > 16) != 0) {
@@ -650,12 +678,9 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(8
           idx[row * k + r - 1] = m == 0xFFFFFFFFu ? -1 : (int)(m & 0x00FFFFFFu);
           dist[row * k + r - 1] = (unsigned char)(m >> 24);
         }
-        if (r == k && ((m >> 24) >= cap || cnt > capL)) evictRows[atomicAdd(evictCount, 1u)] = (u32)row;   // (0xFFFFFFFF, no entry, reads 255)
+        if (r == k && ((m >> 24) >= cap || cnt > capL || logged > capG)) evictRows[atomicAdd(evictCount, 1u)] = (u32)row;   // (0xFFFFFFFF, no entry, reads 255)
       }
     }
-#undef PG_SYM_EARLY
-#undef PG_SYM_LATE
-#undef PG_SYM_MASK
     if (mine && b < k) {
       idx[row * k + b] = res == 0xFFFFFFFFu ? -1 : (int)(res & 0x00FFFFFFu);
       dist[row * k + b] = (unsigned char)(res >> 24);
@@ -1119,6 +1144,7 @@ static int launch_sym(const KnnRun &r) {
   sa.lowCount = (u32 *)(base + pl.symWs.lowCount); sa.lowKeys = (u32 *)(base + pl.symWs.lowKeys);
   sa.capL = pl.symCapL;
   sa.deliver = pl.symDeliver;
+  sa.rowBits = pl.symRowBits;
   pg_sym_set(&s, sa);
   s.mmEvict = nullptr; s.mmEvictRows = nullptr; s.mmPieces = 0; s.mmPieceFrom = 0; s.mmPartial = nullptr;
   s.rowsPerWave = 2 * PG_MM_RB; s.rowsPerPass = 2 * PG_MM_RB; s.mmTailFrom = pl.symPasses; s.mmTailRows = 2 * PG_MM_RB;
@@ -1132,7 +1158,7 @@ static int launch_sym(const KnnRun &r) {
   if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
   if (int rc = pg_launched(kMmSym[r.ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), r.stream), "pg_mm_knn_sym_kernel")) return rc;
   pg_knn_sym_merge_kernel<<<dim3(pl.symMergeGrid), dim3(PG_WG_THREADS), 0, r.stream>>>(
-      sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, r.nrows, r.k, r.idx, r.dist, r.p.knnGuess, r.p.mmEvict,
+      sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, sa.rowBits, r.nrows, r.k, r.idx, r.dist, r.p.knnGuess, r.p.mmEvict,
       r.p.mmEvictRows, s.gate, s.gateMask, gate2, r.p.mmPassCounter + 17, (u32)(pl.symLimit < 0 ? 0 : pl.symLimit));
   return pg_launched("pg_knn_sym_merge_kernel");
 }

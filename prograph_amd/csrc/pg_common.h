@@ -450,19 +450,22 @@ struct NsqParams {
 // pg_mm_knn_sym_kernel (pg_mm.h, KS): the symmetric kNN sweep of a self graph.  Pass i is plan[i] = (row block of 64,
 // first super-tile, end super-tile, -) and leaves its rows' records (PG_MM_KL keys, 16-byte aligned; the sorted list of
 // k + 1 keys is their end) at partial[(i * 64 + row) * PG_MM_KL];
-// a pair (row, col), col > row, below the cap is delivered to lowKeys[col * capL + atomicAdd(lowCount[col])] as
-// distance << 24 | row.  deliver = 0: no delivery (timing experiments: wrong results).
+// a pair (row, col), col > row, below the cap is delivered to the log of col's GROUP of sixteen receiver rows (pg_plan.h:
+// sym_entry): lowKeys[(col & ~15) * capL + pos] = place | distance | row, pos from lowCount[col & ~15], the group's
+// counter - one add per group of a batch.  rowBits: the entry's row field.  deliver = 0: no delivery (timing experiments:
+// wrong results).
 // The launch carries them in fields of NsqParams that only eps launches read (the struct, and with it the argument
-// segment and the code of every other instance, stays what it was): slotIdx, counts, countsLo, slotAux, cap, epsOrdered
+// segment and the code of every other instance, stays what it was): slotIdx, counts, countsLo, slotAux, cap, epsOrdered, span
 struct SymArgs {
   const int4 *plan;
   u32 *partial, *lowCount, *lowKeys;
   u32 capL;
   int deliver;
+  int rowBits;
 };
 static inline void pg_sym_set(NsqParams *p, const SymArgs &a) {
   p->slotIdx = (int *)a.plan; p->counts = a.partial; p->countsLo = a.lowCount; p->slotAux = (int *)a.lowKeys;
-  p->cap = a.capL; p->epsOrdered = a.deliver;
+  p->cap = a.capL; p->epsOrdered = a.deliver; p->span = (u32)a.rowBits;
 }
 #define PG_SYM_MAX_PIECES 16   // symmetric kNN: pieces of a row block's columns at most (the merge holds their lists in LDS)
 #define PG_SYM_MAX_CAPL 256    // ... and delivered keys per row at most

@@ -63,6 +63,7 @@ typedef int pg_v16i __attribute__((ext_vector_type(16)));
 #define PG_MM_PRIO_STEPS 16  // R = 2: steps of the progress-driven issue priority along a sweep
 #define PG_MM_EVICT_MAX 48   // kNN: up to this many rows of a pass that lose their cap at a checkpoint are evicted (NsqParams::mmEvict); more (nearly the
                              // whole pass: data without neighbours inside the cap, e.g. clusters smaller than k + 1): the second phase in the pass
+#include "pg_plan.h"        // the entries of delivered keys (sym_entry, sym_group_cap: one text for sweep, merge and host); wants the constants above
 #ifndef PG_EXP_SAMETILE
 #define PG_EXP_SAMETILE 0   // experiment builds: 1 = every fragment load reads the same super-tile (L1 hits; wrong results)
 #endif
@@ -126,7 +127,7 @@ __device__ __forceinline__ int pg_or16(const pg_v16i &d) {
 // KS: the symmetric kNN sweep of a self graph (pg_mm_knn_sym_kernel below; the 64-row short-list instance only): a pass is
 // (row block, stretch of the super-tiles from the block's own on) out of a plan (SymArgs, pg_common.h), every unordered pair
 // is evaluated once - by the pass of its LOWER row, which keeps the pair for its own list (column >= row) and delivers
-// it to the higher row's slot (SymArgs::lowKeys: one key per pair, d < cap only).  Bounds stay at the optimistic cap for the
+// it to the log of the higher row's group (SymArgs::lowKeys: one entry per pair, d < cap only).  Bounds stay at the optimistic cap for the
 // whole sweep (no publish, no checkpoints, no second phase: the owner of a pair cannot know the other row's threshold;
 // what the cap hides the merge detects, as for column pieces), lists go to SymArgs::partial, pg_knn_sym_merge_kernel
 // (pg_api.hip) makes the rows' results.

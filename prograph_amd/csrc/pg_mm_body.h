@@ -238,23 +238,48 @@
       return pos;
     };
     // KS: pair (rowg, col), col > rowg, at distance d below the cap also belongs to row `col` (another pass's): its key
-    // goes to that row's slot of symCapL keys through an atomic counter; the merge sorts it in.  (A slot that overflows
-    // is counted on: the merge evicts the row.)
+    // goes to the log of that row's GROUP of sixteen receiver rows (pg_plan.h: sym_entry), and the merge bins and sorts it
+    // in.  Called wave-wide.  The lanes of a batch are gathered by group first - a wave-uniform loop over the distinct
+    // groups among them, no memory operation in it: the first lane left names its group, the equal lanes note their rank
+    // among themselves - then the lowest lane of every group adds the group's population to its counter (ONE returning
+    // atomic instruction for the batch), the others take the base from it, and every lane stores its entry behind it: the
+    // entries of a group are consecutive words.  (cfg3: the mates of 64 consecutive rows sit in 64 consecutive columns, a
+    // batch of 64 lands in four or five groups.)  A log that overflows is counted on: the merge evicts the group.
     auto deliver = [&](bool on, u32 rowg, u32 col, u32 d) {
       if constexpr (KS) {
         const auto &kd = K();                               // (cold arguments: read where they are used)
-        if (on && kd.epsOrdered) {
-          const u32 capL = kd.cap;
+        on = on && kd.epsOrdered;
+        u64 left = __builtin_amdgcn_ballot_w64(on);
+        if (left) {
+          const u32 entry = sym_entry(col & 15u, d, rowg, (int)kd.span);
+          u32 pk = 0;                                       // the lane's rank in its group << 16 | the group's lanes << 8 | its lowest lane
+          do {
+            const int j = __builtin_ctzll(left);            // (the lowest lane of its group: whole groups leave `left`)
+            const bool mine = on && (col ^ (u32)__builtin_amdgcn_readlane((int)col, j)) < 16u;
+            const u64 same = __builtin_amdgcn_ballot_w64(mine);
+            pk = mine ? (mask_rank(same) << 16 | ((u32)__popcll(same) << 8 | (u32)j)) : pk;
+            left &= ~same;
+          } while (left);
+          const u32 rank = pk >> 16, pop = (pk >> 8) & 0xFFu;
+          const int leader = (int)(pk & 0xFFu);
+          const u32 first = col & ~15u;                     // the group's first row: its counter's word, its log's rows
+          [[maybe_unused]] const u32 capG = sym_group_cap(ncols, first, kd.cap);
+          u32 *log = reinterpret_cast<u32 *>(kd.slotAux) + (long long)first * kd.cap;
 #if defined(PG_KNN_SYM_DELIVER_TIMING) && PG_KNN_SYM_DELIVER_TIMING == 1
-          // (timing builds only, wrong results: the returning atomic without the store)
-          const u32 pos = atomicAdd(&kd.countsLo[col], 1u);
-          if (pos == 0xFFFFFFFFu) reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL] = (d << 24) | rowg;
+          // (timing builds only, wrong results: the groups' returning atomic without the stores)
+          u32 base = 0;
+          if (on && lane == leader) base = atomicAdd(&kd.countsLo[first], pop);
+          base = (u32)__builtin_amdgcn_ds_bpermute(leader << 2, (int)base);
+          if (on && base == 0xFFFFFFFFu) log[rank] = entry;
 #elif defined(PG_KNN_SYM_DELIVER_TIMING) && PG_KNN_SYM_DELIVER_TIMING == 2
-          // (timing builds only, wrong results: the store without the atomic, at a place in the slot the sender row fixes)
-          reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL + rowg % capL] = (d << 24) | rowg;
+          // (timing builds only, wrong results: the runs without the atomic, at a place in the log the leader's row fixes)
+          const u32 base = (u32)__builtin_amdgcn_ds_bpermute(leader << 2, (int)(rowg * 64u)) % (capG > pop ? capG - pop : 1u);
+          if (on && pop <= capG) log[base + rank] = entry;
 #else
-          const u32 pos = atomicAdd(&kd.countsLo[col], 1u);
-          if (pos < capL) reinterpret_cast<u32 *>(kd.slotAux)[(long long)col * capL + pos] = (d << 24) | rowg;
+          u32 base = 0;
+          if (on && lane == leader) base = atomicAdd(&kd.countsLo[first], pop);
+          base = (u32)__builtin_amdgcn_ds_bpermute(leader << 2, (int)base);
+          if (on && base + rank < capG) log[base + rank] = entry;
 #endif
         }
       }

@@ -40,6 +40,39 @@ static_assert(PG_MODE_KNN == 1 && PG_MODE_KNN_SHORT == 3 && PG_MODE_KNN_SHORT2 =
                   PG_MM_DENSE_L2 == 48 && PG_MM_DIRECT_RUN == 8 && PG_SYM_MAX_PIECES == 16 && PG_SYM_MAX_CAPL == 256,
               "pg_plan.h: the host-only copies of the engine's constants follow pg_common.h and pg_mm.h");
 
+// ---------------------------------------------------------------------------------------
+// Delivered keys of the symmetric kNN sweep (pg_mm.h KS, pg_knn_sym_merge_kernel).  Sixteen consecutive
+// receiver rows are a GROUP: group g = row >> 4 owns the words [16 g capL, 16 g capL + sym_group_cap) of the lowKeys region
+// - the sixteen rows' former slots - as one append log, and word 16 g of the lowCount region as its counter.  An entry is
+// 4 bytes: the receiver's place in its group (4 bits) | the distance (dBits = bits of cap - 1: delivered distances are below
+// the cap) | the sender row (the other 28 - dBits bits, 24 at most).  The widths are constants of a launch: the host plan computes the
+// row field's, knn_plan declines the sweep where a row does not fit it, and sweep and merge run the text below.
+// ---------------------------------------------------------------------------------------
+PG_HD static inline int sym_dist_bits(uint32_t cap) {
+  int b = 0;
+  for (uint32_t v = cap > 0 ? cap - 1u : 0u; v; v >>= 1) ++b;
+  return b;
+}
+// (a key has 24 index bits: caps up to 16 leave the row field at those, and the entry is the key under its place)
+PG_HD static inline int sym_row_bits(uint32_t cap) { return 28 - sym_dist_bits(cap) < 24 ? 28 - sym_dist_bits(cap) : 24; }
+// rows 0 .. n - 1 fit the row field
+PG_HD static inline bool sym_rows_fit(int64_t n, uint32_t cap) {
+  const int rb = sym_row_bits(cap);
+  return rb >= 1 && n <= ((int64_t)1 << rb);
+}
+PG_HD static inline uint32_t sym_entry(uint32_t place, uint32_t d, uint32_t row, int rowBits) { return place << 28 | d << rowBits | row; }
+PG_HD static inline uint32_t sym_entry_place(uint32_t e) { return e >> 28; }
+// ... back to distance << 24 | sender row, the key order of the rectangular sweep
+PG_HD static inline uint32_t sym_entry_key(uint32_t e, int rowBits) {
+  return ((e & 0x0FFFFFFFu) >> rowBits) << 24 | (e & ((1u << rowBits) - 1u));
+}
+// entries the log of the group from row `first` (a multiple of 16) holds: its rows' capL words each (a last group of fewer
+// than sixteen rows ends with the region)
+PG_HD static inline uint32_t sym_group_cap(uint32_t n, uint32_t first, uint32_t capL) {
+  const uint32_t rows = n > first ? n - first : 0u;
+  return (rows < 16u ? rows : 16u) * capL;
+}
+
 #define PG_PROBE_ROWS 64        // sample rows
 #define PG_PROBE_WAVES 128      // waves per sample row: every 8th column tile (PG_PROBE_STRIDE), one turn of four tiles each at N = 200k
                                 // (a turn = one L2 / Infinity-Cache round trip, ~2 us: 1 x 1 wave 206 us, 64 x 4 67 us, 64 x 32 22 us)
@@ -503,6 +536,7 @@ struct KnnPlan {
   long long symSlots, symPasses, symNb, symNst, symGridWaves, symLimit, symZero4;
   int symPiece, symPieceMin;
   uint32_t symCapL;
+  int symRowBits;            // the sender row's field of a delivered entry (sym_row_bits of the cap)
   bool symDeliver;
   unsigned symPlanGrid, symMergeGrid;
   int64_t symBase;           // ws_sym_offset; the regions behind it:
@@ -580,7 +614,8 @@ static inline KnnPlan knn_plan(const KnnShape &s, const KnnHw &hw, const PgKnobs
   pl.symWs = sym_ws(nrows, hw.cus, kn);
   pl.symBase = ws_sym_offset(nrows);
   const bool sym = pl.shortList && pl.evict && s.bits == PG_BITS_5 && nq <= 3 && s.samePlanes && s.row0 == 0 && nrows == ncols &&
-                   filter != 0 && pl.symWs.bytes > 0 && (kn.knnSym.v == 1 || pl.two);
+                   filter != 0 && pl.symWs.bytes > 0 && (kn.knnSym.v == 1 || pl.two) &&
+                   sym_rows_fit(nrows, pl.guess);            // (a sender row fits its field of a delivered entry: sym_entry)
   const long long symSlots = sym ? sym_slots(hw.occSym, hw.cus, kn) : 0;
   const long long symPasses = sym ? sym_plan_host(nrows, symSlots, (int)kn.symPiece.v, (int)kn.symPieceMin.v, nullptr, 0) : 0;
   // (a plan the workspace was not sized for - it is sized for the most slots the instance can have - is not taken:
@@ -592,6 +627,7 @@ static inline KnnPlan knn_plan(const KnnShape &s, const KnnHw &hw, const PgKnobs
     pl.symNb = (nrows + 63) / 64; pl.symNst = (nrows + PG_MM_ST - 1) / PG_MM_ST;
     pl.symGateMask = 1u << 0;
     pl.symCapL = (uint32_t)kn.symCapL.v;
+    pl.symRowBits = sym_row_bits(pl.guess);
     pl.symDeliver = kn.symDeliver.v != 0;
     pl.symGridWaves = ((pl.symPasses < pl.symSlots ? pl.symPasses : pl.symSlots) + PG_WG_WAVES - 1) / PG_WG_WAVES * PG_WG_WAVES;
     // (lowCount: 256-byte aligned and padded to it, so whole uint4 stay inside)
