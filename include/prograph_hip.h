@@ -244,6 +244,14 @@ int pg_knn_hamming(const void *row_planes, int64_t row_npad, int64_t row0, int64
  * (tests); piece = 0: the guided rule, pieces of at least piece_min super-tiles (0: the library's default).
  */
 int64_t pg_knn_sym_plan(int64_t n, int64_t slots, int piece, int piece_min, int32_t *out, int64_t max_passes);
+/*
+ * pg_knn_sym_plan_device — the same plan as the device computes it for a launch (tests: it is compared with
+ * pg_knn_sym_plan without a kNN launch).  plan_out: device memory for max_passes entries of four int32,
+ * piece_start_out: device memory for (n + 63) / 64 + 1 uint32 - the first pass of every row block, then the
+ * number of passes.  Returns the number of passes; a plan of more than max_passes is an error, nothing runs.
+ */
+int64_t pg_knn_sym_plan_device(int64_t n, int64_t slots, int piece, int piece_min, int32_t *plan_out,
+                               uint32_t *piece_start_out, int64_t max_passes, void *stream);
 
 /*
  * pg_knn_hamming_round — kNN beyond 63 neighbours, 63/64 ranks per all-pairs round.

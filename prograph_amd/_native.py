@@ -41,7 +41,7 @@ SYMBOLS = [
     "pg_version", "pg_last_error", "pg_device_info", "pg_npad", "pg_ngroups", "pg_nchunks", "pg_planes_bytes", "pg_workspace_bytes",
     "pg_pack_planes", "pg_pack_bytes",
     "pg_hamming_dense", "pg_eps_slots", "pg_scan_scratch_bytes", "pg_exclusive_scan",
-    "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_sym_plan", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
+    "pg_eps_compact", "pg_eps_fill_rows", "pg_eps_slots_sym", "pg_eps_compact_sym", "pg_knn_hamming", "pg_knn_sym_plan", "pg_knn_sym_plan_device", "pg_knn_hamming_round", "pg_index_flags", "pg_compact_flags",
     "pg_lev_profile", "pg_lev_candidates", "pg_lev_candidates_sym", "pg_lev_knn", "pg_csr_row_stats",
     "pg_levenshtein_dense", "pg_lev_eps_pairs", "pg_lev_eps_count", "pg_lev_eps_fill",
     "pg_lev_long_pack", "pg_levenshtein_long_dense",
@@ -131,6 +131,8 @@ def _load():
         lib.pg_knn_hamming.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]
         lib.pg_knn_sym_plan.restype = _i64
         lib.pg_knn_sym_plan.argtypes = [_i64, _i64, _i32, _i32, _vp, _i64]
+        lib.pg_knn_sym_plan_device.restype = _i64
+        lib.pg_knn_sym_plan_device.argtypes = [_i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp]
         lib.pg_knn_hamming_round.argtypes = [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp,
                                              _vp, _vp, _vp]
         lib.pg_query_workspace_bytes.restype = _i64

@@ -67,37 +67,78 @@ int64_t pg_workspace_bytes(int64_t nrows) { return workspace_bytes(nrows, cu_cou
 // workgroup 0: thread t takes a contiguous run of blocks - their piece counts, a scan over the threads, then the
 // entries and pieceStart[b] = the first pass of block b (pieceStart[nb] = passes in all).  The workgroups behind it zero
 // the rows' counts of delivered keys meanwhile (`zero4` uint4 of lowCount: the launch's memset, folded in)
-__global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(long long nb, long long nst, long long slots, int piece, int pmin,
-                                                                int4 *plan, u32 *pieceStart, uint4 *zero, long long zero4) {
-  __shared__ u32 sums[1024];
-  const int t = threadIdx.x;
-  if (blockIdx.x > 0) {
-    for (long long i = (long long)(blockIdx.x - 1) * 1024 + t; i < zero4; i += (long long)(gridDim.x - 1) * 1024) zero[i] = make_uint4(0u, 0u, 0u, 0u);
+// The scan: a thread of up to four blocks (up to 262 144 rows) keeps their counts in a register - one sym_block_pieces, with its
+// 64-bit division, a block - and recomputes them beyond; an inclusive scan inside every wave (six shuffles), the sixteen
+// waves' totals through LDS behind ONE barrier, every thread adds up the totals of the waves in front of it.
+// The function is the whole workgroup's (1024 threads, a barrier in it): workgroup `vb` of `vgrid`.  pg_knn_sym_plan_kernel
+// is a launch of its own - symmetric launches without a probe -, behind a probe its workgroups ride in pg_decide_kernel's
+// launch (KnnPlan::symPlanRides): the plan needs the shape and the workspace alone, and the sweep waits for neither twice.
+struct SymPlanArgs {
+  long long nb, nst, slots;
+  int piece, pmin;
+  int4 *plan;
+  u32 *pieceStart;
+  uint4 *zero;
+  long long zero4;
+  unsigned grid;             // workgroups: one plans, the rest zero (0: nothing rides)
+};
+static __device__ __forceinline__ void sym_plan_workgroup(unsigned vb, unsigned vgrid, const SymPlanArgs &a) {
+  __shared__ u32 waveTotal[16];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  if (vb > 0) {
+    for (long long i = (long long)(vb - 1) * 1024 + t; i < a.zero4; i += (long long)(vgrid - 1) * 1024) a.zero[i] = make_uint4(0u, 0u, 0u, 0u);
     return;
   }
-  const long long per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
-  u32 mine = 0;
-  for (long long b = b0; b < b1; ++b) mine += (u32)sym_block_pieces(b, nst, slots, piece, pmin);
-  sums[t] = mine;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const u32 x = t >= o ? sums[t - o] : 0u;
-    __syncthreads();
-    sums[t] += x;
-    __syncthreads();
-  }
-  u32 at = sums[t] - mine;
-  for (long long b = b0; b < b1; ++b) {
-    const int np = sym_block_pieces(b, nst, slots, piece, pmin);
-    pieceStart[b] = at;
-    for (int q = 0; q < np; ++q, ++at) {
-      int f, e;
-      sym_piece_range(b, nst, np, q, &f, &e);
-      plan[at] = make_int4((int)b, f, e, q);
+  const long long nb = a.nb, per = (nb + 1023) / 1024, b0 = t * per, b1 = b0 + per < nb ? b0 + per : nb;
+  const bool few = per <= 4;
+  u32 np4 = 0u, mine = 0;                                  // (four counts of at most 16, a byte each; one copy of the division: no unrolling)
+  if (few) {
+#pragma unroll 1
+    for (int j = 0; b0 + j < b1; ++j) {
+      const u32 np = (u32)sym_block_pieces(b0 + j, a.nst, a.slots, a.piece, a.pmin);
+      np4 |= np << (8 * j);
+      mine += np;
     }
+  } else {
+    // (one copy here too: the loop vectoriser makes sixteen of the division, which spill)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (long long b = b0; b < b1; ++b) mine += (u32)sym_block_pieces(b, a.nst, a.slots, a.piece, a.pmin);
   }
-  if (t == 1023) pieceStart[nb] = sums[1023];
+  u32 incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u32 x = (u32)__shfl_up((int)incl, o);
+    incl += lane >= o ? x : 0u;
+  }
+  if (lane == 63) waveTotal[wv] = incl;
+  __syncthreads();
+  u32 front = 0, total = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const u32 x = waveTotal[i];
+    front += i < wv ? x : 0u;
+    total += x;
+  }
+  u32 at = front + incl - mine;
+  auto entries = [&](long long b, int np) {
+    a.pieceStart[b] = at;
+#pragma unroll 1
+    for (int q = 0; q < np; ++q, ++at) {                     // (one copy of the loop body: unrolled it spills, and the decision launch would need scratch)
+      int f, e;
+      sym_piece_range(b, a.nst, np, q, &f, &e);
+      a.plan[at] = make_int4((int)b, f, e, q);
+    }
+  };
+  if (few) {
+#pragma unroll 1
+    for (int j = 0; b0 + j < b1; ++j) entries(b0 + j, (int)((np4 >> (8 * j)) & 0xFFu));
+  } else {
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (long long b = b0; b < b1; ++b) entries(b, sym_block_pieces(b, a.nst, a.slots, a.piece, a.pmin));
+  }
+  if (t == 1023) a.pieceStart[nb] = total;
 }
+__global__ __launch_bounds__(1024) void pg_knn_sym_plan_kernel(SymPlanArgs a) { sym_plan_workgroup(blockIdx.x, gridDim.x, a); }
 extern "C" {
 // the plan of the symmetric kNN sweep of an n x n self graph for `slots` waves (host only, no device needed): up to
 // max_passes entries (row block, first super-tile, end super-tile, piece of the block) to out[4 * i ..]; returns the
@@ -105,6 +146,20 @@ extern "C" {
 int64_t pg_knn_sym_plan(int64_t n, int64_t slots, int piece, int piece_min, int32_t *out, int64_t max_passes) {
   if (n <= 0 || slots <= 0) return pg_fail(PG_E_BADARG, "pg_knn_sym_plan: bad argument");
   return sym_plan_host(n, slots, piece, piece_min > 0 ? piece_min : (int)read_knobs().symPieceMin.v, out, max_passes);
+}
+// the same plan as pg_knn_sym_plan_kernel writes it (tests: the device plan against the host's without a kNN launch):
+// plan_out: device memory for max_passes entries of four ints, piece_start_out: (n + 63) / 64 + 1 words; returns the number
+// of passes, an error where they exceed max_passes (nothing is launched then)
+int64_t pg_knn_sym_plan_device(int64_t n, int64_t slots, int piece, int piece_min, int32_t *plan_out, uint32_t *piece_start_out,
+                               int64_t max_passes, void *stream) {
+  if (n <= 0 || n > PG_MAX_N_KNN || slots <= 0 || !plan_out || !piece_start_out) return pg_fail(PG_E_BADARG, "pg_knn_sym_plan_device: bad argument");
+  const int pmin = piece_min > 0 ? piece_min : (int)read_knobs().symPieceMin.v;
+  const int64_t passes = sym_plan_host(n, slots, piece, pmin, nullptr, 0);
+  if (passes > max_passes) return pg_fail(PG_E_BADARG, "pg_knn_sym_plan_device: the plan has more passes than max_passes");
+  SymPlanArgs a = {(n + 63) / 64, (n + PG_MM_ST - 1) / PG_MM_ST, slots, piece, pmin, (int4 *)plan_out, piece_start_out, nullptr, 0, 1u};
+  pg_knn_sym_plan_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(a);
+  if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
+  return passes;
 }
 }  // extern "C"
 
@@ -460,7 +515,10 @@ static void eps_interval(int cmp, double eps, u32 *lo, u32 *span, long long dmin
 // one workgroup: 16 threads per sample row (a quarter wave) sum the row's per-wave counts, the wave of a row then the
 // workgroup combine the verdicts
 __global__ __launch_bounds__(1024) void pg_decide_kernel(const u32 *counts, int nsample, int wavesPerRow, u32 need, long long ncols,
-                                                          int force, u32 *gate, u32 *line, int lineWords) {
+                                                          int force, u32 *gate, u32 *line, int lineWords, SymPlanArgs ride) {
+  // the workgroups behind the first: the plan of the symmetric sweep this launch is followed by (sym_plan_workgroup; their
+  // writes - the plan, pieceStart, the zeroed counts of delivered keys - and the decision's are disjoint regions)
+  if (blockIdx.x > 0) { sym_plan_workgroup(blockIdx.x - 1u, gridDim.x - 1u, ride); return; }
   __shared__ u32 sClustered[16];
   __shared__ unsigned long long sEps[16], sNear[16];
   const int tid = threadIdx.x, s = tid >> 4, sub = tid & 15;
@@ -556,7 +614,10 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
 // Selection: lane b takes entries b, b + 16, ... of its row's bin into sixteen registers and sorts them once (a network of
 // 63 compare-exchanges), then k + 1
 // rounds of "smallest head wins and advances" over the sixteen lanes' two heads - list b's, a pointer into the staged
-// record, and the lane's delivered keys', which move down one register when they win: one reduction a round, nothing is
+// record, and the lane's delivered keys', of which a WINDOW of W (template parameter: 4; 1 and 2 for tests,
+// PG_KNN_SYM_MERGE_WINDOW) moves down one register when the head wins, refilled from the registers behind it in a cold
+// branch (pg_plan.h: sym_window_pop, sym_window_refill - a lane wins about once a trip at cfg3, and the whole list's
+// shift was 16 of a round's ~35 instructions): one reduction a round, nothing is
 // scanned twice (keys are unique; equal heads advance together; 0xFFFFFFFF = no entry).
 // Every list is complete below the cap only: a row whose (k+1)-th distance is not below it, or whose bin overflowed, joins
 // the evicted rows (pg_knn_rows_kernel finishes them) - and so do all sixteen rows of a group whose LOG overflowed: entries
@@ -566,11 +627,13 @@ __global__ __launch_bounds__(PG_WG_THREADS) void pg_knn_merge_kernel(const u32 *
 // without neighbours below the cap) - the rectangular launch behind this kernel runs instead and starts from no evicted
 // rows.  gate2: what the launches behind test: 3 = the symmetric sweep stands (only pg_knn_rows_kernel runs), else the
 // probe's word (0 without one).  Workgroups that have no rows, or leave at the gate, take their ticket all the same.
-// Resource line (hipcc -O3, gfx950): 72 VGPRs, no scratch, LDS 20 608 B, 7 waves per SIMD (profiles/r17_knn_sym_group_delivery.json
-// has the builds measured: the parent's per-row slots 81 us, bins beside the records 118, this form 106).
+// Resource line (hipcc -O3, gfx950; W = 1, 2 and 4 alike): 72 VGPRs, 75 SGPRs, no scratch, LDS 20 608 B, 7 waves per SIMD
+// (profiles/r17_knn_sym_group_delivery.json has the builds measured: the parent's per-row slots 81 us, bins beside the records
+// 118, the whole-list shift 106; profiles/r18_knn_sym_merge_window.json: 112 -> 94 us with the window, SQ_INSTS_VALU 3.92e7 -> 3.24e7).
 // lane i of a row of sixteen reads lane (i + N) & 15
 #define PG_SYM_ROR(x, N) ((u32)__builtin_amdgcn_update_dpp(0, (int)(x), 0x120 + (N), 0xF, 0xF, false))
 #define PG_SYM_CE(a, b) { const u32 x_ = a, y_ = b; a = x_ < y_ ? x_ : y_; b = x_ < y_ ? y_ : x_; }
+template <int W>
 __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8))) void pg_knn_sym_merge_kernel(const u32 *partial, const u32 *pieceStart, const u32 *lowCount,
                                                                          const u32 *lowKeys, u32 capL, int rowBits, long long nrows, int k, int *idx,
                                                                          unsigned char *dist, u32 cap, u32 *evictCount, u32 *evictRows,
@@ -588,17 +651,24 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7
   const bool open = !gate || ((gateMask >> gv) & 1u);
   if (threadIdx.x < 4 * PG_WG_WAVES) binCount[0][threadIdx.x] = 0u;
   int trip = 0;
+  // a trip's header - the passes of its block, pieceStart[blk] and pieceStart[blk + 1], and the group's count - is read a
+  // trip ahead (the first one here)
+  u32 hs0 = 0u, hs1 = 0u, hlogged = 0u;
+  if (open && (long long)blockIdx.x * (4 * PG_WG_WAVES) < nrows) {
+    const long long f0 = (long long)blockIdx.x * (4 * PG_WG_WAVES);
+    hs0 = pieceStart[f0 >> 6]; hs1 = pieceStart[(f0 >> 6) + 1]; hlogged = lowCount[f0];
+  }
   // (whole workgroups; the grid is a few workgroups a CU, every one takes a group of sixteen rows in turns: few tickets on one word)
   for (long long first = (long long)blockIdx.x * (4 * PG_WG_WAVES); open && first < nrows; first += (long long)gridDim.x * (4 * PG_WG_WAVES), trip ^= 1) {
     const int k1 = k + 1, off = kRec - k1;
-    const long long blk = first >> 6;                        // (sixteen consecutive rows from a multiple of sixteen: one block)
+    // (sixteen consecutive rows from a multiple of sixteen: one block, first >> 6)
     const long long row = first + 4 * wv + g;
     const bool mine = row < nrows;
     const long long rowIn = mine ? row : first;              // (idle lanes read the group's first row: in bounds, unused)
     // level 1: the block's passes and the group's count; then record b - unconditional loads from addresses inside the
     // workspace (a lane without a piece reads record 0 of its block), masked afterwards
-    const u32 s0 = pieceStart[blk], s1 = pieceStart[blk + 1];
-    const u32 logged = lowCount[first];
+    const u32 s0 = hs0, s1 = hs1;
+    const u32 logged = (u32)__builtin_amdgcn_readfirstlane((int)hlogged);
     u32 np = s1 - s0;
     np = np > PG_SYM_MAX_PIECES ? PG_SYM_MAX_PIECES : np;
     u32 *own = &keys[wv][g][0];
@@ -626,14 +696,14 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7
     if (threadIdx.x < 4 * PG_WG_WAVES) binCount[trip ^ 1][threadIdx.x] = 0u;   // (last read before the last trip's third barrier)
     __syncthreads();
     // lane b: entries b, b + 16, ... of its row's bin
-    // (the sixteen delivered keys of a lane are sixteen names, not an array: every one stays in its register)
+    // (the sixteen delivered keys of a lane are indexed by constants only: every one stays in its register)
     const u32 cnt = mine ? binCount[trip][4 * wv + g] : 0u;
     const int nl = (int)(cnt < capL ? cnt : capL);
     const u32 *low = &bins[4 * wv + g][b];
-    u32 d0, d1, d2, d3, d4, d5, d6, d7, d8, d9, d10, d11, d12, d13, d14, d15;
+    u32 d[16];
 #define PG_SYM_BIN(j, d) d = 16 * j + b < nl ? low[16 * j] : 0xFFFFFFFFu;
-    PG_SYM_BIN(0, d0) PG_SYM_BIN(1, d1) PG_SYM_BIN(2, d2) PG_SYM_BIN(3, d3) PG_SYM_BIN(4, d4) PG_SYM_BIN(5, d5) PG_SYM_BIN(6, d6) PG_SYM_BIN(7, d7)
-    PG_SYM_BIN(8, d8) PG_SYM_BIN(9, d9) PG_SYM_BIN(10, d10) PG_SYM_BIN(11, d11) PG_SYM_BIN(12, d12) PG_SYM_BIN(13, d13) PG_SYM_BIN(14, d14) PG_SYM_BIN(15, d15)
+    PG_SYM_BIN(0, d[0]) PG_SYM_BIN(1, d[1]) PG_SYM_BIN(2, d[2]) PG_SYM_BIN(3, d[3]) PG_SYM_BIN(4, d[4]) PG_SYM_BIN(5, d[5]) PG_SYM_BIN(6, d[6]) PG_SYM_BIN(7, d[7])
+    PG_SYM_BIN(8, d[8]) PG_SYM_BIN(9, d[9]) PG_SYM_BIN(10, d[10]) PG_SYM_BIN(11, d[11]) PG_SYM_BIN(12, d[12]) PG_SYM_BIN(13, d[13]) PG_SYM_BIN(14, d[14]) PG_SYM_BIN(15, d[15])
 #undef PG_SYM_BIN
     __syncthreads();                                         // (the bins are in registers: the block takes the records)
     {
@@ -643,21 +713,31 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7
     // the lane's delivered keys in ascending order (no entries last: Batcher's odd-even merge sort of sixteen); rows of
     // up to sixteen keys hold one a lane, as it stands
     if (__builtin_amdgcn_ballot_w64(nl > 16) != 0) {
-      PG_SYM_CE(d0, d1) PG_SYM_CE(d2, d3) PG_SYM_CE(d4, d5) PG_SYM_CE(d6, d7) PG_SYM_CE(d8, d9) PG_SYM_CE(d10, d11) PG_SYM_CE(d12, d13) PG_SYM_CE(d14, d15)
-      PG_SYM_CE(d0, d2) PG_SYM_CE(d1, d3) PG_SYM_CE(d4, d6) PG_SYM_CE(d5, d7) PG_SYM_CE(d8, d10) PG_SYM_CE(d9, d11) PG_SYM_CE(d12, d14) PG_SYM_CE(d13, d15)
-      PG_SYM_CE(d1, d2) PG_SYM_CE(d5, d6) PG_SYM_CE(d9, d10) PG_SYM_CE(d13, d14) PG_SYM_CE(d0, d4) PG_SYM_CE(d1, d5) PG_SYM_CE(d2, d6) PG_SYM_CE(d3, d7)
-      PG_SYM_CE(d8, d12) PG_SYM_CE(d9, d13) PG_SYM_CE(d10, d14) PG_SYM_CE(d11, d15) PG_SYM_CE(d2, d4) PG_SYM_CE(d3, d5) PG_SYM_CE(d10, d12) PG_SYM_CE(d11, d13)
-      PG_SYM_CE(d1, d2) PG_SYM_CE(d3, d4) PG_SYM_CE(d5, d6) PG_SYM_CE(d9, d10) PG_SYM_CE(d11, d12) PG_SYM_CE(d13, d14) PG_SYM_CE(d0, d8) PG_SYM_CE(d1, d9)
-      PG_SYM_CE(d2, d10) PG_SYM_CE(d3, d11) PG_SYM_CE(d4, d12) PG_SYM_CE(d5, d13) PG_SYM_CE(d6, d14) PG_SYM_CE(d7, d15) PG_SYM_CE(d4, d8) PG_SYM_CE(d5, d9)
-      PG_SYM_CE(d6, d10) PG_SYM_CE(d7, d11) PG_SYM_CE(d2, d4) PG_SYM_CE(d3, d5) PG_SYM_CE(d6, d8) PG_SYM_CE(d7, d9) PG_SYM_CE(d10, d12) PG_SYM_CE(d11, d13)
-      PG_SYM_CE(d1, d2) PG_SYM_CE(d3, d4) PG_SYM_CE(d5, d6) PG_SYM_CE(d7, d8) PG_SYM_CE(d9, d10) PG_SYM_CE(d11, d12) PG_SYM_CE(d13, d14)
+      PG_SYM_CE(d[0], d[1]) PG_SYM_CE(d[2], d[3]) PG_SYM_CE(d[4], d[5]) PG_SYM_CE(d[6], d[7]) PG_SYM_CE(d[8], d[9]) PG_SYM_CE(d[10], d[11]) PG_SYM_CE(d[12], d[13]) PG_SYM_CE(d[14], d[15])
+      PG_SYM_CE(d[0], d[2]) PG_SYM_CE(d[1], d[3]) PG_SYM_CE(d[4], d[6]) PG_SYM_CE(d[5], d[7]) PG_SYM_CE(d[8], d[10]) PG_SYM_CE(d[9], d[11]) PG_SYM_CE(d[12], d[14]) PG_SYM_CE(d[13], d[15])
+      PG_SYM_CE(d[1], d[2]) PG_SYM_CE(d[5], d[6]) PG_SYM_CE(d[9], d[10]) PG_SYM_CE(d[13], d[14]) PG_SYM_CE(d[0], d[4]) PG_SYM_CE(d[1], d[5]) PG_SYM_CE(d[2], d[6]) PG_SYM_CE(d[3], d[7])
+      PG_SYM_CE(d[8], d[12]) PG_SYM_CE(d[9], d[13]) PG_SYM_CE(d[10], d[14]) PG_SYM_CE(d[11], d[15]) PG_SYM_CE(d[2], d[4]) PG_SYM_CE(d[3], d[5]) PG_SYM_CE(d[10], d[12]) PG_SYM_CE(d[11], d[13])
+      PG_SYM_CE(d[1], d[2]) PG_SYM_CE(d[3], d[4]) PG_SYM_CE(d[5], d[6]) PG_SYM_CE(d[9], d[10]) PG_SYM_CE(d[11], d[12]) PG_SYM_CE(d[13], d[14]) PG_SYM_CE(d[0], d[8]) PG_SYM_CE(d[1], d[9])
+      PG_SYM_CE(d[2], d[10]) PG_SYM_CE(d[3], d[11]) PG_SYM_CE(d[4], d[12]) PG_SYM_CE(d[5], d[13]) PG_SYM_CE(d[6], d[14]) PG_SYM_CE(d[7], d[15]) PG_SYM_CE(d[4], d[8]) PG_SYM_CE(d[5], d[9])
+      PG_SYM_CE(d[6], d[10]) PG_SYM_CE(d[7], d[11]) PG_SYM_CE(d[2], d[4]) PG_SYM_CE(d[3], d[5]) PG_SYM_CE(d[6], d[8]) PG_SYM_CE(d[7], d[9]) PG_SYM_CE(d[10], d[12]) PG_SYM_CE(d[11], d[13])
+      PG_SYM_CE(d[1], d[2]) PG_SYM_CE(d[3], d[4]) PG_SYM_CE(d[5], d[6]) PG_SYM_CE(d[7], d[8]) PG_SYM_CE(d[9], d[10]) PG_SYM_CE(d[11], d[12]) PG_SYM_CE(d[13], d[14])
     }
     // heads of the own list (a pointer: the lane reads what it staged itself) and of the delivered keys (d0); lane r - 1
     // keeps rank r (ranks from 17 on: lane 0 writes)
-    int pos = 0;
+    // the next trip's header: three words, the same for the whole workgroup, asked for here so that the records' addresses
+    // and the log's bound do not wait for a round trip at the top of the trip (a last trip asks for nothing)
+    {
+      const long long next = first + (long long)gridDim.x * (4 * PG_WG_WAVES);
+      // (a zero the compiler cannot see in the count's address: a load it knows to be uniform is read into an SGPR where
+      //  it is issued, and the wave would wait for it here, in front of the rounds; the trip's top reads the first lane)
+      u32 zero = 0u;
+      asm volatile("" : "+v"(zero));
+      if (next < nrows) { hs0 = pieceStart[next >> 6]; hs1 = pieceStart[(next >> 6) + 1]; hlogged = lowCount[next + zero]; }
+    }
+    int pos = 0, used = 0;
     u32 head = has ? own[b * kRec + off] : 0xFFFFFFFFu, res = 0xFFFFFFFFu;
     for (int r = 0; r <= k; ++r) {
-      u32 m = head < d0 ? head : d0, x;
+      u32 m = head < d[0] ? head : d[0], x;
       x = PG_SYM_ROR(m, 8); m = x < m ? x : m;
       x = PG_SYM_ROR(m, 4); m = x < m ? x : m;
       x = PG_SYM_ROR(m, 2); m = x < m ? x : m;
@@ -667,11 +747,10 @@ __global__ __launch_bounds__(PG_WG_THREADS) __attribute__((amdgpu_waves_per_eu(7
         ++pos;
         head = pos < k1 ? own[b * kRec + off + pos] : 0xFFFFFFFFu;
       }
-      const bool dwin = any && d0 == m;                      // ... or its delivered keys move down a register
-      d0 = dwin ? d1 : d0; d1 = dwin ? d2 : d1; d2 = dwin ? d3 : d2; d3 = dwin ? d4 : d3;
-      d4 = dwin ? d5 : d4; d5 = dwin ? d6 : d5; d6 = dwin ? d7 : d6; d7 = dwin ? d8 : d7;
-      d8 = dwin ? d9 : d8; d9 = dwin ? d10 : d9; d10 = dwin ? d11 : d10; d11 = dwin ? d12 : d11;
-      d12 = dwin ? d13 : d12; d13 = dwin ? d14 : d13; d14 = dwin ? d15 : d14; d15 = dwin ? 0xFFFFFFFFu : d15;
+      // ... or the window of its delivered keys moves down a register (pg_plan.h: sym_window_pop); a lane whose window has
+      // run empty takes the W keys behind it - the cold path, where some lane of the wave won W times since its last refill
+      sym_window_pop<W>(d, used, any && d[0] == m);
+      if (__builtin_amdgcn_ballot_w64(sym_window_empty<W>(used)) != 0) sym_window_refill<W>(d, used);
       if (b == r - 1) res = m;
       if (b == 0 && mine) {
         if (r > 16) {
@@ -722,7 +801,7 @@ static const probe_fn kProbe[8] = {pg_launch_probe_g1, pg_launch_probe_g2, pg_la
 // zeroes workspace[0, 576) (the counter block: pass_counter issues no fill behind a probe) and fills workspace[576, ...):
 // returns the gate words through *gate
 static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 span, u32 need, void *workspace, hipStream_t s,
-                     const PgKnobs &kn, const u32 **gate) {
+                     const PgKnobs &kn, const u32 **gate, const SymPlanArgs *ride = nullptr) {
   if (!workspace) return pg_fail(PG_E_BADARG, "workspace required (pg_workspace_bytes)");
   u32 *gates = (u32 *)((char *)workspace + PG_WS_GATES), *counts = (u32 *)((char *)workspace + PG_WS_COUNTS);
   ProbeParams pp;
@@ -737,8 +816,10 @@ static int run_probe(const NsqParams &e, int l, int bits, u32 near, u32 lo, u32 
   const int force = (int)kn.gateForce.v;
   // (counts of a short sample: pg_decide_kernel reads counts[nsample + s] - same layout as the probe wrote)
   static_assert(PG_WS_GATES / 4 <= 1024, "pg_decide_kernel zeroes one word per thread");
-  pg_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates, (u32 *)workspace,
-                                                  PG_WS_GATES / 4);   // (PG_PROBE_ROWS <= 64)
+  // (ride: the plan of the symmetric sweep behind this launch, in workgroups of its own - KnnPlan::symPlanRides)
+  const SymPlanArgs none = {};
+  pg_decide_kernel<<<dim3(1u + (ride ? ride->grid : 0u)), dim3(1024), 0, s>>>(counts, pp.nsample, pp.wavesPerRow, need, e.ncols, force, gates, (u32 *)workspace,
+                                                                              PG_WS_GATES / 4, ride ? *ride : none);   // (PG_PROBE_ROWS <= 64)
   if (int rc = pg_launched("pg_decide_kernel")) return rc;
   *gate = gates;
   return 0;
@@ -1132,7 +1213,14 @@ static int launch_valu(const KnnRun &r, bool gated) {
   set_rows_plan(&q, &grid, r.pl.valu, r.kn);
   return pg_launched(kNsq[r.ng - 1](PG_MODE_KNN, r.bits, q, grid, r.stream), "pg_nsq_kernel(knn)");
 }
-// the symmetric sweep of a self graph, in front of the rectangular launch: its plan kernel, the sweep, its merge
+// the arguments of the sweep's plan, for its own launch or the probe's decision launch
+static SymPlanArgs sym_plan_args(const KnnPlan &pl, void *workspace) {
+  char *base = (char *)workspace + pl.symBase;
+  return SymPlanArgs{pl.symNb, pl.symNst, pl.symSlots, pl.symPiece, pl.symPieceMin, (int4 *)(base + pl.symWs.plan), (u32 *)(base + pl.symWs.pieceStart),
+                     (uint4 *)(base + pl.symWs.lowCount), pl.symZero4, pl.symPlanGrid};
+}
+// the symmetric sweep of a self graph, in front of the rectangular launch: its plan kernel (where the plan did not ride in
+// the probe's decision launch), the sweep, its merge
 static int launch_sym(const KnnRun &r) {
   const KnnPlan &pl = r.pl;
   char *base = (char *)r.workspace + pl.symBase;
@@ -1152,12 +1240,15 @@ static int launch_sym(const KnnRun &r) {
   s.mmGridWaves = pl.symGridWaves;
   s.mmPassCounter = r.p.mmPassCounter + 16;
   u32 *pieceStart = (u32 *)(base + pl.symWs.pieceStart), *gate2 = r.gates() + 2;
-  if (r.kn.debugPlan.set) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots\n", (long long)r.nrows, pl.symPasses, pl.symSlots);
-  pg_knn_sym_plan_kernel<<<dim3(pl.symPlanGrid), dim3(1024), 0, r.stream>>>(pl.symNb, pl.symNst, pl.symSlots, pl.symPiece, pl.symPieceMin, (int4 *)(base + pl.symWs.plan),
-                                                                            pieceStart, (uint4 *)sa.lowCount, pl.symZero4);
-  if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
+  if (r.kn.debugPlan.set) fprintf(stderr, "[pg plan sym] rows=%lld: %lld passes for %lld slots, plan %s, merge window %d\n", (long long)r.nrows, pl.symPasses, pl.symSlots,
+                                 pl.symPlanRides ? "rides in the decide launch" : "launched", pl.symMergeWindow);
+  if (!pl.symPlanRides) {
+    pg_knn_sym_plan_kernel<<<dim3(pl.symPlanGrid), dim3(1024), 0, r.stream>>>(sym_plan_args(pl, r.workspace));
+    if (int rc = pg_launched("pg_knn_sym_plan_kernel")) return rc;
+  }
   if (int rc = pg_launched(kMmSym[r.ng - 1](s, (int)(s.mmGridWaves / PG_WG_WAVES), r.stream), "pg_mm_knn_sym_kernel")) return rc;
-  pg_knn_sym_merge_kernel<<<dim3(pl.symMergeGrid), dim3(PG_WG_THREADS), 0, r.stream>>>(
+  auto *merge = pl.symMergeWindow == 1 ? pg_knn_sym_merge_kernel<1> : (pl.symMergeWindow == 2 ? pg_knn_sym_merge_kernel<2> : pg_knn_sym_merge_kernel<4>);
+  merge<<<dim3(pl.symMergeGrid), dim3(PG_WG_THREADS), 0, r.stream>>>(
       sa.partial, pieceStart, sa.lowCount, sa.lowKeys, sa.capL, sa.rowBits, r.nrows, r.k, r.idx, r.dist, r.p.knnGuess, r.p.mmEvict,
       r.p.mmEvictRows, s.gate, s.gateMask, gate2, r.p.mmPassCounter + 17, (u32)(pl.symLimit < 0 ? 0 : pl.symLimit));
   return pg_launched("pg_knn_sym_merge_kernel");
@@ -1224,7 +1315,8 @@ static int knn_launch(const void *row_planes, int64_t row_npad, int64_t row0, in
   if (!pl.mm) return launch_valu(r, false);
   if (pl.probe) {
     const u32 *gate = nullptr;
-    if (int rc = run_probe(r.p, l, bits, pl.guess, 1u, 0u, (u32)(first + k), workspace, r.stream, kn, &gate)) return rc;
+    const SymPlanArgs ride = pl.symPlanRides ? sym_plan_args(pl, workspace) : SymPlanArgs{};
+    if (int rc = run_probe(r.p, l, bits, pl.guess, 1u, 0u, (u32)(first + k), workspace, r.stream, kn, &gate, pl.symPlanRides ? &ride : nullptr)) return rc;
     if (int rc = launch_valu(r, true)) return rc;
     r.p.gate = gate;
   }

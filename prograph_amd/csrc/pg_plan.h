@@ -72,6 +72,31 @@ PG_HD static inline uint32_t sym_group_cap(uint32_t n, uint32_t first, uint32_t 
   const uint32_t rows = n > first ? n - first : 0u;
   return (rows < 16u ? rows : 16u) * capL;
 }
+// The merge's rounds on a lane's sixteen delivered keys, d[0] <= ... <= d[15] (no entry = 0xFFFFFFFF last).  The head of the
+// list is d[0]; only a WINDOW of W keys, d[0 .. W - 1], moves when the head wins: W selects and an add a round, not sixteen.
+// `used` counts the wins since the window was filled; at used == W the window holds no entry at all and the next W keys
+// stand right behind it: the refill moves d[W ..] down by W (no entry at the top) - the cold path, taken by a wave where a
+// ballot finds such a lane.  Between a pop and the refill that follows it d[0] is read by nobody, so d[0] is the head of the
+// same sorted list in every round.  Lane-local, without a branch: the kernel and tests/capi_sym_window run this text.
+#define PG_SYM_NONE 0xFFFFFFFFu
+template <int W> PG_HD static inline void sym_window_pop(uint32_t (&d)[16], int &used, bool win) {
+  static_assert(W == 1 || W == 2 || W == 4 || W == 16, "window widths that divide sixteen");
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int j = 0; j < W - 1; ++j) d[j] = win ? d[j + 1] : d[j];
+  d[W - 1] = win ? PG_SYM_NONE : d[W - 1];
+  used += win ? 1 : 0;
+}
+template <int W> PG_HD static inline bool sym_window_empty(int used) { return W < 16 && used == W; }
+template <int W> PG_HD static inline void sym_window_refill(uint32_t (&d)[16], int &used) {
+  const bool full = sym_window_empty<W>(used);
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+  for (int j = 0; j < 16; ++j) d[j] = full ? (j + W < 16 ? d[j + W < 16 ? j + W : 15] : PG_SYM_NONE) : d[j];
+  used = full ? 0 : used;
+}
 
 #define PG_PROBE_ROWS 64        // sample rows
 #define PG_PROBE_WAVES 128      // waves per sample row: every 8th column tile (PG_PROBE_STRIDE), one turn of four tiles each at N = 200k
@@ -94,7 +119,7 @@ struct PgKnob {
 struct PgKnobs {
   PgKnob lbFilter, wavesPerCu, rowsPerWave, debugPlan, engine, engineMinRows, probe, probeS, probeW, gateForce, epsOrdered;
   PgKnob knnGuess, mmShort, mmR, mmSplit, mmEvict, mmPieces, mmPiecesAhead, mmPlan, mmTail, mmPersistent, mmL1, mmL2, mmRun;
-  PgKnob knnSym, symCapL, symPiece, symPieceMin, symOcc, symDeliver, symEvictLimit, symMergeWgs;
+  PgKnob knnSym, symCapL, symPiece, symPieceMin, symOcc, symDeliver, symEvictLimit, symMergeWgs, symMergeWindow;
 };
 enum { PG_ENGINE_AUTO = 0, PG_ENGINE_MFMA = 1, PG_ENGINE_VALU = 2 };
 // how a value is taken: ANY as it is; CLAMP into [lo, hi]; RANGE only inside [lo, hi], the default otherwise; WIDE as ANY, read as
@@ -141,6 +166,7 @@ static const PgKnobSpec kPgKnobs[] = {
     {"PG_KNN_SYM_DELIVER", &PgKnobs::symDeliver, 1, 0, 0, PG_KNOB_ANY, "0: timing experiments, wrong results"},
     {"PG_KNN_SYM_EVICT_LIMIT", &PgKnobs::symEvictLimit, 0, 0, 0, PG_KNOB_WIDE, "evicted rows up to which the sweep's results stand (default: a sixteenth of the rows)"},
     {"PG_KNN_SYM_MERGE_WGS", &PgKnobs::symMergeWgs, 0, 1, PG_KNOB_MAX, PG_KNOB_RANGE, "workgroups of the sweep's merge at most (tests; default and bound: eight a CU)"},
+    {"PG_KNN_SYM_MERGE_WINDOW", &PgKnobs::symMergeWindow, 0, 1, 2, PG_KNOB_RANGE, "delivered keys in the window of the merge's rounds: 1 or 2 (tests: the refill runs often; default: four)"},
 };
 
 static inline PgKnob pg_knob_parse(const PgKnobSpec &s, const char *text) {
@@ -539,7 +565,9 @@ struct KnnPlan {
   int symRowBits;            // the sender row's field of a delivered entry (sym_row_bits of the cap)
   bool symDeliver;
   unsigned symPlanGrid, symMergeGrid;
-  int64_t symBase;           // ws_sym_offset; the regions behind it:
+  int symMergeWindow;        // delivered keys in the window of the merge's rounds: 4; 1 or 2 by PG_KNN_SYM_MERGE_WINDOW (tests)
+  bool symPlanRides;         // behind a probe: the plan's workgroups ride in pg_decide_kernel's launch, no plan launch
+  int64_t symBase;          // ws_sym_offset; the regions behind it:
   SymWs symWs;
   bool alt32;                // the gated 32-row alternative (the probe's "one cluster")
   PassPlan alt;
@@ -640,6 +668,10 @@ static inline KnnPlan knn_plan(const KnnShape &s, const KnnHw &hw, const PgKnobs
     long long mergeCap = rowsCap;
     if (kn.symMergeWgs.v >= 1 && kn.symMergeWgs.v < mergeCap) mergeCap = kn.symMergeWgs.v;
     pl.symMergeGrid = (unsigned)(mergeWgs < mergeCap ? mergeWgs : mergeCap);
+    // (PG_KNN_SYM_MERGE_WINDOW: tests - a narrow window makes the refill, the rounds' cold path, run on ordinary inputs)
+    pl.symMergeWindow = kn.symMergeWindow.v >= 1 ? (int)kn.symMergeWindow.v : 4;
+    // the plan needs the shape and the workspace alone, and the probe's decision launch is one workgroup on an empty chip
+    pl.symPlanRides = pl.probe;
     if (!pl.probe) pl.mainGateMask = (1u << 0) | (1u << 2);
   }
   pl.evictGateMask = pl.mainGateMask | (pl.sym ? 1u << 3 : 0u);
