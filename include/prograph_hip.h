@@ -318,6 +318,7 @@ int pg_query_eps_fill(const void *q_planes, int64_t nq, int64_t q_npad, const vo
  *   pos_ok  = pos_mode == 0, or: (pos_mode 1 "or": some byte selected by pos_mask
  *             differs from the reference row; 2 "and": all selected bytes differ) and no
  *             byte selected by not_mask differs          (:316-325)
+ * l: the number of positions of the packed rows, 1..255 with 5 bit planes, 1..128 with 8; anything beyond is refused.
  * pos_mask / not_mask: uint32[pg_ngroups(l)] device arrays, bit j of word g selects position 32g+j.
  *   dist_out uint8[n] (may be NULL), hist uint64[256] (may be NULL; must be zeroed by
  *   the caller), flags uint8[n] (may be NULL)

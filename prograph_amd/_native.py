@@ -629,7 +629,7 @@ def index_flags(planes, ref, want=None, pos_mode=0, pos_mask=None, not_mask=None
     if pos_mode:
         pm = torch.from_numpy(position_bitmask(pos_mask, planes.g).view(np.int32)).to(dev)
         nm = torch.from_numpy(position_bitmask(not_mask, planes.g).view(np.int32)).to(dev)
-    _check(lib().pg_index_flags(_ptr(planes.buf), n, planes.npad, planes.g * 32, planes.bits, int(ref), _ptr(wt),
+    _check(lib().pg_index_flags(_ptr(planes.buf), n, planes.npad, planes.l, planes.bits, int(ref), _ptr(wt),
                                 int(pos_mode), _ptr(pm), _ptr(nm), _ptr(dist), _ptr(hist), _ptr(flags), _stream()),
            "pg_index_flags")
     return dist, hist, flags

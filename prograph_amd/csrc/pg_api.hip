@@ -1555,7 +1555,7 @@ int pg_index_flags(const void *planes, int64_t n, int64_t npad, int l, int bits,
                    uint8_t *dist_out, uint64_t *hist, uint8_t *flags, void *stream) {
   if (!planes || n <= 0 || npad < n || ref < 0 || ref >= n) return pg_fail(PG_E_BADARG, "pg_index_flags: bad argument");
   if (int rc = check_bits(bits)) return rc;
-  if (int rc = check_l(l, bits)) return rc;
+  if (int rc = check_l(l, bits, true)) return rc;         // the positions, not the padded width: 256 is beyond 5 bit planes
   if (pos_mode < 0 || pos_mode > 2 || (pos_mode && (!pos_mask || !not_mask)))
     return pg_fail(PG_E_BADARG, "pg_index_flags: bad position mode / masks");
   const dim3 grid((unsigned)((n + 255) / 256)), block(256);
